@@ -6,7 +6,20 @@ over one batch of synthetic PCM already resident in HBM: configs[1] = 1,024 clip
 8 kHz per GPU (960,512 fingerprints). Multi-GPU: one process per GPU (torchrun), each rank
 fingerprints its own 1,024 clips (clip-sharded, no collective on the data path): weak scaling.
 
-Also reported (same JSON line):
+A plain run (`--gpus 1 --steps N --warmup W`) does only that: set-up, W warm-up steps, the clock
+warm-up, the N timed steps, then the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds per timed step, and the fingerprint kernel's `roofline`, which is
+computed from HIP events around those same N steps). Every other leg below takes runs of its own and
+is measured only with --full.
+
+--dump-outputs DIR: after the timed steps, write what the last timed step left in the caller's
+output buffer (the stored micro-unit pairs, one row per frame: what a caller of
+tfp_fingerprint_device receives) as DIR/fingerprints.npy in float64 (exact for int32 values); with N
+ranks each writes DIR/fingerprints_rank<r>.npy. At most 64 MB in all: a larger output is cut to a
+fixed seeded sample of its rows. The PCM is a pure function of the seed and the clip ids, so the
+same arguments give the same inputs and two builds can be compared value for value.
+
+Reported on the same JSON line (`roofline` always, the other legs under --full):
   roofline      the fingerprint kernel: algorithmic 520 B/fingerprint (512 B PCM in + 8 B out,
                 SURVEY §8d) / average launch time measured with HIP events on the launch stream,
                 against 8 TB/s HBM; traffic = PMC-measured HBM bytes per launch if a profile exists.
@@ -53,6 +66,8 @@ HOP = 256
 BYTES_PER_FP = 512 + 8
 HBM_PEAK_GBS = 8000.0
 SEED_DB, SEED_Q = 0x7153A1, 0x7153B2
+SEED_DUMP = 0x7153D0
+DUMP_CAP_BYTES = 64 * 2**20
 
 
 def log(*a):
@@ -129,6 +144,20 @@ def launch_check(args):
                           "group_fields": list(GROUP_FIELDS)}), flush=True)
 
 
+def dump_outputs(out_dir, micro, rank, world):
+    """--dump-outputs: the timed path's output buffer as the last timed step left it, int32 micro-unit
+    pairs [frames, 2] written as float64 (every int32 is exact in it). Over the cap (64 MB shared by
+    the ranks) a fixed seeded sample of the rows, in row order, is written instead."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = micro.cpu().numpy()
+    cap_rows = DUMP_CAP_BYTES // world // (a.shape[1] * 8)
+    if len(a) > cap_rows:
+        a = a[np.sort(np.random.default_rng(SEED_DUMP).choice(len(a), cap_rows, replace=False))]
+    name = "fingerprints.npy" if world == 1 else "fingerprints_rank%d.npy" % rank
+    np.save(os.path.join(out_dir, name), a.astype(np.float64))
+    return name, len(a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,7 +185,13 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on MI355X; gloo only to rehearse N ranks on one GPU")
     ap.add_argument("--no-group", action="store_true", help="skip the in-process device-group leg")
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, meet over gloo, print, exit (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: strong scaling, CPU baselines, match, stream, group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/fingerprints.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: need at least 1 timed step")
 
     # --gpus N: every rank process exists before any GPU call (a child launcher, never an exec)
     how, what = launch_plan(args.gpus, os.environ, sys.argv[1:])
@@ -300,20 +335,24 @@ def main():
     }
     if dist_info:
         out["dist"] = dist_info
+    if args.dump_outputs:
+        name, nrows = dump_outputs(args.dump_outputs, micro, rank, world)
+        out["outputs"] = {"file": name, "rows": nrows, "of": F, "dtype": "float64"}
     del micro
+    out["full"] = args.full
 
     # ---------------------------------------------------------------- strong scaling (C2 fixed)
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         out["strong"] = run_strong(args, eng, torch, dev, sh, pcm, nclips, n, rank, world, barrier, max_over_ranks)
 
     # ---------------------------------------------------------------- CPU baseline (oracle)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = fingerprint_cpu_baseline(args, pcm, nclips, n, F)
     del pcm
     torch.cuda.empty_cache()
 
     # ---------------------------------------------------------------- match (C3 / C4)
-    if not args.no_match and args.db_clips > 0:
+    if args.full and not args.no_match and args.db_clips > 0:
         out["match"] = run_match(args, eng, torch, dev, sh, rank, world, dist, barrier, max_over_ranks, T)
         if args.stream_channels > 0:
             out["stream"] = run_stream(args, eng, T, torch, dev, sh, rank, world, dist, barrier)

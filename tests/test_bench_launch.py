@@ -26,6 +26,27 @@ def test_launch_plan_cases():
     assert cmd[-4:] == ["--gpus", "2", "--dist-backend", "gloo"]
 
 
+def test_dump_outputs_exact_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs: int32 values (NULL = -2^31 included) survive float64 exactly; over the cap a
+    fixed sample of the rows is written, the same rows on every call, in row order."""
+    torch = pytest.importorskip("torch")
+    import numpy as np
+    a = np.arange(2000, dtype=np.int64).reshape(1000, 2) * 2147483 - 2**31
+    t = torch.from_numpy(a.astype(np.int32))
+    name, rows = bench.dump_outputs(str(tmp_path / "all"), t, 0, 1)
+    got = np.load(tmp_path / "all" / name)
+    assert (name, rows) == ("fingerprints.npy", 1000) and got.dtype == np.float64 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 2 * 100 * 16)  # 100 rows for each of 2 ranks
+    picks = []
+    for d in ("x", "y"):
+        name, rows = bench.dump_outputs(str(tmp_path / d), t, 1, 2)
+        assert (name, rows) == ("fingerprints_rank1.npy", 100)
+        picks.append(np.load(tmp_path / d / name))
+    assert np.array_equal(picks[0], picks[1]) and picks[0].nbytes == 100 * 16
+    idx = ((picks[0][:, 0] + 2**31) / 2147483 / 2).astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(picks[0], a[idx])
+
+
 def _run(args, env_extra=None):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
