@@ -28,6 +28,7 @@
 #include "tfp_math.hpp"
 #include "tfp_synth.hpp"
 #include "tfp_tables.hpp"
+#include "tfp_tolcache.hpp"
 
 using namespace tfp;
 
@@ -56,24 +57,68 @@ struct DevBuf {
   }
 };
 
-// A tolerance's key row ranges and key bitsets kept beside the active ones (tfp_engine::tol_lru):
-// the dialplan passes the tolerance per call (application_handler.c:114-122), so extensions at
-// different tolerances alternate on one engine. Valid while the index is at `version`.
-struct TolSlot {
-  double tol = 0.0;
+// One tolerance's key row ranges (of every key's box) and the key-presence bitsets built from them
+// (launch_key_bits; the vote paths), cached per index version (tfp_engine::tc.ranges).
+struct KeyRanges {
   DevBuf rng_all, key_bits;
-  bool rng_valid = false, bits_valid = false;
-  int32_t bits_cols = -1;
-  uint64_t version = 0, used = 0;
+  bool bits_valid = false;
+  int32_t bits_cols = -1;  // the column count key_bits was laid out for (its row width)
 };
 
-// A tolerance's clip-set cache kept beside the active one (tfp_engine::cell_lru, round 6): callers
-// alternating coefs = 2 tolerances do not rebuild it per call. Valid while the index is at `version`.
-struct CellSlot {
-  CellCache c;
-  double tol = 0.0;
-  bool has = false;
-  uint64_t version = 0, used = 0;
+// The index rows in clip order (tfp_kernels.hpp), the source of the clip-set caches at tolerances up
+// to kOrderMaxTol: built on the first search that needs it, then carried through every merge.
+struct ClipOrder {
+  DevBuf key, m1, key_b, m1_b, newcol;
+  int64_t rows = 0;
+  bool valid = false;
+  int64_t n_builds = 0, n_merges = 0;
+  CacheBuf sort_tmp;
+  OrderScratch merge;
+};
+
+// The index delta's staged rows in clip order (sorted once per delta version, for any tolerance).
+struct DeltaOrder {
+  DevBuf key, m1, key_b, m1_b;
+  CacheBuf sort_tmp;
+};
+
+// Index delta (round 4, tfp_index.hpp): the live clips added since the last build, searched by the
+// coefs = 1 vote paths beside the main index instead of merged into it per enrolment.
+struct IndexDelta {
+  static constexpr int32_t kMaxClips = 512;        // columns reserved for them
+  static constexpr int64_t kMaxRows = 1ll << 20;  // beyond either limit the next update merges
+  bool use = true;  // TFP_INDEX_DELTA=0: every update merges (A/B, tests)
+  // The delta pads the main columns to a multiple of 1024 and reserves kMaxClips columns after
+  // them, which a small DB's vote passes would pay for on every search (300 clips -> 1,536
+  // columns); below this many main columns an update merges instead (cheap at that size).
+  // TFP_INDEX_DELTA=1 (tests) takes the delta at any size.
+  int64_t min_cols = 4096;
+  bool force_merge = false;  // consolidate(): the next rebuild merges the delta
+  bool wide = true;          // TFP_DELTA_WIDE=0: coefs = 2 searches merge the delta first (A/B, tests)
+  std::vector<int32_t> clip;  // delta column col0 + j -> clip id (uuid order)
+  std::vector<int32_t> at;    // delta j's insertion point among the main columns' uuids
+  int32_t col0 = 0;           // first delta column (a multiple of 1024)
+  int64_t rows = 0;           // staged rows of the delta's clips
+  int64_t n_updates = 0;
+  std::unordered_map<int32_t, int32_t> key_col;  // tie-break key -> delta column (with an override)
+  DevBuf d_clips, d_at;
+  void reset(int32_t c0) { clip.clear(), at.clear(), key_col.clear(), col0 = c0, rows = 0; }  // no clip beside the c0 main columns
+};
+
+// The search-side caches, served only at the (tolerance, version) they were committed at (tfp_tolcache.hpp).
+struct SearchCaches {
+  TolCache<KeyRanges, 4> ranges;  // per index_version (every index update; merge_index and delta_update carry the active one)
+  // general path: the clip-set caches (tfp_scan.hip), per main_version: they hold main-index rows
+  // only, so they stay valid across delta updates
+  TolCache<CellCache, 4> cells;
+  // coefs = 2 with an index delta (round 6): the delta's own clip-set cache (its staged rows in clip
+  // order, columns numbered from 0 in uuid order), swept after the main cache into the same maxima,
+  // so an enrolment followed by a coefs = 2 search does not merge the index (fp_handler.c:559-571:
+  // the reference's INSERT makes a clip searchable for the cost of its own rows)
+  TolEntry<CellCache> dcells;  // per index_version
+  TolEntry<DeltaOrder> dorder;  // per index_version (committed at tolerance 0: it serves every tolerance)
+  TolEntry<DevBuf> kbox;        // the keys' "%f" boxes (launch_key_boxes); version 0: they do not depend on the index
+  int64_t n_builds = 0, n_hits = 0, n_from_order = 0, n_delta_builds = 0, n_delta_sweeps = 0;
 };
 
 // Pinned host staging (one H2D copy per small call instead of one per array).
@@ -171,7 +216,6 @@ struct tfp_engine {
   int32_t ncols = 0;       // live clips
   std::vector<int32_t> col_clip;                 // column (uuid rank) -> clip id
   std::unordered_map<int32_t, int32_t> key_col;  // tie-break key -> main column (with an override)
-  std::unordered_map<int32_t, int32_t> key_col_delta;  // ... -> the index delta's columns
   bool key_identity = true;                      // no override: key == column
   std::vector<int32_t> tiebreak_override;        // clip id -> key (empty = uuid rank)
   // with an override: key_col / the device tie keys of the main columns no longer match it (a full
@@ -199,10 +243,8 @@ struct tfp_engine {
   hipStream_t qoff_stream = nullptr;
   hipEvent_t qoff_ev = nullptr;
   bool qoff_pending = false;
-  DevBuf key_bits;           // key-presence bitsets at tolerance rng_tol (launch_key_bits; small path)
-  DevBuf key_bits_b;         // the other buffer of an update carried across a merge (merge_index)
+  DevBuf key_bits_b;         // the other buffer of a key-bitset update (merge_index, delta_update)
   int64_t tiekey_ident = -1; // tiekey on the device holds the identity over this many columns (-1: not known)
-  bool key_bits_valid = false;
   HostBuf vres_pin;         // pinned (VoteMeta, best[]) of the vote path
   HostBuf spec_pin;         // pinned copy of the speculative sweep's counts (WideScratch::info), host-mapped
   void* spec_pin_host = nullptr;   // the allocation spec_pin_dev was taken for
@@ -210,53 +252,16 @@ struct tfp_engine {
   HostBuf small_res;        // host-mapped SmallResult, written by small_vote_kernel (no copy back)
   SmallResult* small_res_dev = nullptr;
   void* small_res_host = nullptr;  // the allocation small_res_dev was taken for
-  DevBuf rng_all;            // row ranges of all keys' boxes at tolerance rng_tol (valid for this index)
-  double rng_tol = 0.0;
-  bool rng_valid = false;
-  // other tolerances' ranges and bitsets (least recently used first out), valid at index_version;
-  // index_version changes with every index update (rebuild, delta update), which carries only the
-  // active tolerance's
-  static constexpr int kTolSlots = 3;
-  TolSlot tol_lru[kTolSlots];
-  uint64_t index_version = 1, tol_clock = 0;
-  // the main index's own version (builds and merges; a delta update leaves it): the clip-set caches
-  // hold main-index rows only, so they stay valid across delta updates
-  uint64_t main_version = 1;
-  // general path: clip-set cache at tolerance cell_tol (tfp_scan.hip), built on first use per
-  // index version and tolerance
-  CellCache cells;
+  // index_version changes with every index update (rebuild, delta update); main_version is the main
+  // index's own (builds and merges; a delta update leaves it)
+  uint64_t index_version = 1, main_version = 1;
+  SearchCaches tc;
   WideScratch wide;         // the general path's sweep by groups
   double wide_min_tol = 0;  // TFP_WIDE_MIN_TOL: general-path batches below it take the clip-set cells (tests)
-  double cell_tol = 0.0;
-  bool cell_fresh = false;  // cells holds the cache of cell_tol at index version cell_version
-  uint64_t cell_version = 0;
-  // other tolerances' clip-set caches (round 6), least recently used out, valid at their version
-  static constexpr int kCellSlots = 3;
-  CellSlot cell_lru[kCellSlots];
-  int64_t n_cell_builds = 0, n_cell_hits = 0, n_cell_from_order = 0;
   // the coefs = 2 sweep's sort path per batch (tfp_sweep_stats): the bin sort's speculative pass
   // stood, the library sort ran, a speculative pass was redone; crowd bins the bin sort copied
   int64_t n_sweep_bins = 0, n_sweep_lib = 0, n_sweep_redo = 0, n_sweep_crowd = 0;
-  // coefs = 2 with an index delta (round 6): the delta's own clip-set cache (its staged rows in clip
-  // order, columns numbered from 0 in uuid order), swept after the main cache into the same maxima,
-  // so an enrolment followed by a coefs = 2 search does not merge the index (fp_handler.c:559-571:
-  // the reference's INSERT makes a clip searchable for the cost of its own rows)
-  CellCache dcells;
-  double dcell_tol = 0.0;
-  uint64_t dcell_version = 0, dl_version = 0;  // index versions of dcells and of the delta rows' order
-  bool dcell_fresh = false;
-  DevBuf dl_key, dl_m1, dl_key_b, dl_m1_b;
-  CacheBuf dl_sort_tmp;
-  bool delta_wide = true;  // TFP_DELTA_WIDE=0: coefs = 2 searches merge the delta first (A/B, tests)
-  int64_t n_delta_cell_builds = 0, n_delta_sweeps = 0;
-  // the index rows in clip order (tfp_kernels.hpp), the source of the caches at tolerances up to
-  // kOrderMaxTol: built on the first search that needs it, then carried through every merge
-  DevBuf o_key, o_m1, o_key_b, o_m1_b, o_newcol;
-  int64_t o_rows = 0;
-  bool o_valid = false;
-  int64_t n_order_builds = 0, n_order_merges = 0;
-  CacheBuf o_sort_tmp;
-  OrderScratch o_merge;
+  ClipOrder order;
   // scan scratch: stamp / score / touched nq x ncols int32 each, tcnt nq int32; kept all-zero
   // by the scan kernels themselves
   DevBuf touched, tcnt;
@@ -267,31 +272,16 @@ struct tfp_engine {
   bool dbg_vote = false;      // TFP_DEBUG_VOTE: log the vote path's shape per batch
   bool dbg_index = false;     // TFP_DEBUG_INDEX: log each index update's phases (host ms)
   int32_t fail_compact = 0;   // TFP_TEST_FAIL_COMPACT=n: the next n staging compactions fail (tests)
+  // TFP_TEST_FAIL_CELLS=k / TFP_TEST_FAIL_DELTA_CELLS=k: the k-th main / delta clip-set cache build
+  // fails in its preparation, as an allocation failure of the clip order would (tests)
+  int64_t fail_cells = 0, fail_delta_cells = 0;
+  int quiet = 0;  // > 0: failures are not recorded in err (quietly(): an optional cache's build)
   int64_t fail_query_len = -1;  // TFP_TEST_FAIL_QUERY_SAMPLES=n: a search with a query of n samples fails (tests)
   int32_t kb_win = 0;           // TFP_KEYBITS_WIN: LDS words per column window of launch_key_bits (tests; 0 = default)
   int64_t kb_direct = -1;       // TFP_KEYBITS_DIRECT: pieces below this many rows use global atomics (tests; -1 = default)
   DevBuf logfix_key, logfix_val, logfix_bits;  // device copy of the glibc log correction table (LogFix)
   LogFix logfix{nullptr, nullptr, 0};
-  // index delta (round 4, tfp_index.hpp): the live clips added since the last build, searched by the
-  // coefs = 1 vote paths beside the main index instead of merged into it per enrolment
-  static constexpr int32_t kDeltaMaxClips = 512;        // columns reserved for them
-  static constexpr int64_t kDeltaMaxRows = 1ll << 20;  // beyond either limit the next update merges
-  bool use_delta = true;          // TFP_INDEX_DELTA=0: every update merges (A/B, tests)
-  // The delta pads the main columns to a multiple of 1024 and reserves kDeltaMaxClips columns
-  // after them, which a small DB's vote passes would pay for on every search (300 clips -> 1,536
-  // columns); below this many main columns an update merges instead (cheap at that size).
-  // TFP_INDEX_DELTA=1 (tests) takes the delta at any size.
-  int64_t delta_min_cols = 4096;
-  bool force_merge = false;       // consolidate(): the next rebuild merges the delta
-  std::vector<int32_t> delta_clip;  // delta column delta_col0 + j -> clip id (uuid order)
-  std::vector<int32_t> delta_at;    // delta j's insertion point among the main columns' uuids
-  int32_t delta_col0 = 0;           // first delta column (a multiple of 1024)
-  int64_t delta_rows = 0;           // staged rows of the delta's clips
-  int64_t n_delta_updates = 0;
-  DevBuf d_delta, d_delta_at, kbox;
-  double kbox_tol = 0.0;
-  bool kbox_valid = false;
-  int32_t key_bits_cols = -1;       // the column count key_bits was laid out for (its row width)
+  IndexDelta delta;
   Coalescer coal;          // concurrent small host-sample searches share one batch (tfp_coalesce.hpp)
   bool coalesce = true;    // TFP_COALESCE=0: every call runs alone (A/B)
   hipEvent_t null_in = nullptr, null_out = nullptr;  // (NullStreamOrder)
@@ -311,8 +301,18 @@ int fail(tfp_engine* e, int code, const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
-  if (e) e->err.note(e, buf);
+  if (e && !e->quiet) e->err.note(e, buf);
   return code;
+}
+
+// f() with its failures left out of the last-error messages: the build of an optional cache, whose
+// failure the search recovers from (the caller holds the engine mutex).
+template <class F>
+int quietly(tfp_engine* e, F f) {
+  e->quiet++;
+  const int rc = f();
+  e->quiet--;
+  return rc;
 }
 
 #define HIPCHK(e, expr)                                                                          \
@@ -656,9 +656,9 @@ int stage_reserve(tfp_engine* e, int64_t extra) {
     HIPCHK(e, hipMemcpyAsync(nc.p, e->st_clip.p, sizeof(int32_t) * e->n_staged, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
   }
-  std::swap(e->st_m1.p, n1.p); std::swap(e->st_m1.bytes, n1.bytes);
-  std::swap(e->st_m2.p, n2.p); std::swap(e->st_m2.bytes, n2.bytes);
-  std::swap(e->st_clip.p, nc.p); std::swap(e->st_clip.bytes, nc.bytes);
+  e->st_m1.swap_with(n1);
+  e->st_m2.swap_with(n2);
+  e->st_clip.swap_with(nc);
   e->cap_staged = cap;
   return TFP_OK;
 }
@@ -730,9 +730,9 @@ int compact_staging(tfp_engine* e) {
     HIPCHK(e, hipGetLastError());
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  std::swap(e->st_m1.p, n1.p); std::swap(e->st_m1.bytes, n1.bytes);
-  std::swap(e->st_m2.p, n2.p); std::swap(e->st_m2.bytes, n2.bytes);
-  std::swap(e->st_clip.p, nc.p); std::swap(e->st_clip.bytes, nc.bytes);
+  e->st_m1.swap_with(n1);
+  e->st_m2.swap_with(n2);
+  e->st_clip.swap_with(nc);
   for (size_t i = 0; i < e->clips.size(); i++) {
     Clip& c = e->clips[i];
     if (c.alive) c.off = new_off[i];
@@ -884,14 +884,14 @@ int merge_index(tfp_engine* e, const std::vector<int32_t>& rank, const MergeBrea
   int64_t valid = 0;
   if (n > 0 && (rc = read_sorted_count(e, &valid))) return rc;
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  std::swap(e->m1s.p, e->m1s_b.p); std::swap(e->m1s.bytes, e->m1s_b.bytes);
-  std::swap(e->m2s.p, e->m2s_b.p); std::swap(e->m2s.bytes, e->m2s_b.bytes);
-  std::swap(e->cols.p, e->cols_b.p); std::swap(e->cols.bytes, e->cols_b.bytes);
+  e->m1s.swap_with(e->m1s_b);
+  e->m2s.swap_with(e->m2s_b);
+  e->cols.swap_with(e->cols_b);
   e->nrows = kept + valid;
   // The clip order (when built) through the same update: its old rows renumbered, the new rows
   // inserted (tfp_index.hpp). Best effort: on failure it is rebuilt when next needed.
-  if (e->o_valid) {
-    e->o_valid = false;
+  if (e->order.valid) {
+    e->order.valid = false;
     auto by_uuid = [&](int32_t a, int32_t c) { return e->clips[a].uuid < e->clips[c].uuid; };
     std::vector<int32_t> add;
     for (int32_t i = (int32_t)e->built_clips; i < (int32_t)e->clips.size(); i++)
@@ -905,20 +905,20 @@ int merge_index(tfp_engine* e, const std::vector<int32_t>& rank, const MergeBrea
                             : (int32_t)(std::lower_bound(e->col_clip.begin(), e->col_clip.end(), add[j], by_uuid) - e->col_clip.begin());
     }
     int64_t orows = 0;
-    const size_t on = (size_t)std::max<int64_t>(e->o_rows + valid, 1);
-    if ((!D || upload(e, e->o_newcol, nca.data(), sizeof(int32_t) * nca.size()) == TFP_OK) &&
-        e->o_key_b.reserve_grow(sizeof(unsigned long long) * on) == hipSuccess &&
-        e->o_m1_b.reserve_grow(sizeof(int32_t) * on) == hipSuccess &&
-        launch_order_merge(e->o_key.as<unsigned long long>(), e->o_m1.as<int32_t>(), e->o_rows, e->remap.as<int32_t>(), removed,
+    const size_t on = (size_t)std::max<int64_t>(e->order.rows + valid, 1);
+    if ((!D || upload(e, e->order.newcol, nca.data(), sizeof(int32_t) * nca.size()) == TFP_OK) &&
+        e->order.key_b.reserve_grow(sizeof(unsigned long long) * on) == hipSuccess &&
+        e->order.m1_b.reserve_grow(sizeof(int32_t) * on) == hipSuccess &&
+        launch_order_merge(e->order.key.as<unsigned long long>(), e->order.m1.as<int32_t>(), e->order.rows, e->remap.as<int32_t>(), removed,
                            brk, e->keys_b.as<int32_t>(), e->vals_a.as<int32_t>(), e->keys_a.as<int32_t>(), valid,
-                           e->o_newcol.as<int32_t>(), e->o_newcol.as<int32_t>() + D, D, &e->merge, &e->o_merge,
-                           e->o_key_b.as<unsigned long long>(), e->o_m1_b.as<int32_t>(), &orows, e->stream) == hipSuccess &&
+                           e->order.newcol.as<int32_t>(), e->order.newcol.as<int32_t>() + D, D, &e->merge, &e->order.merge,
+                           e->order.key_b.as<unsigned long long>(), e->order.m1_b.as<int32_t>(), &orows, e->stream) == hipSuccess &&
         hipStreamSynchronize(e->stream) == hipSuccess && orows == e->nrows) {  // (nca is read by then)
-      e->o_key.swap_with(e->o_key_b);
-      e->o_m1.swap_with(e->o_m1_b);
-      e->o_rows = orows;
-      e->o_valid = true;
-      e->n_order_merges++;
+      e->order.key.swap_with(e->order.key_b);
+      e->order.m1.swap_with(e->order.m1_b);
+      e->order.rows = orows;
+      e->order.valid = true;
+      e->order.n_merges++;
     } else {
       (void)hipGetLastError();
     }
@@ -930,21 +930,19 @@ int merge_index(tfp_engine* e, const std::vector<int32_t>& rank, const MergeBrea
   // effort: on any failure the bitsets are rebuilt when next needed.
   const int32_t W = key_bits_words(new_cols);
   const int32_t Cm = (int32_t)e->col_clip.size();
-  if (e->rng_valid && e->key_bits_valid && e->key_bits_cols >= Cm &&
-      e->key_bits.bytes >= sizeof(uint32_t) * (size_t)kKeyRange * key_bits_words(e->key_bits_cols)) {
+  KeyRanges& kr = e->tc.ranges.active();
+  if (e->tc.ranges.active_valid() && kr.bits_valid && kr.bits_cols >= Cm &&
+      kr.key_bits.bytes >= sizeof(uint32_t) * (size_t)kKeyRange * key_bits_words(kr.bits_cols)) {
     hipStream_t s = e->stream;
-    bool ok = launch_key_ranges_all(e->m1s.as<int32_t>(), e->nrows, e->rng_tol, e->rng_all.as<int64_t>(), s) == hipSuccess &&
+    bool ok = launch_key_ranges_all(e->m1s.as<int32_t>(), e->nrows, e->tc.ranges.active_tol(), kr.rng_all.as<int64_t>(), s) == hipSuccess &&
               e->key_bits_b.reserve(sizeof(uint32_t) * (size_t)kKeyRange * W) == hipSuccess &&
-              launch_key_bits_remap(e->key_bits.as<uint32_t>(), key_bits_words(e->key_bits_cols), Cm,
+              launch_key_bits_remap(kr.key_bits.as<uint32_t>(), key_bits_words(kr.bits_cols), Cm,
                                     brk.n >= 0 ? nullptr : e->remap.as<int32_t>(), brk, e->key_bits_b.as<uint32_t>(), W,
                                     s) == hipSuccess;
-    if (ok) {
-      std::swap(e->key_bits.p, e->key_bits_b.p);
-      std::swap(e->key_bits.bytes, e->key_bits_b.bytes);
-    }
+    if (ok) kr.key_bits.swap_with(e->key_bits_b);
     if (ok && valid > 0)
-      ok = launch_key_bits_add(e->rng_all.as<int64_t>(), e->m1s.as<int32_t>(), e->keys_b.as<int32_t>(), e->keys_a.as<int32_t>(),
-                               valid, W, e->key_bits.as<uint32_t>(), s) == hipSuccess;
+      ok = launch_key_bits_add(kr.rng_all.as<int64_t>(), e->m1s.as<int32_t>(), e->keys_b.as<int32_t>(), e->keys_a.as<int32_t>(),
+                               valid, W, kr.key_bits.as<uint32_t>(), s) == hipSuccess;
     if (!ok) (void)hipGetLastError();
     *carried = ok;
   }
@@ -1032,18 +1030,14 @@ int rebuild(tfp_engine* e) {
     e->n_merges++;
   } else {
     e->nrows = 0;
-    e->o_valid = false;  // (the clip order is rebuilt from the new index when next needed)
+    e->order.valid = false;  // (the clip order is rebuilt from the new index when next needed)
     if ((rc = full_index(e))) return rc;
     e->n_full_builds++;
   }
   e->ncols = (int32_t)live.size();
   e->col_clip = std::move(live);
-  e->delta_clip.clear();  // (every clip is in the main index now)
-  e->delta_at.clear();
-  e->delta_col0 = e->ncols;
-  e->delta_rows = 0;
+  e->delta.reset(e->ncols);  // (every clip is in the main index now)
   e->key_col = std::move(key_col);
-  e->key_col_delta.clear();
   e->ovr_main_stale = !ovr;  // (with an override: its keys for these columns are on the device now)
   e->key_identity = !ovr;
   e->built = true;
@@ -1051,12 +1045,16 @@ int rebuild(tfp_engine* e) {
   e->built_staged = e->n_staged;
   e->removed_built = false;
   e->dirty = false;
-  e->index_version++;  // (other tolerances' cached ranges and bitsets are for the previous index)
+  // the key-range and clip-set caches follow the index: every entry is for the previous versions
+  // now, but the active ranges and bitsets when merge_index carried them
+  e->index_version++;
   e->main_version++;
-  e->rng_valid = carried;  // the key-range and clip-set caches follow the index (merge_index may carry the ranges and bitsets)
-  e->key_bits_valid = carried && e->key_bits_valid;
-  if (e->key_bits_valid) e->key_bits_cols = e->ncols;
-  e->cell_fresh = false;
+  if (carried) {
+    e->tc.ranges.carry(e->index_version);
+    e->tc.ranges.active().bits_cols = e->ncols;
+  } else {
+    e->tc.ranges.invalidate_active();
+  }
   if (e->dbg_index)
     fprintf(stderr, "[tfp] index %s: %lld rows, %d clips; order %.3f keys %.3f total %.3f ms\n",
             incremental ? "merge" : "full build", (long long)e->nrows, e->ncols, t_order, t_keys, ms_since(t0));
@@ -1072,9 +1070,9 @@ int full_index(tfp_engine* e) {
     int rc = sort_staged_rows(e, 0, n);
     if (!rc) rc = read_sorted_count(e, &valid);
     if (rc) return rc;
-    std::swap(e->m1s.p, e->keys_b.p); std::swap(e->m1s.bytes, e->keys_b.bytes);
-    std::swap(e->m2s.p, e->vals_a.p); std::swap(e->m2s.bytes, e->vals_a.bytes);
-    std::swap(e->cols.p, e->keys_a.p); std::swap(e->cols.bytes, e->keys_a.bytes);
+    e->m1s.swap_with(e->keys_b);
+    e->m2s.swap_with(e->vals_a);
+    e->cols.swap_with(e->keys_a);
   } else {
     HIPCHK(e, e->m1s.reserve(4));
     HIPCHK(e, e->m2s.reserve(4));
@@ -1084,45 +1082,16 @@ int full_index(tfp_engine* e) {
   return TFP_OK;
 }
 
-// The active tolerance's ranges and bitsets exchanged with slot t's.
-void swap_active(tfp_engine* e, TolSlot& t) {
-  e->rng_all.swap_with(t.rng_all);
-  e->key_bits.swap_with(t.key_bits);
-  std::swap(e->rng_tol, t.tol);
-  std::swap(e->rng_valid, t.rng_valid);
-  std::swap(e->key_bits_valid, t.bits_valid);
-  std::swap(e->key_bits_cols, t.bits_cols);
-}
-
-// Row ranges of every key's box at tolerance tole, cached per index version and tolerance: the
-// active tolerance's, and up to kTolSlots others (a search at another tolerance moves the active
-// ones into the least recently used slot, and takes its tolerance's from a slot when it is there).
+// Row ranges of every key's box at tolerance tole, cached per index version and tolerance
+// (tc.ranges); a tolerance first seen gets the ranges only: its bitsets are built when a vote path
+// asks for them (ensure_key_bits).
 int ensure_ranges(tfp_engine* e, double tole, hipStream_t s) {
-  if (e->rng_valid && memcmp(&e->rng_tol, &tole, sizeof tole) == 0) return TFP_OK;
-  TolSlot* hit = nullptr;
-  TolSlot* victim = &e->tol_lru[0];
-  for (TolSlot& t : e->tol_lru) {
-    if (t.version != e->index_version) t.rng_valid = t.bits_valid = false;
-    if (t.rng_valid && memcmp(&t.tol, &tole, sizeof tole) == 0) hit = &t;
-    // the victim: a slot holding nothing valid, else the least recently used
-    if (t.rng_valid != victim->rng_valid ? !t.rng_valid : t.used < victim->used) victim = &t;
-  }
-  if (hit) {
-    swap_active(e, *hit);  // (the previous active ones, valid or not, into the slot)
-    hit->version = e->index_version;
-    hit->used = ++e->tol_clock;
-    return TFP_OK;
-  }
-  if (e->rng_valid) {
-    swap_active(e, *victim);  // the active ones kept; their buffers' old contents reused below
-    victim->version = e->index_version;
-    victim->used = ++e->tol_clock;
-  }
-  HIPCHK(e, e->rng_all.reserve(sizeof(int64_t) * 2 * kKeyRange));
-  HIPCHK(e, launch_key_ranges_all(e->m1s.as<int32_t>(), e->nrows, tole, e->rng_all.as<int64_t>(), s));
-  e->rng_tol = tole;
-  e->rng_valid = true;
-  e->key_bits_valid = false;
+  if (e->tc.ranges.find(tole, e->index_version)) return TFP_OK;
+  KeyRanges* kr = e->tc.ranges.claim(e->index_version);
+  kr->bits_valid = false;
+  HIPCHK(e, kr->rng_all.reserve(sizeof(int64_t) * 2 * kKeyRange));
+  HIPCHK(e, launch_key_ranges_all(e->m1s.as<int32_t>(), e->nrows, tole, kr->rng_all.as<int64_t>(), s));
+  e->tc.ranges.commit(tole, e->index_version);
   return TFP_OK;
 }
 
@@ -1130,34 +1099,44 @@ int ensure_ranges(tfp_engine* e, double tole, hipStream_t s) {
 int delta_bits(tfp_engine* e, hipStream_t s);
 
 int ensure_key_bits(tfp_engine* e, hipStream_t s) {
-  if (e->key_bits_valid) return TFP_OK;
-  HIPCHK(e, e->key_bits.reserve(sizeof(uint32_t) * (size_t)kKeyRange * key_bits_words(e->ncols)));
+  KeyRanges& kr = e->tc.ranges.active();
+  if (kr.bits_valid) return TFP_OK;
+  HIPCHK(e, kr.key_bits.reserve(sizeof(uint32_t) * (size_t)kKeyRange * key_bits_words(e->ncols)));
   // the boxes' rows in all: a row is in the boxes of the keys within tol of its m1
-  const double tl = e->rng_tol;
+  const double tl = e->tc.ranges.active_tol();
   const int64_t per_row = std::isfinite(tl) && tl >= 0 && tl < kKeyRange ? 2 * (int64_t)ceil(tl) + 2 : kKeyRange;
-  HIPCHK(e, launch_key_bits(e->rng_all.as<int64_t>(), e->cols.as<int32_t>(), e->ncols, e->nrows * std::min<int64_t>(per_row, kKeyRange),
-                            e->kb_win, e->kb_direct, e->key_bits.as<uint32_t>(), s));
+  HIPCHK(e, launch_key_bits(kr.rng_all.as<int64_t>(), e->cols.as<int32_t>(), e->ncols, e->nrows * std::min<int64_t>(per_row, kKeyRange),
+                            e->kb_win, e->kb_direct, kr.key_bits.as<uint32_t>(), s));
   int rc = delta_bits(e, s);  // (the delta's columns, from its staged rows)
   if (rc) return rc;
-  e->key_bits_valid = true;
-  e->key_bits_cols = e->ncols;
+  kr.bits_valid = true;
+  kr.bits_cols = e->ncols;
   return TFP_OK;
 }
 
 // ---- index delta ---------------------------------------------------------------------------
 
-// The delta's key bits at the bitsets' tolerance (rng_tol), into columns that hold no bit.
+// The keys' "%f" boxes at tolerance tole (launch_key_boxes), for the caches built from a clip order
+// and the delta's key bits.
+int ensure_kbox(tfp_engine* e, double tole, hipStream_t s) {
+  if (e->tc.kbox.holds(tole, 0)) return TFP_OK;
+  DevBuf* kbox = e->tc.kbox.begin();
+  HIPCHK(e, kbox->reserve(sizeof(int64_t) * 2 * kKeyRange));
+  HIPCHK(e, launch_key_boxes(tole, kbox->as<int64_t>(), s));
+  e->tc.kbox.commit(tole, 0);
+  return TFP_OK;
+}
+
+// The delta's key bits at the active bitsets' tolerance, into columns that hold no bit.
 int delta_bits(tfp_engine* e, hipStream_t s) {
-  if (e->delta_clip.empty()) return TFP_OK;
-  if (!e->kbox_valid || memcmp(&e->kbox_tol, &e->rng_tol, sizeof e->rng_tol) != 0) {
-    HIPCHK(e, e->kbox.reserve(sizeof(int64_t) * 2 * kKeyRange));
-    HIPCHK(e, launch_key_boxes(e->rng_tol, e->kbox.as<int64_t>(), s));
-    e->kbox_tol = e->rng_tol;
-    e->kbox_valid = true;
-  }
-  const int32_t kspan = (int32_t)ceil(e->rng_tol) + 1;  // (delta_tol_ok: tol <= 8)
-  HIPCHK(e, launch_delta_bits(e->d_delta.as<DeltaClip>(), (int32_t)e->delta_clip.size(), e->st_m1.as<int32_t>(),
-                              e->kbox.as<int64_t>(), kspan, key_bits_words(e->ncols), e->key_bits.as<uint32_t>(), s));
+  if (e->delta.clip.empty()) return TFP_OK;
+  const double tole = e->tc.ranges.active_tol();
+  int rc = ensure_kbox(e, tole, s);
+  if (rc) return rc;
+  const int32_t kspan = (int32_t)ceil(tole) + 1;  // (delta_tol_ok: tol <= 8)
+  HIPCHK(e, launch_delta_bits(e->delta.d_clips.as<DeltaClip>(), (int32_t)e->delta.clip.size(), e->st_m1.as<int32_t>(),
+                              e->tc.kbox.p.as<int64_t>(), kspan, key_bits_words(e->ncols),
+                              e->tc.ranges.active().key_bits.as<uint32_t>(), s));
   return TFP_OK;
 }
 
@@ -1166,8 +1145,8 @@ int delta_bits(tfp_engine* e, hipStream_t s) {
 bool delta_tol_ok(double tol) { return std::isfinite(tol) && tol >= 0.0 && tol <= 8.0; }
 
 bool delta_eligible(const tfp_engine* e) {
-  if (!e->use_delta || !e->built || e->force_full || e->force_merge || e->removed_built || e->n_staged >= INT32_MAX ||
-      (int64_t)e->col_clip.size() < e->delta_min_cols)
+  if (!e->delta.use || !e->built || e->force_full || e->delta.force_merge || e->removed_built || e->n_staged >= INT32_MAX ||
+      (int64_t)e->col_clip.size() < e->delta.min_cols)
     return false;
   int64_t n = 0, rows = 0;
   for (size_t i = e->built_clips; i < e->clips.size(); i++)
@@ -1175,7 +1154,7 @@ bool delta_eligible(const tfp_engine* e) {
       n++;
       rows += e->clips[i].nrows;
     }
-  return n <= tfp_engine::kDeltaMaxClips && rows <= tfp_engine::kDeltaMaxRows;
+  return n <= IndexDelta::kMaxClips && rows <= IndexDelta::kMaxRows;
 }
 
 // An update that only adds (or removes clips added since the last build): the new clips become the
@@ -1200,7 +1179,7 @@ int delta_update(tfp_engine* e) {
   for (int32_t j = 0; j < D; j++)
     at[j] = (int32_t)(std::lower_bound(e->col_clip.begin(), e->col_clip.end(), add[j], by_uuid) - e->col_clip.begin());
   const int32_t col0 = D ? (Cm + 1023) / 1024 * 1024 : Cm;
-  const int32_t ncols = D ? col0 + tfp_engine::kDeltaMaxClips : Cm;
+  const int32_t ncols = D ? col0 + IndexDelta::kMaxClips : Cm;
   // tie keys (and the key -> column maps with an override)
   const bool ovr = !e->tiebreak_override.empty();
   const void* tk_before = e->tiekey.p;
@@ -1247,9 +1226,9 @@ int delta_update(tfp_engine* e) {
     e->ovr_main_stale = false;
     e->tiekey_ident = -1;
   } else {
-    HIPCHK(e, e->d_delta_at.reserve(sizeof(int32_t) * std::max(D, 1)));
-    if (D) HIPCHK(e, hipMemcpyAsync(e->d_delta_at.p, at.data(), sizeof(int32_t) * D, hipMemcpyHostToDevice, s));
-    HIPCHK(e, launch_delta_tiekey(e->d_delta_at.as<int32_t>(), D, Cm, col0, ncols, e->tiekey.as<int32_t>(), s));
+    HIPCHK(e, e->delta.d_at.reserve(sizeof(int32_t) * std::max(D, 1)));
+    if (D) HIPCHK(e, hipMemcpyAsync(e->delta.d_at.p, at.data(), sizeof(int32_t) * D, hipMemcpyHostToDevice, s));
+    HIPCHK(e, launch_delta_tiekey(e->delta.d_at.as<int32_t>(), D, Cm, col0, ncols, e->tiekey.as<int32_t>(), s));
     e->tiekey_ident = D ? -1 : Cm;
   }
   // the delta's clips for the bits kernel
@@ -1258,45 +1237,47 @@ int delta_update(tfp_engine* e) {
     const Clip& c = e->clips[add[j]];
     dc[j] = DeltaClip{c.off, (int32_t)c.nrows, col0 + j};
   }
-  HIPCHK(e, e->d_delta.reserve(sizeof(DeltaClip) * std::max(D, 1)));
-  if (D) HIPCHK(e, hipMemcpyAsync(e->d_delta.p, dc.data(), sizeof(DeltaClip) * D, hipMemcpyHostToDevice, s));
-  e->delta_clip = std::move(add);
-  e->delta_at.assign(at.begin(), at.begin() + D);
-  e->delta_col0 = col0;
-  e->delta_rows = rows;
+  HIPCHK(e, e->delta.d_clips.reserve(sizeof(DeltaClip) * std::max(D, 1)));
+  if (D) HIPCHK(e, hipMemcpyAsync(e->delta.d_clips.p, dc.data(), sizeof(DeltaClip) * D, hipMemcpyHostToDevice, s));
+  e->delta.clip = std::move(add);
+  e->delta.at.assign(at.begin(), at.begin() + D);
+  e->delta.col0 = col0;
+  e->delta.rows = rows;
   e->ncols = ncols;
-  e->key_col_delta = std::move(key_col_delta);
+  e->delta.key_col = std::move(key_col_delta);
   e->key_identity = !ovr;
   // key bits: the first delta after a build widens the rows (the delta's columns start at a
   // multiple of 1024): the main columns' words move to the wider rows in one 2-D device copy
   // (~13 MB at 100k clips) instead of a rebuild from the index rows (46 ms at 100k clips)
-  if (e->key_bits_valid && D > 0 && e->key_bits_cols != ncols && e->key_bits_cols <= col0) {
-    const int32_t Wo = key_bits_words(e->key_bits_cols), Wn = key_bits_words(ncols);
+  KeyRanges& kr = e->tc.ranges.active();
+  const bool bits = e->tc.ranges.active_valid() && kr.bits_valid;
+  if (bits && D > 0 && kr.bits_cols != ncols && kr.bits_cols <= col0) {
+    const int32_t Wo = key_bits_words(kr.bits_cols), Wn = key_bits_words(ncols);
     if (Wn > Wo) {
       const size_t nb = sizeof(uint32_t) * (size_t)kKeyRange * Wn;
       HIPCHK(e, e->key_bits_b.reserve(nb));
       HIPCHK(e, hipMemsetAsync(e->key_bits_b.p, 0, nb, s));
-      HIPCHK(e, hipMemcpy2DAsync(e->key_bits_b.p, sizeof(uint32_t) * Wn, e->key_bits.p, sizeof(uint32_t) * Wo,
+      HIPCHK(e, hipMemcpy2DAsync(e->key_bits_b.p, sizeof(uint32_t) * Wn, kr.key_bits.p, sizeof(uint32_t) * Wo,
                                  sizeof(uint32_t) * Wo, kKeyRange, hipMemcpyDeviceToDevice, s));
-      std::swap(e->key_bits.p, e->key_bits_b.p);
-      std::swap(e->key_bits.bytes, e->key_bits_b.bytes);
+      kr.key_bits.swap_with(e->key_bits_b);
     }
-    e->key_bits_cols = ncols;
+    kr.bits_cols = ncols;
   }
   // the delta columns cleared and set again when the layout stands, else rebuilt later
-  if (e->key_bits_valid && e->key_bits_cols == ncols && D > 0) {
+  if (bits && kr.bits_cols == ncols && D > 0) {
     const int32_t W = key_bits_words(ncols);
-    HIPCHK(e, hipMemset2DAsync(e->key_bits.as<uint32_t>() + col0 / 32, sizeof(uint32_t) * W, 0,
-                               sizeof(uint32_t) * (tfp_engine::kDeltaMaxClips / 32), kKeyRange, s));
+    HIPCHK(e, hipMemset2DAsync(kr.key_bits.as<uint32_t>() + col0 / 32, sizeof(uint32_t) * W, 0,
+                               sizeof(uint32_t) * (IndexDelta::kMaxClips / 32), kKeyRange, s));
     int rc = delta_bits(e, s);
     if (rc) return rc;
   } else {
-    e->key_bits_valid = false;
+    kr.bits_valid = false;
   }
   HIPCHK(e, hipStreamSynchronize(s));  // (dc and at are released on return)
   e->dirty = false;
-  e->index_version++;  // (other tolerances' cached ranges and bitsets are for the previous index)
-  e->n_delta_updates++;
+  e->index_version++;  // (other tolerances' cached ranges and bitsets are for the previous index;
+  e->tc.ranges.carry(e->index_version);  // the main index, so the active ones, stand)
+  e->delta.n_updates++;
   if (e->dbg_index)
     fprintf(stderr, "[tfp] index delta: %d clips (%lld rows) beside %d main columns; %.3f ms\n", D, (long long)rows, Cm,
             std::chrono::duration<double, std::milli>(clk::now() - t0).count());
@@ -1306,101 +1287,78 @@ int delta_update(tfp_engine* e) {
 // The delta merged into the main index now (coefs = 2, a fallback to the row scan, a tolerance the
 // delta's bits do not cover).
 int consolidate(tfp_engine* e) {
-  if (e->delta_clip.empty() && !e->dirty) return TFP_OK;
-  e->force_merge = true;
+  if (e->delta.clip.empty() && !e->dirty) return TFP_OK;
+  e->delta.force_merge = true;
   e->dirty = true;
   const int rc = rebuild(e);
-  e->force_merge = false;
+  e->delta.force_merge = false;
   return rc;
 }
 
 // The clip order of the current index (tfp_kernels.hpp), built when first needed: the index rows'
 // keys (nearest-integer key, column, m2) radix-sorted once; merge_index carries it afterwards.
 int ensure_order(tfp_engine* e, hipStream_t s) {
-  if (e->o_valid) return TFP_OK;
+  if (e->order.valid) return TFP_OK;
   const int64_t R = e->nrows;
   if (R >= INT32_MAX) return fail(e, TFP_E_CAPACITY, "clip order: %lld rows", (long long)R);
   const size_t n = (size_t)std::max<int64_t>(R, 1);
-  HIPCHK(e, e->o_key.reserve_grow(sizeof(unsigned long long) * n));
-  HIPCHK(e, e->o_m1.reserve_grow(sizeof(int32_t) * n));
-  HIPCHK(e, e->o_key_b.reserve_grow(sizeof(unsigned long long) * n));
-  HIPCHK(e, e->o_m1_b.reserve_grow(sizeof(int32_t) * n));
+  HIPCHK(e, e->order.key.reserve_grow(sizeof(unsigned long long) * n));
+  HIPCHK(e, e->order.m1.reserve_grow(sizeof(int32_t) * n));
+  HIPCHK(e, e->order.key_b.reserve_grow(sizeof(unsigned long long) * n));
+  HIPCHK(e, e->order.m1_b.reserve_grow(sizeof(int32_t) * n));
   HIPCHK(e, launch_order_fill(e->m1s.as<int32_t>(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(), R,
-                              e->o_key_b.as<unsigned long long>(), e->o_m1_b.as<int32_t>(), s));
-  HIPCHK(e, order_sort(e->o_key_b.as<unsigned long long>(), e->o_key.as<unsigned long long>(), e->o_m1_b.as<int32_t>(),
-                       e->o_m1.as<int32_t>(), R, &e->o_sort_tmp, s));
-  e->o_rows = R;
-  e->o_valid = true;
-  e->n_order_builds++;
+                              e->order.key_b.as<unsigned long long>(), e->order.m1_b.as<int32_t>(), s));
+  HIPCHK(e, order_sort(e->order.key_b.as<unsigned long long>(), e->order.key.as<unsigned long long>(), e->order.m1_b.as<int32_t>(),
+                       e->order.m1.as<int32_t>(), R, &e->order.sort_tmp, s));
+  e->order.rows = R;
+  e->order.valid = true;
+  e->order.n_builds++;
   return TFP_OK;
 }
 
-// The keys' "%f" boxes at tolerance tole (launch_key_boxes), for the caches built from a clip order.
-int ensure_kbox(tfp_engine* e, double tole, hipStream_t s) {
-  if (e->kbox_valid && memcmp(&e->kbox_tol, &tole, sizeof tole) == 0) return TFP_OK;
-  HIPCHK(e, e->kbox.reserve(sizeof(int64_t) * 2 * kKeyRange));
-  HIPCHK(e, launch_key_boxes(tole, e->kbox.as<int64_t>(), s));
-  e->kbox_tol = tole;
-  e->kbox_valid = true;
-  return TFP_OK;
-}
-
-// The general path's clip-set cache at tolerance tole (after ensure_ranges at tole): the active one,
-// or one of kCellSlots others (least recently used out), per index version. Built from the clip
-// order for tolerances up to kOrderMaxTol (no sort), else from the boxes' rows.
-int ensure_cells(tfp_engine* e, double tole, hipStream_t s) {
-  if (e->cell_fresh && e->cell_version == e->main_version && memcmp(&e->cell_tol, &tole, sizeof tole) == 0) return TFP_OK;
-  CellSlot* hit = nullptr;
-  CellSlot* victim = &e->cell_lru[0];
-  for (CellSlot& t : e->cell_lru) {
-    if (t.version != e->main_version) t.has = false;
-    if (t.has && memcmp(&t.tol, &tole, sizeof tole) == 0) hit = &t;
-    if (t.has != victim->has ? !t.has : t.used < victim->used) victim = &t;
-  }
-  const bool active = e->cell_fresh && e->cell_version == e->main_version;
-  CellSlot* into = hit ? hit : victim;
-  // the active cache (when current) goes into the slot the wanted one comes from (or the victim's,
-  // whose buffers the build below then reuses)
-  e->cells.swap(into->c);
-  std::swap(e->cell_tol, into->tol);
-  into->has = active;
-  into->version = e->main_version;
-  into->used = ++e->tol_clock;
-  if (hit) {
-    e->cell_tol = tole;
-    e->cell_fresh = true;
-    e->cell_version = e->main_version;
-    e->n_cell_hits++;
-    return TFP_OK;
-  }
-  e->n_cell_builds++;
-  // The cache is optional: if building it fails (an allocation or a library call), the batch takes
-  // the row scan, which needs none of it (tfp_scan.hip).
-  hipError_t st = hipSuccess;
+// One build of the main clip-set cache at tolerance tole into c (after ensure_ranges at tole): from
+// the clip order for tolerances up to kOrderMaxTol (no sort), else from the boxes' rows.
+int build_cells(tfp_engine* e, CellCache* c, double tole, hipStream_t s) {
+  if (e->fail_cells > 0 && --e->fail_cells == 0)  // TFP_TEST_FAIL_CELLS
+    return fail(e, TFP_E_NOMEM, "clip order: injected allocation failure");
   if (tole >= 0.0 && tole <= kOrderMaxTol && e->nrows > 0 && e->nrows < INT32_MAX) {
     int rc = ensure_order(e, s);
-    if (rc) return rc;
-    if ((rc = ensure_kbox(e, tole, s))) return rc;
-    st = e->cells.build_from_order(e->o_key.as<unsigned long long>(), e->o_m1.as<int32_t>(), e->o_rows, e->kbox.as<int64_t>(),
-                                   (int32_t)e->col_clip.size(), tole, s);
-    if (st == hipSuccess && e->cells.valid) e->n_cell_from_order++;
+    if (rc || (rc = ensure_kbox(e, tole, s))) return rc;
+    HIPCHK(e, c->build_from_order(e->order.key.as<unsigned long long>(), e->order.m1.as<int32_t>(), e->order.rows,
+                                  e->tc.kbox.p.as<int64_t>(), (int32_t)e->col_clip.size(), tole, s));
+    if (c->valid) e->tc.n_from_order++;
   } else {
+    const DevBuf& rng_all = e->tc.ranges.active().rng_all;
     std::vector<int64_t> rng(2 * kKeyRange), off(kKeyRange + 1, 0);
-    HIPCHK(e, hipMemcpyAsync(rng.data(), e->rng_all.p, sizeof(int64_t) * rng.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(rng.data(), rng_all.p, sizeof(int64_t) * rng.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     for (int k = 0; k < kKeyRange; k++) off[k + 1] = off[k] + std::max<int64_t>(0, rng[2 * k + 1] - rng[2 * k]);
-    st = e->cells.build(e->rng_all.as<int64_t>(), off.data(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(),
-                        (int32_t)e->col_clip.size(), e->nrows, tole, s);
+    HIPCHK(e, c->build(rng_all.as<int64_t>(), off.data(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(),
+                       (int32_t)e->col_clip.size(), e->nrows, tole, s));
   }
-  if (st != hipSuccess) {
-    (void)hipGetLastError();
-    if (e->dbg_vote) fprintf(stderr, "[tfp] clip-set cache not built (%s): row scan\n", hipGetErrorString(st));
-    e->cells.invalidate();
-    HIPCHK(e, hipStreamSynchronize(s));
+  return TFP_OK;
+}
+
+// The general path's clip-set cache at tolerance tole, per main index version and tolerance
+// (tc.cells): afterwards tc.cells.active() is the cache to search with. It is optional: if preparing
+// or building it fails (an allocation, a library call), nothing is committed or recorded, the active
+// cache is left not valid and the batch takes the row scan (tfp_scan.hip); the next search tries again.
+int ensure_cells(tfp_engine* e, double tole, hipStream_t s) {
+  const CellCache* was = &e->tc.cells.active();
+  if (const CellCache* c = e->tc.cells.find(tole, e->main_version)) {
+    e->tc.n_hits += c != was;  // (taken from beside the active one)
+    return TFP_OK;
   }
-  e->cell_tol = tole;
-  e->cell_fresh = true;
-  e->cell_version = e->main_version;
+  CellCache* c = e->tc.cells.claim(e->main_version);
+  e->tc.n_builds++;
+  if (quietly(e, [&] { return build_cells(e, c, tole, s); }) == TFP_OK) {
+    e->tc.cells.commit(tole, e->main_version);
+    return TFP_OK;
+  }
+  (void)hipGetLastError();
+  if (e->dbg_vote) fprintf(stderr, "[tfp] clip-set cache not built: row scan\n");
+  c->invalidate();
+  HIPCHK(e, hipStreamSynchronize(s));
   return TFP_OK;
 }
 
@@ -1408,211 +1366,190 @@ int ensure_cells(tfp_engine* e, double tole, hipStream_t s) {
 // clip order (sorted once per delta version, for any tolerance), then the main cache's filter.
 // Valid (or known empty: no delta row in a box) at the current index version.
 int ensure_delta_cells(tfp_engine* e, double tole, hipStream_t s) {
-  if (e->dcell_fresh && e->dcell_version == e->index_version && memcmp(&e->dcell_tol, &tole, sizeof tole) == 0) return TFP_OK;
-  e->dcell_fresh = false;
-  e->dcells.invalidate();
-  const int32_t D = (int32_t)e->delta_clip.size();
-  const int64_t n = e->delta_rows;
+  if (e->tc.dcells.holds(tole, e->index_version)) return TFP_OK;
+  CellCache* dc = e->tc.dcells.begin();
+  dc->invalidate();
+  const int32_t D = (int32_t)e->delta.clip.size();
+  const int64_t n = e->delta.rows;
   if (D > 0 && n > 0) {
-    if (e->dl_version != e->index_version) {
-      HIPCHK(e, e->dl_key.reserve_grow(sizeof(unsigned long long) * n));
-      HIPCHK(e, e->dl_m1.reserve_grow(sizeof(int32_t) * n));
-      HIPCHK(e, e->dl_key_b.reserve_grow(sizeof(unsigned long long) * n));
-      HIPCHK(e, e->dl_m1_b.reserve_grow(sizeof(int32_t) * n));
-      HIPCHK(e, launch_delta_order_fill(e->d_delta.as<DeltaClip>(), D, e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(),
-                                        e->dl_key_b.as<unsigned long long>(), e->dl_m1_b.as<int32_t>(), s));
-      HIPCHK(e, order_sort(e->dl_key_b.as<unsigned long long>(), e->dl_key.as<unsigned long long>(), e->dl_m1_b.as<int32_t>(),
-                           e->dl_m1.as<int32_t>(), n, &e->dl_sort_tmp, s));
-      e->dl_version = e->index_version;
+    if (e->fail_delta_cells > 0 && --e->fail_delta_cells == 0)  // TFP_TEST_FAIL_DELTA_CELLS
+      return fail(e, TFP_E_NOMEM, "delta clip order: injected allocation failure");
+    if (!e->tc.dorder.holds(0.0, e->index_version)) {
+      DeltaOrder* o = e->tc.dorder.begin();
+      HIPCHK(e, o->key.reserve_grow(sizeof(unsigned long long) * n));
+      HIPCHK(e, o->m1.reserve_grow(sizeof(int32_t) * n));
+      HIPCHK(e, o->key_b.reserve_grow(sizeof(unsigned long long) * n));
+      HIPCHK(e, o->m1_b.reserve_grow(sizeof(int32_t) * n));
+      HIPCHK(e, launch_delta_order_fill(e->delta.d_clips.as<DeltaClip>(), D, e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(),
+                                        o->key_b.as<unsigned long long>(), o->m1_b.as<int32_t>(), s));
+      HIPCHK(e, order_sort(o->key_b.as<unsigned long long>(), o->key.as<unsigned long long>(), o->m1_b.as<int32_t>(),
+                           o->m1.as<int32_t>(), n, &o->sort_tmp, s));
+      e->tc.dorder.commit(0.0, e->index_version);
     }
     int rc = ensure_kbox(e, tole, s);
     if (rc) return rc;
-    HIPCHK(e, e->dcells.build_from_order(e->dl_key.as<unsigned long long>(), e->dl_m1.as<int32_t>(), n, e->kbox.as<int64_t>(),
-                                         D, tole, s));
-    e->n_delta_cell_builds++;
+    const DeltaOrder& o = e->tc.dorder.p;
+    HIPCHK(e, dc->build_from_order(o.key.as<unsigned long long>(), o.m1.as<int32_t>(), n, e->tc.kbox.p.as<int64_t>(), D, tole,
+                                   s));
+    e->tc.n_delta_builds++;
   }
-  e->dcell_tol = tole;
-  e->dcell_version = e->index_version;
-  e->dcell_fresh = true;
+  e->tc.dcells.commit(tole, e->index_version);
   return TFP_OK;
 }
 
 // Can the sweep serve a search at tolerance tole with the index delta beside the main index?
 bool delta_wide_ok(const tfp_engine* e, double tole) {
-  return e->delta_wide && tole >= 0.0 && tole <= kOrderMaxTol && tole >= e->wide_min_tol;
+  return e->delta.wide && tole >= 0.0 && tole <= kOrderMaxTol && tole >= e->wide_min_tol;
 }
 
 // ---- search core: frames' q values already on device (e->q, 2 doubles per frame) -----------
 
-int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_q, const tfp_search_params* P,
-                std::vector<unsigned long long>& keys, unsigned long long* d_keys_out, hipStream_t s) {
-  int rc = rebuild(e);  // synchronous on e->stream
-  if (rc) return rc;
-  keys.assign(nq, 0ull);
-  const int64_t nf = h_qoff[nq] - h_qoff[0];
-  SearchConsts sc;
-  memset(&sc, 0, sizeof sc);
-  sc.coefs = P->coefs;
-  sc.tole = P->tolerance < 0 ? TFP_DEFAULT_TOLERANCE : P->tolerance;  // fp_handler.c:252-256
-  sc.has_low = P->freq_ignore_low > 0;
-  sc.has_high = P->freq_ignore_high > 0;
-  if (sc.has_low) sc.thr_low = 10 * log10((double)P->freq_ignore_low);
-  if (sc.has_high) sc.thr_high = 10 * log10((double)P->freq_ignore_high);
-  // the index delta serves the coefs = 1 vote paths at the tolerances its bits cover, and the sweep
-  // (its own clip-set cache beside the main one) at tolerances up to kOrderMaxTol; any other search
-  // reads the sorted rows, so the delta is merged into them first
-  if (!e->delta_clip.empty() && ((sc.coefs == 1 && !delta_tol_ok(sc.tole)) || (sc.coefs != 1 && !delta_wide_ok(e, sc.tole))) &&
-      (rc = consolidate(e)))
-    return rc;
-  const bool has_delta = !e->delta_clip.empty();
-  const int64_t R_all = e->nrows + e->delta_rows;  // rows that may match (main index + delta)
+// What a search form returns besides TFP_OK (the results are out) and an error (< 0):
+constexpr int kNext = 1;         // not for this batch, or it could not finish it: the next form
+constexpr int kNeedsSorted = 2;  // it needs the sorted rows to hold every clip: merge the index delta, start over
 
-  std::vector<int64_t> qo(h_qoff, h_qoff + nq + 1);
-  for (auto& v : qo) v -= h_qoff[0];
-  if (!d_keys_out && sc.coefs == 1 && nq >= 1 && nq <= kSmallQ && e->ncols > 0 && R_all > 0) {
-    // small batch (batch-1 latency): one vote launch over the cached key bitsets, results into
-    // host-mapped memory
-    bool fits = true;
-    for (int32_t i = 0; i < nq; i++) fits &= qo[i + 1] - qo[i] <= 2048;  // counts bounded like the fp16 path
-    if (fits) {
-      SmallQueries sq;
-      memset(&sq, 0, sizeof sq);
-      sq.nq = nq;
-      for (int32_t i = 0; i <= nq; i++) sq.qoff[i] = qo[i];
-      const int32_t C = e->ncols;
-      HIPCHK(e, e->small_res.reserve(small_result_bytes(C), hipHostMallocMapped | hipHostMallocCoherent));
-      if (e->small_res.p != e->small_res_host) {
-        HIPCHK(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&e->small_res_dev), e->small_res.p, 0));
-        e->small_res_host = e->small_res.p;
-      }
-      if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s))) return rc;
-      HIPCHK(e, launch_search_small(d_q, sq, sc, e->key_bits.as<uint32_t>(), C, e->tiekey.as<int32_t>(), e->small_res_dev,
-                                    s));
-      HIPCHK(e, hipStreamSynchronize(s));
-      // the vote ran after the fingerprint kernel, which read the staged upload: it is free again
-      e->stage_pending = false;
-      // the vote's blocks wrote their per-query maxima into host memory: the max over the blocks
-      SmallResult* h = e->small_res.as<SmallResult>();
-      if (!h->bad) {
-        if (h->ku > 0) {
-          const unsigned long long* part = small_result_parts(h);
-          const int32_t nb = small_vote_blocks(C);
-          for (int32_t i = 0; i < nq; i++) {
-            unsigned long long k = 0ull;
-            for (int32_t b = 0; b < nb; b++) k = std::max(k, part[(size_t)b * kSmallQ + i]);
-            keys[i] = k;
-          }
-        }
-        return TFP_OK;
-      }
-      // a key outside the vote range: redo the batch on the general path below (the index's rows:
-      // the delta merged first)
-      if (has_delta) {
-        if ((rc = consolidate(e))) return rc;
-        return search_core(e, h_qoff, nq, d_q, P, keys, d_keys_out, s);
-      }
-    }
-  }
-  // Query offsets are the same on every call of one plan or stream: copy them only when they
-  // change, from pinned memory so the copy is asynchronous (a pageable copy would make the host
-  // wait for the queries' fingerprint kernels before it could launch the search).
-  if (qo != e->qoff_host || s != e->qoff_stream) {
-    const size_t bytes = sizeof(int64_t) * qo.size();
-    if (e->qoff_pending) HIPCHK(e, hipEventSynchronize(e->qoff_ev));  // previous copy done reading
-    HIPCHK(e, e->qoff.reserve(bytes));
-    HIPCHK(e, e->qoff_pin.reserve(bytes));
-    memcpy(e->qoff_pin.p, qo.data(), bytes);
-    HIPCHK(e, hipMemcpyAsync(e->qoff.p, e->qoff_pin.p, bytes, hipMemcpyHostToDevice, s));
-    if (!e->qoff_ev) HIPCHK(e, hipEventCreateWithFlags(&e->qoff_ev, hipEventDisableTiming));
-    HIPCHK(e, hipEventRecord(e->qoff_ev, s));
-    e->qoff_pending = true;
-    e->qoff_host = qo;
-    e->qoff_stream = s;
-  }
-  HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (nf + 1)));
-  const int32_t Qp = ((nq + 127) / 128) * 128;
+// One batch on its way through the forms (search_core): the call's arguments, then the set-up the
+// forms share.
+struct Batch {
+  int32_t nq;
+  const double* d_q;
+  std::vector<unsigned long long>& keys;
+  unsigned long long* d_keys_out;
+  hipStream_t s;
+  SearchConsts sc;
+  std::vector<int64_t> qo;  // query offsets from 0
+  int64_t nf = 0, max_frames = 0;
+  bool has_delta = false;
+  int32_t C = 0;             // columns (with a delta: its reserved ones too)
+  int64_t R = 0, R_all = 0;  // rows of the main index; with the delta's
   // one buffer: the vote path's key mask (32 words), max count (1), pad (1), VoteMeta (4), then
   // best[Qp] (u64); zeroed by prep_boxes. VoteMeta directly before best[]: one copy brings both back.
-  constexpr int kMaskWords = kKeyRange / 32, kMetaWord = kMaskWords + 2, kMiscWords = kMetaWord + 4;
+  static constexpr int kMaskWords = kKeyRange / 32, kMetaWord = kMaskWords + 2, kMiscWords = kMetaWord + 4;
   static_assert(sizeof(VoteMeta) == 16 && kMiscWords % 2 == 0, "meta + 8-byte aligned best[]");
-  const int32_t nzero = kMiscWords + 2 * Qp;
-  HIPCHK(e, e->best.reserve(sizeof(uint32_t) * nzero));
-  uint32_t* d_mask = e->best.as<uint32_t>();
-  int32_t* d_max = reinterpret_cast<int32_t*>(d_mask + kMaskWords);
-  unsigned long long* d_best = reinterpret_cast<unsigned long long*>(d_mask + kMiscWords);
-  const int32_t C = e->ncols;
-  const int64_t R = e->nrows;
-  int64_t max_frames = 0;
-  for (int32_t i = 0; i < nq; i++) max_frames = std::max<int64_t>(max_frames, qo[i + 1] - qo[i]);
-  const bool vote = sc.coefs == 1 && C > 0 && R_all > 0 && max_frames < 16384;  // packed scores exact below 16384 frames
-  if (!vote && has_delta && !delta_wide_ok(e, sc.tole)) {  // (the cells form and the row scan read the sorted rows)
-    if ((rc = consolidate(e))) return rc;
-    return search_core(e, h_qoff, nq, d_q, P, keys, d_keys_out, s);
-  }
-  // the vote path needs only the zeroing; the scan path the frames' boxes too
-  HIPCHK(e, launch_prep_boxes(d_q, vote ? 0 : nf, sc, e->boxes.as<FrameBox>(), d_mask, nzero, s));
+  int32_t Qp = 0, nzero = 0;
+  uint32_t* d_mask = nullptr;
+  int32_t* d_max = nullptr;
+  unsigned long long* d_best = nullptr;
+};
 
-  bool done = false;
-  if (vote) {
-    // vote-matrix path, no host round trip: key mask -> used-key compaction -> A (per-query
-    // counts) and Bt -> GEMM
-    const int32_t Cp = ((C + 31) / 32) * 32;
-    HIPCHK(e, e->A.reserve(sizeof(_Float16) * (size_t)Qp * kVoteKpMax));
-    HIPCHK(e, e->Bt.reserve(sizeof(_Float16) * (size_t)Cp * kVoteKpMax));
-    VoteMeta* d_meta = reinterpret_cast<VoteMeta*>(d_mask + kMetaWord);
-    if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s))) return rc;
-    HIPCHK(e, launch_key_mask(d_q, sc, nf, d_mask, d_max, d_meta, s));
-    HIPCHK(e, launch_build_A(d_q, sc, e->qoff.as<int64_t>(), nq, Qp, d_mask, d_max, d_meta, e->class_ku_max,
-                             e->A.as<_Float16>(), e->Bt.as<_Float16>(), Cp, s));
-    HIPCHK(e, launch_build_B(d_mask, e->key_bits.as<uint32_t>(), C, d_meta, Cp, e->Bt.as<_Float16>(), s));
-    HIPCHK(e, e->vote_part.reserve(sizeof(unsigned long long) * (size_t)vote_chunks(Cp) * Qp));
-    HIPCHK(e, launch_vote_gemm(e->A.as<_Float16>(), e->Bt.as<_Float16>(), Qp, Cp, d_meta, e->tiekey.as<int32_t>(),
-                               e->vote_part.as<unsigned long long>(), d_best, d_mask, e->key_bits.as<uint32_t>(), C, s));
-    // the results go out before the ok flag is known (one host wait); a redo overwrites them.
-    // Host results: (VoteMeta, best[nq]) in one copy into pinned memory.
-    const size_t back = sizeof(VoteMeta) + (d_keys_out ? 0 : sizeof(unsigned long long) * nq);
-    HIPCHK(e, e->vres_pin.reserve(back));
-    if (d_keys_out)
-      HIPCHK(e, hipMemcpyAsync(d_keys_out, d_best, sizeof(unsigned long long) * nq, hipMemcpyDeviceToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(e->vres_pin.p, d_meta, back, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-    VoteMeta hm;
-    memcpy(&hm, e->vres_pin.p, sizeof hm);
-    if (!d_keys_out && nq)
-      memcpy(keys.data(), e->vres_pin.as<char>() + sizeof(VoteMeta), sizeof(unsigned long long) * nq);
-    if (e->dbg_vote) fprintf(stderr, "[tfp] vote: nq %d Qp %d C %d ku %d kp %d ok %d\n", nq, Qp, C, hm.ku, hm.kp, hm.ok);
-    if (hm.ok) return TFP_OK;
-    // a count above fp16's exact range or a key outside the vote range: the scan path below (over
-    // the sorted rows: the delta merged into them first)
-    if (has_delta) {
-      if ((rc = consolidate(e))) return rc;
-      return search_core(e, h_qoff, nq, d_q, P, keys, d_keys_out, s);
-    }
-    HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->boxes.as<FrameBox>(), d_mask, nzero, s));
+// Small batch (batch-1 latency): one vote launch over the cached key bitsets, results into
+// host-mapped memory.
+int search_small(tfp_engine* e, Batch& b) {
+  const int32_t nq = b.nq;
+  hipStream_t s = b.s;
+  if (b.d_keys_out || b.sc.coefs != 1 || nq < 1 || nq > kSmallQ || b.C <= 0 || b.R_all <= 0) return kNext;
+  for (int32_t i = 0; i < nq; i++)
+    if (b.qo[i + 1] - b.qo[i] > 2048) return kNext;  // counts bounded like the fp16 path
+  SmallQueries sq;
+  memset(&sq, 0, sizeof sq);
+  sq.nq = nq;
+  for (int32_t i = 0; i <= nq; i++) sq.qoff[i] = b.qo[i];
+  const int32_t C = b.C;
+  HIPCHK(e, e->small_res.reserve(small_result_bytes(C), hipHostMallocMapped | hipHostMallocCoherent));
+  if (e->small_res.p != e->small_res_host) {
+    HIPCHK(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&e->small_res_dev), e->small_res.p, 0));
+    e->small_res_host = e->small_res.p;
   }
+  int rc;
+  if ((rc = ensure_ranges(e, b.sc.tole, s)) || (rc = ensure_key_bits(e, s))) return rc;
+  HIPCHK(e, launch_search_small(b.d_q, sq, b.sc, e->tc.ranges.active().key_bits.as<uint32_t>(), C, e->tiekey.as<int32_t>(),
+                                e->small_res_dev, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  // the vote ran after the fingerprint kernel, which read the staged upload: it is free again
+  e->stage_pending = false;
+  // the vote's blocks wrote their per-query maxima into host memory: the max over the blocks
+  SmallResult* h = e->small_res.as<SmallResult>();
+  if (h->bad) return b.has_delta ? kNeedsSorted : kNext;  // a key outside the vote range: the general path (over the index's rows)
+  if (h->ku > 0) {
+    const unsigned long long* part = small_result_parts(h);
+    const int32_t nb = small_vote_blocks(C);
+    for (int32_t i = 0; i < nq; i++) {
+      unsigned long long k = 0ull;
+      for (int32_t blk = 0; blk < nb; blk++) k = std::max(k, part[(size_t)blk * kSmallQ + i]);
+      b.keys[i] = k;
+    }
+  }
+  return TFP_OK;
+}
+
+// Vote-matrix path (after prep_boxes' zeroing), no host round trip: key mask -> used-key compaction
+// -> A (per-query counts) and Bt -> GEMM.
+int search_vote(tfp_engine* e, Batch& b) {
+  const int32_t nq = b.nq, Qp = b.Qp, C = b.C;
+  hipStream_t s = b.s;
+  const SearchConsts& sc = b.sc;
+  const int32_t Cp = ((C + 31) / 32) * 32;
+  HIPCHK(e, e->A.reserve(sizeof(_Float16) * (size_t)Qp * kVoteKpMax));
+  HIPCHK(e, e->Bt.reserve(sizeof(_Float16) * (size_t)Cp * kVoteKpMax));
+  VoteMeta* d_meta = reinterpret_cast<VoteMeta*>(b.d_mask + Batch::kMetaWord);
+  int rc;
+  if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s))) return rc;
+  const uint32_t* key_bits = e->tc.ranges.active().key_bits.as<uint32_t>();
+  HIPCHK(e, launch_key_mask(b.d_q, sc, b.nf, b.d_mask, b.d_max, d_meta, s));
+  HIPCHK(e, launch_build_A(b.d_q, sc, e->qoff.as<int64_t>(), nq, Qp, b.d_mask, b.d_max, d_meta, e->class_ku_max,
+                           e->A.as<_Float16>(), e->Bt.as<_Float16>(), Cp, s));
+  HIPCHK(e, launch_build_B(b.d_mask, key_bits, C, d_meta, Cp, e->Bt.as<_Float16>(), s));
+  HIPCHK(e, e->vote_part.reserve(sizeof(unsigned long long) * (size_t)vote_chunks(Cp) * Qp));
+  HIPCHK(e, launch_vote_gemm(e->A.as<_Float16>(), e->Bt.as<_Float16>(), Qp, Cp, d_meta, e->tiekey.as<int32_t>(),
+                             e->vote_part.as<unsigned long long>(), b.d_best, b.d_mask, key_bits, C, s));
+  // the results go out before the ok flag is known (one host wait); a redo overwrites them.
+  // Host results: (VoteMeta, best[nq]) in one copy into pinned memory.
+  const size_t back = sizeof(VoteMeta) + (b.d_keys_out ? 0 : sizeof(unsigned long long) * nq);
+  HIPCHK(e, e->vres_pin.reserve(back));
+  if (b.d_keys_out)
+    HIPCHK(e, hipMemcpyAsync(b.d_keys_out, b.d_best, sizeof(unsigned long long) * nq, hipMemcpyDeviceToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(e->vres_pin.p, d_meta, back, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  VoteMeta hm;
+  memcpy(&hm, e->vres_pin.p, sizeof hm);
+  if (!b.d_keys_out && nq)
+    memcpy(b.keys.data(), e->vres_pin.as<char>() + sizeof(VoteMeta), sizeof(unsigned long long) * nq);
+  if (e->dbg_vote) fprintf(stderr, "[tfp] vote: nq %d Qp %d C %d ku %d kp %d ok %d\n", nq, Qp, C, hm.ku, hm.kp, hm.ok);
+  if (hm.ok) return TFP_OK;
+  // a count above fp16's exact range or a key outside the vote range: the scan path (over the
+  // sorted rows), which needs the frames' boxes too
+  if (b.has_delta) return kNeedsSorted;
+  HIPCHK(e, launch_prep_boxes(b.d_q, b.nf, sc, e->boxes.as<FrameBox>(), b.d_mask, b.nzero, s));
+  return kNext;
+}
+
+// General path (tfp_scan.hip), after prep_boxes over every frame: the sweep by groups, run
+// speculatively (its sort's counts checked with the results: one host wait per batch) and redone
+// when they say so; else the cells form / row scan over the sorted rows.
+int search_general(tfp_engine* e, Batch& b) {
+  const int32_t nq = b.nq, C = b.C;
+  const int64_t nf = b.nf, R = b.R;
+  hipStream_t s = b.s;
+  const SearchConsts& sc = b.sc;
+  unsigned long long *const d_keys_out = b.d_keys_out, *const d_best = b.d_best;
+  const bool general = C > 0 && R > 0 && (sc.coefs == 1 || sc.coefs == 2);
+  int rc;
   for (int pass = 0;; pass++) {
     bool spec = false;  // the sweep ran without the host reading its sort's counts (checked below)
     bool spec_mapped = false;  // its counts were written to spec_pin by its last kernel
     bool out_written = false;  // the sweep wrote its keys straight into d_keys_out
     bool swept = false;        // the sweep by groups ran (not the cells form / row scan)
     bool bins_used = false;
-    if (!done && C > 0 && R > 0 && (sc.coefs == 1 || sc.coefs == 2) && sc.tole >= e->wide_min_tol) {
-      // general path: the sweep by groups (tfp_scan.hip), unless a frame needs the row scan
+    CellCache* cells = nullptr;  // this pass's clip-set cache (not valid: none, the row scan)
+    if (general) {
       if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_cells(e, sc.tole, s))) return rc;
-      if (e->dbg_vote && !e->cells.valid) fprintf(stderr, "[tfp] general path: no clip-set cache (row scan)\n");
-      // with a delta: its cache too (a failure to build it merges the delta, below)
-      bool dsweep = has_delta && e->cells.valid;
-      if (dsweep && ensure_delta_cells(e, sc.tole, s) != TFP_OK) {
+      cells = &e->tc.cells.active();
+    }
+    if (general && sc.tole >= e->wide_min_tol) {
+      // the sweep by groups, unless a frame needs the row scan
+      if (e->dbg_vote && !cells->valid) fprintf(stderr, "[tfp] general path: no clip-set cache (row scan)\n");
+      // with a delta: its cache too (a failure to build it is recovered: the delta is merged, below)
+      bool dsweep = b.has_delta && cells->valid;
+      if (dsweep && quietly(e, [&] { return ensure_delta_cells(e, sc.tole, s); }) != TFP_OK) {
         (void)hipGetLastError();
-        e->err.clear_own();  // (recovered: the merge below serves the batch)
         dsweep = false;
       }
-      if (e->cells.valid && (dsweep || !has_delta)) {
+      if (cells->valid && (dsweep || !b.has_delta)) {
         HIPCHK(e, e->wide.reserve(nf, nq, s));
         bool ok = false;
         // (a device caller's output buffer takes the sweep's keys directly: zeroed by the prepare)
-        unsigned long long* wbest = d_keys_out ? reinterpret_cast<unsigned long long*>(d_keys_out) : d_best;
-        HIPCHK(e, launch_scan_wide_prepare(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), nq, nf, max_frames, sc.tole,
+        unsigned long long* wbest = d_keys_out ? d_keys_out : d_best;
+        HIPCHK(e, launch_scan_wide_prepare(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), nq, nf, b.max_frames, sc.tole,
                                            &e->wide, &ok, s, pass == 0, d_keys_out ? wbest : nullptr));
         bins_used = e->wide.ukeys_ready;  // (the bin sort ran on this pass)
         if (ok) {
@@ -1626,13 +1563,12 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
             }
             d_info = e->spec_pin_dev;
           }
-          HIPCHK(e, launch_scan_wide(nq, nf, &e->cells, e->tiekey.as<int32_t>(), C, &e->wide, wbest, s, d_info, &spec_mapped));
-          if (dsweep && e->dcells.valid) {  // the delta's clips into the same maxima
-            HIPCHK(e, launch_scan_wide(nq, nf, &e->dcells, e->tiekey.as<int32_t>(), C, &e->wide, wbest, s, d_info, &spec_mapped,
-                                       e->delta_col0));
-            e->n_delta_sweeps++;
+          HIPCHK(e, launch_scan_wide(nq, nf, cells, e->tiekey.as<int32_t>(), C, &e->wide, wbest, s, d_info, &spec_mapped));
+          if (dsweep && e->tc.dcells.p.valid) {  // the delta's clips into the same maxima
+            HIPCHK(e, launch_scan_wide(nq, nf, &e->tc.dcells.p, e->tiekey.as<int32_t>(), C, &e->wide, wbest, s, d_info,
+                                       &spec_mapped, e->delta.col0));
+            e->tc.n_delta_sweeps++;
           }
-          done = true;
           swept = true;
           out_written = d_keys_out != nullptr;
           spec = e->wide.spec;
@@ -1641,13 +1577,9 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
                                  sc.tole, ok ? "sweep by groups" : "cells / row scan", spec ? " (speculative)" : "");
       }
     }
-    if (!done && has_delta) {  // the cells form and the row scan read the sorted rows: the delta merged first
-      if ((rc = consolidate(e))) return rc;
-      return search_core(e, h_qoff, nq, d_q, P, keys, d_keys_out, s);
-    }
-    if (!done && C > 0 && R > 0 && (sc.coefs == 1 || sc.coefs == 2)) {
-      // general path (tfp_scan.hip): queries in chunks of <= 256 MB of scratch per array
-      if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_cells(e, sc.tole, s))) return rc;
+    if (!swept && b.has_delta) return kNeedsSorted;  // the cells form and the row scan read the sorted rows
+    if (!swept && general) {
+      // queries in chunks of <= 256 MB of scratch per array
       int64_t chunk = (int64_t)(256ll << 20) / (4ll * C);
       chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, nq));
       const size_t bytes = sizeof(int32_t) * chunk * C;
@@ -1663,14 +1595,14 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
         HIPCHK(e, hipMemsetAsync(e->tcnt.p, 0, e->tcnt.bytes, s));
         e->scan_zeroed = z;  // (touched is written before it is read)
       }
-      if (e->cells.valid && e->cells.ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
+      if (cells->valid && cells->ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
         (void)hipGetLastError();
-        e->cells.invalidate();  // every frame takes the row scan
+        cells->invalidate();  // every frame takes the row scan
       }
       for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
         const int32_t n = (int32_t)std::min<int64_t>(chunk, nq - q0);
-        HIPCHK(e, launch_scan(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), qo.data(), (int32_t)q0, n,
-                              e->m1s.as<int32_t>(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(), R, &e->cells,
+        HIPCHK(e, launch_scan(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), b.qo.data(), (int32_t)q0, n,
+                              e->m1s.as<int32_t>(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(), R, cells,
                               e->tiekey.as<int32_t>(), C, e->stamp.as<int32_t>(), e->score.as<int32_t>(),
                               e->touched.as<int32_t>(), e->tcnt.as<int32_t>(), d_best, s));
       }
@@ -1684,7 +1616,7 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
       if (!out_written)
         HIPCHK(e, hipMemcpyAsync(d_keys_out, d_best, sizeof(unsigned long long) * nq, hipMemcpyDeviceToDevice, s));
     } else if (nq) {
-      HIPCHK(e, hipMemcpyAsync(keys.data(), d_best, sizeof(unsigned long long) * nq, hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(b.keys.data(), d_best, sizeof(unsigned long long) * nq, hipMemcpyDeviceToHost, s));
     }
     // (the scan kernels read and write engine scratch: the next call, on any stream or thread, may
     // reuse it only once they are done)
@@ -1694,7 +1626,6 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
       if (info[1] > 0 || info[2] > 0) {  // a frame for the row scan, or a window the one-sort key cannot order
         if (e->dbg_vote) fprintf(stderr, "[tfp] speculative sweep redone (info %d %d %d)\n", info[0], info[1], info[2]);
         e->n_sweep_redo++;
-        done = false;
         HIPCHK(e, hipMemsetAsync(d_best, 0, sizeof(unsigned long long) * nq, s));
         continue;
       }
@@ -1705,32 +1636,99 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
   }
 }
 
+// The forms in turn: the small batch, the vote GEMM, the general path. The index delta serves the
+// coefs = 1 vote paths at the tolerances its bits cover, and the sweep (its own clip-set cache
+// beside the main one) at tolerances up to kOrderMaxTol; any other search reads the sorted rows.
+// Whether a batch is one of those is known up front, or a form finds out (kNeedsSorted):
+// either way the delta is merged here, and the batch starts over on the merged index.
+int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_q, const tfp_search_params* P,
+                std::vector<unsigned long long>& keys, unsigned long long* d_keys_out, hipStream_t s) {
+  int rc = rebuild(e);  // synchronous on e->stream
+  if (rc) return rc;
+  Batch b{nq, d_q, keys, d_keys_out, s};
+  SearchConsts& sc = b.sc;
+  memset(&sc, 0, sizeof sc);
+  sc.coefs = P->coefs;
+  sc.tole = P->tolerance < 0 ? TFP_DEFAULT_TOLERANCE : P->tolerance;  // fp_handler.c:252-256
+  sc.has_low = P->freq_ignore_low > 0;
+  sc.has_high = P->freq_ignore_high > 0;
+  if (sc.has_low) sc.thr_low = 10 * log10((double)P->freq_ignore_low);
+  if (sc.has_high) sc.thr_high = 10 * log10((double)P->freq_ignore_high);
+  b.qo.assign(h_qoff, h_qoff + nq + 1);
+  for (auto& v : b.qo) v -= h_qoff[0];
+  b.nf = b.qo[nq];
+  for (int32_t i = 0; i < nq; i++) b.max_frames = std::max<int64_t>(b.max_frames, b.qo[i + 1] - b.qo[i]);
+  b.Qp = ((nq + 127) / 128) * 128;
+  b.nzero = Batch::kMiscWords + 2 * b.Qp;
+
+  for (bool merge = false;; merge = true) {
+    if (merge && (rc = consolidate(e))) return rc;
+    keys.assign(nq, 0ull);
+    b.has_delta = !e->delta.clip.empty();
+    b.C = e->ncols;
+    b.R = e->nrows;
+    b.R_all = e->nrows + e->delta.rows;  // rows that may match (main index + delta)
+    const bool vote = sc.coefs == 1 && b.C > 0 && b.R_all > 0 && b.max_frames < 16384;  // packed scores exact below 16384 frames
+    // up front: a tolerance the delta's bits do not cover; a batch for the cells form / row scan
+    if (b.has_delta && (sc.coefs == 1 ? !delta_tol_ok(sc.tole) || (!vote && !delta_wide_ok(e, sc.tole))
+                                      : !delta_wide_ok(e, sc.tole)))
+      continue;
+    if ((rc = search_small(e, b)) <= 0) return rc;
+    if (rc == kNeedsSorted) continue;
+    // Query offsets are the same on every call of one plan or stream: copy them only when they
+    // change, from pinned memory so the copy is asynchronous (a pageable copy would make the host
+    // wait for the queries' fingerprint kernels before it could launch the search).
+    if (b.qo != e->qoff_host || s != e->qoff_stream) {
+      const size_t bytes = sizeof(int64_t) * b.qo.size();
+      if (e->qoff_pending) HIPCHK(e, hipEventSynchronize(e->qoff_ev));  // previous copy done reading
+      HIPCHK(e, e->qoff.reserve(bytes));
+      HIPCHK(e, e->qoff_pin.reserve(bytes));
+      memcpy(e->qoff_pin.p, b.qo.data(), bytes);
+      HIPCHK(e, hipMemcpyAsync(e->qoff.p, e->qoff_pin.p, bytes, hipMemcpyHostToDevice, s));
+      if (!e->qoff_ev) HIPCHK(e, hipEventCreateWithFlags(&e->qoff_ev, hipEventDisableTiming));
+      HIPCHK(e, hipEventRecord(e->qoff_ev, s));
+      e->qoff_pending = true;
+      e->qoff_host = b.qo;
+      e->qoff_stream = s;
+    }
+    HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (b.nf + 1)));
+    HIPCHK(e, e->best.reserve(sizeof(uint32_t) * b.nzero));
+    b.d_mask = e->best.as<uint32_t>();
+    b.d_max = reinterpret_cast<int32_t*>(b.d_mask + Batch::kMaskWords);
+    b.d_best = reinterpret_cast<unsigned long long*>(b.d_mask + Batch::kMiscWords);
+    // the vote path needs only the zeroing; the scan path the frames' boxes too
+    HIPCHK(e, launch_prep_boxes(d_q, vote ? 0 : b.nf, sc, e->boxes.as<FrameBox>(), b.d_mask, b.nzero, s));
+    if (vote && (rc = search_vote(e, b)) <= 0) return rc;
+    if ((!vote || rc == kNext) && (rc = search_general(e, b)) <= 0) return rc;
+  }
+}
+
 // The index column of a tie-break key (-1: none). Without an override the key is the clip's rank
 // among all live uuids: a main column's, or with a delta (ranks at[j] + j, ascending) either a delta
 // column's or main column k - #{delta ranks below k}.
 int32_t col_of_key(const tfp_engine* e, int32_t k) {
   if (e->key_identity) {
-    const int32_t Cm = (int32_t)e->col_clip.size(), D = (int32_t)e->delta_clip.size();
+    const int32_t Cm = (int32_t)e->col_clip.size(), D = (int32_t)e->delta.clip.size();
     if (k < 0 || k >= Cm + D) return -1;
     int32_t lo = 0, hi = D;  // first delta j with rank >= k
     while (lo < hi) {
       const int32_t mid = (lo + hi) >> 1;
-      if (e->delta_at[mid] + mid < k) lo = mid + 1; else hi = mid;
+      if (e->delta.at[mid] + mid < k) lo = mid + 1; else hi = mid;
     }
-    if (lo < D && e->delta_at[lo] + lo == k) return e->delta_col0 + lo;
+    if (lo < D && e->delta.at[lo] + lo == k) return e->delta.col0 + lo;
     return k - lo;
   }
   auto it = e->key_col.find(k);
   if (it != e->key_col.end()) return it->second;
-  auto jt = e->key_col_delta.find(k);
-  return jt == e->key_col_delta.end() ? -1 : jt->second;
+  auto jt = e->delta.key_col.find(k);
+  return jt == e->delta.key_col.end() ? -1 : jt->second;
 }
 
 // The clip of an index column (-1: none): a main column or a delta column.
 int32_t clip_of_col(const tfp_engine* e, int32_t col) {
   if (col >= 0 && (size_t)col < e->col_clip.size()) return e->col_clip[col];
-  const int32_t j = col - e->delta_col0;
-  return j >= 0 && (size_t)j < e->delta_clip.size() ? e->delta_clip[j] : -1;
+  const int32_t j = col - e->delta.col0;
+  return j >= 0 && (size_t)j < e->delta.clip.size() ? e->delta.clip[j] : -1;
 }
 
 void fill_results(tfp_engine* e, const std::vector<unsigned long long>& keys, const int64_t* qoff, int32_t nq,
@@ -1791,6 +1789,8 @@ int tfp_engine_create(int32_t device, tfp_engine** out) {
   e->dbg_vote = tfp::knob("TFP_DEBUG_VOTE") != nullptr;
   e->dbg_index = tfp::knob("TFP_DEBUG_INDEX") != nullptr;
   if (const char* v = tfp::knob("TFP_TEST_FAIL_COMPACT")) e->fail_compact = (int32_t)atoi(v);
+  if (const char* v = tfp::knob("TFP_TEST_FAIL_CELLS")) e->fail_cells = atoll(v);
+  if (const char* v = tfp::knob("TFP_TEST_FAIL_DELTA_CELLS")) e->fail_delta_cells = atoll(v);
   if (const char* v = tfp::knob("TFP_TEST_FAIL_QUERY_SAMPLES")) e->fail_query_len = atoll(v);
   if (const char* v = tfp::knob("TFP_KEYBITS_WIN")) e->kb_win = atoi(v);
   if (const char* v = tfp::knob("TFP_KEYBITS_DIRECT")) e->kb_direct = atoll(v);
@@ -1801,13 +1801,13 @@ int tfp_engine_create(int32_t device, tfp_engine** out) {
   e->wide.unpacked = tfp::knob("TFP_WIDE_UNPACKED") != nullptr;
   e->wide.libsort = tfp::knob("TFP_WIDE_LIBSORT") != nullptr;
   e->wide.debug_bins = tfp::knob("TFP_DEBUG_BINS") != nullptr;
-  if (const char* v = tfp::knob("TFP_DELTA_WIDE")) e->delta_wide = atoi(v) != 0;
+  if (const char* v = tfp::knob("TFP_DELTA_WIDE")) e->delta.wide = atoi(v) != 0;
   // operational switches (documented: tiresias_fp.h), read as plain environment variables
   if (const char* v = tfp::op_env("TFP_COALESCE")) e->coalesce = atoi(v) != 0;
-  if (const char* v = tfp::op_env("TFP_INDEX_DELTA")) e->use_delta = atoi(v) != 0;
+  if (const char* v = tfp::op_env("TFP_INDEX_DELTA")) e->delta.use = atoi(v) != 0;
   // test form: the delta even below delta_min_cols main columns (small test DBs)
   if (const char* v = tfp::knob("TFP_INDEX_DELTA"))
-    if (atoi(v) != 0) e->delta_min_cols = 0;
+    if (atoi(v) != 0) e->delta.min_cols = 0;
   if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
     delete e;
     return TFP_E_HIP;
@@ -2140,10 +2140,7 @@ int tfp_index_clear(tfp_engine* e) {
   e->removed_built = false;
   e->live_rows = 0;
   e->col_clip.clear();
-  e->delta_clip.clear();
-  e->delta_at.clear();
-  e->delta_col0 = 0;
-  e->delta_rows = 0;
+  e->delta.reset(0);
   e->dirty = true;
   return TFP_OK;
 }
@@ -2178,8 +2175,8 @@ int tfp_index_build_stats(tfp_engine* e, int64_t* full_builds, int64_t* merges) 
 int tfp_index_delta_stats(tfp_engine* e, int64_t* delta_updates, int32_t* delta_clips) {
   if (!e) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (delta_updates) *delta_updates = e->n_delta_updates;
-  if (delta_clips) *delta_clips = (int32_t)e->delta_clip.size();
+  if (delta_updates) *delta_updates = e->delta.n_updates;
+  if (delta_clips) *delta_clips = (int32_t)e->delta.clip.size();
   return TFP_OK;
 }
 
@@ -2337,13 +2334,13 @@ int tfp_index_cache_stats(tfp_engine* e, int64_t* cache_builds, int64_t* cache_h
                           int64_t* delta_sweeps) {
   if (!e) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (cache_builds) *cache_builds = e->n_cell_builds;
-  if (cache_hits) *cache_hits = e->n_cell_hits;
-  if (from_order) *from_order = e->n_cell_from_order;
-  if (order_builds) *order_builds = e->n_order_builds;
-  if (order_merges) *order_merges = e->n_order_merges;
-  if (delta_cache_builds) *delta_cache_builds = e->n_delta_cell_builds;
-  if (delta_sweeps) *delta_sweeps = e->n_delta_sweeps;
+  if (cache_builds) *cache_builds = e->tc.n_builds;
+  if (cache_hits) *cache_hits = e->tc.n_hits;
+  if (from_order) *from_order = e->tc.n_from_order;
+  if (order_builds) *order_builds = e->order.n_builds;
+  if (order_merges) *order_merges = e->order.n_merges;
+  if (delta_cache_builds) *delta_cache_builds = e->tc.n_delta_builds;
+  if (delta_sweeps) *delta_sweeps = e->tc.n_delta_sweeps;
   return TFP_OK;
 }
 

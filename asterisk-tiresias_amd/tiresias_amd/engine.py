@@ -116,6 +116,10 @@ class Engine:
     def _chk(self, rc):
         return check(rc, self._h)
 
+    def last_error(self) -> str:
+        """tfp_engine_last_error for the calling thread ("" when no call has failed)."""
+        return (lib().tfp_engine_last_error(self._h) or b"").decode()
+
     # ---- fingerprinting -----------------------------------------------------------
     def fingerprint(self, pcm: np.ndarray, sample_rate: int = 8000) -> np.ndarray:
         pcm = np.ascontiguousarray(pcm, np.int16)

@@ -203,15 +203,15 @@ int tfp_index_delta_stats(tfp_engine* eng, int64_t* delta_updates, int32_t* delt
  * radix sort per full index build, when first needed) and merges (carried through every index
  * merge), and the index delta's caches built and sweeps run over them (an enrolment followed by a
  * coefs = 2 search: the main caches stay, the delta's rows get their own). Any pointer may be NULL. */
+int tfp_index_cache_stats(tfp_engine* eng, int64_t* cache_builds, int64_t* cache_hits, int64_t* from_order,
+                          int64_t* order_builds, int64_t* order_merges, int64_t* delta_cache_builds,
+                          int64_t* delta_sweeps);
 /* The coefs = 2 sweep's frame sort per batch (new in round 6): batches whose hand-written bin sort
  * stood, batches sorted by the library sort (a first pass that could not take the bin sort, or the
  * redo), speculative passes redone (an overfull bin, a window width outside the packed key, a frame
  * for the row scan), and the crowd bins (one value: the silence floor) the bin sort copied unsorted.
  * Any pointer may be NULL. */
 int tfp_sweep_stats(tfp_engine* eng, int64_t* bins, int64_t* library, int64_t* redone, int64_t* crowd_bins);
-int tfp_index_cache_stats(tfp_engine* eng, int64_t* cache_builds, int64_t* cache_hits, int64_t* from_order,
-                          int64_t* order_builds, int64_t* order_merges, int64_t* delta_cache_builds,
-                          int64_t* delta_sweeps);
 /* Multi-GPU sharding: override the tie-break key of each live clip (default: its rank among
  * this engine's uuids). keys[clip_id] must order like the uuids across all shards and be
  * distinct over live clips. A clip added after this call has no key: the next search (or

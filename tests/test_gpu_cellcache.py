@@ -6,6 +6,8 @@ swept beside the main one (no merge per enrolment). The dialplan passes the tole
 (application_handler.c:114-122) and every enrolment's rows are searchable at once
 (fp_handler.c:559-571): callers alternating coefs = 2 tolerances between enrolments and removals get
 the oracle's answer (fp_handler.c:318-353) at every step."""
+import threading
+
 import numpy as np
 import pytest
 
@@ -184,5 +186,107 @@ def test_coefs2_delta_sweep_without_merge(tfp_lib, oracle, tol):
         _check(eng, oracle, tfp_lib, mir, qdb, qoff, tfp_lib.params(2, 0.7), "merged")
         assert eng.index_build_stats()[1] == mg0 + 1 and eng.index_delta_stats()[1] == 0
         _check(eng, oracle, tfp_lib, mir, qdb, qoff, p, "after the merge")
+    finally:
+        eng.close()
+
+
+def _enrolled(tfp_lib, env, seed):
+    """An engine created under env with _clustered_db's 300 clips x 40 rows committed, and its mirror."""
+    rng = np.random.default_rng(seed)
+    data = _clustered_db(rng, 300, 40)
+    uu = _uuids(rng, 300)
+    eng = _engine_with(tfp_lib, env)
+    mir = Mirror()
+    for c in range(300):
+        eng.index_add(uu[c], *data[c])
+        mir.rows[uu[c]] = data[c]
+    eng.index_commit()
+    return rng, data, uu, eng, mir
+
+
+def _winning_copy(oracle, tfp_lib, data, uu, mir, tol):
+    """(x, uuid, query): a clip x, a uuid right above its own and 30 frames of x's rows such that,
+    by the oracle, a copy of x's rows enrolled under that uuid wins the query at coefs = 2, tolerance
+    tol (the copy ties with x on every frame and has the greater uuid)."""
+    for x in range(len(uu)):
+        if uu[x][-1] in "f9":
+            continue
+        ux = uu[x][:-1] + "%x" % (int(uu[x][-1], 16) + 1)
+        qx, qo = _queries(np.random.default_rng(x), data, [x])
+        mir.rows[ux] = data[x]
+        win = mir.search(oracle, qx[:, 0], qx[:, 1], qo, tfp_lib.params(2, tol))[0]
+        del mir.rows[ux]
+        if win is not None and win[0] == ux:
+            return x, ux, qx
+    raise AssertionError("no clip whose copy wins its own rows' query")
+
+
+def _queries_with(rng, data, qx, n_other):
+    """A batch whose first query is qx (30 frames), then n_other queries from random clips."""
+    q1, _ = _queries(rng, data, [int(v) for v in rng.integers(0, 300, n_other)], jitter=2)
+    return np.concatenate([qx, q1]), np.arange(n_other + 2, dtype=np.int64) * 30
+
+
+def test_failed_cache_build_takes_row_scan_and_leaves_nothing_stale(tfp_lib, oracle):
+    """A main clip-set cache build that fails in its preparation (TFP_TEST_FAIL_CELLS=4: the engine's
+    4th build, as an allocation failure of the clip order would) is not a failed search: the batch
+    takes the row scan and equals the oracle. Nothing stale is left behind either: the caches of
+    tolerances 0.001 and 0.01 were built before clip X was merged into the index, the failing build
+    claims a cache entry, and the 0.01 search after it must see X (a copy of a main clip's rows under
+    a greater uuid: it wins the tie), not a cache of the index before X. The failed tolerance's cache
+    is then built by the next search at it."""
+    rng, data, uu, eng, mir = _enrolled(tfp_lib, {"TFP_INDEX_DELTA": "0", "TFP_TEST_FAIL_CELLS": "4"}, 4141)
+    try:
+        x, ux, qx = _winning_copy(oracle, tfp_lib, data, uu, mir, 0.01)
+
+        def batch(tol, step):
+            qdb, qoff = _queries_with(rng, data, qx, 7)
+            return _check(eng, oracle, tfp_lib, mir, qdb, qoff, tfp_lib.params(2, tol), step)
+        batch(0.001, "0.001")
+        batch(0.01, "0.01")
+        eng.index_add(ux, *data[x])  # (no index delta: the next search merges it)
+        mir.rows[ux] = data[x]
+        batch(0.01, "0.01 after the merge")
+        st3 = eng.index_cache_stats()
+        assert st3["builds"] == 3 and eng.index_build_stats()[1] == 1, st3
+        batch(0.1, "0.1: the failing build")  # OK and == the oracle (the row scan)
+        st4 = eng.index_cache_stats()
+        assert st4["builds"] == st3["builds"] + 1 and st4["from_order"] == st3["from_order"], (st3, st4)
+        qdb, qoff = _queries_with(rng, data, qx, 7)
+        p = tfp_lib.params(2, 0.01)
+        exp = mir.search(oracle, qdb[:, 0], qdb[:, 1], qoff, p)
+        assert exp[0] is not None and exp[0][0] == ux, exp[0]  # X wins its rows' query
+        _check(eng, oracle, tfp_lib, mir, qdb, qoff, p, "0.01 after the failed build")
+        batch(0.1, "0.1 again")
+        st5 = eng.index_cache_stats()
+        assert st5["from_order"] == st4["from_order"] + 1, (st4, st5)  # built now
+    finally:
+        eng.close()
+
+
+def test_recovered_delta_cache_failure_leaves_no_error(tfp_lib, oracle):
+    """A delta clip-set cache build that fails (TFP_TEST_FAIL_DELTA_CELLS=1) is recovered: the delta
+    is merged, the batch equals the oracle, and the handle keeps no message of the failure, for the
+    calling thread or for any other (tfp_engine_last_error after a successful search)."""
+    rng, data, uu, eng, mir = _enrolled(tfp_lib, {"TFP_INDEX_DELTA": "1", "TFP_TEST_FAIL_DELTA_CELLS": "1"}, 5151)
+    try:
+        p = tfp_lib.params(2, 0.001)
+        qdb, qoff = _queries(rng, data, [int(v) for v in rng.integers(0, 300, 8)], jitter=2)
+        _check(eng, oracle, tfp_lib, mir, qdb, qoff, p, "main")
+        mg0 = eng.index_build_stats()[1]
+        x, ux, qx = _winning_copy(oracle, tfp_lib, data, uu, mir, 0.001)
+        eng.index_add(ux, *data[x])
+        mir.rows[ux] = data[x]
+        qdb, qoff = _queries_with(rng, data, qx, 7)
+        exp = mir.search(oracle, qdb[:, 0], qdb[:, 1], qoff, p)
+        assert exp[0] is not None and exp[0][0] == ux, exp[0]  # the new clip wins its rows' query
+        _check(eng, oracle, tfp_lib, mir, qdb, qoff, p, "with the new clip")
+        assert eng.index_build_stats()[1] == mg0 + 1 and eng.index_delta_stats()[1] == 0
+        assert eng.index_cache_stats()["delta_builds"] == 0
+        seen = []
+        t = threading.Thread(target=lambda: seen.append(eng.last_error()))
+        t.start()
+        t.join()
+        assert eng.last_error() == "" and seen == [""], (eng.last_error(), seen)
     finally:
         eng.close()

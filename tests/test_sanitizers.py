@@ -52,6 +52,15 @@ def test_host_code_asan_ubsan(tmp_path):
     assert _run([exe]).strip().endswith("ok")
 
 
+def test_tolcache_asan_ubsan(tmp_path):
+    """The engine's per-(tolerance, version) cache discipline (csrc/tfp_tolcache.hpp) with a counting
+    dummy payload: hits, the eviction order, version expiry and carry, claim without commit, bitwise
+    tolerance keys, payload reuse (tests/native/check_tolcache.cpp)."""
+    exe = str(tmp_path / "check_tolcache")
+    subprocess.run(["g++", "-std=c++17", *ASAN, os.path.join(NATIVE, "check_tolcache.cpp"), "-o", exe], check=True)
+    assert _run([exe]).strip().endswith("OK")
+
+
 def test_shard_pool_and_coalescer_tsan(tmp_path):
     exe = str(tmp_path / "tsan_threads")
     subprocess.run(["g++", "-std=c++17", *TSAN, "-I" + os.path.join(REPO, "include"),
