@@ -26,6 +26,7 @@
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
 #include "tfp_math.hpp"
+#include "tfp_rank.hpp"
 #include "tfp_synth.hpp"
 #include "tfp_tables.hpp"
 #include "tfp_tolcache.hpp"
@@ -266,6 +267,11 @@ struct tfp_engine {
   // by the scan kernels themselves
   DevBuf touched, tcnt;
   size_t scan_zeroed = 0;  // bytes of stamp / score / touched known to be zero
+  // ranked search (rank_core): the vote form's per-block partial keys, the batch's keys [nq][k] with
+  // the vote form's bad flag after them, their pinned copy, and the batches each form served
+  DevBuf rank_part, rank_keys;
+  HostBuf rank_pin;
+  int64_t n_rank_vote = 0, n_rank_general = 0;
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   int32_t class_ku_max = 10;  // TFP_VOTE_CLASS_MAX: pattern-class vote up to this many used keys (-1: always the GEMM)
@@ -1408,6 +1414,58 @@ bool delta_wide_ok(const tfp_engine* e, double tole) {
 constexpr int kNext = 1;         // not for this batch, or it could not finish it: the next form
 constexpr int kNeedsSorted = 2;  // it needs the sorted rows to hold every clip: merge the index delta, start over
 
+// fp_search_fingerprint_info's arguments as the kernels take them (search_core, rank_core).
+SearchConsts search_consts(const tfp_search_params* P) {
+  SearchConsts sc;
+  memset(&sc, 0, sizeof sc);
+  sc.coefs = P->coefs;
+  sc.tole = P->tolerance < 0 ? TFP_DEFAULT_TOLERANCE : P->tolerance;  // fp_handler.c:252-256
+  sc.has_low = P->freq_ignore_low > 0;
+  sc.has_high = P->freq_ignore_high > 0;
+  if (sc.has_low) sc.thr_low = 10 * log10((double)P->freq_ignore_low);
+  if (sc.has_high) sc.thr_high = 10 * log10((double)P->freq_ignore_high);
+  return sc;
+}
+
+// The batch's relative query offsets qo on the device (e->qoff), copied when they change.
+int ensure_qoff(tfp_engine* e, const std::vector<int64_t>& qo, hipStream_t s) {
+  if (qo == e->qoff_host && s == e->qoff_stream) return TFP_OK;
+  const size_t bytes = sizeof(int64_t) * qo.size();
+  if (e->qoff_pending) HIPCHK(e, hipEventSynchronize(e->qoff_ev));  // previous copy done reading
+  HIPCHK(e, e->qoff.reserve(bytes));
+  HIPCHK(e, e->qoff_pin.reserve(bytes));
+  memcpy(e->qoff_pin.p, qo.data(), bytes);
+  HIPCHK(e, hipMemcpyAsync(e->qoff.p, e->qoff_pin.p, bytes, hipMemcpyHostToDevice, s));
+  if (!e->qoff_ev) HIPCHK(e, hipEventCreateWithFlags(&e->qoff_ev, hipEventDisableTiming));
+  HIPCHK(e, hipEventRecord(e->qoff_ev, s));
+  e->qoff_pending = true;
+  e->qoff_host = qo;
+  e->qoff_stream = s;
+  return TFP_OK;
+}
+
+// The row scan's scratch for queries in chunks of <= 256 MB per array (*chunk queries at a time):
+// stamp / score / touched chunk x C int32, tcnt chunk int32, zero here and after every scan.
+int ensure_scan_scratch(tfp_engine* e, int32_t nq, int32_t C, int64_t* chunk_out, hipStream_t s) {
+  int64_t chunk = (int64_t)(256ll << 20) / (4ll * C);
+  chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, nq));
+  *chunk_out = chunk;
+  const size_t bytes = sizeof(int32_t) * chunk * C;
+  if (bytes > e->scan_zeroed || bytes > e->stamp.bytes || bytes > e->score.bytes || bytes > e->touched.bytes ||
+      sizeof(int32_t) * chunk > e->tcnt.bytes) {
+    HIPCHK(e, e->stamp.reserve(bytes));
+    HIPCHK(e, e->score.reserve(bytes));
+    HIPCHK(e, e->touched.reserve(bytes));
+    HIPCHK(e, e->tcnt.reserve(sizeof(int32_t) * chunk));
+    const size_t z = std::min(std::min(e->stamp.bytes, e->score.bytes), e->touched.bytes);
+    HIPCHK(e, hipMemsetAsync(e->stamp.p, 0, z, s));
+    HIPCHK(e, hipMemsetAsync(e->score.p, 0, z, s));
+    HIPCHK(e, hipMemsetAsync(e->tcnt.p, 0, e->tcnt.bytes, s));
+    e->scan_zeroed = z;  // (touched is written before it is read)
+  }
+  return TFP_OK;
+}
+
 // One batch on its way through the forms (search_core): the call's arguments, then the set-up the
 // forms share.
 struct Batch {
@@ -1580,21 +1638,8 @@ int search_general(tfp_engine* e, Batch& b) {
     if (!swept && b.has_delta) return kNeedsSorted;  // the cells form and the row scan read the sorted rows
     if (!swept && general) {
       // queries in chunks of <= 256 MB of scratch per array
-      int64_t chunk = (int64_t)(256ll << 20) / (4ll * C);
-      chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, nq));
-      const size_t bytes = sizeof(int32_t) * chunk * C;
-      if (bytes > e->scan_zeroed || bytes > e->stamp.bytes || bytes > e->score.bytes || bytes > e->touched.bytes ||
-          sizeof(int32_t) * chunk > e->tcnt.bytes) {
-        HIPCHK(e, e->stamp.reserve(bytes));
-        HIPCHK(e, e->score.reserve(bytes));
-        HIPCHK(e, e->touched.reserve(bytes));
-        HIPCHK(e, e->tcnt.reserve(sizeof(int32_t) * chunk));
-        const size_t z = std::min(std::min(e->stamp.bytes, e->score.bytes), e->touched.bytes);
-        HIPCHK(e, hipMemsetAsync(e->stamp.p, 0, z, s));
-        HIPCHK(e, hipMemsetAsync(e->score.p, 0, z, s));
-        HIPCHK(e, hipMemsetAsync(e->tcnt.p, 0, e->tcnt.bytes, s));
-        e->scan_zeroed = z;  // (touched is written before it is read)
-      }
+      int64_t chunk;
+      if ((rc = ensure_scan_scratch(e, nq, C, &chunk, s))) return rc;
       if (cells->valid && cells->ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
         (void)hipGetLastError();
         cells->invalidate();  // every frame takes the row scan
@@ -1647,13 +1692,7 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
   if (rc) return rc;
   Batch b{nq, d_q, keys, d_keys_out, s};
   SearchConsts& sc = b.sc;
-  memset(&sc, 0, sizeof sc);
-  sc.coefs = P->coefs;
-  sc.tole = P->tolerance < 0 ? TFP_DEFAULT_TOLERANCE : P->tolerance;  // fp_handler.c:252-256
-  sc.has_low = P->freq_ignore_low > 0;
-  sc.has_high = P->freq_ignore_high > 0;
-  if (sc.has_low) sc.thr_low = 10 * log10((double)P->freq_ignore_low);
-  if (sc.has_high) sc.thr_high = 10 * log10((double)P->freq_ignore_high);
+  sc = search_consts(P);
   b.qo.assign(h_qoff, h_qoff + nq + 1);
   for (auto& v : b.qo) v -= h_qoff[0];
   b.nf = b.qo[nq];
@@ -1678,19 +1717,7 @@ int search_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
     // Query offsets are the same on every call of one plan or stream: copy them only when they
     // change, from pinned memory so the copy is asynchronous (a pageable copy would make the host
     // wait for the queries' fingerprint kernels before it could launch the search).
-    if (b.qo != e->qoff_host || s != e->qoff_stream) {
-      const size_t bytes = sizeof(int64_t) * b.qo.size();
-      if (e->qoff_pending) HIPCHK(e, hipEventSynchronize(e->qoff_ev));  // previous copy done reading
-      HIPCHK(e, e->qoff.reserve(bytes));
-      HIPCHK(e, e->qoff_pin.reserve(bytes));
-      memcpy(e->qoff_pin.p, b.qo.data(), bytes);
-      HIPCHK(e, hipMemcpyAsync(e->qoff.p, e->qoff_pin.p, bytes, hipMemcpyHostToDevice, s));
-      if (!e->qoff_ev) HIPCHK(e, hipEventCreateWithFlags(&e->qoff_ev, hipEventDisableTiming));
-      HIPCHK(e, hipEventRecord(e->qoff_ev, s));
-      e->qoff_pending = true;
-      e->qoff_host = b.qo;
-      e->qoff_stream = s;
-    }
+    if ((rc = ensure_qoff(e, b.qo, s))) return rc;
     HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (b.nf + 1)));
     HIPCHK(e, e->best.reserve(sizeof(uint32_t) * b.nzero));
     b.d_mask = e->best.as<uint32_t>();
@@ -1750,6 +1777,127 @@ void fill_results(tfp_engine* e, const std::vector<unsigned long long>& keys, co
 }
 
 bool valid_params(const tfp_search_params* P) { return P && P->coefs >= 1 && P->coefs <= 2; }
+
+// ---- ranked search (tfp_rank.hpp): keys[q * K + r] = row r of query q's result set, 0 past the last
+
+// The vote form (coefs = 1): *bad when a frame's key lies outside the vote range (keys undefined).
+int rank_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
+              int32_t K, std::vector<unsigned long long>& keys, bool* bad, hipStream_t s) {
+  const int32_t C = e->ncols, nb = rank_vote_blocks(C);
+  int rc;
+  if ((rc = ensure_qoff(e, qo, s)) || (rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s))) return rc;
+  // queries in chunks of <= 256 MB of partial keys (and of the launch grid's second dimension)
+  int64_t chunk = (int64_t)(256ll << 20) / ((int64_t)sizeof(unsigned long long) * nb * K);
+  chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(chunk, 65535), nq));
+  const size_t nkeys = (size_t)nq * K;
+  HIPCHK(e, e->rank_part.reserve(sizeof(unsigned long long) * (size_t)chunk * nb * K));
+  HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  unsigned long long* d_keys = e->rank_keys.as<unsigned long long>();
+  int32_t* d_bad = reinterpret_cast<int32_t*>(d_keys + nkeys);
+  HIPCHK(e, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int32_t n = (int32_t)std::min<int64_t>(chunk, nq - q0);
+    HIPCHK(e, launch_rank_vote(d_q, e->qoff.as<int64_t>() + q0, n, sc, e->tc.ranges.active().key_bits.as<uint32_t>(), C,
+                               e->tiekey.as<int32_t>(), K, e->rank_part.as<unsigned long long>(), d_keys + q0 * K, d_bad,
+                               s));
+  }
+  HIPCHK(e, hipMemcpyAsync(e->rank_pin.p, d_keys, sizeof(unsigned long long) * (nkeys + 1), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  const unsigned long long* h = e->rank_pin.as<unsigned long long>();
+  *bad = (uint32_t)h[nkeys] != 0;
+  if (!*bad) std::copy(h, h + nkeys, keys.begin());
+  return TFP_OK;
+}
+
+// The general form (any coefs / tolerance / key), over the sorted rows of the merged index.
+int rank_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
+                 int32_t K, std::vector<unsigned long long>& keys, hipStream_t s) {
+  const int32_t C = e->ncols;
+  const int64_t R = e->nrows, nf = qo[nq];
+  if (C <= 0 || R <= 0) return TFP_OK;  // an empty index: no row
+  int rc;
+  if ((rc = ensure_qoff(e, qo, s))) return rc;
+  HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (nf + 1)));
+  HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->boxes.as<FrameBox>(), nullptr, 0, s));
+  if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_cells(e, sc.tole, s))) return rc;
+  CellCache* cells = &e->tc.cells.active();
+  int64_t chunk;
+  if ((rc = ensure_scan_scratch(e, nq, C, &chunk, s))) return rc;
+  if (cells->valid && cells->ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
+    (void)hipGetLastError();
+    cells->invalidate();  // every frame takes the row scan
+  }
+  const size_t nkeys = (size_t)nq * K;
+  HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int32_t n = (int32_t)std::min<int64_t>(chunk, nq - q0);
+    HIPCHK(e, launch_scan_ranked(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), qo.data(), (int32_t)q0, n,
+                                 e->m1s.as<int32_t>(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(), R, cells,
+                                 e->tiekey.as<int32_t>(), C, e->stamp.as<int32_t>(), e->score.as<int32_t>(),
+                                 e->touched.as<int32_t>(), e->tcnt.as<int32_t>(), K, e->rank_keys.as<unsigned long long>(),
+                                 s));
+  }
+  HIPCHK(e, hipMemcpyAsync(e->rank_pin.p, e->rank_keys.p, sizeof(unsigned long long) * nkeys, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (the scan's scratch is free for the next call)
+  const unsigned long long* h = e->rank_pin.as<unsigned long long>();
+  std::copy(h, h + nkeys, keys.begin());
+  return TFP_OK;
+}
+
+// Shaped like search_core. The vote form reads the key bitsets, which hold a live index delta's
+// columns at the tolerances delta_tol_ok() names; every other ranked search merges the delta first.
+int rank_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_q, const tfp_search_params* P, int32_t K,
+              std::vector<unsigned long long>& keys, hipStream_t s) {
+  int rc = rebuild(e);  // synchronous on e->stream
+  if (rc) return rc;
+  const SearchConsts sc = search_consts(P);
+  std::vector<int64_t> qo(h_qoff, h_qoff + nq + 1);
+  for (auto& v : qo) v -= h_qoff[0];
+  keys.assign((size_t)nq * K, 0ull);
+  if (sc.coefs == 1) {
+    if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
+    if (e->ncols <= 0 || e->nrows + e->delta.rows <= 0) return TFP_OK;
+    bool bad = false;
+    if ((rc = rank_vote(e, qo, nq, d_q, sc, K, keys, &bad, s))) return rc;
+    if (!bad) {
+      e->n_rank_vote++;
+      return TFP_OK;
+    }
+  }
+  if ((rc = consolidate(e)) || (rc = rank_general(e, qo, nq, d_q, sc, K, keys, s))) return rc;
+  e->n_rank_general++;
+  return TFP_OK;
+}
+
+// Keys to rows, as fill_results maps the winner's; counts[q] = the query's rows.
+void fill_candidates(tfp_engine* e, const std::vector<unsigned long long>& keys, int32_t nq, int32_t K, tfp_candidate* out,
+                     int32_t* counts) {
+  memset(out, 0, sizeof(tfp_candidate) * (size_t)nq * K);
+  for (int32_t i = 0; i < nq; i++) {
+    int32_t n = 0;
+    for (int32_t r = 0; r < K; r++) {
+      const unsigned long long k = keys[(size_t)i * K + r];
+      if (!k) break;
+      const int32_t clip = clip_of_col(e, col_of_key(e, (int32_t)(uint32_t)(k & 0xffffffffu)));
+      if (clip < 0) continue;
+      tfp_candidate& c = out[(size_t)i * K + n++];
+      c.match_count = (int32_t)(k >> 32);
+      c.clip_id = clip;
+      snprintf(c.uuid, sizeof c.uuid, "%s", e->clips[clip].uuid.c_str());
+    }
+    counts[i] = n;
+  }
+}
+
+int rank_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, const void* out, const void* counts) {
+  if (!e) return TFP_E_ARG;
+  if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
+  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "ranked search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+  if (!valid_params(P)) return fail(e, TFP_E_ARG, "ranked search: coefs outside [1, 2]");
+  return TFP_OK;
+}
 
 }  // namespace
 
@@ -2238,6 +2386,76 @@ int tfp_search(tfp_engine* e, const tfp_frame* frames, int32_t nframes, const tf
   if (nframes < 0) return TFP_E_ARG;
   int64_t qoff[2] = {0, nframes};
   return tfp_search_batch(e, frames, qoff, 1, P, out);
+}
+
+// ---- ranked search: the result query's first k rows (fp_handler.c:367-374) ----------------
+static_assert(kRankMax == TFP_RANK_MAX, "tfp_rank.hpp and the public header agree");
+
+int tfp_search_ranked_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                            const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = rank_args(e, P, k, nq, out, counts);
+  if (rc) return rc;
+  for (int32_t i = 0; i < nq; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  const int64_t nf = nq ? qoff[nq] - qoff[0] : 0;
+  if (nf && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
+  std::vector<unsigned long long> keys((size_t)nq * k, 0ull);
+  if (nq) {
+    HIPCHK(e, hipSetDevice(e->device));
+    std::vector<double> q(2 * (nf + 1));
+    for (int64_t i = 0; i < nf; i++) {
+      q[2 * i] = frames[qoff[0] + i].q1;
+      q[2 * i + 1] = frames[qoff[0] + i].q2;
+    }
+    if ((rc = upload(e, e->q, q.data(), sizeof(double) * q.size()))) return rc;
+    if ((rc = rank_core(e, qoff, nq, e->q.as<double>(), P, k, keys, e->stream))) return rc;
+  }
+  fill_candidates(e, keys, nq, k, out, counts);
+  return TFP_OK;
+}
+
+int tfp_search_ranked(tfp_engine* e, const tfp_frame* frames, int32_t nframes, const tfp_search_params* P, int32_t k,
+                      tfp_candidate* out, int32_t* count) {
+  if (nframes < 0) return TFP_E_ARG;
+  int64_t qoff[2] = {0, nframes};
+  return tfp_search_ranked_batch(e, frames, qoff, 1, P, k, out, count);
+}
+
+int tfp_search_ranked_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                                const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = rank_args(e, P, k, nq, out, counts);
+  if (rc) return rc;
+  for (int32_t i = 0; i < nq; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  if (!pcm && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
+  std::vector<const void*> ptrs;
+  std::vector<int64_t> lens;
+  split_offsets(pcm, sizeof(int16_t), offsets, nq, &ptrs, &lens);
+  std::vector<int64_t> foff(nq + 1, 0);
+  for (int32_t i = 0; i < nq; i++) foff[i + 1] = foff[i] + tfp_frame_count(lens[i]);
+  std::vector<unsigned long long> keys((size_t)nq * k, 0ull);
+  if (nq && foff[nq] > 0) {
+    HIPCHK(e, hipSetDevice(e->device));
+    int64_t nf;
+    if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nq, sr, &nf, nullptr, P->coefs == 2))) return rc;
+    if ((rc = rank_core(e, foff.data(), nq, e->db.as<double>(), P, k, keys, e->stream))) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
+    e->stage_pending = false;
+  }
+  fill_candidates(e, keys, nq, k, out, counts);
+  return TFP_OK;
+}
+
+int tfp_rank_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (vote_batches) *vote_batches = e->n_rank_vote;
+  if (general_batches) *general_batches = e->n_rank_general;
+  return TFP_OK;
 }
 
 namespace {

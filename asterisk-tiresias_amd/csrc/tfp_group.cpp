@@ -40,6 +40,7 @@
 #include "tfp_coalesce.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
+#include "tfp_rank_merge.hpp"
 #include "tfp_shardpool.hpp"
 
 namespace {
@@ -679,6 +680,68 @@ int tfp_group_search_batch(tfp_group* g, const tfp_frame* frames, const int64_t*
   if (rc) return rc;
   combine(g, res, nq, out);
   return TFP_OK;
+}
+
+namespace {
+// Ranked search on a group: every shard's first k rows (search(s, out, counts)) mapped to their
+// global keys as key_of does; per query the at most n * k keys sorted descending and k kept
+// (rank_merge_keep). A failing shard fails the call: no partial list goes out.
+int group_rank(tfp_group* g, int32_t nq, const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts,
+               const std::function<int(int, tfp_candidate*, int32_t*)>& search) {
+  if (nq < 0 || !out || !counts) return gfail(g, TFP_E_ARG, "ranked search: bad query count or NULL output");
+  if (k < 1 || k > TFP_RANK_MAX) return gfail(g, TFP_E_ARG, "ranked search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+  if (!valid_params(P)) return gfail(g, TFP_E_ARG, "ranked search: coefs outside [1, 2]");
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  int rc = refresh_ranks(g);
+  if (rc) return rc;
+  const int n = (int)g->eng.size();
+  const size_t per = (size_t)std::max(nq, 1) * k;
+  std::vector<std::vector<tfp_candidate>> res(n, std::vector<tfp_candidate>(per));
+  std::vector<std::vector<int32_t>> cnt(n, std::vector<int32_t>(std::max(nq, 1), 0));
+  rc = run_all(g, [&](int s) { return search(s, res[s].data(), cnt[s].data()); });
+  if (rc) return rc;
+  memset(out, 0, sizeof(tfp_candidate) * (size_t)nq * k);
+  std::vector<unsigned long long> keys((size_t)n * k), top(k);
+  for (int32_t i = 0; i < nq; i++) {
+    int64_t nk = 0;
+    for (int s = 0; s < n; s++)
+      for (int32_t r = 0; r < cnt[s][i]; r++) {
+        const tfp_candidate& c = res[s][(size_t)i * k + r];
+        tfp_result as_result;
+        as_result.found = 1, as_result.match_count = c.match_count, as_result.clip_id = c.clip_id;
+        keys[nk++] = key_of(g, s, as_result);
+      }
+    const int32_t m = tfp::rank_merge_keep(keys.data(), nk, k, top.data());
+    int32_t w = 0;
+    for (int32_t r = 0; r < m; r++) {
+      const auto it = g->key2member.find((int32_t)(uint32_t)(top[r] & 0xffffffffu));
+      if (it == g->key2member.end()) continue;
+      const Member& mb = g->members[it->second];
+      tfp_candidate& c = out[(size_t)i * k + w++];
+      c.match_count = (int32_t)(top[r] >> 32);
+      c.clip_id = mb.shard;
+      snprintf(c.uuid, sizeof c.uuid, "%s", mb.uuid.c_str());
+    }
+    counts[i] = w;
+  }
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_group_search_ranked_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                                  const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
+  if (!g || !qoff) return TFP_E_ARG;
+  return group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    return tfp_search_ranked_batch(g->eng[s], frames, qoff, nq, P, k, o, c);
+  });
+}
+
+int tfp_group_search_ranked_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                                      const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
+  if (!g || !offsets) return TFP_E_ARG;
+  return group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    return tfp_search_ranked_pcm_batch(g->eng[s], pcm, offsets, nq, sr, P, k, o, c);
+  });
 }
 
 namespace {

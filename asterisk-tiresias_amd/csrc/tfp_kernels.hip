@@ -1599,17 +1599,7 @@ constexpr float kVoteScale = 1024.f;      // Bt's box entries: acc = 1024 * scor
 // ---- coefs = 1: vote matrix. score[q][clip] = sum_k N[q][k] * B[k][clip], where N counts the
 // query's non-ignored frames with trunc key k and B[k][clip] = 1 iff the clip has a row in
 // [fmt6(k - tol), fmt6(k + tol)] — exactly the per-frame "group by audio_uuid" hit count.
-// The trunc key of a query frame and whether its SQL runs (prep_boxes' flags & 1, restated for
-// the vote path, which needs nothing else of the box).
-__device__ __forceinline__ bool frame_key(const double* __restrict__ q, int64_t i, const SearchConsts& sc, int32_t& k) {
-  const double q1 = q[2 * i];
-  const double v1 = __builtin_isfinite(q1) ? q1 : 0.0;  // ast_json_real_get(NULL) = 0.0
-  k = (v1 > -2147483649.0 && v1 < 2147483648.0) ? (int32_t)v1 : INT32_MIN;  // (int) truncation, :290
-  const double freq = (double)k;
-  if (sc.has_low && freq < sc.thr_low) return false;   // :293-306
-  if (sc.has_high && freq > sc.thr_high) return false;
-  return __builtin_isfinite(freq - sc.tole) && __builtin_isfinite(freq + sc.tole);
-}
+// frame_key (tfp_kernels.hpp): the trunc key of a query frame and whether its SQL runs.
 
 // The batch's used-key mask over all frames at once (every frame's key is independent of its
 // query): bits set in a 32-word LDS mask per block, ORed into the global mask; a key outside the

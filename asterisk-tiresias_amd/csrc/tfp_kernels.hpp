@@ -54,6 +54,20 @@ struct SearchConsts {
   double tole, thr_low, thr_high;
 };
 
+#ifdef __HIPCC__
+// The trunc key of a query frame and whether its SQL runs (prep_boxes' flags & 1, restated for
+// the vote paths, which need nothing else of the box).
+__device__ __forceinline__ bool frame_key(const double* __restrict__ q, int64_t i, const SearchConsts& sc, int32_t& k) {
+  const double q1 = q[2 * i];
+  const double v1 = __builtin_isfinite(q1) ? q1 : 0.0;  // ast_json_real_get(NULL) = 0.0
+  k = (v1 > -2147483649.0 && v1 < 2147483648.0) ? (int32_t)v1 : INT32_MIN;  // (int) truncation, :290
+  const double freq = (double)k;
+  if (sc.has_low && freq < sc.thr_low) return false;   // :293-306
+  if (sc.has_high && freq > sc.thr_high) return false;
+  return __builtin_isfinite(freq - sc.tole) && __builtin_isfinite(freq + sc.tole);
+}
+#endif
+
 struct SynthSpecDev {
   uint64_t seed;
   int64_t clip;
@@ -279,6 +293,13 @@ hipError_t launch_scan(const FrameBox* boxes, const int64_t* d_qoff, const int64
                        const int32_t* m1s, const int32_t* m2s, const int32_t* cols, int64_t R, const CellCache* cells,
                        const int32_t* d_tiekey, int32_t C, int32_t* d_stamp, int32_t* d_score, int32_t* d_touched,
                        int32_t* d_tcnt, unsigned long long* d_best, hipStream_t s);
+// The same counts, ranked (tfp_rank.hpp): d_keys[(q_begin + q) * K + r] = the query's r-th greatest
+// key, 0 past its last scoring clip (1 <= K <= 32). Scratch as launch_scan: zero on entry and on return.
+hipError_t launch_scan_ranked(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin,
+                              int32_t nq, const int32_t* m1s, const int32_t* m2s, const int32_t* cols, int64_t R,
+                              const CellCache* cells, const int32_t* d_tiekey, int32_t C, int32_t* d_stamp,
+                              int32_t* d_score, int32_t* d_touched, int32_t* d_tcnt, int32_t K,
+                              unsigned long long* d_keys, hipStream_t s);
 
 // The general path's sweep by groups (tfp_scan.hip): every query frame of the batch sorted by
 // (query chunk, key, max2 window); per chunk and window of 16 clip columns, one wave counts, for

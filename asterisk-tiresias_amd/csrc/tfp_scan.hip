@@ -953,6 +953,59 @@ __global__ __launch_bounds__(256) void scan_final_kernel(int32_t q_begin, int32_
   }
 }
 
+// Ranked form of scan_final_kernel (tfp_rank.hpp), one block per query: K rounds of "the greatest
+// key strictly below the previous round's" over the query's touched clips (tie keys of live clips
+// are distinct, so each round takes one clip), from UINT64_MAX down, ended by a round that finds
+// none; then the scratch restored to zero as scan_final_kernel leaves it.
+__global__ __launch_bounds__(256) void rank_final_kernel(int32_t q_begin, const int32_t* __restrict__ tiekey, int32_t C,
+                                                         int32_t* __restrict__ stamp, int32_t* __restrict__ score,
+                                                         const int32_t* __restrict__ touched, int32_t* __restrict__ tcnt,
+                                                         int32_t K, unsigned long long* __restrict__ keys) {
+  __shared__ unsigned long long wmax[2][4];
+  const int wq = blockIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int32_t* st = stamp + (int64_t)wq * C;
+  int32_t* sc = score + (int64_t)wq * C;
+  const int32_t* tl = touched + (int64_t)wq * C;
+  const int32_t n = tcnt[wq];
+  unsigned long long* out = keys + (int64_t)(q_begin + wq) * K;
+  unsigned long long prev = ~0ull;
+  for (int32_t r = 0; r < K; r++) {
+    unsigned long long key = 0;
+    if (prev)  // (0: the rows ran out; the remaining ones are 0)
+      for (int32_t j = threadIdx.x; j < n; j += 256) {
+        const int32_t c = tl[j];
+        const unsigned long long k = ((unsigned long long)(uint32_t)sc[c] << 32) | (uint32_t)tiekey[c];
+        key = (k < prev && k > key) ? k : key;
+      }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(key, o, 64);
+      key = other > key ? other : key;
+    }
+    if (lane == 0) wmax[r & 1][wv] = key;
+    __syncthreads();  // (wmax[r & 1] is next written two rounds on, after the barrier of round r + 1)
+    key = wmax[r & 1][0];
+#pragma unroll
+    for (int i = 1; i < 4; i++) key = wmax[r & 1][i] > key ? wmax[r & 1][i] : key;
+    if (threadIdx.x == 0) out[r] = key;
+    prev = key;
+  }
+  for (int32_t j = threadIdx.x; j < n; j += 256) {
+    const int32_t c = tl[j];
+    sc[c] = 0;
+    st[c] = 0;
+  }
+  __syncthreads();  // every thread has read tcnt[wq]
+  if (threadIdx.x == 0) tcnt[wq] = 0;
+}
+
+// The chunk's counts (score, touched, tcnt) of launch_scan and launch_scan_ranked.
+void launch_scan_counts(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin, int32_t nq,
+                        const int32_t* m1s, const int32_t* m2s, const int32_t* cols, int64_t R, const CellCache* cells,
+                        int32_t C, int32_t* d_stamp, int32_t* d_score, int32_t* d_touched, int32_t* d_tcnt, hipStream_t s,
+                        hipError_t* err);
+
 }  // namespace
 
 hipError_t launch_scan(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin, int32_t nq,
@@ -960,6 +1013,37 @@ hipError_t launch_scan(const FrameBox* boxes, const int64_t* d_qoff, const int64
                        const int32_t* d_tiekey, int32_t C, int32_t* d_stamp, int32_t* d_score, int32_t* d_touched,
                        int32_t* d_tcnt, unsigned long long* d_best, hipStream_t s) {
   if (nq <= 0) return hipSuccess;
+  hipError_t err = hipSuccess;
+  launch_scan_counts(boxes, d_qoff, h_qoff, q_begin, nq, m1s, m2s, cols, R, cells, C, d_stamp, d_score, d_touched, d_tcnt,
+                     s, &err);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(scan_final_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, q_begin, nq, d_tiekey, C, d_stamp, d_score,
+                     d_touched, d_tcnt, d_best);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_ranked(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin,
+                              int32_t nq, const int32_t* m1s, const int32_t* m2s, const int32_t* cols, int64_t R,
+                              const CellCache* cells, const int32_t* d_tiekey, int32_t C, int32_t* d_stamp,
+                              int32_t* d_score, int32_t* d_touched, int32_t* d_tcnt, int32_t K,
+                              unsigned long long* d_keys, hipStream_t s) {
+  if (nq <= 0) return hipSuccess;
+  if (K < 1 || K > 32) return hipErrorInvalidValue;
+  hipError_t err = hipSuccess;
+  launch_scan_counts(boxes, d_qoff, h_qoff, q_begin, nq, m1s, m2s, cols, R, cells, C, d_stamp, d_score, d_touched, d_tcnt,
+                     s, &err);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(rank_final_kernel, dim3(nq), dim3(256), 0, s, q_begin, d_tiekey, C, d_stamp, d_score, d_touched,
+                     d_tcnt, K, d_keys);
+  return hipGetLastError();
+}
+
+namespace {
+
+void launch_scan_counts(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin, int32_t nq,
+                        const int32_t* m1s, const int32_t* m2s, const int32_t* cols, int64_t R, const CellCache* cells,
+                        int32_t C, int32_t* d_stamp, int32_t* d_score, int32_t* d_touched, int32_t* d_tcnt, hipStream_t s,
+                        hipError_t* err) {
   CellView cv;
   memset(&cv, 0, sizeof cv);
   if (cells && cells->valid) {
@@ -976,16 +1060,18 @@ hipError_t launch_scan(const FrameBox* boxes, const int64_t* d_qoff, const int64
   const int64_t nf = h_qoff[q_begin + nq] - h_qoff[q_begin];
   if (cv.valid && nf > 0) {
     const int64_t blocks = (nf + 3) / 4;
-    if (blocks >= INT32_MAX) return hipErrorInvalidValue;
+    if (blocks >= INT32_MAX) {
+      *err = hipErrorInvalidValue;
+      return;
+    }
     hipLaunchKernelGGL(scan_cells_kernel, dim3((unsigned)blocks), dim3(256), 0, s, boxes, d_qoff, q_begin, nq, cv, C,
                        d_score, d_touched, d_tcnt);
   }
   hipLaunchKernelGGL(scan_rows_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, boxes, d_qoff, q_begin, nq, cv, m1s, m2s,
                      cols, R, C, d_stamp, d_score, d_touched, d_tcnt);
-  hipLaunchKernelGGL(scan_final_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, q_begin, nq, d_tiekey, C, d_stamp, d_score,
-                     d_touched, d_tcnt, d_best);
-  return hipGetLastError();
 }
+
+}  // namespace
 
 
 // ---- wide max2 windows: sweep by groups ----------------------------------------------------

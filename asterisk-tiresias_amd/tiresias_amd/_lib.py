@@ -41,6 +41,13 @@ class Result(C.Structure):
                 ("clip_id", C.c_int32), ("uuid", C.c_char * 64)]
 
 
+TFP_RANK_MAX = 32
+
+
+class Candidate(C.Structure):
+    _fields_ = [("match_count", C.c_int32), ("clip_id", C.c_int32), ("uuid", C.c_char * 64)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("clip", C.c_int64), ("offset", C.c_int64)]
 
@@ -121,6 +128,13 @@ _SIGS = {
     "tfp_group_stream_destroy": (None, [P]),
     "tfp_group_stream_reset": (C.c_int, [P, C.c_int32]),
     "tfp_group_stream_push": (C.c_int, [P, P, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_search_ranked": (C.c_int, [P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, C.POINTER(C.c_int32)]),
+    "tfp_search_ranked_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P]),
+    "tfp_search_ranked_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P]),
+    "tfp_rank_stats": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tfp_group_search_ranked_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P]),
+    "tfp_group_search_ranked_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32, P,
+                                                    P]),
 }
 
 _lib = None

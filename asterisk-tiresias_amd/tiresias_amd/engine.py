@@ -6,7 +6,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import Frame, Result, SearchParams, SynthSpec, TfpError, check, lib
+from ._lib import Candidate, Frame, Result, SearchParams, SynthSpec, TfpError, check, lib
 
 FRAME_DTYPE = np.dtype([("frame_idx", "<i4"), ("m1", "<i4"), ("m2", "<i4"), ("reserved", "<i4"),
                         ("q1", "<f8"), ("q2", "<f8")])
@@ -273,6 +273,43 @@ class Engine:
                                              C.byref(p), res))
         return self._results(res, nq)
 
+    # ---- ranked search: per query the first k rows of the reference's result set, in rank order
+    @staticmethod
+    def _candidates(out, counts, nq, k):
+        return [[{"audio_uuid": c.uuid.decode(), "match_count": c.match_count, "clip_id": c.clip_id}
+                 for c in out[q * k:q * k + counts[q]]] for q in range(nq)]
+
+    def search_ranked_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, k: int):
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        nq, k = len(qoffsets) - 1, int(k)
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        self._chk(lib().tfp_search_ranked_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, nq, C.byref(p), k,
+                                                out, counts))
+        return self._candidates(out, counts, nq, k)
+
+    def search_ranked(self, frames: np.ndarray, p: SearchParams, k: int):
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        k = int(k)
+        out, count = (Candidate * max(1, k))(), C.c_int32()
+        self._chk(lib().tfp_search_ranked(self._h, frames.ctypes.data, len(frames), C.byref(p), k, out, C.byref(count)))
+        return self._candidates(out, [count.value], 1, k)[0]
+
+    def search_ranked_pcm_batch(self, pcm: np.ndarray, offsets, p: SearchParams, k: int, sample_rate: int = 8000):
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq, k = len(offsets) - 1, int(k)
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        self._chk(lib().tfp_search_ranked_pcm_batch(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, sample_rate,
+                                                    C.byref(p), k, out, counts))
+        return self._candidates(out, counts, nq, k)
+
+    def rank_stats(self) -> dict:
+        """tfp_rank_stats: ranked batches served by the vote form and by the general form."""
+        v, g = C.c_int64(), C.c_int64()
+        self._chk(lib().tfp_rank_stats(self._h, C.byref(v), C.byref(g)))
+        return {"vote_batches": v.value, "general_batches": g.value}
+
     # ---- device-resident paths (pointers are raw device addresses, e.g. tensor.data_ptr())
     def plan(self, offsets, sample_rate: int = 8000) -> "Plan":
         return Plan(self, offsets, sample_rate)
@@ -501,6 +538,25 @@ class Group:
         self._chk(lib().tfp_group_search_f32_batch(self._h, x.ctypes.data, offsets.ctypes.data, nq, sample_rate,
                                                    C.byref(p), res))
         return Engine._results(res, nq)
+
+    def search_ranked_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, k: int):
+        """Engine.search_ranked_batch over every shard's clips (clip_id = the shard holding the clip)."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        nq, k = len(qoffsets) - 1, int(k)
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        self._chk(lib().tfp_group_search_ranked_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, nq, C.byref(p),
+                                                      k, out, counts))
+        return Engine._candidates(out, counts, nq, k)
+
+    def search_ranked_pcm_batch(self, pcm, offsets, p: SearchParams, k: int, sample_rate: int = 8000):
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq, k = len(offsets) - 1, int(k)
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        self._chk(lib().tfp_group_search_ranked_pcm_batch(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, sample_rate,
+                                                          C.byref(p), k, out, counts))
+        return Engine._candidates(out, counts, nq, k)
 
 
 class GroupStream:

@@ -26,8 +26,8 @@ import wave
 import numpy as np
 
 from . import dbio
-from ._lib import TfpError
-from .engine import Engine, params, read_wav, read_wav_f32
+from ._lib import TFP_RANK_MAX, TfpError
+from .engine import Engine, frame_count as frame_count_of, params, read_wav, read_wav_f32
 
 TFP_E_FORMAT = -8
 
@@ -261,3 +261,33 @@ class FpHandler:
         info["frame_count"] = hit["frame_count"]
         info["match_count"] = hit["match_count"]
         return info
+
+    def fp_search_fingerprint_candidates(self, context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high,
+                                         max_results):
+        """The first max_results rows of the result query fp_search_fingerprint_info reads one row of
+        (fp_handler.c:367-374), each as that call's dict, in rank order; [] where it returns NULL. A
+        row whose audio_list entry is missing is skipped (the reference returns NULL for it)."""
+        if context is None or filename is None:
+            return []
+        if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1:
+            return []
+        try:
+            pcm, sr = read_audio(filename)
+        except TfpError:
+            return []
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        k = min(int(max_results), TFP_RANK_MAX)
+        if pcm.dtype == np.float32:
+            fr = self.engine.fingerprint_f32_batch(pcm, [0, len(pcm)], sr)
+            rows, frame_count = self.engine.search_ranked(fr, p, k), len(fr)
+        else:
+            rows, frame_count = self.engine.search_ranked_pcm_batch(pcm, [0, len(pcm)], p, k, sr)[0], frame_count_of(len(pcm))
+        out = []
+        for row in rows:
+            info = self._audio_list_info(row["audio_uuid"])
+            if info is None:
+                continue
+            info["frame_count"] = frame_count
+            info["match_count"] = row["match_count"]
+            out.append(info)
+        return out

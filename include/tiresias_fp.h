@@ -266,6 +266,36 @@ int tfp_search_q_device(tfp_engine* eng, const double* d_q, const int64_t* qoffs
 /* Map a tie-break key from tfp_search_device back to the uuid (this engine's clips only). */
 int tfp_index_uuid_of_key(tfp_engine* eng, int32_t key, char* uuid, int32_t len);
 
+/* ---- ranked search: the result query's first k rows (fp_handler.c:367-374) ------------ */
+/* The reference's result query, "select *, count(*) from temp group by audio_uuid order by
+ * count(*) DESC" (fp_handler.c:367-374), yields one row per clip that matched a frame; the
+ * reference reads the first (:376-392). SQLite returns the rows by count descending, tied counts
+ * by audio_uuid descending. These calls return the first k rows, so a caller sees the runner-up
+ * and the winner's margin over it. out[q * k + r] is row r of query q; counts[q] = min(k, clips
+ * with a non-zero count); entries past counts[q] are zeroed. Row 0 is what tfp_search_batch
+ * returns for the same call. A query with no frames, or with every frame ignored, has counts[q] =
+ * 0. k < 1, k > TFP_RANK_MAX or coefs outside [1,2] is TFP_E_ARG. Calls are not coalesced. */
+#define TFP_RANK_MAX 32
+typedef struct tfp_candidate {   /* one row of the reference's result set (fp_handler.c:367-374) */
+  int32_t match_count;           /* count(*) of this audio_uuid, > 0 */
+  int32_t clip_id;               /* engine clip id (group calls: the shard, as tfp_result) */
+  char uuid[64];                 /* audio_uuid, NUL-terminated */
+} tfp_candidate;
+/* One query, fp_handler.c:367-374 read to row k; out[k], *count as counts[0]. */
+int tfp_search_ranked(tfp_engine* eng, const tfp_frame* frames, int32_t nframes, const tfp_search_params* params,
+                      int32_t k, tfp_candidate* out, int32_t* count);
+/* fp_handler.c:367-374 per query; qoffsets[nqueries+1] index into frames, out[nqueries*k], counts[nqueries]. */
+int tfp_search_ranked_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                            const tfp_search_params* params, int32_t k, tfp_candidate* out, int32_t* counts);
+/* PCM in (fp_handler.c:275 + :287-374), rows out: the queries as tfp_search_pcm_batch takes them. */
+int tfp_search_ranked_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                int32_t sample_rate, const tfp_search_params* params, int32_t k, tfp_candidate* out,
+                                int32_t* counts);
+/* Ranked batches served so far by the vote form (coefs = 1: the rows of fp_handler.c:367-374 counted
+ * from the key bitsets) and by the general form (coefs = 2, or a frame value outside the key range:
+ * counted over the sorted rows). Either pointer may be NULL. */
+int tfp_rank_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches);
+
 /* ---- live channels: rolling fingerprint + match (configs[4]) --------------------------
  * The dialplan app records `duration` ms of a channel to a WAV and searches it
  * (application_handler.c:152-185, record_voice :248-312). A stream keeps the most recent
@@ -331,6 +361,16 @@ int tfp_group_search_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* 
                                int32_t sample_rate, const tfp_search_params* params, tfp_result* out);
 int tfp_group_search_f32_batch(tfp_group* g, const float* x, const int64_t* offsets, int32_t nqueries,
                                int32_t sample_rate, const tfp_search_params* params, tfp_result* out);
+/* Ranked search on a group (fp_handler.c:367-374 read to row k, as tfp_search_ranked_batch): every
+ * shard returns its first k rows, and per query the greatest k of their global keys are kept, which
+ * are the first k rows over all shards' clips. tfp_candidate.clip_id = the shard holding the clip.
+ * A failing shard fails the call. */
+int tfp_group_search_ranked_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                                  const tfp_search_params* params, int32_t k, tfp_candidate* out, int32_t* counts);
+/* The same from PCM (fp_handler.c:275 + :287-374), every shard fingerprinting the batch. */
+int tfp_group_search_ranked_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                      int32_t sample_rate, const tfp_search_params* params, int32_t k,
+                                      tfp_candidate* out, int32_t* counts);
 /* tfp_search_pcm_gather and the coalescing of concurrent calls (as for one engine) on a group: the
  * channel threads' batch-1 searches through the shim run as shared batches on every GPU. */
 int tfp_group_search_pcm_gather(tfp_group* g, const int16_t* const* pcms, const int64_t* nsamples, int32_t nqueries,

@@ -707,6 +707,72 @@ struct ast_json* fp_search_fingerprint_info(const char* context, const char* fil
 	return search_result(&r);
 }
 
+/* New: the first max_results rows of the result query fp_search_fingerprint_info reads one row of
+ * ("select *, count(*) from temp group by audio_uuid order by count(*) DESC", fp_handler.c:367-374),
+ * as a JSON array of that call's result objects in rank order (tfp_group_search_ranked_pcm_batch).
+ * NULL where fp_search_fingerprint_info returns NULL before the query; an empty array for NOTFOUND. */
+struct ast_json* fp_search_fingerprint_candidates(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results)
+{
+	int16_t* pcm;
+	float* x;
+	int64_t cap, ns, off[2], nf = 0;
+	int32_t sr, count = 0;
+	int rc, k, i;
+	tfp_search_params p;
+	tfp_candidate cand[TFP_RANK_MAX];
+	tfp_result r;
+	struct ast_json* j_res;
+	struct ast_json* j_tmp;
+
+	if((filename == NULL) || (max_results < 1)) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	if(search_params(&p, context, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	if(read_audio(filename, &pcm, &cap, &x, &ns, &sr) != 0) {
+		return NULL;
+	}
+	k = max_results > TFP_RANK_MAX ? TFP_RANK_MAX : max_results;
+	off[0] = 0;
+	off[1] = ns;
+	nf = tfp_frame_count(ns); /* ast_json_array_size(j_fprints), fp_handler.c:286 */
+	if(pcm != NULL) {
+		rc = tfp_group_search_ranked_pcm_batch(g_tfp, pcm, off, 1, sr, &p, k, cand, &count);
+	}
+	else {
+		/* audio tfp_wav_decode refuses (fp32 hop values): its frames, then the frames form */
+		tfp_frame* fr = ast_calloc(nf > 0 ? nf : 1, sizeof(*fr));
+		int64_t qoff[2] = {0, 0};
+		rc = fr ? tfp_group_fingerprint_f32_batch(g_tfp, x, off, 1, sr, fr, nf, &qoff[1]) : TFP_E_NOMEM;
+		if(rc == TFP_OK) {
+			rc = tfp_group_search_ranked_batch(g_tfp, fr, qoff, 1, &p, k, cand, &count);
+		}
+		ast_free(fr);
+	}
+	pcm_put(pcm, cap);
+	ast_free(x);
+	if(rc != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not search %s: %s\n", filename, tfp_group_last_error(g_tfp));
+		return NULL;
+	}
+	j_res = ast_json_array_create();
+	for(i = 0; i < count; i++) {
+		memset(&r, 0, sizeof(r));
+		r.found = 1;
+		r.match_count = cand[i].match_count;
+		r.frame_count = (int32_t)nf;
+		snprintf(r.uuid, sizeof(r.uuid), "%s", cand[i].uuid);
+		j_tmp = search_result(&r); /* a row whose audio_list entry is missing is skipped */
+		if(j_tmp != NULL) {
+			ast_json_array_append(j_res, j_tmp);
+		}
+	}
+	return j_res;
+}
+
 /* ---- live channels: the dialplan application's recording without the /tmp WAV -------------
  * application_handler.c:152-185 records `duration` ms of the channel's voice frames
  * (record_voice, :248-312) into /tmp/tiresias-UUID.wav and searches that file. A channel keeps the

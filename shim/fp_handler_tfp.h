@@ -41,6 +41,15 @@ void fp_set_gpu_devices(const char* list);
  * searches went through the coalescer as *batches batches. false before fp_init. */
 bool fp_get_search_stats(int64_t* calls, int64_t* batches);
 
+/* New: ranked search. fp_search_fingerprint_info returns the first row of its result query
+ * (src/fp_handler.c:367-374: count(*) descending, tied counts by audio_uuid descending); this
+ * returns the first max_results rows (at most 32) as a JSON array of the same objects, each with
+ * frame_count and match_count, in rank order: element 0 is fp_search_fingerprint_info's answer,
+ * element 1 the runner-up a dialplan compares it with. Empty array: NOTFOUND. NULL: bad arguments
+ * or an unreadable file. A row whose audio_list entry is missing is skipped. */
+struct ast_json* fp_search_fingerprint_candidates(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
+
 /* New: a live channel, for the dialplan application's record loop (application_handler.c:152-185,
  * record_voice :248-312) without the /tmp WAV round trip. Open one per call with max_ms >= the
  * recording's duration, push every voice frame's SLIN samples as it is read (160 per 20 ms frame
