@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/tiresias_fp.h"
+#include "tfp_align.hpp"
 #include "tfp_coalesce.hpp"
 #include "tfp_index.hpp"
 #include "tfp_internal.hpp"
@@ -272,6 +273,12 @@ struct tfp_engine {
   DevBuf rank_part, rank_keys;
   HostBuf rank_pin;
   int64_t n_rank_vote = 0, n_rank_general = 0;
+  // aligned search (align_core): the batch's frame boxes (its own: a device-form search may still
+  // read e->boxes on the caller's stream), the pairs, the bands' partial keys, the results, the
+  // pinned copy of pairs and results, and the batches / pairs aligned so far
+  DevBuf align_boxes, align_pairs, align_part, align_out;
+  HostBuf align_pin;
+  int64_t n_align_batches = 0, n_align_pairs = 0;
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   int32_t class_ku_max = 10;  // TFP_VOTE_CLASS_MAX: pattern-class vote up to this many used keys (-1: always the GEMM)
@@ -1899,6 +1906,75 @@ int rank_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, 
   return TFP_OK;
 }
 
+// ---- aligned search (tfp_align.hpp): out[q * K + r] = the alignment of query q with clip
+// ids[q * K + r] (-1: none, a zeroed row). The clips' rows are read where they lie in the staging
+// arrays (Clip::off under the engine lock), so no index build is needed and a clip of the live
+// delta aligns like any other. qo: the queries' relative frame offsets into d_q.
+static_assert(sizeof(tfp_alignment) == sizeof(AlignOut), "tfp_align.hpp and the public header agree");
+
+int align_core(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const tfp_search_params* P,
+               int32_t K, const int32_t* ids, tfp_alignment* out, hipStream_t s) {
+  const int64_t npairs = (int64_t)nq * K;
+  memset(out, 0, sizeof(tfp_alignment) * (size_t)npairs);
+  std::vector<AlignPair> pairs((size_t)npairs, AlignPair{0, 0, 0, 0});
+  int64_t max_bands = 0, named = 0;
+  for (int64_t p = 0; p < npairs; p++) {
+    const int32_t id = ids[p];
+    if (id == -1) continue;
+    if (id < 0 || (size_t)id >= e->clips.size() || !e->clips[id].alive)
+      return fail(e, TFP_E_NOENT, "aligned search: clip id %d is not in the index", id);
+    const Clip& c = e->clips[id];
+    const int64_t F = qo[p / K + 1] - qo[p / K], N = c.nrows;
+    if (F + N > (int64_t(1) << 31))
+      return fail(e, TFP_E_CAPACITY, "aligned search: %lld frames against %lld rows", (long long)F, (long long)N);
+    named++;
+    if (F <= 0 || N <= 0) continue;
+    pairs[p] = AlignPair{c.off, qo[p / K], (int32_t)N, (int32_t)F};
+    max_bands = std::max(max_bands, align_bands(F, N));
+  }
+  if (!max_bands) return TFP_OK;  // nothing to compare: every row stays zero
+  const SearchConsts sc = search_consts(P);
+  const int64_t nf = qo[nq];
+  HIPCHK(e, e->align_boxes.reserve(sizeof(FrameBox) * (nf + 1)));
+  HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->align_boxes.as<FrameBox>(), nullptr, 0, s));
+  // pairs in chunks of <= 256 MB of partial keys (and of the launch grid's second dimension)
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({(int64_t(1) << 25) / max_bands, kAlignMaxPairs, npairs}));
+  const size_t pbytes = sizeof(AlignPair) * (size_t)npairs, obytes = sizeof(AlignOut) * (size_t)npairs;
+  HIPCHK(e, e->align_pairs.reserve(pbytes));
+  HIPCHK(e, e->align_part.reserve(sizeof(unsigned long long) * (size_t)(chunk * max_bands)));
+  HIPCHK(e, e->align_out.reserve(obytes));
+  HIPCHK(e, e->align_pin.reserve(pbytes + obytes));
+  char* pin = e->align_pin.as<char>();
+  memcpy(pin, pairs.data(), pbytes);
+  HIPCHK(e, hipMemcpyAsync(e->align_pairs.p, pin, pbytes, hipMemcpyHostToDevice, s));
+  for (int64_t p0 = 0; p0 < npairs; p0 += chunk) {
+    const int32_t n = (int32_t)std::min<int64_t>(chunk, npairs - p0);
+    HIPCHK(e, launch_align(e->align_pairs.as<AlignPair>() + p0, n, max_bands, e->align_boxes.as<FrameBox>(),
+                           e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(), sc.coefs == 2,
+                           e->align_part.as<unsigned long long>(), e->align_out.as<AlignOut>() + p0, s));
+  }
+  HIPCHK(e, hipMemcpyAsync(pin + pbytes, e->align_out.p, obytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  memcpy(out, pin + pbytes, obytes);
+  e->n_align_batches++;
+  e->n_align_pairs += named;
+  return TFP_OK;
+}
+
+std::vector<int64_t> relative_offsets(const int64_t* off, int32_t nq) {
+  std::vector<int64_t> qo(off, off + nq + 1);
+  for (auto& v : qo) v -= off[0];
+  return qo;
+}
+
+// The candidates' clip ids as align_core takes them: -1 past counts[q].
+std::vector<int32_t> candidate_ids(const tfp_candidate* cand, const int32_t* counts, int32_t nq, int32_t K) {
+  std::vector<int32_t> ids((size_t)nq * K, -1);
+  for (int32_t q = 0; q < nq; q++)
+    for (int32_t r = 0; r < counts[q]; r++) ids[(size_t)q * K + r] = cand[(size_t)q * K + r].clip_id;
+  return ids;
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -2391,10 +2467,21 @@ int tfp_search(tfp_engine* e, const tfp_frame* frames, int32_t nframes, const tf
 // ---- ranked search: the result query's first k rows (fp_handler.c:367-374) ----------------
 static_assert(kRankMax == TFP_RANK_MAX, "tfp_rank.hpp and the public header agree");
 
-int tfp_search_ranked_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
-                            const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
-  if (!e || !qoff) return TFP_E_ARG;
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
+namespace {
+// The queries' frame values (q1, q2) on the device (e->q), as the frames forms search them.
+int upload_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq) {
+  const int64_t nf = qoff[nq] - qoff[0];
+  std::vector<double> q(2 * (nf + 1));
+  for (int64_t i = 0; i < nf; i++) {
+    q[2 * i] = frames[qoff[0] + i].q1;
+    q[2 * i + 1] = frames[qoff[0] + i].q2;
+  }
+  return upload(e, e->q, q.data(), sizeof(double) * q.size());
+}
+
+// tfp_search_ranked_batch, and with align its rows' alignments (tfp_search_aligned_batch).
+int search_ranked_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                         const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align) {
   int rc = rank_args(e, P, k, nq, out, counts);
   if (rc) return rc;
   for (int32_t i = 0; i < nq; i++)
@@ -2404,16 +2491,22 @@ int tfp_search_ranked_batch(tfp_engine* e, const tfp_frame* frames, const int64_
   std::vector<unsigned long long> keys((size_t)nq * k, 0ull);
   if (nq) {
     HIPCHK(e, hipSetDevice(e->device));
-    std::vector<double> q(2 * (nf + 1));
-    for (int64_t i = 0; i < nf; i++) {
-      q[2 * i] = frames[qoff[0] + i].q1;
-      q[2 * i + 1] = frames[qoff[0] + i].q2;
-    }
-    if ((rc = upload(e, e->q, q.data(), sizeof(double) * q.size()))) return rc;
+    if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
     if ((rc = rank_core(e, qoff, nq, e->q.as<double>(), P, k, keys, e->stream))) return rc;
   }
   fill_candidates(e, keys, nq, k, out, counts);
+  if (align && nq)  // (the frame values are still in e->q)
+    return align_core(e, relative_offsets(qoff, nq), nq, e->q.as<double>(), P, k, candidate_ids(out, counts, nq, k).data(),
+                      align, e->stream);
   return TFP_OK;
+}
+}  // namespace
+
+int tfp_search_ranked_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                            const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  return search_ranked_frames(e, frames, qoff, nq, P, k, out, counts, nullptr);
 }
 
 int tfp_search_ranked(tfp_engine* e, const tfp_frame* frames, int32_t nframes, const tfp_search_params* P, int32_t k,
@@ -2423,10 +2516,11 @@ int tfp_search_ranked(tfp_engine* e, const tfp_frame* frames, int32_t nframes, c
   return tfp_search_ranked_batch(e, frames, qoff, 1, P, k, out, count);
 }
 
-int tfp_search_ranked_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
-                                const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
-  if (!e || !offsets) return TFP_E_ARG;
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
+namespace {
+// tfp_search_ranked_pcm_batch, and with align its rows' alignments (tfp_search_aligned_pcm_batch):
+// the frame values stay on the device (e->db) for both.
+int search_ranked_pcm(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                      const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align) {
   int rc = rank_args(e, P, k, nq, out, counts);
   if (rc) return rc;
   for (int32_t i = 0; i < nq; i++)
@@ -2447,6 +2541,71 @@ int tfp_search_ranked_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t
     e->stage_pending = false;
   }
   fill_candidates(e, keys, nq, k, out, counts);
+  if (align && nq) {
+    memset(align, 0, sizeof(tfp_alignment) * (size_t)nq * k);
+    if (foff[nq] > 0)
+      return align_core(e, foff, nq, e->db.as<double>(), P, k, candidate_ids(out, counts, nq, k).data(), align, e->stream);
+  }
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_search_ranked_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                                const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  return search_ranked_pcm(e, pcm, offsets, nq, sr, P, k, out, counts, nullptr);
+}
+
+// ---- aligned search (tfp_align.hpp) -------------------------------------------------------
+namespace {
+int align_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, const void* out) {
+  if (nq < 0 || !out) return fail(e, TFP_E_ARG, "aligned search: bad query count or NULL output");
+  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "aligned search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+  if (!valid_params(P)) return fail(e, TFP_E_ARG, "aligned search: coefs outside [1, 2]");
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_align_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq, const tfp_search_params* P,
+                    const int32_t* clip_ids, int32_t k, tfp_alignment* out) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = align_args(e, P, k, nq, out);
+  if (rc) return rc;
+  if (nq && !clip_ids) return fail(e, TFP_E_ARG, "aligned search: clip_ids is NULL");
+  for (int32_t i = 0; i < nq; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  if (!nq) return TFP_OK;
+  if (qoff[nq] > qoff[0] && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
+  return align_core(e, relative_offsets(qoff, nq), nq, e->q.as<double>(), P, k, clip_ids, out, e->stream);
+}
+
+int tfp_search_aligned_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                             const tfp_search_params* P, int32_t k, tfp_candidate* cand, tfp_alignment* align,
+                             int32_t* counts) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!align) return fail(e, TFP_E_ARG, "aligned search: NULL output");
+  return search_ranked_frames(e, frames, qoff, nq, P, k, cand, counts, align);
+}
+
+int tfp_search_aligned_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                                 const tfp_search_params* P, int32_t k, tfp_candidate* cand, tfp_alignment* align,
+                                 int32_t* counts) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!align) return fail(e, TFP_E_ARG, "aligned search: NULL output");
+  return search_ranked_pcm(e, pcm, offsets, nq, sr, P, k, cand, counts, align);
+}
+
+int tfp_align_stats(tfp_engine* e, int64_t* batches, int64_t* pairs) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (batches) *batches = e->n_align_batches;
+  if (pairs) *pairs = e->n_align_pairs;
   return TFP_OK;
 }
 

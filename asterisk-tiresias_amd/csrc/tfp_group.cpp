@@ -686,8 +686,10 @@ namespace {
 // Ranked search on a group: every shard's first k rows (search(s, out, counts)) mapped to their
 // global keys as key_of does; per query the at most n * k keys sorted descending and k kept
 // (rank_merge_keep). A failing shard fails the call: no partial list goes out.
+// kept (optional): the member behind each row of out, -1 past counts[q] (the aligned search reads
+// the shard and the shard-local clip id from it).
 int group_rank(tfp_group* g, int32_t nq, const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts,
-               const std::function<int(int, tfp_candidate*, int32_t*)>& search) {
+               const std::function<int(int, tfp_candidate*, int32_t*)>& search, std::vector<int32_t>* kept = nullptr) {
   if (nq < 0 || !out || !counts) return gfail(g, TFP_E_ARG, "ranked search: bad query count or NULL output");
   if (k < 1 || k > TFP_RANK_MAX) return gfail(g, TFP_E_ARG, "ranked search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
   if (!valid_params(P)) return gfail(g, TFP_E_ARG, "ranked search: coefs outside [1, 2]");
@@ -701,6 +703,7 @@ int group_rank(tfp_group* g, int32_t nq, const tfp_search_params* P, int32_t k, 
   rc = run_all(g, [&](int s) { return search(s, res[s].data(), cnt[s].data()); });
   if (rc) return rc;
   memset(out, 0, sizeof(tfp_candidate) * (size_t)nq * k);
+  if (kept) kept->assign((size_t)nq * k, -1);
   std::vector<unsigned long long> keys((size_t)n * k), top(k);
   for (int32_t i = 0; i < nq; i++) {
     int64_t nk = 0;
@@ -717,6 +720,7 @@ int group_rank(tfp_group* g, int32_t nq, const tfp_search_params* P, int32_t k, 
       const auto it = g->key2member.find((int32_t)(uint32_t)(top[r] & 0xffffffffu));
       if (it == g->key2member.end()) continue;
       const Member& mb = g->members[it->second];
+      if (kept) (*kept)[(size_t)i * k + w] = it->second;
       tfp_candidate& c = out[(size_t)i * k + w++];
       c.match_count = (int32_t)(top[r] >> 32);
       c.clip_id = mb.shard;
@@ -742,6 +746,42 @@ int tfp_group_search_ranked_pcm_batch(tfp_group* g, const int16_t* pcm, const in
   return group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
     return tfp_search_ranked_pcm_batch(g->eng[s], pcm, offsets, nq, sr, P, k, o, c);
   });
+}
+
+// Aligned search on a group: the ranked search above, then every kept row aligned on the shard
+// that holds its clip (tfp_align_batch with the shard-local clip id; -1 for the other shards' rows).
+int tfp_group_search_aligned_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                                   const tfp_search_params* P, int32_t k, tfp_candidate* cand, tfp_alignment* align,
+                                   int32_t* counts) {
+  if (!g || !qoff) return TFP_E_ARG;
+  if (!align) return gfail(g, TFP_E_ARG, "aligned search: NULL output");
+  std::lock_guard<std::recursive_mutex> lk(g->mu);  // (the shards' clips stay as ranked until they are aligned)
+  std::vector<int32_t> kept;
+  int rc = group_rank(
+      g, nq, P, k, cand, counts,
+      [&](int s, tfp_candidate* o, int32_t* c) { return tfp_search_ranked_batch(g->eng[s], frames, qoff, nq, P, k, o, c); },
+      &kept);
+  if (rc) return rc;
+  const size_t np = (size_t)nq * k;
+  memset(align, 0, sizeof(tfp_alignment) * np);
+  if (!np) return TFP_OK;
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<int32_t>> ids(n, std::vector<int32_t>(np, -1));
+  std::vector<char> used(n, 0);
+  for (size_t p = 0; p < np; p++)
+    if (kept[p] >= 0) {
+      const Member& mb = g->members[kept[p]];
+      ids[mb.shard][p] = mb.id;
+      used[mb.shard] = 1;
+    }
+  std::vector<std::vector<tfp_alignment>> res(n, std::vector<tfp_alignment>(np));
+  rc = run_all(g, [&](int s) {
+    return used[s] ? tfp_align_batch(g->eng[s], frames, qoff, nq, P, ids[s].data(), k, res[s].data()) : TFP_OK;
+  });
+  if (rc) return rc;
+  for (size_t p = 0; p < np; p++)
+    if (kept[p] >= 0) align[p] = res[g->members[kept[p]].shard][p];
+  return TFP_OK;
 }
 
 namespace {

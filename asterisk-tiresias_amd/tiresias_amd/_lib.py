@@ -48,6 +48,11 @@ class Candidate(C.Structure):
     _fields_ = [("match_count", C.c_int32), ("clip_id", C.c_int32), ("uuid", C.c_char * 64)]
 
 
+class Alignment(C.Structure):
+    _fields_ = [("aligned_count", C.c_int32), ("offset", C.c_int32), ("first_frame", C.c_int32),
+                ("last_frame", C.c_int32)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("clip", C.c_int64), ("offset", C.c_int64)]
 
@@ -135,6 +140,12 @@ _SIGS = {
     "tfp_group_search_ranked_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P]),
     "tfp_group_search_ranked_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32, P,
                                                     P]),
+    "tfp_align_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P]),
+    "tfp_search_aligned_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P, P]),
+    "tfp_search_aligned_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P,
+                                               P]),
+    "tfp_align_stats": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tfp_group_search_aligned_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P, P]),
 }
 
 _lib = None

@@ -6,7 +6,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import Candidate, Frame, Result, SearchParams, SynthSpec, TfpError, check, lib
+from ._lib import Alignment, Candidate, Frame, Result, SearchParams, SynthSpec, TfpError, check, lib
 
 FRAME_DTYPE = np.dtype([("frame_idx", "<i4"), ("m1", "<i4"), ("m2", "<i4"), ("reserved", "<i4"),
                         ("q1", "<f8"), ("q2", "<f8")])
@@ -304,6 +304,61 @@ class Engine:
                                                     C.byref(p), k, out, counts))
         return self._candidates(out, counts, nq, k)
 
+    # ---- aligned search: where in each candidate clip the query matches (tfp_alignment)
+    @staticmethod
+    def _alignment(a):
+        return {"aligned_count": a.aligned_count, "offset": a.offset, "first_frame": a.first_frame,
+                "last_frame": a.last_frame}
+
+    @staticmethod
+    def _aligned(out, align, counts, nq, k):
+        """The ranked rows, each with its alignment's four fields."""
+        rows = Engine._candidates(out, counts, nq, k)
+        for q in range(nq):
+            for r, row in enumerate(rows[q]):
+                row.update(Engine._alignment(align[q * k + r]))
+        return rows
+
+    def align_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, clip_ids, k: int):
+        """tfp_align_batch: per query k alignment dicts, query q against clip_ids[q * k + r] (-1: a zeroed row)."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        nq, k = len(qoffsets) - 1, int(k)
+        ids = np.ascontiguousarray(clip_ids, np.int32).reshape(-1)
+        if len(ids) != nq * max(k, 0):
+            raise ValueError("clip_ids must hold nqueries * k ids")
+        out = (Alignment * max(1, nq * max(k, 1)))()
+        self._chk(lib().tfp_align_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, nq, C.byref(p),
+                                        ids.ctypes.data, k, out))
+        return [[self._alignment(out[q * k + r]) for r in range(k)] for q in range(nq)]
+
+    def search_aligned_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, k: int):
+        """search_ranked_batch's rows, each with aligned_count, offset, first_frame, last_frame."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        nq, k = len(qoffsets) - 1, int(k)
+        n = max(1, nq * max(k, 1))
+        out, align, counts = (Candidate * n)(), (Alignment * n)(), (C.c_int32 * max(1, nq))()
+        self._chk(lib().tfp_search_aligned_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, nq, C.byref(p), k,
+                                                 out, align, counts))
+        return self._aligned(out, align, counts, nq, k)
+
+    def search_aligned_pcm_batch(self, pcm: np.ndarray, offsets, p: SearchParams, k: int, sample_rate: int = 8000):
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq, k = len(offsets) - 1, int(k)
+        n = max(1, nq * max(k, 1))
+        out, align, counts = (Candidate * n)(), (Alignment * n)(), (C.c_int32 * max(1, nq))()
+        self._chk(lib().tfp_search_aligned_pcm_batch(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, sample_rate,
+                                                     C.byref(p), k, out, align, counts))
+        return self._aligned(out, align, counts, nq, k)
+
+    def align_stats(self) -> dict:
+        """tfp_align_stats: batches that reached the alignment kernels and the pairs they named."""
+        b, n = C.c_int64(), C.c_int64()
+        self._chk(lib().tfp_align_stats(self._h, C.byref(b), C.byref(n)))
+        return {"batches": b.value, "pairs": n.value}
+
     def rank_stats(self) -> dict:
         """tfp_rank_stats: ranked batches served by the vote form and by the general form."""
         v, g = C.c_int64(), C.c_int64()
@@ -548,6 +603,17 @@ class Group:
         self._chk(lib().tfp_group_search_ranked_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, nq, C.byref(p),
                                                       k, out, counts))
         return Engine._candidates(out, counts, nq, k)
+
+    def search_aligned_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, k: int):
+        """Engine.search_aligned_batch over every shard's clips, each row aligned on the shard holding its clip."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        nq, k = len(qoffsets) - 1, int(k)
+        n = max(1, nq * max(k, 1))
+        out, align, counts = (Candidate * n)(), (Alignment * n)(), (C.c_int32 * max(1, nq))()
+        self._chk(lib().tfp_group_search_aligned_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, nq, C.byref(p),
+                                                       k, out, align, counts))
+        return Engine._aligned(out, align, counts, nq, k)
 
     def search_ranked_pcm_batch(self, pcm, offsets, p: SearchParams, k: int, sample_rate: int = 8000):
         pcm = np.ascontiguousarray(pcm, np.int16)

@@ -291,3 +291,35 @@ class FpHandler:
             info["match_count"] = row["match_count"]
             out.append(info)
         return out
+
+    def fp_search_fingerprint_aligned(self, context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high,
+                                      max_results):
+        """fp_search_fingerprint_candidates' rows, each with where in the clip the recording lies:
+        aligned_count (the hits that agree on one time offset), offset (query frame i lies at clip
+        frame i + offset), first_frame and last_frame (tfp_alignment). The reference's result query
+        (fp_handler.c:367-374) counts the frames that hit; it never reads the rows' frame_idx."""
+        if context is None or filename is None:
+            return []
+        if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1:
+            return []
+        try:
+            pcm, sr = read_audio(filename)
+        except TfpError:
+            return []
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        k = min(int(max_results), TFP_RANK_MAX)
+        if pcm.dtype == np.float32:
+            fr = self.engine.fingerprint_f32_batch(pcm, [0, len(pcm)], sr)
+            rows, frame_count = self.engine.search_aligned_batch(fr, [0, len(fr)], p, k)[0], len(fr)
+        else:
+            rows, frame_count = self.engine.search_aligned_pcm_batch(pcm, [0, len(pcm)], p, k, sr)[0], frame_count_of(len(pcm))
+        out = []
+        for row in rows:
+            info = self._audio_list_info(row["audio_uuid"])
+            if info is None:
+                continue
+            info["frame_count"] = frame_count
+            for key in ("match_count", "aligned_count", "offset", "first_frame", "last_frame"):
+                info[key] = row[key]
+            out.append(info)
+        return out

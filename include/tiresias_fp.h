@@ -296,6 +296,46 @@ int tfp_search_ranked_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64
  * counted over the sorted rows). Either pointer may be NULL. */
 int tfp_rank_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches);
 
+/* ---- aligned search: where in the clip a candidate matches (new; no reference counterpart) --- */
+/* The reference's count (fp_handler.c:287-374) says how many query frames found a row of the clip,
+ * not where, nor whether the hits line up in time: the inserted rows carry frame_idx (:287-359
+ * "select * from audio_fingerprint"), but the result query (:367-374) never reads it. A clip's
+ * stored rows j = 0..N-1 are in frame order, so with the query's frames i = 0..F-1 and hit(i, j) =
+ * "frame i runs its SQL and row j satisfies its predicate" (:287-351: max1, and max2 where the
+ * clause is present, non-NULL and inside the frame's printed bounds), the histogram over the
+ * diagonals hist[d] = #{(i, j) : hit(i, j), j - i = d}, d in [-(F-1), N-1], gives
+ *   aligned_count = max over d of hist[d]           (the hits that agree on one time offset),
+ *   offset        = the smallest d attaining it     (query frame i lies at clip frame i + offset;
+ *                                                    negative: the recording starts before the clip),
+ *   first_frame, last_frame = the least and greatest i with hit(i, i + offset).
+ * All four are 0 when no row hits. For a row a ranked search returns, 1 <= aligned_count <=
+ * match_count. Exact integers; coefs, tolerance < 0 and the ignore filters as in tfp_search_params.
+ * The clip's rows are read as enrolled: no tfp_index_commit is needed. Calls are not coalesced. */
+typedef struct tfp_alignment {
+  int32_t aligned_count;
+  int32_t offset;
+  int32_t first_frame;
+  int32_t last_frame;
+} tfp_alignment;
+/* Query q against clips clip_ids[q * k + r], r < k: out[q * k + r]. An id of -1 gives a zeroed row
+ * (a ranked result's unused entries pass straight through); any other id out of range or of a
+ * removed clip is TFP_E_NOENT. k < 1, k > TFP_RANK_MAX or coefs outside [1,2] is TFP_E_ARG. */
+int tfp_align_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                    const tfp_search_params* params, const int32_t* clip_ids, int32_t k, tfp_alignment* out);
+/* tfp_search_ranked_batch (fp_handler.c:367-374 read to row k: the same cand and counts) plus
+ * align[q * k + r] for row r; entries past counts[q] are zeroed. */
+int tfp_search_aligned_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                             const tfp_search_params* params, int32_t k, tfp_candidate* cand, tfp_alignment* align,
+                             int32_t* counts);
+/* tfp_search_ranked_pcm_batch (fp_handler.c:275 + :287-374) plus the rows' alignments; the frame
+ * values stay on the device between the search and the alignment. */
+int tfp_search_aligned_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                 int32_t sample_rate, const tfp_search_params* params, int32_t k, tfp_candidate* cand,
+                                 tfp_alignment* align, int32_t* counts);
+/* Batches that reached the alignment kernels so far and the (query, clip) pairs they named (the
+ * frames of fp_handler.c:287-351 against the clips' rows). Either pointer may be NULL. */
+int tfp_align_stats(tfp_engine* eng, int64_t* batches, int64_t* pairs);
+
 /* ---- live channels: rolling fingerprint + match (configs[4]) --------------------------
  * The dialplan app records `duration` ms of a channel to a WAV and searches it
  * (application_handler.c:152-185, record_voice :248-312). A stream keeps the most recent
@@ -371,6 +411,12 @@ int tfp_group_search_ranked_batch(tfp_group* g, const tfp_frame* frames, const i
 int tfp_group_search_ranked_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
                                       int32_t sample_rate, const tfp_search_params* params, int32_t k,
                                       tfp_candidate* out, int32_t* counts);
+/* tfp_search_aligned_batch on a group (fp_handler.c:367-374 read to row k, then each kept row's
+ * alignment): the ranked search as tfp_group_search_ranked_batch, then every kept candidate is
+ * aligned on the shard that holds it (tfp_align_batch with its clip id there). cand as that call's. */
+int tfp_group_search_aligned_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                                   const tfp_search_params* params, int32_t k, tfp_candidate* cand,
+                                   tfp_alignment* align, int32_t* counts);
 /* tfp_search_pcm_gather and the coalescing of concurrent calls (as for one engine) on a group: the
  * channel threads' batch-1 searches through the shim run as shared batches on every GPU. */
 int tfp_group_search_pcm_gather(tfp_group* g, const int16_t* const* pcms, const int64_t* nsamples, int32_t nqueries,

@@ -773,6 +773,81 @@ struct ast_json* fp_search_fingerprint_candidates(const char* context, const cha
 	return j_res;
 }
 
+/* New: fp_search_fingerprint_candidates' array with where in each clip the recording lies: every
+ * element also carries aligned_count, offset, first_frame and last_frame (tfp_alignment: the hits
+ * that agree on one time offset, that offset in frames, and the first and last query frame on it).
+ * The reference's result query (fp_handler.c:367-374) counts the frames that hit and never reads
+ * the rows' frame_idx. The file's frames (tfp_group_fingerprint_batch / _f32_batch), then
+ * tfp_group_search_aligned_batch. NULL and the empty array as for the candidates call. */
+struct ast_json* fp_search_fingerprint_aligned(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results)
+{
+	int16_t* pcm;
+	float* x;
+	int64_t cap, ns, off[2], qoff[2] = {0, 0}, nf = 0;
+	int32_t sr, count = 0;
+	int rc, k, i;
+	tfp_search_params p;
+	tfp_candidate cand[TFP_RANK_MAX];
+	tfp_alignment align[TFP_RANK_MAX];
+	tfp_result r;
+	tfp_frame* fr;
+	struct ast_json* j_res;
+	struct ast_json* j_tmp;
+
+	if((filename == NULL) || (max_results < 1)) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	if(search_params(&p, context, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	if(read_audio(filename, &pcm, &cap, &x, &ns, &sr) != 0) {
+		return NULL;
+	}
+	k = max_results > TFP_RANK_MAX ? TFP_RANK_MAX : max_results;
+	off[0] = 0;
+	off[1] = ns;
+	nf = tfp_frame_count(ns); /* ast_json_array_size(j_fprints), fp_handler.c:286 */
+	fr = ast_calloc(nf > 0 ? nf : 1, sizeof(*fr));
+	if(fr == NULL) {
+		rc = TFP_E_NOMEM;
+	}
+	else if(pcm != NULL) {
+		rc = tfp_group_fingerprint_batch(g_tfp, pcm, off, 1, sr, fr, nf, &qoff[1]);
+	}
+	else {
+		rc = tfp_group_fingerprint_f32_batch(g_tfp, x, off, 1, sr, fr, nf, &qoff[1]);
+	}
+	if(rc == TFP_OK) {
+		rc = tfp_group_search_aligned_batch(g_tfp, fr, qoff, 1, &p, k, cand, align, &count);
+	}
+	ast_free(fr);
+	pcm_put(pcm, cap);
+	ast_free(x);
+	if(rc != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not search %s: %s\n", filename, tfp_group_last_error(g_tfp));
+		return NULL;
+	}
+	j_res = ast_json_array_create();
+	for(i = 0; i < count; i++) {
+		memset(&r, 0, sizeof(r));
+		r.found = 1;
+		r.match_count = cand[i].match_count;
+		r.frame_count = (int32_t)nf;
+		snprintf(r.uuid, sizeof(r.uuid), "%s", cand[i].uuid);
+		j_tmp = search_result(&r); /* a row whose audio_list entry is missing is skipped */
+		if(j_tmp != NULL) {
+			ast_json_object_set(j_tmp, "aligned_count", ast_json_integer_create(align[i].aligned_count));
+			ast_json_object_set(j_tmp, "offset", ast_json_integer_create(align[i].offset));
+			ast_json_object_set(j_tmp, "first_frame", ast_json_integer_create(align[i].first_frame));
+			ast_json_object_set(j_tmp, "last_frame", ast_json_integer_create(align[i].last_frame));
+			ast_json_array_append(j_res, j_tmp);
+		}
+	}
+	return j_res;
+}
+
 /* ---- live channels: the dialplan application's recording without the /tmp WAV -------------
  * application_handler.c:152-185 records `duration` ms of the channel's voice frames
  * (record_voice, :248-312) into /tmp/tiresias-UUID.wav and searches that file. A channel keeps the

@@ -50,6 +50,16 @@ bool fp_get_search_stats(int64_t* calls, int64_t* batches);
 struct ast_json* fp_search_fingerprint_candidates(const char* context, const char* filename, const int coefs,
 		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
 
+/* New: aligned search. fp_search_fingerprint_candidates' array (src/fp_handler.c:367-374 read to
+ * row max_results), each element with four more integers saying where in the clip the recording
+ * lies: "aligned_count" (the matching frames that agree on one time offset, <= match_count),
+ * "offset" (query frame i lies at clip frame i + offset; 256 samples per frame; negative: the
+ * recording starts before the clip), "first_frame" and "last_frame" (the first and last query frame
+ * on that offset). A dialplan reads how far into an announcement the call is from offset, and
+ * tells twenty frames in order from twenty scattered coincidences by aligned_count. */
+struct ast_json* fp_search_fingerprint_aligned(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
+
 /* New: a live channel, for the dialplan application's record loop (application_handler.c:152-185,
  * record_voice :248-312) without the /tmp WAV round trip. Open one per call with max_ms >= the
  * recording's duration, push every voice frame's SLIN samples as it is read (160 per 20 ms frame
