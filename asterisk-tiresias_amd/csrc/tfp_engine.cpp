@@ -28,6 +28,7 @@
 #include "tfp_kernels.hpp"
 #include "tfp_math.hpp"
 #include "tfp_rank.hpp"
+#include "tfp_scope.hpp"
 #include "tfp_synth.hpp"
 #include "tfp_tables.hpp"
 #include "tfp_tolcache.hpp"
@@ -144,6 +145,7 @@ struct Clip {
   bool alive = true;
   int64_t nrows = 0;
   int64_t off = 0;  // first staging row (a clip's rows are contiguous, in frame order)
+  int32_t scope = 0;  // tfp_index_set_scope (tfp_scope.hpp); kept by clip id, so through every index update
 };
 
 // tfp_host_alloc's buffers: host address -> (bytes, generation), so a call whose samples lie
@@ -273,6 +275,13 @@ struct tfp_engine {
   DevBuf rank_part, rank_keys;
   HostBuf rank_pin;
   int64_t n_rank_vote = 0, n_rank_general = 0;
+  // scoped search (tfp_scope.hpp): the clips' scopes and the columns' clips as uploaded, the
+  // per-column scope table built from them, the batch's per-query scopes; the table stands for
+  // index version scope_version until a scope changes (scope_dirty)
+  DevBuf scope_clip, scope_colclip, scope_table, scope_q;
+  uint64_t scope_version = 0;
+  bool scope_dirty = true;
+  int64_t n_scope_vote = 0, n_scope_general = 0, n_scope_builds = 0;
   // aligned search (align_core): the batch's frame boxes (its own: a device-form search may still
   // read e->boxes on the caller's stream), the pairs, the bands' partial keys, the results, the
   // pinned copy of pairs and results, and the batches / pairs aligned so far
@@ -1787,12 +1796,45 @@ bool valid_params(const tfp_search_params* P) { return P && P->coefs >= 1 && P->
 
 // ---- ranked search (tfp_rank.hpp): keys[q * K + r] = row r of query q's result set, 0 past the last
 
+// The per-column scope table (tfp_scope.hpp) of the current index: built when the index version or a
+// clip's scope changed since the last build (the columns' clips and the clips' scopes uploaded, one
+// kernel), else it stands and a search does no per-clip work.
+int ensure_scope_table(tfp_engine* e, hipStream_t s) {
+  if (e->scope_version == e->index_version && !e->scope_dirty) return TFP_OK;
+  const int32_t C = e->ncols, Cp = scope_table_cols(C);
+  std::vector<int32_t> cc((size_t)std::max(Cp, 1), -1), cs(std::max<size_t>(e->clips.size(), 1), 0);
+  std::copy(e->col_clip.begin(), e->col_clip.end(), cc.begin());  // (col_clip.size() <= ncols)
+  for (size_t j = 0; j < e->delta.clip.size(); j++) cc[(size_t)e->delta.col0 + j] = e->delta.clip[j];
+  for (size_t i = 0; i < e->clips.size(); i++) cs[i] = e->clips[i].scope;
+  HIPCHK(e, e->scope_colclip.reserve_grow(sizeof(int32_t) * cc.size()));
+  HIPCHK(e, e->scope_clip.reserve_grow(sizeof(int32_t) * cs.size()));
+  HIPCHK(e, e->scope_table.reserve_grow(sizeof(int32_t) * cc.size()));
+  HIPCHK(e, hipMemcpyAsync(e->scope_colclip.p, cc.data(), sizeof(int32_t) * cc.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipMemcpyAsync(e->scope_clip.p, cs.data(), sizeof(int32_t) * cs.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(e, launch_scope_table(e->scope_colclip.as<int32_t>(), e->scope_clip.as<int32_t>(), C, e->scope_table.as<int32_t>(), s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (cc and cs are released on return)
+  e->scope_version = e->index_version;
+  e->scope_dirty = false;
+  e->n_scope_builds++;
+  return TFP_OK;
+}
+
+// A scoped batch's set-up: the table, and the queries' scopes on the device (read from the
+// caller's array, which outlives the batch: every form waits for the stream before it returns).
+int ensure_scopes(tfp_engine* e, const int32_t* scopes, int32_t nq, hipStream_t s) {
+  int rc = ensure_scope_table(e, s);
+  if (rc) return rc;
+  return upload(e, e->scope_q, scopes, sizeof(int32_t) * (size_t)nq, s);
+}
+
 // The vote form (coefs = 1): *bad when a frame's key lies outside the vote range (keys undefined).
+// scopes (or nullptr): the queries' scopes, for the scoped kernels (tfp_scope.hpp).
 int rank_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
-              int32_t K, std::vector<unsigned long long>& keys, bool* bad, hipStream_t s) {
+              int32_t K, const int32_t* scopes, std::vector<unsigned long long>& keys, bool* bad, hipStream_t s) {
   const int32_t C = e->ncols, nb = rank_vote_blocks(C);
   int rc;
   if ((rc = ensure_qoff(e, qo, s)) || (rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s))) return rc;
+  if (scopes && (rc = ensure_scopes(e, scopes, nq, s))) return rc;
   // queries in chunks of <= 256 MB of partial keys (and of the launch grid's second dimension)
   int64_t chunk = (int64_t)(256ll << 20) / ((int64_t)sizeof(unsigned long long) * nb * K);
   chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(chunk, 65535), nq));
@@ -1805,9 +1847,15 @@ int rank_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const d
   HIPCHK(e, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int32_t n = (int32_t)std::min<int64_t>(chunk, nq - q0);
-    HIPCHK(e, launch_rank_vote(d_q, e->qoff.as<int64_t>() + q0, n, sc, e->tc.ranges.active().key_bits.as<uint32_t>(), C,
-                               e->tiekey.as<int32_t>(), K, e->rank_part.as<unsigned long long>(), d_keys + q0 * K, d_bad,
-                               s));
+    if (scopes)
+      HIPCHK(e, launch_scope_vote(d_q, e->qoff.as<int64_t>() + q0, e->scope_q.as<int32_t>() + q0, n, sc,
+                                  e->tc.ranges.active().key_bits.as<uint32_t>(), C, e->tiekey.as<int32_t>(),
+                                  e->scope_table.as<int32_t>(), K, e->rank_part.as<unsigned long long>(), d_keys + q0 * K,
+                                  d_bad, s));
+    else
+      HIPCHK(e, launch_rank_vote(d_q, e->qoff.as<int64_t>() + q0, n, sc, e->tc.ranges.active().key_bits.as<uint32_t>(), C,
+                                 e->tiekey.as<int32_t>(), K, e->rank_part.as<unsigned long long>(), d_keys + q0 * K, d_bad,
+                                 s));
   }
   HIPCHK(e, hipMemcpyAsync(e->rank_pin.p, d_keys, sizeof(unsigned long long) * (nkeys + 1), hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
@@ -1819,7 +1867,7 @@ int rank_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const d
 
 // The general form (any coefs / tolerance / key), over the sorted rows of the merged index.
 int rank_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
-                 int32_t K, std::vector<unsigned long long>& keys, hipStream_t s) {
+                 int32_t K, const int32_t* scopes, std::vector<unsigned long long>& keys, hipStream_t s) {
   const int32_t C = e->ncols;
   const int64_t R = e->nrows, nf = qo[nq];
   if (C <= 0 || R <= 0) return TFP_OK;  // an empty index: no row
@@ -1835,11 +1883,23 @@ int rank_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, cons
     (void)hipGetLastError();
     cells->invalidate();  // every frame takes the row scan
   }
+  if (scopes && (rc = ensure_scopes(e, scopes, nq, s))) return rc;
   const size_t nkeys = (size_t)nq * K;
   HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
   HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int32_t n = (int32_t)std::min<int64_t>(chunk, nq - q0);
+    if (scopes) {  // the same counts, selected among the scope's clips
+      HIPCHK(e, launch_scan_touched(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), qo.data(), (int32_t)q0, n,
+                                    e->m1s.as<int32_t>(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(), R, cells, C,
+                                    e->stamp.as<int32_t>(), e->score.as<int32_t>(), e->touched.as<int32_t>(),
+                                    e->tcnt.as<int32_t>(), s));
+      HIPCHK(e, launch_scope_final((int32_t)q0, n, e->scope_q.as<int32_t>(), e->tiekey.as<int32_t>(),
+                                   e->scope_table.as<int32_t>(), C, e->stamp.as<int32_t>(), e->score.as<int32_t>(),
+                                   e->touched.as<int32_t>(), e->tcnt.as<int32_t>(), K, e->rank_keys.as<unsigned long long>(),
+                                   s));
+      continue;
+    }
     HIPCHK(e, launch_scan_ranked(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), qo.data(), (int32_t)q0, n,
                                  e->m1s.as<int32_t>(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(), R, cells,
                                  e->tiekey.as<int32_t>(), C, e->stamp.as<int32_t>(), e->score.as<int32_t>(),
@@ -1855,8 +1915,9 @@ int rank_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, cons
 
 // Shaped like search_core. The vote form reads the key bitsets, which hold a live index delta's
 // columns at the tolerances delta_tol_ok() names; every other ranked search merges the delta first.
+// scopes (or nullptr: ranked search): scopes[q] restricts query q to that scope's clips (tfp_scope.hpp).
 int rank_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_q, const tfp_search_params* P, int32_t K,
-              std::vector<unsigned long long>& keys, hipStream_t s) {
+              const int32_t* scopes, std::vector<unsigned long long>& keys, hipStream_t s) {
   int rc = rebuild(e);  // synchronous on e->stream
   if (rc) return rc;
   const SearchConsts sc = search_consts(P);
@@ -1867,14 +1928,14 @@ int rank_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_
     if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
     if (e->ncols <= 0 || e->nrows + e->delta.rows <= 0) return TFP_OK;
     bool bad = false;
-    if ((rc = rank_vote(e, qo, nq, d_q, sc, K, keys, &bad, s))) return rc;
+    if ((rc = rank_vote(e, qo, nq, d_q, sc, K, scopes, keys, &bad, s))) return rc;
     if (!bad) {
-      e->n_rank_vote++;
+      (scopes ? e->n_scope_vote : e->n_rank_vote)++;
       return TFP_OK;
     }
   }
-  if ((rc = consolidate(e)) || (rc = rank_general(e, qo, nq, d_q, sc, K, keys, s))) return rc;
-  e->n_rank_general++;
+  if ((rc = consolidate(e)) || (rc = rank_general(e, qo, nq, d_q, sc, K, scopes, keys, s))) return rc;
+  (scopes ? e->n_scope_general : e->n_rank_general)++;
   return TFP_OK;
 }
 
@@ -1903,6 +1964,17 @@ int rank_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, 
   if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
   if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "ranked search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
   if (!valid_params(P)) return fail(e, TFP_E_ARG, "ranked search: coefs outside [1, 2]");
+  return TFP_OK;
+}
+
+// rank_args, and a scope per query of TFP_SCOPE_ANY or above.
+int scope_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, const int32_t* scopes, const void* out,
+               const void* counts) {
+  int rc = rank_args(e, P, k, nq, out, counts);
+  if (rc) return rc;
+  if (nq && !scopes) return fail(e, TFP_E_ARG, "scoped search: scopes is NULL");
+  for (int32_t i = 0; i < nq; i++)
+    if (scopes[i] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "scoped search: scope %d of query %d", scopes[i], i);
   return TFP_OK;
 }
 
@@ -2480,8 +2552,10 @@ int upload_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, i
 }
 
 // tfp_search_ranked_batch, and with align its rows' alignments (tfp_search_aligned_batch).
+// scopes (or nullptr): tfp_search_scoped_batch.
 int search_ranked_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
-                         const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align) {
+                         const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align,
+                         const int32_t* scopes = nullptr) {
   int rc = rank_args(e, P, k, nq, out, counts);
   if (rc) return rc;
   for (int32_t i = 0; i < nq; i++)
@@ -2492,7 +2566,7 @@ int search_ranked_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* 
   if (nq) {
     HIPCHK(e, hipSetDevice(e->device));
     if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
-    if ((rc = rank_core(e, qoff, nq, e->q.as<double>(), P, k, keys, e->stream))) return rc;
+    if ((rc = rank_core(e, qoff, nq, e->q.as<double>(), P, k, scopes, keys, e->stream))) return rc;
   }
   fill_candidates(e, keys, nq, k, out, counts);
   if (align && nq)  // (the frame values are still in e->q)
@@ -2519,8 +2593,10 @@ int tfp_search_ranked(tfp_engine* e, const tfp_frame* frames, int32_t nframes, c
 namespace {
 // tfp_search_ranked_pcm_batch, and with align its rows' alignments (tfp_search_aligned_pcm_batch):
 // the frame values stay on the device (e->db) for both.
+// scopes (or nullptr): tfp_search_scoped_pcm_batch.
 int search_ranked_pcm(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
-                      const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align) {
+                      const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align,
+                      const int32_t* scopes = nullptr) {
   int rc = rank_args(e, P, k, nq, out, counts);
   if (rc) return rc;
   for (int32_t i = 0; i < nq; i++)
@@ -2536,7 +2612,7 @@ int search_ranked_pcm(tfp_engine* e, const int16_t* pcm, const int64_t* offsets,
     HIPCHK(e, hipSetDevice(e->device));
     int64_t nf;
     if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nq, sr, &nf, nullptr, P->coefs == 2))) return rc;
-    if ((rc = rank_core(e, foff.data(), nq, e->db.as<double>(), P, k, keys, e->stream))) return rc;
+    if ((rc = rank_core(e, foff.data(), nq, e->db.as<double>(), P, k, scopes, keys, e->stream))) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
     e->stage_pending = false;
   }
@@ -2614,6 +2690,65 @@ int tfp_rank_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batche
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (vote_batches) *vote_batches = e->n_rank_vote;
   if (general_batches) *general_batches = e->n_rank_general;
+  return TFP_OK;
+}
+
+// ---- scoped search (tfp_scope.hpp): fp_handler.c:367-374 over one context's clips ----------
+static_assert(kScopeAny == TFP_SCOPE_ANY, "tfp_scope.hpp and the public header agree");
+
+int tfp_index_set_scope(tfp_engine* e, int32_t n, const char* const* uuids, const int32_t* scopes) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (n < 0 || (n && (!uuids || !scopes))) return fail(e, TFP_E_ARG, "set scope: bad count or NULL array");
+  std::vector<int32_t> ids((size_t)n);
+  for (int32_t i = 0; i < n; i++) {  // all or nothing: every entry checked before any scope changes
+    if (!uuids[i]) return fail(e, TFP_E_ARG, "set scope: uuid %d is NULL", i);
+    if (scopes[i] < 0) return fail(e, TFP_E_ARG, "set scope: scope %d of %s", scopes[i], uuids[i]);
+    const auto it = e->by_uuid.find(uuids[i]);
+    if (it == e->by_uuid.end()) return fail(e, TFP_E_NOENT, "uuid %s not indexed", uuids[i]);
+    ids[i] = it->second;
+  }
+  for (int32_t i = 0; i < n; i++) {
+    Clip& c = e->clips[ids[i]];
+    e->scope_dirty |= c.scope != scopes[i];
+    c.scope = scopes[i];
+  }
+  return TFP_OK;
+}
+
+int tfp_index_scope(tfp_engine* e, const char* uuid, int32_t* scope) {
+  if (!e || !uuid || !scope) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  const auto it = e->by_uuid.find(uuid);
+  if (it == e->by_uuid.end()) return fail(e, TFP_E_NOENT, "uuid %s not indexed", uuid);
+  *scope = e->clips[it->second].scope;
+  return TFP_OK;
+}
+
+int tfp_search_scoped_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                            const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                            int32_t* counts) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  const int rc = scope_args(e, P, k, nq, scopes, out, counts);
+  return rc ? rc : search_ranked_frames(e, frames, qoff, nq, P, k, out, counts, nullptr, scopes);
+}
+
+int tfp_search_scoped_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                                const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                                int32_t* counts) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  const int rc = scope_args(e, P, k, nq, scopes, out, counts);
+  return rc ? rc : search_ranked_pcm(e, pcm, offsets, nq, sr, P, k, out, counts, nullptr, scopes);
+}
+
+int tfp_scope_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches, int64_t* table_builds) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (vote_batches) *vote_batches = e->n_scope_vote;
+  if (general_batches) *general_batches = e->n_scope_general;
+  if (table_builds) *table_builds = e->n_scope_builds;
   return TFP_OK;
 }
 

@@ -748,6 +748,70 @@ int tfp_group_search_ranked_pcm_batch(tfp_group* g, const int16_t* pcm, const in
   });
 }
 
+// Scoped search on a group (tfp_scope.hpp): a scope lives with its clip on the clip's shard.
+int tfp_group_index_set_scope(tfp_group* g, int32_t n, const char* const* uuids, const int32_t* scopes) {
+  if (!g) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  if (n < 0 || (n && (!uuids || !scopes))) return gfail(g, TFP_E_ARG, "set scope: bad count or NULL array");
+  const int ns = (int)g->eng.size();
+  std::vector<std::vector<const char*>> u(ns);
+  std::vector<std::vector<int32_t>> sc(ns);
+  for (int32_t i = 0; i < n; i++) {  // all or nothing: every entry checked before any shard is told
+    if (!uuids[i]) return gfail(g, TFP_E_ARG, "set scope: uuid %d is NULL", i);
+    if (scopes[i] < 0) return gfail(g, TFP_E_ARG, "set scope: scope %d of %s", scopes[i], uuids[i]);
+    const auto it = g->where.find(uuids[i]);
+    if (it == g->where.end()) return gfail(g, TFP_E_NOENT, "uuid %s not indexed", uuids[i]);
+    const int s = g->members[it->second].shard;
+    u[s].push_back(uuids[i]);
+    sc[s].push_back(scopes[i]);
+  }
+  for (int s = 0; s < ns; s++) {
+    if (u[s].empty()) continue;
+    const int rc = tfp_index_set_scope(g->eng[s], (int32_t)u[s].size(), u[s].data(), sc[s].data());
+    if (rc) return shard_fail(g, rc, s);  // (checked above: a shard refuses only what the group's own maps would)
+  }
+  return TFP_OK;
+}
+
+int tfp_group_index_scope(tfp_group* g, const char* uuid, int32_t* scope) {
+  if (!g || !uuid || !scope) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  auto it = g->where.find(uuid);
+  if (it == g->where.end()) return gfail(g, TFP_E_NOENT, "uuid %s not indexed", uuid);
+  const int s = g->members[it->second].shard;
+  const int rc = tfp_index_scope(g->eng[s], uuid, scope);
+  return rc ? shard_fail(g, rc, s) : TFP_OK;
+}
+
+namespace {
+int group_scope_args(tfp_group* g, const int32_t* scopes, int32_t nq) {
+  if (nq > 0 && !scopes) return gfail(g, TFP_E_ARG, "scoped search: scopes is NULL");
+  for (int32_t i = 0; i < nq; i++)
+    if (scopes[i] < TFP_SCOPE_ANY) return gfail(g, TFP_E_ARG, "scoped search: scope %d of query %d", scopes[i], i);
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_group_search_scoped_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                                  const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                                  int32_t* counts) {
+  if (!g || !qoff) return TFP_E_ARG;
+  if (int rc = group_scope_args(g, scopes, nq)) return rc;
+  return group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    return tfp_search_scoped_batch(g->eng[s], frames, qoff, nq, P, scopes, k, o, c);
+  });
+}
+
+int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                                      const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                                      int32_t* counts) {
+  if (!g || !offsets) return TFP_E_ARG;
+  if (int rc = group_scope_args(g, scopes, nq)) return rc;
+  return group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    return tfp_search_scoped_pcm_batch(g->eng[s], pcm, offsets, nq, sr, P, scopes, k, o, c);
+  });
+}
+
 // Aligned search on a group: the ranked search above, then every kept row aligned on the shard
 // that holds its clip (tfp_align_batch with the shard-local clip id; -1 for the other shards' rows).
 int tfp_group_search_aligned_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nq,

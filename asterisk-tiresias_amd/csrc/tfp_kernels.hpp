@@ -300,6 +300,13 @@ hipError_t launch_scan_ranked(const FrameBox* boxes, const int64_t* d_qoff, cons
                               const CellCache* cells, const int32_t* d_tiekey, int32_t C, int32_t* d_stamp,
                               int32_t* d_score, int32_t* d_touched, int32_t* d_tcnt, int32_t K,
                               unsigned long long* d_keys, hipStream_t s);
+// The counts alone, for a selection of the caller's own (tfp_scope.hpp): on return d_score holds the
+// touched clips' counts, d_touched[q][0, d_tcnt[q]) their columns, and the selection must restore
+// d_stamp / d_score of every touched clip and d_tcnt to zero.
+hipError_t launch_scan_touched(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin,
+                               int32_t nq, const int32_t* m1s, const int32_t* m2s, const int32_t* cols, int64_t R,
+                               const CellCache* cells, int32_t C, int32_t* d_stamp, int32_t* d_score, int32_t* d_touched,
+                               int32_t* d_tcnt, hipStream_t s);
 
 // The general path's sweep by groups (tfp_scan.hip): every query frame of the batch sorted by
 // (query chunk, key, max2 window); per chunk and window of 16 clip columns, one wave counts, for

@@ -165,4 +165,12 @@ hipError_t launch_rank_vote(const double* d_q, const int64_t* d_qoff, int32_t nq
   return hipGetLastError();
 }
 
+// The merge alone, for partial lists of another vote form (tfp_scope.hip).
+hipError_t launch_rank_merge(const unsigned long long* d_part, int32_t nq, int32_t nparts, int32_t K,
+                             unsigned long long* d_keys, hipStream_t s) {
+  if (nq <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rank_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, d_part, nq, nparts, K, d_keys);
+  return hipGetLastError();
+}
+
 }  // namespace tfp

@@ -27,4 +27,8 @@ hipError_t launch_rank_vote(const double* d_q, const int64_t* d_qoff, int32_t nq
                             int32_t C, const int32_t* d_tiekey, int32_t K, unsigned long long* d_part,
                             unsigned long long* d_keys, int32_t* d_bad, hipStream_t s);
 
+// One wave per query: d_keys[q * K + r] = the r-th greatest of query q's nparts partial keys.
+hipError_t launch_rank_merge(const unsigned long long* d_part, int32_t nq, int32_t nparts, int32_t K,
+                             unsigned long long* d_keys, hipStream_t s);
+
 }  // namespace tfp

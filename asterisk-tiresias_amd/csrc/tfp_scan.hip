@@ -1038,6 +1038,17 @@ hipError_t launch_scan_ranked(const FrameBox* boxes, const int64_t* d_qoff, cons
   return hipGetLastError();
 }
 
+hipError_t launch_scan_touched(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin,
+                               int32_t nq, const int32_t* m1s, const int32_t* m2s, const int32_t* cols, int64_t R,
+                               const CellCache* cells, int32_t C, int32_t* d_stamp, int32_t* d_score, int32_t* d_touched,
+                               int32_t* d_tcnt, hipStream_t s) {
+  if (nq <= 0) return hipSuccess;
+  hipError_t err = hipSuccess;
+  launch_scan_counts(boxes, d_qoff, h_qoff, q_begin, nq, m1s, m2s, cols, R, cells, C, d_stamp, d_score, d_touched, d_tcnt,
+                     s, &err);
+  return err != hipSuccess ? err : hipGetLastError();
+}
+
 namespace {
 
 void launch_scan_counts(const FrameBox* boxes, const int64_t* d_qoff, const int64_t* h_qoff, int32_t q_begin, int32_t nq,

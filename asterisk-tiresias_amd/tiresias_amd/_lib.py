@@ -42,6 +42,7 @@ class Result(C.Structure):
 
 
 TFP_RANK_MAX = 32
+TFP_SCOPE_ANY = -1  # a scoped query over every clip
 
 
 class Candidate(C.Structure):
@@ -146,6 +147,17 @@ _SIGS = {
                                                P]),
     "tfp_align_stats": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tfp_group_search_aligned_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, P, P, P]),
+    "tfp_index_set_scope": (C.c_int, [P, C.c_int32, C.POINTER(C.c_char_p), P]),
+    "tfp_index_scope": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int32)]),
+    "tfp_search_scoped_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P, P]),
+    "tfp_search_scoped_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P,
+                                              P]),
+    "tfp_scope_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
+    "tfp_group_index_set_scope": (C.c_int, [P, C.c_int32, C.POINTER(C.c_char_p), P]),
+    "tfp_group_index_scope": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int32)]),
+    "tfp_group_search_scoped_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P, P]),
+    "tfp_group_search_scoped_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32,
+                                                    P, P]),
 }
 
 _lib = None

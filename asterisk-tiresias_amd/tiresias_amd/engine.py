@@ -79,8 +79,54 @@ def synth_pcm(seed: int, clips, samples_per_clip: int, offsets=None) -> np.ndarr
     return out
 
 
-class Engine:
+class _ScopedCalls:
+    """Scoped search, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*): _PFX names which."""
+
+    def _fn(self, name):
+        return getattr(lib(), self._PFX + name)
+
+    def index_set_scope(self, uuids, scopes):
+        """tfp_index_set_scope: clip uuids[i] gets scope scopes[i] (>= 0); all or nothing."""
+        scopes = np.ascontiguousarray(scopes, np.int32)
+        if len(scopes) != len(uuids):
+            raise ValueError("one scope per uuid")
+        arr = (C.c_char_p * max(1, len(uuids)))(*[u.encode() for u in uuids])
+        self._chk(self._fn("_index_set_scope")(self._h, len(uuids), arr, scopes.ctypes.data))
+
+    def index_scope(self, uuid: str) -> int:
+        s = C.c_int32()
+        self._chk(self._fn("_index_scope")(self._h, uuid.encode(), C.byref(s)))
+        return s.value
+
+    def search_scoped_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, scopes, k: int):
+        """search_ranked_batch with query q restricted to the clips of scopes[q] (TFP_SCOPE_ANY: every clip)."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        nq, k = len(qoffsets) - 1, int(k)
+        scopes = np.ascontiguousarray(scopes, np.int32)
+        if len(scopes) != nq:
+            raise ValueError("one scope per query")
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        self._chk(self._fn("_search_scoped_batch")(self._h, frames.ctypes.data, qoffsets.ctypes.data, nq, C.byref(p),
+                                                   scopes.ctypes.data, k, out, counts))
+        return Engine._candidates(out, counts, nq, k)
+
+    def search_scoped_pcm_batch(self, pcm, offsets, p: SearchParams, scopes, k: int, sample_rate: int = 8000):
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq, k = len(offsets) - 1, int(k)
+        scopes = np.ascontiguousarray(scopes, np.int32)
+        if len(scopes) != nq:
+            raise ValueError("one scope per query")
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        self._chk(self._fn("_search_scoped_pcm_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, sample_rate,
+                                                       C.byref(p), scopes.ctypes.data, k, out, counts))
+        return Engine._candidates(out, counts, nq, k)
+
+
+class Engine(_ScopedCalls):
     """One engine per GPU (tfp_engine)."""
+    _PFX = "tfp"
 
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
@@ -365,6 +411,12 @@ class Engine:
         self._chk(lib().tfp_rank_stats(self._h, C.byref(v), C.byref(g)))
         return {"vote_batches": v.value, "general_batches": g.value}
 
+    def scope_stats(self) -> dict:
+        """tfp_scope_stats: scoped batches by form, and builds of the per-column scope table."""
+        v, g, t = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(lib().tfp_scope_stats(self._h, C.byref(v), C.byref(g), C.byref(t)))
+        return {"vote_batches": v.value, "general_batches": g.value, "table_builds": t.value}
+
     # ---- device-resident paths (pointers are raw device addresses, e.g. tensor.data_ptr())
     def plan(self, offsets, sample_rate: int = 8000) -> "Plan":
         return Plan(self, offsets, sample_rate)
@@ -458,9 +510,10 @@ class Plan:
             self._h = C.c_void_p()
 
 
-class Group:
+class Group(_ScopedCalls):
     """tfp_group: one engine per listed device (a device may repeat), the enrolled clips sharded
     over them, searches combined on the host (tiresias_fp.h, device groups)."""
+    _PFX = "tfp_group"
 
     def __init__(self, devices):
         devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
@@ -623,6 +676,16 @@ class Group:
         self._chk(lib().tfp_group_search_ranked_pcm_batch(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, sample_rate,
                                                           C.byref(p), k, out, counts))
         return Engine._candidates(out, counts, nq, k)
+
+    def scope_stats(self) -> dict:
+        """Engine.scope_stats summed over the shards' engines."""
+        tot = {"vote_batches": 0, "general_batches": 0, "table_builds": 0}
+        for s in range(self.size()):
+            v, g, t = C.c_int64(), C.c_int64(), C.c_int64()
+            check(lib().tfp_scope_stats(lib().tfp_group_engine(self._h, s), C.byref(v), C.byref(g), C.byref(t)))
+            for key, x in zip(tot, (v, g, t)):
+                tot[key] += x.value
+        return tot
 
 
 class GroupStream:

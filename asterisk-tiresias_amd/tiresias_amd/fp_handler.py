@@ -72,17 +72,42 @@ class FpHandler:
         self.backup_path = backup_path
         self.db = None
         self.engine = None
+        # context name -> scope id of its clips in the engine (tfp_index_set_scope), from 1 in order of
+        # first enrolment: scope 0, a new clip's, belongs to no context
+        self._scopes = {}
+
+    def _scope_of(self, context: str, create: bool) -> int:
+        """The context's scope id; for a context without clips an id no clip has (create: now its own)."""
+        sid = self._scopes.get(context)
+        if sid is None:
+            sid = len(self._scopes) + 1
+            if create:
+                self._scopes[context] = sid
+        return sid
 
     # fp_handler.c:68-90 — init_database (the catalog tables) + engine, then the snapshot
     def fp_init(self) -> bool:
         self.db = sqlite3.connect(":memory:", check_same_thread=False)
         dbio.create_catalog(self.db)
         self.engine = Engine(self.device)
+        self._scopes = {}
         if self.backup_path:
             try:
                 dbio.load_backup(self.db, self.engine, self.backup_path)
+                # the loaded clips' scopes from audio_list's context column (one catalog read)
+                rows = self.db.execute("select uuid, context from audio_list order by rowid;").fetchall()
+                known = [(u, c) for u, c in rows if c is not None and self._indexed(u)]
+                if known:
+                    self.engine.index_set_scope([u for u, _ in known], [self._scope_of(c, True) for _, c in known])
             except Exception:
                 return False  # "Could not load the database data."
+        return True
+
+    def _indexed(self, uuid: str) -> bool:
+        try:
+            self.engine.index_scope(uuid)
+        except TfpError:
+            return False  # a catalog row without fingerprint rows
         return True
 
     # fp_handler.c:92-108 — backup, then tear down
@@ -170,6 +195,7 @@ class FpHandler:
             pcm, sr = read_audio(filename)
             fr = self._fingerprint(pcm, [0, len(pcm)], sr)
             self.engine.index_add(uuid, fr["m1"], fr["m2"])
+            self.engine.index_set_scope([uuid], [self._scope_of(context, True)])
         except Exception:
             self.fp_delete_audio_list_info(uuid)
             return False
@@ -222,6 +248,7 @@ class FpHandler:
             fr = self._fingerprint(np.concatenate([n[1] for n in group]), off, sr)
             foff = np.concatenate([[0], np.cumsum([(n + 255) // 256 for n in lens])]).astype(np.int64)
             self.engine.index_add_batch([n[0] for n in group], foff, fr["m1"], fr["m2"])
+            self.engine.index_set_scope([n[0] for n in group], [self._scope_of(context, True)] * len(group))
         return True
 
     def fp_delete_audio_list_info(self, uuid: str) -> bool:
@@ -282,6 +309,40 @@ class FpHandler:
             rows, frame_count = self.engine.search_ranked(fr, p, k), len(fr)
         else:
             rows, frame_count = self.engine.search_ranked_pcm_batch(pcm, [0, len(pcm)], p, k, sr)[0], frame_count_of(len(pcm))
+        out = []
+        for row in rows:
+            info = self._audio_list_info(row["audio_uuid"])
+            if info is None:
+                continue
+            info["frame_count"] = frame_count
+            info["match_count"] = row["match_count"]
+            out.append(info)
+        return out
+
+    def fp_search_fingerprint_in_context(self, context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high,
+                                         max_results=1):
+        """fp_search_fingerprint_candidates restricted to the clips enrolled in `context`: the search
+        the reference documents ("from the context's audio list", doc/dialplan_application.rst:11,
+        :52-53) and its per-frame SQL (fp_handler.c:308-314, no context predicate) does not run. The
+        rows are the first max_results of fp_handler.c:367-374 over that context's clips alone; [] for a
+        context without clips."""
+        if context is None or filename is None:
+            return []
+        if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1:
+            return []
+        try:
+            pcm, sr = read_audio(filename)
+        except TfpError:
+            return []
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        k = min(int(max_results), TFP_RANK_MAX)
+        scope = [self._scope_of(context, False)]
+        if pcm.dtype == np.float32:
+            fr = self.engine.fingerprint_f32_batch(pcm, [0, len(pcm)], sr)
+            rows, frame_count = self.engine.search_scoped_batch(fr, [0, len(fr)], p, scope, k)[0], len(fr)
+        else:
+            rows = self.engine.search_scoped_pcm_batch(pcm, [0, len(pcm)], p, scope, k, sr)[0]
+            frame_count = frame_count_of(len(pcm))
         out = []
         for row in rows:
             info = self._audio_list_info(row["audio_uuid"])

@@ -296,6 +296,47 @@ int tfp_search_ranked_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64
  * counted over the sorted rows). Either pointer may be NULL. */
 int tfp_rank_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches);
 
+/* ---- context-scoped search: the result query over one context's clips (new) ------------- */
+/* Every search entry point of the reference takes a context, and its documentation promises a scoped
+ * search: the application "attempts to detect the given channel's voice is in the list of the given
+ * tiresias's context" (doc/dialplan_application.rst:11) and FOUND means found "from the context's
+ * audio list" (doc/dialplan_application.rst:52-53). Its per-frame insert (fp_handler.c:308-314) has
+ * no context predicate, so tfp_search_batch and every call above span all contexts, as the reference
+ * does. The calls below run the search the documentation describes.
+ *
+ * A clip carries a scope, an int32 >= 0; a new clip has scope 0. The engine knows nothing of context
+ * names: the caller maps them to scope ids. A scoped search of a query with scope s returns the first
+ * k rows of the result query (fp_handler.c:367-374) when the per-frame insert (fp_handler.c:308-314)
+ * also carries "and context = '<s>'", which is the unmodified SQL over a table holding scope s's
+ * clips only: rows by count descending, tied counts by audio_uuid descending, clips with a non-zero
+ * count only. The restriction is applied where the rows are selected on the GPU, not to the global
+ * first k rows (a scope's best clip may lie below any global row). frame_count is unaffected. */
+#define TFP_SCOPE_ANY (-1) /* a query's scope: every clip (equals tfp_search_ranked_batch row for row) */
+/* Set the scopes of n clips (the context column of fp_handler.c:713-753, which fp_handler.c:308-314
+ * never reads). All or nothing: an unknown uuid is TFP_E_NOENT, a negative scope TFP_E_ARG, and no
+ * scope has changed then. A scope may be changed at any time; the next search sees it. It follows
+ * the clip through every index update and goes away with tfp_index_remove and tfp_index_clear. */
+int tfp_index_set_scope(tfp_engine* eng, int32_t n, const char* const* uuids, const int32_t* scopes);
+/* A clip's scope read back (doc/dialplan_application.rst:52-53: which context's audio list holds it). */
+int tfp_index_scope(tfp_engine* eng, const char* uuid, int32_t* scope);
+/* fp_handler.c:367-374 per query over the clips of scopes[q] (fp_handler.c:308-314 with the context
+ * predicate of doc/dialplan_application.rst:11): out, counts, the zeroing and the argument rules
+ * exactly as tfp_search_ranked_batch; scopes[nqueries], each TFP_SCOPE_ANY or >= 0, below -1 is
+ * TFP_E_ARG. A scope no live clip has gives counts[q] = 0. */
+int tfp_search_scoped_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                            const tfp_search_params* params, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                            int32_t* counts);
+/* PCM in (fp_handler.c:275 + :287-374 with the context predicate at :308-314), rows out (:367-374):
+ * the queries as tfp_search_ranked_pcm_batch takes them (doc/dialplan_application.rst:11). */
+int tfp_search_scoped_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                int32_t sample_rate, const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                                tfp_candidate* out, int32_t* counts);
+/* Scoped batches served so far by the vote form and by the general form (as tfp_rank_stats: the rows
+ * of fp_handler.c:367-374 under the predicate at :308-314, doc/dialplan_application.rst:11), and
+ * builds of the per-column scope table on the device: one after each index update or scope change
+ * that a scoped search follows, none per search. Any pointer may be NULL. */
+int tfp_scope_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches, int64_t* table_builds);
+
 /* ---- aligned search: where in the clip a candidate matches (new; no reference counterpart) --- */
 /* The reference's count (fp_handler.c:287-374) says how many query frames found a row of the clip,
  * not where, nor whether the hits line up in time: the inserted rows carry frame_idx (:287-359
@@ -411,6 +452,18 @@ int tfp_group_search_ranked_batch(tfp_group* g, const tfp_frame* frames, const i
 int tfp_group_search_ranked_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
                                       int32_t sample_rate, const tfp_search_params* params, int32_t k,
                                       tfp_candidate* out, int32_t* counts);
+/* Scoped search on a group (fp_handler.c:308-314 with the context predicate, :367-374 read to row k;
+ * doc/dialplan_application.rst:11, :52-53): a clip's scope is set on the shard that holds it (all or
+ * nothing over the group), every shard returns its scoped first k rows, and they merge as
+ * tfp_group_search_ranked_batch's do. */
+int tfp_group_index_set_scope(tfp_group* g, int32_t n, const char* const* uuids, const int32_t* scopes);
+int tfp_group_index_scope(tfp_group* g, const char* uuid, int32_t* scope);
+int tfp_group_search_scoped_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                                  const tfp_search_params* params, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                                  int32_t* counts);
+int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                      int32_t sample_rate, const tfp_search_params* params, const int32_t* scopes,
+                                      int32_t k, tfp_candidate* out, int32_t* counts);
 /* tfp_search_aligned_batch on a group (fp_handler.c:367-374 read to row k, then each kept row's
  * alignment): the ranked search as tfp_group_search_ranked_batch, then every kept candidate is
  * aligned on the shard that holds it (tfp_align_batch with its clip id there). cand as that call's. */

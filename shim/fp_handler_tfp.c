@@ -79,6 +79,123 @@ static bool create_group(void)
 	return tfp_group_create(dev, n, &g_tfp) == TFP_OK;
 }
 
+/* Context name -> scope id of its clips in the engines (tfp_group_index_set_scope): ids from 1 in
+ * order of first enrolment, so scope 0 (a new clip's) belongs to no context. Rebuilt at fp_init from
+ * audio_list's context column. An unknown context maps to an id no clip has. */
+static struct {
+	char** name;
+	int32_t n, cap;
+} g_ctx;
+static pthread_mutex_t g_ctx_lock = PTHREAD_MUTEX_INITIALIZER;
+
+static int32_t scope_of_context(const char* context, bool create)
+{
+	int32_t i, id = -1;
+
+	pthread_mutex_lock(&g_ctx_lock);
+	for(i = 0; i < g_ctx.n; i++) {
+		if(strcmp(g_ctx.name[i], context) == 0) {
+			id = i + 1;
+			break;
+		}
+	}
+	if(id < 0 && create == false) {
+		id = g_ctx.n + 1; /* no clip has it */
+	}
+	else if(id < 0) {
+		if(g_ctx.n == g_ctx.cap) {
+			const int32_t cap = g_ctx.cap ? 2 * g_ctx.cap : 16;
+			char** grown = ast_realloc(g_ctx.name, sizeof(char*) * cap);
+			if(grown != NULL) {
+				g_ctx.name = grown;
+				g_ctx.cap = cap;
+			}
+		}
+		if(g_ctx.n < g_ctx.cap && (g_ctx.name[g_ctx.n] = ast_malloc(strlen(context) + 1)) != NULL) {
+			strcpy(g_ctx.name[g_ctx.n], context);
+			id = ++g_ctx.n;
+		}
+	}
+	pthread_mutex_unlock(&g_ctx_lock);
+	return id; /* -1: out of memory */
+}
+
+static void scopes_reset(void)
+{
+	int32_t i;
+
+	pthread_mutex_lock(&g_ctx_lock);
+	for(i = 0; i < g_ctx.n; i++) {
+		ast_free(g_ctx.name[i]);
+	}
+	ast_free(g_ctx.name);
+	g_ctx.name = NULL;
+	g_ctx.n = g_ctx.cap = 0;
+	pthread_mutex_unlock(&g_ctx_lock);
+}
+
+/* n clips of one context into its scope; false when the engines refuse (the caller undoes the enrolment) */
+static bool set_scopes(const char* context, const char* const* uuids, int32_t n)
+{
+	int32_t i, id, *sc;
+	bool ret;
+
+	if(n <= 0) {
+		return true;
+	}
+	id = scope_of_context(context, true);
+	sc = ast_malloc(sizeof(int32_t) * n);
+	if(id < 0 || sc == NULL) {
+		ast_free(sc);
+		return false;
+	}
+	for(i = 0; i < n; i++) {
+		sc[i] = id;
+	}
+	ret = tfp_group_index_set_scope(g_tfp, n, uuids, sc) == TFP_OK;
+	if(ret == false) {
+		ast_log(LOG_ERROR, "Could not set the context of %d clips: %s\n", n, tfp_group_last_error(g_tfp));
+	}
+	ast_free(sc);
+	return ret;
+}
+
+/* fp_init: the loaded clips' scopes from audio_list's context column (clips without a catalog row
+ * stay in scope 0: no context finds them, as no fp_search result can name them) */
+static bool load_scopes(const fpc_rows* rows)
+{
+	int32_t c, n = 0, *sc;
+	const char** uu;
+	bool ret = true;
+
+	if(rows->nclips <= 0) {
+		return true;
+	}
+	sc = ast_malloc(sizeof(int32_t) * rows->nclips);
+	uu = ast_malloc(sizeof(char*) * rows->nclips);
+	if(sc == NULL || uu == NULL) {
+		ast_free(sc);
+		ast_free(uu);
+		return false;
+	}
+	for(c = 0; c < rows->nclips && ret == true; c++) {
+		struct ast_json* j = fpc_get_audio_list_info(rows->uuids[c]);
+		const char* ctx = j ? ast_json_string_get(ast_json_object_get(j, "context")) : NULL;
+		if(ctx != NULL) {
+			sc[n] = scope_of_context(ctx, true);
+			uu[n] = rows->uuids[c];
+			ret = sc[n++] >= 0;
+		}
+		if(j != NULL) {
+			ast_json_unref(j);
+		}
+	}
+	ret = ret && (n == 0 || tfp_group_index_set_scope(g_tfp, n, uu, sc) == TFP_OK);
+	ast_free(sc);
+	ast_free(uu);
+	return ret;
+}
+
 bool fp_get_search_stats(int64_t* calls, int64_t* batches)
 {
 	return g_tfp != NULL && tfp_group_search_coalesce_stats(g_tfp, calls, batches) == TFP_OK;
@@ -91,6 +208,7 @@ bool fp_init(void)
 {
 	fpc_rows rows;
 
+	scopes_reset();
 	if(fpc_db_init() == false) {
 		ast_log(LOG_ERROR, "Could not initiate database.\n");
 		return false;
@@ -109,7 +227,8 @@ bool fp_init(void)
 		return false;
 	}
 	if((rows.nclips > 0 && tfp_group_index_add_batch(g_tfp, rows.nclips, (const char* const*)rows.uuids,
-			rows.frame_offsets, rows.m1, rows.m2) != TFP_OK) || tfp_group_index_commit(g_tfp) != TFP_OK) {
+			rows.frame_offsets, rows.m1, rows.m2) != TFP_OK) || load_scopes(&rows) == false ||
+			tfp_group_index_commit(g_tfp) != TFP_OK) {
 		ast_log(LOG_ERROR, "Could not load the fingerprint index: %s\n", tfp_group_last_error(g_tfp));
 		fpc_rows_free(&rows);
 		tfp_group_destroy(g_tfp);
@@ -129,6 +248,7 @@ bool fp_term(void)
 	pcm_pool_drain();
 	tfp_group_destroy(g_tfp);
 	g_tfp = NULL;
+	scopes_reset();
 	if(ret == false) {
 		ast_log(LOG_ERROR, "Could not write database.\n");
 	}
@@ -271,6 +391,10 @@ static bool create_audio_fingerprint_info(const char* context, const char* filen
 	ret = fpc_store_fingerprints(context, uuid, m1, m2, n);
 	if(ret == true && tfp_group_index_add(g_tfp, uuid, m1, m2, (int32_t)n) != TFP_OK) {
 		ast_log(LOG_ERROR, "Could not index %s: %s\n", filename, tfp_group_last_error(g_tfp));
+		ret = false;
+	}
+	else if(ret == true && set_scopes(context, &uuid, 1) == false) {
+		tfp_group_index_remove(g_tfp, uuid); /* undone as a failed index add: the caller drops the catalog rows */
 		ret = false;
 	}
 	ast_free(rows);
@@ -430,6 +554,12 @@ static int group_flush(const char* context, enrol_group* g, bool* ok)
 		if(tfp_group_index_add_batch(g_tfp, kept, (const char* const*)uu, foff, m1, m2) != TFP_OK) {
 			ast_log(LOG_ERROR, "Could not index %d files: %s\n", kept, tfp_group_last_error(g_tfp));
 			for(c = 0; c < kept; c++) {
+				fpc_delete_audio_list_info(uu[c]);
+			}
+		}
+		else if(set_scopes(context, (const char* const*)uu, kept) == false) {
+			for(c = 0; c < kept; c++) { /* undone as a failed index add */
+				tfp_group_index_remove(g_tfp, uu[c]);
 				fpc_delete_audio_list_info(uu[c]);
 			}
 		}
@@ -711,13 +841,14 @@ struct ast_json* fp_search_fingerprint_info(const char* context, const char* fil
  * ("select *, count(*) from temp group by audio_uuid order by count(*) DESC", fp_handler.c:367-374),
  * as a JSON array of that call's result objects in rank order (tfp_group_search_ranked_pcm_batch).
  * NULL where fp_search_fingerprint_info returns NULL before the query; an empty array for NOTFOUND. */
-struct ast_json* fp_search_fingerprint_candidates(const char* context, const char* filename, const int coefs,
-		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results)
+static struct ast_json* search_candidates(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results,
+		const bool in_context)
 {
 	int16_t* pcm;
 	float* x;
 	int64_t cap, ns, off[2], nf = 0;
-	int32_t sr, count = 0;
+	int32_t sr, count = 0, scope = TFP_SCOPE_ANY;
 	int rc, k, i;
 	tfp_search_params p;
 	tfp_candidate cand[TFP_RANK_MAX];
@@ -739,8 +870,12 @@ struct ast_json* fp_search_fingerprint_candidates(const char* context, const cha
 	off[0] = 0;
 	off[1] = ns;
 	nf = tfp_frame_count(ns); /* ast_json_array_size(j_fprints), fp_handler.c:286 */
+	if(in_context == true) {
+		scope = scope_of_context(context, false);
+	}
 	if(pcm != NULL) {
-		rc = tfp_group_search_ranked_pcm_batch(g_tfp, pcm, off, 1, sr, &p, k, cand, &count);
+		rc = in_context ? tfp_group_search_scoped_pcm_batch(g_tfp, pcm, off, 1, sr, &p, &scope, k, cand, &count)
+		                : tfp_group_search_ranked_pcm_batch(g_tfp, pcm, off, 1, sr, &p, k, cand, &count);
 	}
 	else {
 		/* audio tfp_wav_decode refuses (fp32 hop values): its frames, then the frames form */
@@ -748,7 +883,8 @@ struct ast_json* fp_search_fingerprint_candidates(const char* context, const cha
 		int64_t qoff[2] = {0, 0};
 		rc = fr ? tfp_group_fingerprint_f32_batch(g_tfp, x, off, 1, sr, fr, nf, &qoff[1]) : TFP_E_NOMEM;
 		if(rc == TFP_OK) {
-			rc = tfp_group_search_ranked_batch(g_tfp, fr, qoff, 1, &p, k, cand, &count);
+			rc = in_context ? tfp_group_search_scoped_batch(g_tfp, fr, qoff, 1, &p, &scope, k, cand, &count)
+			                : tfp_group_search_ranked_batch(g_tfp, fr, qoff, 1, &p, k, cand, &count);
 		}
 		ast_free(fr);
 	}
@@ -771,6 +907,23 @@ struct ast_json* fp_search_fingerprint_candidates(const char* context, const cha
 		}
 	}
 	return j_res;
+}
+
+struct ast_json* fp_search_fingerprint_candidates(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results)
+{
+	return search_candidates(context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high, max_results, false);
+}
+
+/* New: fp_search_fingerprint_candidates over the clips enrolled in `context` alone: the search the
+ * reference documents ("from the context's audio list", doc/dialplan_application.rst:11, :52-53)
+ * and its per-frame SQL (fp_handler.c:308-314, no context predicate) does not run. The rows are the
+ * first max_results of fp_handler.c:367-374 with "and context = '<context>'" in that insert
+ * (tfp_group_search_scoped_pcm_batch); a context without clips gives the empty array. */
+struct ast_json* fp_search_fingerprint_in_context(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results)
+{
+	return search_candidates(context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high, max_results, true);
 }
 
 /* New: fp_search_fingerprint_candidates' array with where in each clip the recording lies: every

@@ -50,6 +50,16 @@ bool fp_get_search_stats(int64_t* calls, int64_t* batches);
 struct ast_json* fp_search_fingerprint_candidates(const char* context, const char* filename, const int coefs,
 		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
 
+/* New: context-scoped search. fp_search_fingerprint_info and the calls above span every context, as
+ * the reference's per-frame SQL does (src/fp_handler.c:308-314 has no context predicate) although
+ * its documentation promises a search "from the context's audio list"
+ * (doc/dialplan_application.rst:11, :52-53). This returns fp_search_fingerprint_candidates' array
+ * over the clips enrolled in `context` alone: the first max_results rows of src/fp_handler.c:367-374
+ * with "and context = '<context>'" in the insert, selected on the GPU among that context's clips
+ * (not filtered out of the global rows). Empty array: NOTFOUND, also for a context without clips. */
+struct ast_json* fp_search_fingerprint_in_context(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
+
 /* New: aligned search. fp_search_fingerprint_candidates' array (src/fp_handler.c:367-374 read to
  * row max_results), each element with four more integers saying where in the clip the recording
  * lies: "aligned_count" (the matching frames that agree on one time offset, <= match_count),
