@@ -29,6 +29,7 @@
 #include "tfp_math.hpp"
 #include "tfp_rank.hpp"
 #include "tfp_scope.hpp"
+#include "tfp_slide.hpp"
 #include "tfp_synth.hpp"
 #include "tfp_tables.hpp"
 #include "tfp_tolcache.hpp"
@@ -282,6 +283,10 @@ struct tfp_engine {
   uint64_t scope_version = 0;
   bool scope_dirty = true;
   int64_t n_scope_vote = 0, n_scope_general = 0, n_scope_builds = 0;
+  // sliding search (tfp_slide.hpp): the recordings' key slots, the launch's runs, the general form's
+  // window starts and gathered frame values, and the batches / windows served so far
+  DevBuf slide_slots, slide_runs, slide_wsrc, slide_q;
+  int64_t n_slide_vote = 0, n_slide_general = 0, n_slide_windows = 0;
   // aligned search (align_core): the batch's frame boxes (its own: a device-form search may still
   // read e->boxes on the caller's stream), the pairs, the bands' partial keys, the results, the
   // pinned copy of pairs and results, and the batches / pairs aligned so far
@@ -1978,6 +1983,143 @@ int scope_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq,
   return TFP_OK;
 }
 
+// ---- sliding search (tfp_slide.hpp): keys[j * K + r] = row r of window j, 0 past the last. fo: the
+// recordings' relative frame offsets into d_q; woff: the first window of each recording.
+
+// The tolerances at which the vote form runs: those at which the key bitsets hold every column, a
+// live index delta's included (delta_tol_ok), so the vote form never needs the delta merged.
+bool slide_vote_tol(double tole) { return delta_tol_ok(tole); }
+
+// The vote form: *bad when a frame's key lies outside the vote range (keys undefined).
+int slide_vote(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, const double* d_q, const SearchConsts& sc,
+               int32_t window, int32_t hop, const int32_t* scopes, int32_t K, const std::vector<int64_t>& woff,
+               std::vector<unsigned long long>& keys, bool* bad, hipStream_t s) {
+  const int32_t C = e->ncols, nb = rank_vote_blocks(C);
+  const int64_t nf = fo[nrec], nw = woff[nrec];
+  int rc;
+  if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s)) || (rc = ensure_scope_table(e, s))) return rc;
+  // runs of <= kSlideRun windows, launched in groups of <= 256 MB of partial keys (and of the launch
+  // grid's second dimension); a run's w0 counts from its group's first window
+  const int64_t gwin = std::max<int64_t>(kSlideRun, (int64_t)(256ll << 20) / ((int64_t)sizeof(unsigned long long) * nb * K));
+  struct Group { size_t r0, r1; int64_t w0, n; };
+  std::vector<SlideRun> runs;
+  std::vector<Group> groups;
+  for (int32_t r = 0; r < nrec; r++) {
+    const int64_t n = woff[r + 1] - woff[r];
+    for (int64_t w = 0; w < n; w += kSlideRun) {
+      const int32_t len = (int32_t)std::min<int64_t>(kSlideRun, n - w);
+      if (groups.empty() || groups.back().n + len > gwin || groups.back().r1 - groups.back().r0 >= 65535)
+        groups.push_back(Group{runs.size(), runs.size(), woff[r] + w, 0});
+      Group& g = groups.back();
+      runs.push_back(SlideRun{fo[r] + w * hop, (int32_t)g.n, len, scopes ? scopes[r] : kScopeAny, 0});
+      g.n += len;
+      g.r1++;
+    }
+  }
+  int64_t maxw = 0;
+  for (const Group& g : groups) maxw = std::max(maxw, g.n);
+  const size_t nkeys = (size_t)nw * K;
+  HIPCHK(e, e->slide_slots.reserve(sizeof(int16_t) * (size_t)(nf + 1)));
+  if ((rc = upload(e, e->slide_runs, runs.data(), sizeof(SlideRun) * runs.size(), s))) return rc;
+  HIPCHK(e, e->rank_part.reserve(sizeof(unsigned long long) * (size_t)maxw * nb * K));
+  HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  unsigned long long* d_keys = e->rank_keys.as<unsigned long long>();
+  int32_t* d_bad = reinterpret_cast<int32_t*>(d_keys + nkeys);
+  HIPCHK(e, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
+  HIPCHK(e, launch_slide_keys(d_q, nf, sc, e->slide_slots.as<int16_t>(), d_bad, s));
+  for (const Group& g : groups)
+    HIPCHK(e, launch_slide_vote(e->slide_slots.as<int16_t>(), e->slide_runs.as<SlideRun>() + g.r0, (int32_t)(g.r1 - g.r0),
+                                (int32_t)g.n, window, hop, e->tc.ranges.active().key_bits.as<uint32_t>(), C,
+                                e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
+                                e->rank_part.as<unsigned long long>(), d_keys + g.w0 * K, s));
+  HIPCHK(e, hipMemcpyAsync(e->rank_pin.p, d_keys, sizeof(unsigned long long) * (nkeys + 1), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  const unsigned long long* h = e->rank_pin.as<unsigned long long>();
+  *bad = (uint32_t)h[nkeys] != 0;
+  if (!*bad) std::copy(h, h + nkeys, keys.begin());
+  return TFP_OK;
+}
+
+// The general form: the windows' frame values laid end to end in chunks of <= 256 MB, each chunk a
+// batch of ranked search's general form (a window in a query's place).
+int slide_general(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, const double* d_q, const SearchConsts& sc,
+                  int32_t window, int32_t hop, const int32_t* scopes, int32_t K, const std::vector<int64_t>& woff,
+                  std::vector<unsigned long long>& keys, hipStream_t s) {
+  const int64_t nw = woff[nrec];
+  if (e->ncols <= 0 || e->nrows <= 0) return TFP_OK;  // an empty index: no row
+  std::vector<int64_t> wsrc((size_t)nw);
+  std::vector<int32_t> wscope(scopes ? (size_t)nw : 0);
+  for (int32_t r = 0; r < nrec; r++)
+    for (int64_t j = woff[r]; j < woff[r + 1]; j++) {
+      wsrc[(size_t)j] = fo[r] + (j - woff[r]) * hop;
+      if (scopes) wscope[(size_t)j] = scopes[r];
+    }
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nw, (int64_t)(256ll << 20) / (2 * sizeof(double)) / window));
+  std::vector<int64_t> qo;
+  std::vector<unsigned long long> ck;
+  int rc;
+  for (int64_t j0 = 0; j0 < nw; j0 += chunk) {
+    const int32_t n = (int32_t)std::min<int64_t>(chunk, nw - j0);
+    if ((rc = upload(e, e->slide_wsrc, wsrc.data() + j0, sizeof(int64_t) * (size_t)n, s))) return rc;
+    HIPCHK(e, e->slide_q.reserve(2 * sizeof(double) * ((size_t)n * window + 1)));
+    HIPCHK(e, launch_slide_gather(d_q, e->slide_wsrc.as<int64_t>(), n, window, e->slide_q.as<double>(), s));
+    qo.resize((size_t)n + 1);
+    for (int32_t i = 0; i <= n; i++) qo[i] = (int64_t)i * window;
+    ck.assign((size_t)n * K, 0ull);
+    if ((rc = rank_general(e, qo, n, e->slide_q.as<double>(), sc, K, scopes ? wscope.data() + j0 : nullptr, ck, s)))
+      return rc;  // (waits for the stream: the chunk's buffers are free again)
+    std::copy(ck.begin(), ck.end(), keys.begin() + (size_t)j0 * K);
+  }
+  return TFP_OK;
+}
+
+// Shaped like rank_core. scopes (or nullptr: every clip): scopes[r] restricts recording r's windows.
+int slide_core(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, const double* d_q, const tfp_search_params* P,
+               int32_t window, int32_t hop, const int32_t* scopes, int32_t K, const std::vector<int64_t>& woff,
+               std::vector<unsigned long long>& keys, hipStream_t s) {
+  int rc = rebuild(e);  // synchronous on e->stream
+  if (rc) return rc;
+  const SearchConsts sc = search_consts(P);
+  const int64_t nw = woff[nrec];
+  keys.assign((size_t)nw * K, 0ull);
+  if (sc.coefs == 1 && slide_vote_tol(sc.tole)) {
+    if (e->ncols <= 0 || e->nrows + e->delta.rows <= 0) return TFP_OK;
+    bool bad = false;
+    if ((rc = slide_vote(e, fo, nrec, d_q, sc, window, hop, scopes, K, woff, keys, &bad, s))) return rc;
+    if (!bad) {
+      e->n_slide_vote++;
+      e->n_slide_windows += nw;
+      return TFP_OK;
+    }
+  }
+  if ((rc = consolidate(e)) || (rc = slide_general(e, fo, nrec, d_q, sc, window, hop, scopes, K, woff, keys, s))) return rc;
+  e->n_slide_general++;
+  e->n_slide_windows += nw;
+  return TFP_OK;
+}
+
+// The arguments both sliding forms share; on TFP_OK woff[r] = the first window of recording r of
+// the given frame counts and *nwindows = woff[nrec].
+int slide_args(tfp_engine* e, const tfp_search_params* P, int32_t window, int32_t hop, int32_t k, int32_t nrec,
+               const int32_t* scopes, const std::vector<int64_t>& fo, const void* out, const void* counts,
+               int64_t cap_windows, int64_t* nwindows, std::vector<int64_t>& woff) {
+  if (nrec < 0 || !nwindows) return fail(e, TFP_E_ARG, "sliding search: bad recording count or NULL nwindows");
+  if (window < 1 || hop < 1) return fail(e, TFP_E_ARG, "sliding search: window = %d, hop = %d", window, hop);
+  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "sliding search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+  if (!valid_params(P)) return fail(e, TFP_E_ARG, "sliding search: coefs outside [1, 2]");
+  for (int32_t i = 0; scopes && i < nrec; i++)
+    if (scopes[i] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "sliding search: scope %d of recording %d", scopes[i], i);
+  woff.assign((size_t)nrec + 1, 0);
+  for (int32_t i = 0; i < nrec; i++) woff[i + 1] = woff[i] + slide_windows(fo[i + 1] - fo[i], window, hop);
+  *nwindows = woff[nrec];
+  if (woff[nrec] > cap_windows || woff[nrec] > INT32_MAX)
+    return fail(e, TFP_E_CAPACITY, "sliding search: %lld windows, room for %lld", (long long)woff[nrec],
+                (long long)cap_windows);
+  if (woff[nrec] && (!out || !counts)) return fail(e, TFP_E_ARG, "sliding search: NULL output");
+  return TFP_OK;
+}
+
 // ---- aligned search (tfp_align.hpp): out[q * K + r] = the alignment of query q with clip
 // ids[q * K + r] (-1: none, a zeroed row). The clips' rows are read where they lie in the staging
 // arrays (Clip::off under the engine lock), so no index build is needed and a clip of the live
@@ -2749,6 +2891,69 @@ int tfp_scope_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batch
   if (vote_batches) *vote_batches = e->n_scope_vote;
   if (general_batches) *general_batches = e->n_scope_general;
   if (table_builds) *table_builds = e->n_scope_builds;
+  return TFP_OK;
+}
+
+// ---- sliding search (tfp_slide.hpp): fp_handler.c:367-374 for every window of a recording ----
+static_assert(kSlideRun == TFP_SLIDE_RUN, "tfp_slide.hpp and the public header agree");
+
+int64_t tfp_sliding_windows(int64_t nframes, int32_t window, int32_t hop) { return slide_windows(nframes, window, hop); }
+
+int tfp_search_sliding_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
+                             const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes, int32_t k,
+                             tfp_candidate* out, int32_t* counts, int64_t cap_windows, int64_t* nwindows) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  for (int32_t i = 0; i < nrec; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0), woff;
+  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
+  if (rc) return rc;
+  const int32_t nw = (int32_t)woff[nrec];
+  if (!nw) return TFP_OK;  // no full window: nothing is launched
+  if (!frames) return fail(e, TFP_E_ARG, "frames is NULL");
+  std::vector<unsigned long long> keys;
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = upload_frames(e, frames, qoff, nrec))) return rc;
+  if ((rc = slide_core(e, fo, nrec, e->q.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
+  fill_candidates(e, keys, nw, k, out, counts);
+  return TFP_OK;
+}
+
+int tfp_search_sliding_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nrec, int32_t sr,
+                                 const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes, int32_t k,
+                                 tfp_candidate* out, int32_t* counts, int64_t cap_windows, int64_t* nwindows) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  for (int32_t i = 0; i < nrec; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  std::vector<const void*> ptrs;
+  std::vector<int64_t> lens;
+  if (nrec > 0) split_offsets(pcm, sizeof(int16_t), offsets, nrec, &ptrs, &lens);
+  std::vector<int64_t> fo((size_t)std::max(nrec, 0) + 1, 0), woff;
+  for (int32_t i = 0; i < nrec; i++) fo[i + 1] = fo[i] + tfp_frame_count(lens[i]);
+  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
+  if (rc) return rc;
+  const int32_t nw = (int32_t)woff[nrec];
+  if (!nw) return TFP_OK;  // no full window: nothing is fingerprinted
+  if (!pcm) return fail(e, TFP_E_ARG, "samples are NULL");
+  std::vector<unsigned long long> keys;
+  HIPCHK(e, hipSetDevice(e->device));
+  int64_t nf;  // each recording fingerprinted once, as one clip; the frame values stay in e->db
+  if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nrec, sr, &nf, nullptr, P->coefs == 2))) return rc;
+  if ((rc = slide_core(e, fo, nrec, e->db.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
+  e->stage_pending = false;
+  fill_candidates(e, keys, nw, k, out, counts);
+  return TFP_OK;
+}
+
+int tfp_slide_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches, int64_t* windows) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (vote_batches) *vote_batches = e->n_slide_vote;
+  if (general_batches) *general_batches = e->n_slide_general;
+  if (windows) *windows = e->n_slide_windows;
   return TFP_OK;
 }
 

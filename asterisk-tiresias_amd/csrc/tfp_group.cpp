@@ -812,6 +812,60 @@ int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const in
   });
 }
 
+// Sliding search on a group (tfp_slide.hpp): every shard slides over every recording, and per window
+// the shards' rows merge as a query's do (group_rank, a window in a query's place).
+namespace {
+// The windows of the recordings at off[0..nrec] (frames, or samples with pcm) counted as the shards
+// will count them, after the argument checks that decide the count.
+int group_slide_windows(tfp_group* g, const int64_t* off, int32_t nrec, bool pcm, int32_t window, int32_t hop,
+                        const int32_t* scopes, int64_t cap_windows, int64_t* nwindows, int32_t* nw) {
+  if (nrec < 0 || !nwindows) return gfail(g, TFP_E_ARG, "sliding search: bad recording count or NULL nwindows");
+  if (window < 1 || hop < 1) return gfail(g, TFP_E_ARG, "sliding search: window = %d, hop = %d", window, hop);
+  for (int32_t i = 0; scopes && i < nrec; i++)
+    if (scopes[i] < TFP_SCOPE_ANY) return gfail(g, TFP_E_ARG, "sliding search: scope %d of recording %d", scopes[i], i);
+  int64_t total = 0;
+  for (int32_t i = 0; i < nrec; i++) {
+    if (off[i + 1] < off[i]) return gfail(g, TFP_E_ARG, "sliding search: offsets not monotone");
+    const int64_t n = off[i + 1] - off[i];
+    total += tfp_sliding_windows(pcm ? tfp_frame_count(n) : n, window, hop);
+  }
+  *nwindows = total;
+  if (total > cap_windows || total > INT32_MAX)
+    return gfail(g, TFP_E_CAPACITY, "sliding search: %lld windows, room for %lld", (long long)total, (long long)cap_windows);
+  *nw = (int32_t)total;
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_group_search_sliding_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
+                                   const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes, int32_t k,
+                                   tfp_candidate* out, int32_t* counts, int64_t cap_windows, int64_t* nwindows) {
+  if (!g || !qoff) return TFP_E_ARG;
+  if (k < 1 || k > TFP_RANK_MAX || !valid_params(P)) return gfail(g, TFP_E_ARG, "sliding search: k or coefs out of range");
+  int32_t nw = 0;
+  if (int rc = group_slide_windows(g, qoff, nrec, false, window, hop, scopes, cap_windows, nwindows, &nw)) return rc;
+  if (!nw) return TFP_OK;
+  return group_rank(g, nw, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    int64_t n = 0;
+    return tfp_search_sliding_batch(g->eng[s], frames, qoff, nrec, P, window, hop, scopes, k, o, c, nw, &n);
+  });
+}
+
+int tfp_group_search_sliding_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nrec, int32_t sr,
+                                       const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes,
+                                       int32_t k, tfp_candidate* out, int32_t* counts, int64_t cap_windows,
+                                       int64_t* nwindows) {
+  if (!g || !offsets) return TFP_E_ARG;
+  if (k < 1 || k > TFP_RANK_MAX || !valid_params(P)) return gfail(g, TFP_E_ARG, "sliding search: k or coefs out of range");
+  int32_t nw = 0;
+  if (int rc = group_slide_windows(g, offsets, nrec, true, window, hop, scopes, cap_windows, nwindows, &nw)) return rc;
+  if (!nw) return TFP_OK;
+  return group_rank(g, nw, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    int64_t n = 0;
+    return tfp_search_sliding_pcm_batch(g->eng[s], pcm, offsets, nrec, sr, P, window, hop, scopes, k, o, c, nw, &n);
+  });
+}
+
 // Aligned search on a group: the ranked search above, then every kept row aligned on the shard
 // that holds its clip (tfp_align_batch with the shard-local clip id; -1 for the other shards' rows).
 int tfp_group_search_aligned_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nq,

@@ -5,5 +5,5 @@ this package is its ctypes binding plus a mirror of the reference's fp_handler i
 """
 from ._lib import LIB_PATH, NULL_MICRO, TfpError, header_symbols, lib  # noqa: F401
 from .engine import (FRAME_DTYPE, Engine, Group, GroupStream, Plan, Stream, device_count, frame_count,  # noqa: F401
-                     params, synth_pcm)
+                     params, sliding_windows, synth_pcm)
 from .fp_handler import FpHandler  # noqa: F401

@@ -43,6 +43,7 @@ class Result(C.Structure):
 
 TFP_RANK_MAX = 32
 TFP_SCOPE_ANY = -1  # a scoped query over every clip
+TFP_SLIDE_RUN = 32  # sliding search: consecutive windows one GPU block scores in turn
 
 
 class Candidate(C.Structure):
@@ -158,6 +159,16 @@ _SIGS = {
     "tfp_group_search_scoped_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P, P]),
     "tfp_group_search_scoped_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32,
                                                     P, P]),
+    "tfp_sliding_windows": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "tfp_search_sliding_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32, P, C.c_int32,
+                                           P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_search_sliding_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32,
+                                               P, C.c_int32, P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_slide_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
+    "tfp_group_search_sliding_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32, P,
+                                                 C.c_int32, P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_group_search_sliding_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32,
+                                                     C.c_int32, P, C.c_int32, P, P, C.c_int64, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

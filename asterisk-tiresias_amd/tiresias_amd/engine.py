@@ -79,6 +79,49 @@ def synth_pcm(seed: int, clips, samples_per_clip: int, offsets=None) -> np.ndarr
     return out
 
 
+def sliding_windows(nframes: int, window: int, hop: int) -> int:
+    """tfp_sliding_windows: full windows of `window` frames, `hop` apart, in a recording of nframes frames."""
+    return int(lib().tfp_sliding_windows(int(nframes), int(window), int(hop)))
+
+
+class _SlidingCalls:
+    """Sliding search, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*), as _ScopedCalls."""
+
+    def _sliding(self, name, data, offsets, nframes, head, p, window, hop, scopes, k):
+        nrec, k = len(offsets) - 1, int(k)
+        if scopes is not None:
+            scopes = np.ascontiguousarray(scopes, np.int32)
+            if len(scopes) != nrec:
+                raise ValueError("one scope per recording")
+        per = [sliding_windows(n, window, hop) for n in nframes]
+        cap, nw = sum(per), C.c_int64()
+        out, counts = (Candidate * max(1, cap * max(k, 1)))(), (C.c_int32 * max(1, cap))()
+        self._chk(self._fn(name)(self._h, data.ctypes.data, offsets.ctypes.data, nrec, *head, C.byref(p), int(window),
+                                 int(hop), None if scopes is None else scopes.ctypes.data, k, out, counts, cap,
+                                 C.byref(nw)))
+        assert nw.value == cap
+        rows = Engine._candidates(out, counts, cap, k)
+        woff = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+        return [rows[woff[r]:woff[r + 1]] for r in range(nrec)]
+
+    def search_sliding_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, window: int, hop: int, k: int,
+                             scopes=None):
+        """tfp_search_sliding_batch: per recording a list over its windows (window w = frames [w * hop, w * hop +
+        window) of the recording) of the rows search_scoped_batch gives for that window's frames with the
+        recording's scope (None: every clip)."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        return self._sliding("_search_sliding_batch", frames, qoffsets, np.diff(qoffsets), (), p, window, hop, scopes, k)
+
+    def search_sliding_pcm_batch(self, pcm, offsets, p: SearchParams, window: int, hop: int, k: int, scopes=None,
+                                 sample_rate: int = 8000):
+        """tfp_search_sliding_pcm_batch: search_sliding_batch over each recording's own fingerprint."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        return self._sliding("_search_sliding_pcm_batch", pcm, offsets, [frame_count(n) for n in np.diff(offsets)],
+                             (int(sample_rate),), p, window, hop, scopes, k)
+
+
 class _ScopedCalls:
     """Scoped search, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*): _PFX names which."""
 
@@ -124,7 +167,7 @@ class _ScopedCalls:
         return Engine._candidates(out, counts, nq, k)
 
 
-class Engine(_ScopedCalls):
+class Engine(_ScopedCalls, _SlidingCalls):
     """One engine per GPU (tfp_engine)."""
     _PFX = "tfp"
 
@@ -417,6 +460,12 @@ class Engine(_ScopedCalls):
         self._chk(lib().tfp_scope_stats(self._h, C.byref(v), C.byref(g), C.byref(t)))
         return {"vote_batches": v.value, "general_batches": g.value, "table_builds": t.value}
 
+    def slide_stats(self) -> dict:
+        """tfp_slide_stats: sliding batches by form, and the windows they held."""
+        v, g, w = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(lib().tfp_slide_stats(self._h, C.byref(v), C.byref(g), C.byref(w)))
+        return {"vote_batches": v.value, "general_batches": g.value, "windows": w.value}
+
     # ---- device-resident paths (pointers are raw device addresses, e.g. tensor.data_ptr())
     def plan(self, offsets, sample_rate: int = 8000) -> "Plan":
         return Plan(self, offsets, sample_rate)
@@ -510,7 +559,7 @@ class Plan:
             self._h = C.c_void_p()
 
 
-class Group(_ScopedCalls):
+class Group(_ScopedCalls, _SlidingCalls):
     """tfp_group: one engine per listed device (a device may repeat), the enrolled clips sharded
     over them, searches combined on the host (tiresias_fp.h, device groups)."""
     _PFX = "tfp_group"

@@ -384,3 +384,42 @@ class FpHandler:
                 info[key] = row[key]
             out.append(info)
         return out
+
+    def fp_search_fingerprint_timeline(self, context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high,
+                                       window_frames, hop_frames, max_results, in_context=False):
+        """fp_search_fingerprint_candidates for every window of a long recording: the reference searches
+        one fixed window of audio (application_handler.c:152-185, fp_handler.c:275-374); this returns
+        [{"frame": w * hop_frames, "rows": [...]}] for each full window of window_frames frames,
+        hop_frames apart, rows being the first max_results rows of fp_handler.c:367-374 over that
+        window's frames, each the dict fp_search_fingerprint_candidates builds with frame_count =
+        window_frames. in_context restricts every window to the clips enrolled in `context`, as
+        fp_search_fingerprint_in_context does. The recording is fingerprinted once. [] for bad arguments
+        or a recording shorter than one window."""
+        if context is None or filename is None:
+            return []
+        if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1 or window_frames < 1 or hop_frames < 1:
+            return []
+        try:
+            pcm, sr = read_audio(filename)
+        except TfpError:
+            return []
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        k = min(int(max_results), TFP_RANK_MAX)
+        scopes = [self._scope_of(context, False)] if in_context else None
+        if pcm.dtype == np.float32:
+            fr = self.engine.fingerprint_f32_batch(pcm, [0, len(pcm)], sr)
+            wins = self.engine.search_sliding_batch(fr, [0, len(fr)], p, window_frames, hop_frames, k, scopes)[0]
+        else:
+            wins = self.engine.search_sliding_pcm_batch(pcm, [0, len(pcm)], p, window_frames, hop_frames, k, scopes, sr)[0]
+        out = []
+        for w, rows in enumerate(wins):
+            infos = []
+            for row in rows:
+                info = self._audio_list_info(row["audio_uuid"])
+                if info is None:
+                    continue
+                info["frame_count"] = int(window_frames)
+                info["match_count"] = row["match_count"]
+                infos.append(info)
+            out.append({"frame": w * int(hop_frames), "rows": infos})
+        return out

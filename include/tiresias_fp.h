@@ -337,6 +337,60 @@ int tfp_search_scoped_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64
  * that a scoped search follows, none per search. Any pointer may be NULL. */
 int tfp_scope_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches, int64_t* table_builds);
 
+/* ---- sliding search: the ranked rows of every window of a long recording (new) ------------- */
+/* The reference records a fixed `duration` ms (default 3000) and searches that one window
+ * (application_handler.c:152-185, fp_handler.c:275-374). A caller with a whole call recording wants
+ * to know whether, and when, an enrolled clip occurs in it. The calls below search every window of a
+ * recording in one call: the recording is fingerprinted once, and the vote moves from one window to
+ * the next (the hop frames that left are subtracted, the hop that entered added) instead of being
+ * rebuilt, in exact integer arithmetic over the same key bitsets ranked search reads.
+ *
+ * Windows. A recording is the frames [qoffsets[r], qoffsets[r+1]) of frames, F_r of them. With
+ * window >= 1 and hop >= 1, window w of recording r is the `window` consecutive frames from
+ * qoffsets[r] + w * hop, and a recording of F frames has
+ *     nwin(F) = F < window ? 0 : (F - window) / hop + 1
+ * windows: trailing frames no full window covers are not searched. The windows of all recordings are
+ * numbered in order: woff[0] = 0, woff[r+1] = woff[r] + nwin(F_r).
+ *
+ * Rows. For window j = woff[r] + w, out[j * k + i] and counts[j] are exactly what
+ * tfp_search_scoped_batch returns for one query made of that window's frames with scope scopes[r]
+ * (TFP_SCOPE_ANY: tfp_search_ranked_batch's rows): the first k rows of fp_handler.c:367-374 run over
+ * those frames alone, by count descending, tied counts by audio_uuid descending, clips with a
+ * non-zero count only; entries past counts[j] are zeroed; every window's frame_count is `window`.
+ *
+ * PCM form. Each recording is fingerprinted once, as one clip (fp_handler.c:275), and a window's rows
+ * are those of the recording's own frame values, not of a fresh fingerprint of the cut-out samples:
+ * the two differ only in each cut's frame 0, which would see zero history where the recording has
+ * the previous hop (aubio_pvoc_do's sliding buffer, fp_handler.c:577-671). Window 0 of a recording
+ * equals tfp_search_ranked_pcm_batch on its first window * 256 samples. */
+#define TFP_SLIDE_RUN 32 /* consecutive windows of a recording one GPU block scores in turn */
+/* nwin above for a recording of nframes frames (the window fp_handler.c:275-374 searches, moved by
+ * hop); 0 for any non-positive argument. Host-only. */
+int64_t tfp_sliding_windows(int64_t nframes, int32_t window, int32_t hop);
+/* fp_handler.c:367-374 per window of each of nrecordings recordings (application_handler.c:152-185
+ * moved along the recording). scopes[nrecordings], or NULL for TFP_SCOPE_ANY everywhere. *nwindows
+ * always receives woff[nrecordings]; if that exceeds cap_windows (the rows out holds: out[cap_windows
+ * * k], counts[cap_windows]) the call returns TFP_E_CAPACITY and writes nothing else. TFP_E_ARG:
+ * window < 1, hop < 1, k outside [1, TFP_RANK_MAX], coefs outside [1,2], a scope below -1,
+ * non-monotone offsets. No recordings, empty recordings and recordings shorter than window give no
+ * window, and a call without a window or with an empty index launches nothing (an empty index: every
+ * counts[j] = 0). Calls are not coalesced. */
+int tfp_search_sliding_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nrecordings,
+                             const tfp_search_params* params, int32_t window, int32_t hop, const int32_t* scopes,
+                             int32_t k, tfp_candidate* out, int32_t* counts, int64_t cap_windows, int64_t* nwindows);
+/* PCM in (fp_handler.c:275, each recording once), rows out per window (:287-374): the recordings as
+ * tfp_search_ranked_pcm_batch takes its queries; a recording of n samples has tfp_frame_count(n)
+ * frames. The frame values stay on the device between the fingerprint and the slide. */
+int tfp_search_sliding_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nrecordings,
+                                 int32_t sample_rate, const tfp_search_params* params, int32_t window, int32_t hop,
+                                 const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                 int64_t cap_windows, int64_t* nwindows);
+/* Sliding batches served so far by the vote form (coefs = 1, every key in range, tolerance in [0, 8]:
+ * the rows of fp_handler.c:367-374 slid over the key bitsets) and by the general form (every other
+ * batch: the windows laid end to end and counted over the sorted rows), and the windows they held.
+ * Any pointer may be NULL. */
+int tfp_slide_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches, int64_t* windows);
+
 /* ---- aligned search: where in the clip a candidate matches (new; no reference counterpart) --- */
 /* The reference's count (fp_handler.c:287-374) says how many query frames found a row of the clip,
  * not where, nor whether the hits line up in time: the inserted rows carry frame_idx (:287-359
@@ -464,6 +518,17 @@ int tfp_group_search_scoped_batch(tfp_group* g, const tfp_frame* frames, const i
 int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
                                       int32_t sample_rate, const tfp_search_params* params, const int32_t* scopes,
                                       int32_t k, tfp_candidate* out, int32_t* counts);
+/* Sliding search on a group (fp_handler.c:367-374 read to row k for every window,
+ * application_handler.c:152-185 moved along the recording): every shard slides over every recording,
+ * and per window the shards' rows merge as tfp_group_search_ranked_batch's do; clip_id is the shard;
+ * scopes as tfp_group_search_scoped_batch. The other arguments and rules as the engine calls'. */
+int tfp_group_search_sliding_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets, int32_t nrecordings,
+                                   const tfp_search_params* params, int32_t window, int32_t hop, const int32_t* scopes,
+                                   int32_t k, tfp_candidate* out, int32_t* counts, int64_t cap_windows, int64_t* nwindows);
+int tfp_group_search_sliding_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nrecordings,
+                                       int32_t sample_rate, const tfp_search_params* params, int32_t window, int32_t hop,
+                                       const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                       int64_t cap_windows, int64_t* nwindows);
 /* tfp_search_aligned_batch on a group (fp_handler.c:367-374 read to row k, then each kept row's
  * alignment): the ranked search as tfp_group_search_ranked_batch, then every kept candidate is
  * aligned on the shard that holds it (tfp_align_batch with its clip id there). cand as that call's. */

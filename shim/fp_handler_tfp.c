@@ -926,6 +926,103 @@ struct ast_json* fp_search_fingerprint_in_context(const char* context, const cha
 	return search_candidates(context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high, max_results, true);
 }
 
+/* New: fp_search_fingerprint_candidates for every window of a long recording. The reference records
+ * a fixed duration and searches that one window (application_handler.c:152-185, fp_handler.c:275-374);
+ * this returns a JSON array with one object per full window of window_frames frames, hop_frames
+ * apart: {"frame": w * hop_frames, "rows": [...]}, rows being the first max_results rows of
+ * fp_handler.c:367-374 over that window's frames, each fp_search_fingerprint_candidates' object with
+ * frame_count = window_frames. in_context restricts every window to the clips enrolled in `context`,
+ * as fp_search_fingerprint_in_context does. The recording is fingerprinted once
+ * (tfp_group_search_sliding_pcm_batch). NULL where the candidates call returns NULL; an empty array
+ * for a recording shorter than one window. */
+struct ast_json* fp_search_fingerprint_timeline(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int window_frames,
+		const int hop_frames, const int max_results, const bool in_context)
+{
+	int16_t* pcm;
+	float* x;
+	int64_t cap, ns, off[2], nf = 0, nw = 0, got = 0, w;
+	int32_t sr, scope = TFP_SCOPE_ANY;
+	int rc, k, i;
+	tfp_search_params p;
+	tfp_candidate* cand;
+	int32_t* counts;
+	tfp_result r;
+	struct ast_json* j_res;
+	struct ast_json* j_win;
+	struct ast_json* j_rows;
+	struct ast_json* j_tmp;
+
+	if((filename == NULL) || (max_results < 1) || (window_frames < 1) || (hop_frames < 1)) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	if(search_params(&p, context, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	if(read_audio(filename, &pcm, &cap, &x, &ns, &sr) != 0) {
+		return NULL;
+	}
+	k = max_results > TFP_RANK_MAX ? TFP_RANK_MAX : max_results;
+	off[0] = 0;
+	off[1] = ns;
+	nf = tfp_frame_count(ns); /* ast_json_array_size(j_fprints), fp_handler.c:286 */
+	nw = tfp_sliding_windows(nf, window_frames, hop_frames);
+	if(in_context == true) {
+		scope = scope_of_context(context, false);
+	}
+	cand = ast_calloc((nw > 0 ? nw : 1) * k, sizeof(*cand));
+	counts = ast_calloc(nw > 0 ? nw : 1, sizeof(*counts));
+	if((cand == NULL) || (counts == NULL)) {
+		rc = TFP_E_NOMEM;
+	}
+	else if(pcm != NULL) {
+		rc = tfp_group_search_sliding_pcm_batch(g_tfp, pcm, off, 1, sr, &p, window_frames, hop_frames, &scope, k, cand,
+				counts, nw, &got);
+	}
+	else {
+		/* audio tfp_wav_decode refuses (fp32 hop values): its frames, then the frames form */
+		tfp_frame* fr = ast_calloc(nf > 0 ? nf : 1, sizeof(*fr));
+		int64_t qoff[2] = {0, 0};
+		rc = fr ? tfp_group_fingerprint_f32_batch(g_tfp, x, off, 1, sr, fr, nf, &qoff[1]) : TFP_E_NOMEM;
+		if(rc == TFP_OK) {
+			rc = tfp_group_search_sliding_batch(g_tfp, fr, qoff, 1, &p, window_frames, hop_frames, &scope, k, cand,
+					counts, nw, &got);
+		}
+		ast_free(fr);
+	}
+	pcm_put(pcm, cap);
+	ast_free(x);
+	if(rc != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not search %s: %s\n", filename, tfp_group_last_error(g_tfp));
+		ast_free(cand);
+		ast_free(counts);
+		return NULL;
+	}
+	j_res = ast_json_array_create();
+	for(w = 0; w < got; w++) {
+		j_rows = ast_json_array_create();
+		for(i = 0; i < counts[w]; i++) {
+			memset(&r, 0, sizeof(r));
+			r.found = 1;
+			r.match_count = cand[w * k + i].match_count;
+			r.frame_count = window_frames;
+			snprintf(r.uuid, sizeof(r.uuid), "%s", cand[w * k + i].uuid);
+			j_tmp = search_result(&r); /* a row whose audio_list entry is missing is skipped */
+			if(j_tmp != NULL) {
+				ast_json_array_append(j_rows, j_tmp);
+			}
+		}
+		j_win = ast_json_object_create();
+		ast_json_object_set(j_win, "frame", ast_json_integer_create(w * hop_frames));
+		ast_json_object_set(j_win, "rows", j_rows);
+		ast_json_array_append(j_res, j_win);
+	}
+	ast_free(cand);
+	ast_free(counts);
+	return j_res;
+}
+
 /* New: fp_search_fingerprint_candidates' array with where in each clip the recording lies: every
  * element also carries aligned_count, offset, first_frame and last_frame (tfp_alignment: the hits
  * that agree on one time offset, that offset in frames, and the first and last query frame on it).

@@ -60,6 +60,18 @@ struct ast_json* fp_search_fingerprint_candidates(const char* context, const cha
 struct ast_json* fp_search_fingerprint_in_context(const char* context, const char* filename, const int coefs,
 		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
 
+/* New: sliding search. The reference records a fixed duration and searches that one window
+ * (src/application_handler.c:152-185, src/fp_handler.c:275-374). This searches every full window of
+ * window_frames frames (256 samples each), hop_frames apart, of a longer recording, fingerprinting it
+ * once: a JSON array of {"frame": <the window's first frame>, "rows": <fp_search_fingerprint_candidates'
+ * array for that window's frames, frame_count = window_frames>} in time order, so a caller reads
+ * whether, and when, an enrolled clip occurs in the recording. in_context: every window searches the
+ * clips enrolled in `context` alone, as fp_search_fingerprint_in_context. Empty array: the recording
+ * is shorter than one window. NULL: bad arguments or an unreadable file. */
+struct ast_json* fp_search_fingerprint_timeline(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int window_frames,
+		const int hop_frames, const int max_results, const bool in_context);
+
 /* New: aligned search. fp_search_fingerprint_candidates' array (src/fp_handler.c:367-374 read to
  * row max_results), each element with four more integers saying where in the clip the recording
  * lies: "aligned_count" (the matching frames that agree on one time offset, <= match_count),
