@@ -17,6 +17,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -30,6 +31,7 @@
 #include "tfp_rank.hpp"
 #include "tfp_scope.hpp"
 #include "tfp_slide.hpp"
+#include "tfp_slide_align.hpp"
 #include "tfp_synth.hpp"
 #include "tfp_tables.hpp"
 #include "tfp_tolcache.hpp"
@@ -293,6 +295,11 @@ struct tfp_engine {
   DevBuf align_boxes, align_pairs, align_part, align_out;
   HostBuf align_pin;
   int64_t n_align_batches = 0, n_align_pairs = 0;
+  // sliding aligned search (slide_align_core): the launch's runs, their step tables and the entries'
+  // band counts (the boxes, pairs, partials and results are aligned search's buffers), and the
+  // batches / entries aligned so far by form
+  DevBuf sa_runs, sa_steps, sa_nb;
+  int64_t n_sa_batches = 0, n_sa_slid = 0, n_sa_direct = 0;
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   int32_t class_ku_max = 10;  // TFP_VOTE_CLASS_MAX: pattern-class vote up to this many used keys (-1: always the GEMM)
@@ -2189,6 +2196,155 @@ std::vector<int32_t> candidate_ids(const tfp_candidate* cand, const int32_t* cou
   return ids;
 }
 
+// ---- sliding aligned search (tfp_slide_align.hpp) ----
+// The sizes slide_align_core's launches hold, checked against the longest live clip before a call
+// writes anything (TFP_E_CAPACITY leaves all but *nwindows untouched): window + N within the 2^31
+// align_core allows, and a run's bands within 2^20. A run has at most kSlideAlignRun entries, each
+// less than `window` frames after the one before, so it covers fewer than kSlideAlignRun * window
+// frames.
+int slide_align_limits(tfp_engine* e, int32_t window) {
+  int64_t N = 0;
+  for (const Clip& c : e->clips)
+    if (c.alive) N = std::max(N, c.nrows);
+  if (window + N > (int64_t(1) << 31) || align_bands((int64_t)kSlideAlignRun * window, N) > (int64_t(1) << 20))
+    return fail(e, TFP_E_CAPACITY, "sliding aligned search: windows of %d frames against clips of up to %lld rows", window,
+                (long long)N);
+  return TFP_OK;
+}
+
+// out[j * K + i] = the alignment of window j of the recordings with clip ids[j * K + i] (-1: none, a
+// zeroed row). fo, woff as slide_core takes them; the clips' rows are read where they lie in the
+// staging arrays, as align_core reads them. The caller has passed slide_align_limits.
+int slide_align_core(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, const double* d_q,
+                     const tfp_search_params* P, int32_t window, int32_t hop, int32_t K, const std::vector<int64_t>& woff,
+                     const int32_t* ids, tfp_alignment* out, hipStream_t s) {
+  const int64_t nw = woff[nrec];
+  memset(out, 0, sizeof(tfp_alignment) * (size_t)nw * K);
+  // the named entries by (recording, clip), windows ascending
+  struct Ent { int32_t rec, clip; int64_t w, slot; };
+  std::vector<Ent> ents;
+  for (int32_t r = 0; r < nrec; r++)
+    for (int64_t j = woff[r]; j < woff[r + 1]; j++)
+      for (int32_t i = 0; i < K; i++) {
+        const int32_t id = ids[j * K + i];
+        if (id == -1) continue;
+        if (id < 0 || (size_t)id >= e->clips.size() || !e->clips[id].alive)
+          return fail(e, TFP_E_NOENT, "sliding aligned search: clip id %d is not in the index", id);
+        if (e->clips[id].nrows > 0) ents.push_back(Ent{r, id, j - woff[r], j * K + i});
+      }
+  if (ents.empty()) return TFP_OK;  // nothing to compare: every row stays zero
+  std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) {
+    return std::tie(a.rec, a.clip, a.w, a.slot) < std::tie(b.rec, b.clip, b.w, b.slot);
+  });
+  // direct pairs first, then the slid entries run by run; slot[i]: where work entry i's result goes
+  std::vector<AlignPair> direct, slid;
+  std::vector<int64_t> dslot, sslot;
+  std::vector<std::pair<int64_t, int64_t>> dups;  // (slot, the slot of the same (window, clip) before it)
+  std::vector<SlideAlignRun> runs;
+  std::vector<int32_t> steps, nbs;
+  int64_t bands_d = 0, bands_s = 0;
+  const bool slide = 2 * (int64_t)hop < window;
+  for (size_t a = 0; a < ents.size();) {
+    // one run: successive needed windows of one (recording, clip) that share a frame
+    std::vector<size_t> run(1, a);
+    size_t b = a + 1;
+    for (; b < ents.size() && ents[b].rec == ents[a].rec && ents[b].clip == ents[a].clip; b++) {
+      const Ent& prev = ents[run.back()];
+      if (ents[b].w == prev.w) {
+        dups.emplace_back(ents[b].slot, prev.slot);
+        continue;
+      }
+      if ((ents[b].w - prev.w) * hop >= window) break;
+      run.push_back(b);
+    }
+    const Clip& c = e->clips[ents[a].clip];
+    const int64_t N = c.nrows, f0 = fo[ents[a].rec], n = (int64_t)run.size();
+    if (n == 1 || !slide) {
+      for (const size_t i : run) {
+        direct.push_back(AlignPair{c.off, f0 + ents[i].w * hop, (int32_t)N, window});
+        dslot.push_back(ents[i].slot);
+      }
+      bands_d = std::max(bands_d, align_bands(window, N));
+    } else {
+      const int64_t pieces = (n + kSlideAlignRun - 1) / kSlideAlignRun;  // near-equal, each of >= 2 entries
+      for (int64_t p = 0; p < pieces; p++) {
+        const int64_t i0 = p * n / pieces, i1 = (p + 1) * n / pieces;
+        const int64_t w0 = ents[run[i0]].w, nsteps = ents[run[i1 - 1]].w - w0 + 1;
+        const int64_t nb = slide_align_bands(nsteps, window, hop, N);
+        runs.push_back(SlideAlignRun{c.off, f0 + w0 * hop, (int32_t)N, (int32_t)nsteps, (int32_t)steps.size(), 0});
+        steps.resize(steps.size() + (size_t)nsteps, -1);
+        for (int64_t i = i0; i < i1; i++) {
+          const Ent& en = ents[run[i]];
+          steps[(size_t)runs.back().e0 + (size_t)(en.w - w0)] = (int32_t)slid.size();
+          slid.push_back(AlignPair{c.off, f0 + en.w * hop, (int32_t)N, window});
+          sslot.push_back(en.slot);
+          nbs.push_back((int32_t)nb);
+        }
+        bands_s = std::max(bands_s, nb);
+      }
+    }
+    a = b;
+  }
+  const SearchConsts sc = search_consts(P);
+  const int64_t nf = fo[nrec], nd = (int64_t)direct.size(), ns = (int64_t)slid.size(), np = nd + ns;
+  HIPCHK(e, e->align_boxes.reserve(sizeof(FrameBox) * (nf + 1)));
+  HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->align_boxes.as<FrameBox>(), nullptr, 0, s));  // once per recording frame
+  // in chunks of <= 256 MB of partial keys (and of the launch grid's second dimension), as align_core
+  const int64_t chunk_d = nd ? std::max<int64_t>(1, std::min<int64_t>({(int64_t(1) << 25) / bands_d, kAlignMaxPairs, nd})) : 0;
+  const int64_t chunk_s = ns ? std::max<int64_t>(kSlideAlignRun, (int64_t(1) << 25) / bands_s) : 0;
+  const size_t pbytes = sizeof(AlignPair) * (size_t)np, obytes = sizeof(AlignOut) * (size_t)np;
+  HIPCHK(e, e->align_pairs.reserve(pbytes));
+  HIPCHK(e, e->align_part.reserve(sizeof(unsigned long long) *
+                                  (size_t)std::max(chunk_d * bands_d, std::min(chunk_s, ns) * bands_s)));
+  HIPCHK(e, e->align_out.reserve(obytes));
+  HIPCHK(e, e->align_pin.reserve(pbytes + obytes));
+  char* pin = e->align_pin.as<char>();
+  memcpy(pin, direct.data(), sizeof(AlignPair) * (size_t)nd);
+  memcpy(pin + sizeof(AlignPair) * (size_t)nd, slid.data(), sizeof(AlignPair) * (size_t)ns);
+  HIPCHK(e, hipMemcpyAsync(e->align_pairs.p, pin, pbytes, hipMemcpyHostToDevice, s));
+  const FrameBox* boxes = e->align_boxes.as<FrameBox>();
+  unsigned long long* d_part = e->align_part.as<unsigned long long>();
+  for (int64_t p0 = 0; p0 < nd; p0 += chunk_d) {
+    const int32_t n = (int32_t)std::min<int64_t>(chunk_d, nd - p0);
+    HIPCHK(e, launch_align(e->align_pairs.as<AlignPair>() + p0, n, bands_d, boxes, e->st_m1.as<int32_t>(),
+                           e->st_m2.as<int32_t>(), sc.coefs == 2, d_part, e->align_out.as<AlignOut>() + p0, s));
+  }
+  if (ns) {
+    int rc;
+    if ((rc = upload(e, e->sa_runs, runs.data(), sizeof(SlideAlignRun) * runs.size(), s)) ||
+        (rc = upload(e, e->sa_steps, steps.data(), sizeof(int32_t) * steps.size(), s)) ||
+        (rc = upload(e, e->sa_nb, nbs.data(), sizeof(int32_t) * nbs.size(), s)))
+      return rc;
+    // whole runs per launch: a run's entries are consecutive, steps[run.e0] onwards names them
+    for (size_t r0 = 0; r0 < runs.size();) {
+      const int64_t ent0 = steps[(size_t)runs[r0].e0];  // (a run's first window is needed)
+      int64_t ent1 = ent0;
+      size_t r1 = r0;
+      for (; r1 < runs.size() && r1 - r0 < (size_t)kSlideAlignMaxRuns; r1++) {
+        const int64_t last = steps[(size_t)runs[r1].e0 + (size_t)runs[r1].nsteps - 1] + 1;  // (and its last)
+        if (r1 > r0 && last - ent0 > chunk_s) break;
+        ent1 = last;
+      }
+      HIPCHK(e, launch_slide_align(e->sa_runs.as<SlideAlignRun>() + r0, (int32_t)(r1 - r0), e->sa_steps.as<int32_t>(),
+                                   (int32_t)ent0, (int32_t)(ent1 - ent0), e->align_pairs.as<AlignPair>() + nd + ent0,
+                                   e->sa_nb.as<int32_t>() + ent0, bands_s, window, hop, boxes, e->st_m1.as<int32_t>(),
+                                   e->st_m2.as<int32_t>(), sc.coefs == 2, d_part, e->align_out.as<AlignOut>() + nd + ent0,
+                                   s));
+      r0 = r1;
+    }
+  }
+  HIPCHK(e, hipMemcpyAsync(pin + pbytes, e->align_out.p, obytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  const tfp_alignment* res = reinterpret_cast<const tfp_alignment*>(pin + pbytes);
+  for (int64_t i = 0; i < nd; i++) out[dslot[(size_t)i]] = res[i];
+  for (int64_t i = 0; i < ns; i++) out[sslot[(size_t)i]] = res[nd + i];
+  for (const auto& d : dups) out[d.first] = out[d.second];  // (in order: a copy's source is filled before it)
+  e->n_sa_batches++;
+  e->n_sa_slid += ns;
+  e->n_sa_direct += nd;
+  return TFP_OK;
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -2954,6 +3110,92 @@ int tfp_slide_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batch
   if (vote_batches) *vote_batches = e->n_slide_vote;
   if (general_batches) *general_batches = e->n_slide_general;
   if (windows) *windows = e->n_slide_windows;
+  return TFP_OK;
+}
+
+// ---- sliding aligned search (tfp_slide_align.hpp): fp_handler.c:287-351 per window frame against
+// the rows of each window's clips ----
+int tfp_align_sliding_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
+                            const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* clip_ids, int32_t k,
+                            tfp_alignment* out, int64_t cap_windows, int64_t* nwindows) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  for (int32_t i = 0; i < nrec; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0), woff;
+  int rc = slide_args(e, P, window, hop, k, nrec, nullptr, fo, out, clip_ids, cap_windows, nwindows, woff);
+  if (rc || (rc = slide_align_limits(e, window))) return rc;
+  if (!woff[nrec]) return TFP_OK;  // no full window: nothing is launched
+  if (!frames) return fail(e, TFP_E_ARG, "frames is NULL");
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = upload_frames(e, frames, qoff, nrec))) return rc;
+  return slide_align_core(e, fo, nrec, e->q.as<double>(), P, window, hop, k, woff, clip_ids, out, e->stream);
+}
+
+int tfp_search_sliding_aligned_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
+                                     const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes,
+                                     int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align,
+                                     int64_t cap_windows, int64_t* nwindows) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  for (int32_t i = 0; i < nrec; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0), woff;
+  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
+  if (rc) return rc;
+  const int32_t nw = (int32_t)woff[nrec];
+  if (!nw) return TFP_OK;  // no full window: nothing is launched
+  if (!align) return fail(e, TFP_E_ARG, "sliding aligned search: NULL output");
+  if ((rc = slide_align_limits(e, window))) return rc;
+  if (!frames) return fail(e, TFP_E_ARG, "frames is NULL");
+  std::vector<unsigned long long> keys;
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = upload_frames(e, frames, qoff, nrec))) return rc;
+  if ((rc = slide_core(e, fo, nrec, e->q.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
+  fill_candidates(e, keys, nw, k, out, counts);
+  // (the frame values are still in e->q)
+  return slide_align_core(e, fo, nrec, e->q.as<double>(), P, window, hop, k, woff, candidate_ids(out, counts, nw, k).data(),
+                          align, e->stream);
+}
+
+int tfp_search_sliding_aligned_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nrec, int32_t sr,
+                                         const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes,
+                                         int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align,
+                                         int64_t cap_windows, int64_t* nwindows) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  for (int32_t i = 0; i < nrec; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  std::vector<const void*> ptrs;
+  std::vector<int64_t> lens;
+  if (nrec > 0) split_offsets(pcm, sizeof(int16_t), offsets, nrec, &ptrs, &lens);
+  std::vector<int64_t> fo((size_t)std::max(nrec, 0) + 1, 0), woff;
+  for (int32_t i = 0; i < nrec; i++) fo[i + 1] = fo[i] + tfp_frame_count(lens[i]);
+  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
+  if (rc) return rc;
+  const int32_t nw = (int32_t)woff[nrec];
+  if (!nw) return TFP_OK;  // no full window: nothing is fingerprinted
+  if (!align) return fail(e, TFP_E_ARG, "sliding aligned search: NULL output");
+  if ((rc = slide_align_limits(e, window))) return rc;
+  if (!pcm) return fail(e, TFP_E_ARG, "samples are NULL");
+  std::vector<unsigned long long> keys;
+  HIPCHK(e, hipSetDevice(e->device));
+  int64_t nf;  // each recording fingerprinted once; the frame values stay in e->db for the slide and the alignment
+  if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nrec, sr, &nf, nullptr, P->coefs == 2))) return rc;
+  if ((rc = slide_core(e, fo, nrec, e->db.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
+  e->stage_pending = false;
+  fill_candidates(e, keys, nw, k, out, counts);
+  return slide_align_core(e, fo, nrec, e->db.as<double>(), P, window, hop, k, woff,
+                          candidate_ids(out, counts, nw, k).data(), align, e->stream);
+}
+
+int tfp_slide_align_stats(tfp_engine* e, int64_t* batches, int64_t* slid_entries, int64_t* direct_entries) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (batches) *batches = e->n_sa_batches;
+  if (slid_entries) *slid_entries = e->n_sa_slid;
+  if (direct_entries) *direct_entries = e->n_sa_direct;
   return TFP_OK;
 }
 

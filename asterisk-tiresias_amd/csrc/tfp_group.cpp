@@ -902,6 +902,53 @@ int tfp_group_search_aligned_batch(tfp_group* g, const tfp_frame* frames, const 
   return TFP_OK;
 }
 
+// Sliding aligned search on a group (tfp_slide_align.hpp): the sliding search above, then every kept
+// row aligned on the shard that holds its clip (tfp_align_sliding_batch with the shard-local clip id;
+// -1 for the other shards' rows), a window in a query's place.
+int tfp_group_search_sliding_aligned_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
+                                           const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes,
+                                           int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align,
+                                           int64_t cap_windows, int64_t* nwindows) {
+  if (!g || !qoff) return TFP_E_ARG;
+  if (k < 1 || k > TFP_RANK_MAX || !valid_params(P)) return gfail(g, TFP_E_ARG, "sliding search: k or coefs out of range");
+  int32_t nw = 0;
+  if (int rc = group_slide_windows(g, qoff, nrec, false, window, hop, scopes, cap_windows, nwindows, &nw)) return rc;
+  if (!nw) return TFP_OK;
+  if (!align) return gfail(g, TFP_E_ARG, "sliding aligned search: NULL output");
+  std::lock_guard<std::recursive_mutex> lk(g->mu);  // (the shards' clips stay as ranked until they are aligned)
+  std::vector<int32_t> kept;
+  int rc = group_rank(
+      g, nw, P, k, out, counts,
+      [&](int s, tfp_candidate* o, int32_t* c) {
+        int64_t n = 0;
+        return tfp_search_sliding_batch(g->eng[s], frames, qoff, nrec, P, window, hop, scopes, k, o, c, nw, &n);
+      },
+      &kept);
+  if (rc) return rc;
+  const size_t np = (size_t)nw * k;
+  memset(align, 0, sizeof(tfp_alignment) * np);
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<int32_t>> ids(n, std::vector<int32_t>(np, -1));
+  std::vector<char> used(n, 0);
+  for (size_t p = 0; p < np; p++)
+    if (kept[p] >= 0) {
+      const Member& mb = g->members[kept[p]];
+      ids[mb.shard][p] = mb.id;
+      used[mb.shard] = 1;
+    }
+  std::vector<std::vector<tfp_alignment>> res(n, std::vector<tfp_alignment>(np));
+  rc = run_all(g, [&](int s) {
+    int64_t got = 0;
+    return used[s] ? tfp_align_sliding_batch(g->eng[s], frames, qoff, nrec, P, window, hop, ids[s].data(), k,
+                                             res[s].data(), nw, &got)
+                   : TFP_OK;
+  });
+  if (rc) return rc;
+  for (size_t p = 0; p < np; p++)
+    if (kept[p] >= 0) align[p] = res[g->members[kept[p]].shard][p];
+  return TFP_OK;
+}
+
 namespace {
 // One search over host samples on every shard (each fingerprints the whole batch: no exchange on
 // the latency path), combined by the integer max of the keys.

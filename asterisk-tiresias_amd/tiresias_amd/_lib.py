@@ -169,6 +169,16 @@ _SIGS = {
                                                  C.c_int32, P, P, C.c_int64, C.POINTER(C.c_int64)]),
     "tfp_group_search_sliding_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32,
                                                      C.c_int32, P, C.c_int32, P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_align_sliding_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32, P, C.c_int32,
+                                          P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_search_sliding_aligned_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32, P,
+                                                   C.c_int32, P, P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_search_sliding_aligned_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32,
+                                                       C.c_int32, P, C.c_int32, P, P, P, C.c_int64,
+                                                       C.POINTER(C.c_int64)]),
+    "tfp_slide_align_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
+    "tfp_group_search_sliding_aligned_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32,
+                                                         P, C.c_int32, P, P, P, C.c_int64, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

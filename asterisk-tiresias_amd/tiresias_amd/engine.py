@@ -87,7 +87,7 @@ def sliding_windows(nframes: int, window: int, hop: int) -> int:
 class _SlidingCalls:
     """Sliding search, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*), as _ScopedCalls."""
 
-    def _sliding(self, name, data, offsets, nframes, head, p, window, hop, scopes, k):
+    def _sliding(self, name, data, offsets, nframes, head, p, window, hop, scopes, k, aligned=False):
         nrec, k = len(offsets) - 1, int(k)
         if scopes is not None:
             scopes = np.ascontiguousarray(scopes, np.int32)
@@ -96,11 +96,12 @@ class _SlidingCalls:
         per = [sliding_windows(n, window, hop) for n in nframes]
         cap, nw = sum(per), C.c_int64()
         out, counts = (Candidate * max(1, cap * max(k, 1)))(), (C.c_int32 * max(1, cap))()
+        align = ((Alignment * max(1, cap * max(k, 1)))(),) if aligned else ()
         self._chk(self._fn(name)(self._h, data.ctypes.data, offsets.ctypes.data, nrec, *head, C.byref(p), int(window),
-                                 int(hop), None if scopes is None else scopes.ctypes.data, k, out, counts, cap,
+                                 int(hop), None if scopes is None else scopes.ctypes.data, k, out, counts, *align, cap,
                                  C.byref(nw)))
         assert nw.value == cap
-        rows = Engine._candidates(out, counts, cap, k)
+        rows = Engine._aligned(out, align[0], counts, cap, k) if aligned else Engine._candidates(out, counts, cap, k)
         woff = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
         return [rows[woff[r]:woff[r + 1]] for r in range(nrec)]
 
@@ -120,6 +121,17 @@ class _SlidingCalls:
         offsets = np.ascontiguousarray(offsets, np.int64)
         return self._sliding("_search_sliding_pcm_batch", pcm, offsets, [frame_count(n) for n in np.diff(offsets)],
                              (int(sample_rate),), p, window, hop, scopes, k)
+
+
+    def search_sliding_aligned_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, window: int, hop: int, k: int,
+                                     scopes=None):
+        """tfp_search_sliding_aligned_batch: search_sliding_batch's rows, each with the alignment (aligned_count,
+        offset, first_frame, last_frame, window-relative) of its window's frames with its clip. The rows of one
+        occurrence of a clip share w * hop - offset across windows wherever that offset alone attains the count."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        return self._sliding("_search_sliding_aligned_batch", frames, qoffsets, np.diff(qoffsets), (), p, window, hop,
+                             scopes, k, aligned=True)
 
 
 class _ScopedCalls:
@@ -447,6 +459,40 @@ class Engine(_ScopedCalls, _SlidingCalls):
         b, n = C.c_int64(), C.c_int64()
         self._chk(lib().tfp_align_stats(self._h, C.byref(b), C.byref(n)))
         return {"batches": b.value, "pairs": n.value}
+
+    # ---- sliding aligned search: each window's rows with where the clip lies
+    def align_sliding_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, window: int, hop: int, clip_ids, k: int):
+        """tfp_align_sliding_batch: per recording a list over its windows of k alignment dicts, window j (numbered
+        over all recordings) against clip_ids[j * k + i] (-1: a zeroed row)."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        nrec, k = len(qoffsets) - 1, int(k)
+        per = [sliding_windows(n, window, hop) for n in np.diff(qoffsets)]
+        cap, nw = sum(per), C.c_int64()
+        ids = np.ascontiguousarray(clip_ids, np.int32).reshape(-1)
+        if len(ids) != cap * max(k, 0):
+            raise ValueError("clip_ids must hold nwindows * k ids")
+        out = (Alignment * max(1, cap * max(k, 1)))()
+        self._chk(lib().tfp_align_sliding_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, nrec, C.byref(p),
+                                                int(window), int(hop), ids.ctypes.data, k, out, cap, C.byref(nw)))
+        assert nw.value == cap
+        woff = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+        return [[[self._alignment(out[j * k + i]) for i in range(k)] for j in range(woff[r], woff[r + 1])]
+                for r in range(nrec)]
+
+    def search_sliding_aligned_pcm_batch(self, pcm, offsets, p: SearchParams, window: int, hop: int, k: int, scopes=None,
+                                         sample_rate: int = 8000):
+        """tfp_search_sliding_aligned_pcm_batch: search_sliding_aligned_batch over each recording's own fingerprint."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        return self._sliding("_search_sliding_aligned_pcm_batch", pcm, offsets, [frame_count(n) for n in np.diff(offsets)],
+                             (int(sample_rate),), p, window, hop, scopes, k, aligned=True)
+
+    def slide_align_stats(self) -> dict:
+        """tfp_slide_align_stats: batches that reached the sliding alignment, and the entries aligned by form."""
+        b, s, d = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(lib().tfp_slide_align_stats(self._h, C.byref(b), C.byref(s), C.byref(d)))
+        return {"batches": b.value, "slid_entries": s.value, "direct_entries": d.value}
 
     def rank_stats(self) -> dict:
         """tfp_rank_stats: ranked batches served by the vote form and by the general form."""

@@ -423,3 +423,43 @@ class FpHandler:
                 infos.append(info)
             out.append({"frame": w * int(hop_frames), "rows": infos})
         return out
+
+    def fp_search_fingerprint_timeline_aligned(self, context, filename, coefs, tolerance, freq_ignore_low,
+                                               freq_ignore_high, window_frames, hop_frames, max_results, in_context=False):
+        """fp_search_fingerprint_timeline's array, each row also carrying where in the clip its window lies:
+        aligned_count, offset, first_frame and last_frame as fp_search_fingerprint_aligned words them
+        (window-relative: window frame x lies at clip frame x + offset), and clip_start_frame = frame -
+        offset, the recording frame at which clip frame 0 lies, equal across the windows of one
+        occurrence of the clip wherever the occurrence's offset alone attains the window's aligned_count (a
+        window that fits the clip as well in an earlier place reports that one: the smallest offset wins). The reference's result query (fp_handler.c:367-374) never reads the
+        rows' frame_idx. The file is fingerprinted once, then search_sliding_aligned_batch."""
+        if context is None or filename is None:
+            return []
+        if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1 or window_frames < 1 or hop_frames < 1:
+            return []
+        try:
+            pcm, sr = read_audio(filename)
+        except TfpError:
+            return []
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        k = min(int(max_results), TFP_RANK_MAX)
+        scopes = [self._scope_of(context, False)] if in_context else None
+        if pcm.dtype == np.float32:
+            fr = self.engine.fingerprint_f32_batch(pcm, [0, len(pcm)], sr)
+        else:
+            fr = self.engine.fingerprint_batch(pcm, [0, len(pcm)], sr)
+        wins = self.engine.search_sliding_aligned_batch(fr, [0, len(fr)], p, window_frames, hop_frames, k, scopes)[0]
+        out = []
+        for w, rows in enumerate(wins):
+            infos = []
+            for row in rows:
+                info = self._audio_list_info(row["audio_uuid"])
+                if info is None:
+                    continue
+                info["frame_count"] = int(window_frames)
+                for key in ("match_count", "aligned_count", "offset", "first_frame", "last_frame"):
+                    info[key] = row[key]
+                info["clip_start_frame"] = w * int(hop_frames) - row["offset"]
+                infos.append(info)
+            out.append({"frame": w * int(hop_frames), "rows": infos})
+        return out

@@ -431,6 +431,67 @@ int tfp_search_aligned_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int6
  * frames of fp_handler.c:287-351 against the clips' rows). Either pointer may be NULL. */
 int tfp_align_stats(tfp_engine* eng, int64_t* batches, int64_t* pairs);
 
+/* ---- sliding aligned search: each window's rows with where the clip lies (new) -------------- */
+/* Sliding search above says which clips win each window of a recording by the bag count of
+ * fp_handler.c:367-374; aligned search says for one query and a clip on which time offset the hits
+ * line up. The calls below do both for every window: window, hop, woff, the rows, counts and k are
+ * tfp_search_sliding_batch's, and for window j = woff[r] + w and row i < counts[j], align[j * k + i]
+ * is exactly the tfp_alignment tfp_align_batch returns for a query made of that window's `window`
+ * frames alone and that row's clip (the per-frame predicate of fp_handler.c:287-351): aligned_count,
+ * the smallest offset attaining it, first_frame and last_frame, all window-relative. Window frame x
+ * lies at clip frame x + offset, and recording frame w * hop + x lies there too. Entries past
+ * counts[j] are zeroed.
+ *
+ * Joining windows. w * hop - offset is the recording frame at which clip frame 0 lies. Where the
+ * occurrence's diagonal is the only one of the window that attains aligned_count, the rows of one
+ * occurrence of a clip share that value across windows, and a caller joins the windows with equal
+ * (clip, w * hop - offset) into one occurrence, from recording frame w * hop + first_frame of its
+ * first window to w * hop + last_frame of its last. Where a window fits the clip equally well in an
+ * earlier place (offset is the smallest diagonal attaining the count), that window reports the
+ * earlier place: short windows, a high tolerance, and audio whose max1 hardly moves (8 kHz speech
+ * and noise span about 1 dB) make such ties common, so a caller takes the value most windows of a
+ * stretch agree on, or lengthens the window (48 frames of a clip with varying level were unique in
+ * the tests where 24 were not).
+ *
+ * Consecutive windows share all but hop frames: a clip's diagonal counts move from one window to the
+ * next by subtracting the hop frames that left and adding the hop that entered, in exact integer
+ * arithmetic over the predicate aligned search tests. The (window, row) entries are grouped by
+ * (recording, clip) and cut into runs wherever two successive needed windows share no frame
+ * ((w' - w) * hop >= window); a run with one entry, and every run when 2 * hop >= window (a slid step
+ * tests 2 * hop * N boxes, a window from scratch window * N), is aligned from scratch (direct), the
+ * rest slid. Both give the same integers. Calls are not coalesced. */
+/* The primitive (fp_handler.c:287-351 per window frame against the named clips' rows): window j of
+ * the recordings (as tfp_search_sliding_batch numbers them) against clips clip_ids[j * k + i], i < k:
+ * out[j * k + i]; clip_ids[nwindows * k] and out[nwindows * k]. An id of -1 gives a zeroed row; any
+ * other id out of range or of a removed clip is TFP_E_NOENT. The argument and capacity rules are
+ * tfp_search_sliding_batch's (cap_windows: the windows clip_ids and out hold): *nwindows is always
+ * set, and on TFP_E_CAPACITY nothing else is written. TFP_E_CAPACITY also, before anything is
+ * written, when window + N exceeds 2^31 or 32 * window + N nears 2^28 for the N rows of the longest
+ * enrolled clip (the sizes one launch holds); in the group form a shard finds this after out and
+ * counts are written. The clips' rows are read as enrolled: no tfp_index_commit is needed. */
+int tfp_align_sliding_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nrecordings,
+                            const tfp_search_params* params, int32_t window, int32_t hop, const int32_t* clip_ids,
+                            int32_t k, tfp_alignment* out, int64_t cap_windows, int64_t* nwindows);
+/* tfp_search_sliding_batch (fp_handler.c:367-374 per window: the same out, counts and *nwindows,
+ * byte for byte) plus align[j * k + i] for row i of window j (align[cap_windows * k]). */
+int tfp_search_sliding_aligned_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets,
+                                     int32_t nrecordings, const tfp_search_params* params, int32_t window, int32_t hop,
+                                     const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                     tfp_alignment* align, int64_t cap_windows, int64_t* nwindows);
+/* tfp_search_sliding_pcm_batch (fp_handler.c:275 once per recording, :287-374 per window) plus the
+ * rows' alignments. The frame values and their boxes stay on the device between the fingerprint, the
+ * slide and the alignment. */
+int tfp_search_sliding_aligned_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nrecordings,
+                                         int32_t sample_rate, const tfp_search_params* params, int32_t window,
+                                         int32_t hop, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                                         int32_t* counts, tfp_alignment* align, int64_t cap_windows, int64_t* nwindows);
+/* Batches that reached the sliding alignment so far, and the (window, clip) entries they computed by
+ * the slid form and by the direct form (the frames of fp_handler.c:287-351 against the clips' rows,
+ * by the run rule above). An entry is counted where it is computed: a (window, clip) named twice in
+ * clip_ids counts once (the second row is a copy), and a clip without rows, an id of -1 and a call
+ * that launches nothing count nothing. Any pointer may be NULL. */
+int tfp_slide_align_stats(tfp_engine* eng, int64_t* batches, int64_t* slid_entries, int64_t* direct_entries);
+
 /* ---- live channels: rolling fingerprint + match (configs[4]) --------------------------
  * The dialplan app records `duration` ms of a channel to a WAV and searches it
  * (application_handler.c:152-185, record_voice :248-312). A stream keeps the most recent
@@ -535,6 +596,15 @@ int tfp_group_search_sliding_pcm_batch(tfp_group* g, const int16_t* pcm, const i
 int tfp_group_search_aligned_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
                                    const tfp_search_params* params, int32_t k, tfp_candidate* cand,
                                    tfp_alignment* align, int32_t* counts);
+/* tfp_search_sliding_aligned_batch on a group (fp_handler.c:367-374 read to row k for every window,
+ * then each kept row's alignment): the sliding search as tfp_group_search_sliding_batch, then every
+ * kept row is aligned on the shard that holds its clip (tfp_align_sliding_batch with the shard-local
+ * clip id, -1 for the other shards' rows), as tfp_group_search_aligned_batch does per query. */
+int tfp_group_search_sliding_aligned_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets,
+                                           int32_t nrecordings, const tfp_search_params* params, int32_t window,
+                                           int32_t hop, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                                           int32_t* counts, tfp_alignment* align, int64_t cap_windows,
+                                           int64_t* nwindows);
 /* tfp_search_pcm_gather and the coalescing of concurrent calls (as for one engine) on a group: the
  * channel threads' batch-1 searches through the shim run as shared batches on every GPU. */
 int tfp_group_search_pcm_gather(tfp_group* g, const int16_t* const* pcms, const int64_t* nsamples, int32_t nqueries,

@@ -1098,6 +1098,109 @@ struct ast_json* fp_search_fingerprint_aligned(const char* context, const char* 
 	return j_res;
 }
 
+/* New: fp_search_fingerprint_timeline's array with where in its clip each row's window lies: every
+ * row also carries aligned_count, offset, first_frame and last_frame (tfp_alignment of the window's
+ * frames alone with the row's clip, as fp_search_fingerprint_aligned words them) and
+ * clip_start_frame = frame - offset, the recording frame at which clip frame 0 lies, equal across
+ * the windows of one occurrence wherever its offset alone attains the window's aligned_count. The reference's result query (fp_handler.c:367-374) never reads the
+ * rows' frame_idx. The file's frames once (tfp_group_fingerprint_batch / _f32_batch), then
+ * tfp_group_search_sliding_aligned_batch. NULL and the empty array as for the timeline call. */
+struct ast_json* fp_search_fingerprint_timeline_aligned(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int window_frames,
+		const int hop_frames, const int max_results, const bool in_context)
+{
+	int16_t* pcm;
+	float* x;
+	int64_t cap, ns, off[2], qoff[2] = {0, 0}, nf = 0, nw = 0, got = 0, w;
+	int32_t sr, scope = TFP_SCOPE_ANY;
+	int rc, k, i;
+	tfp_search_params p;
+	tfp_candidate* cand;
+	tfp_alignment* align;
+	int32_t* counts;
+	tfp_frame* fr;
+	tfp_result r;
+	struct ast_json* j_res;
+	struct ast_json* j_win;
+	struct ast_json* j_rows;
+	struct ast_json* j_tmp;
+
+	if((filename == NULL) || (max_results < 1) || (window_frames < 1) || (hop_frames < 1)) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	if(search_params(&p, context, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	if(read_audio(filename, &pcm, &cap, &x, &ns, &sr) != 0) {
+		return NULL;
+	}
+	k = max_results > TFP_RANK_MAX ? TFP_RANK_MAX : max_results;
+	off[0] = 0;
+	off[1] = ns;
+	nf = tfp_frame_count(ns); /* ast_json_array_size(j_fprints), fp_handler.c:286 */
+	nw = tfp_sliding_windows(nf, window_frames, hop_frames);
+	if(in_context == true) {
+		scope = scope_of_context(context, false);
+	}
+	cand = ast_calloc((nw > 0 ? nw : 1) * k, sizeof(*cand));
+	align = ast_calloc((nw > 0 ? nw : 1) * k, sizeof(*align));
+	counts = ast_calloc(nw > 0 ? nw : 1, sizeof(*counts));
+	fr = ast_calloc(nf > 0 ? nf : 1, sizeof(*fr));
+	if((cand == NULL) || (align == NULL) || (counts == NULL) || (fr == NULL)) {
+		rc = TFP_E_NOMEM;
+	}
+	else if(pcm != NULL) {
+		rc = tfp_group_fingerprint_batch(g_tfp, pcm, off, 1, sr, fr, nf, &qoff[1]);
+	}
+	else {
+		rc = tfp_group_fingerprint_f32_batch(g_tfp, x, off, 1, sr, fr, nf, &qoff[1]);
+	}
+	if(rc == TFP_OK) {
+		rc = tfp_group_search_sliding_aligned_batch(g_tfp, fr, qoff, 1, &p, window_frames, hop_frames, &scope, k, cand,
+				counts, align, nw, &got);
+	}
+	ast_free(fr);
+	pcm_put(pcm, cap);
+	ast_free(x);
+	if(rc != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not search %s: %s\n", filename, tfp_group_last_error(g_tfp));
+		ast_free(cand);
+		ast_free(align);
+		ast_free(counts);
+		return NULL;
+	}
+	j_res = ast_json_array_create();
+	for(w = 0; w < got; w++) {
+		j_rows = ast_json_array_create();
+		for(i = 0; i < counts[w]; i++) {
+			const tfp_alignment* a = &align[w * k + i];
+			memset(&r, 0, sizeof(r));
+			r.found = 1;
+			r.match_count = cand[w * k + i].match_count;
+			r.frame_count = window_frames;
+			snprintf(r.uuid, sizeof(r.uuid), "%s", cand[w * k + i].uuid);
+			j_tmp = search_result(&r); /* a row whose audio_list entry is missing is skipped */
+			if(j_tmp != NULL) {
+				ast_json_object_set(j_tmp, "aligned_count", ast_json_integer_create(a->aligned_count));
+				ast_json_object_set(j_tmp, "offset", ast_json_integer_create(a->offset));
+				ast_json_object_set(j_tmp, "first_frame", ast_json_integer_create(a->first_frame));
+				ast_json_object_set(j_tmp, "last_frame", ast_json_integer_create(a->last_frame));
+				ast_json_object_set(j_tmp, "clip_start_frame", ast_json_integer_create(w * hop_frames - a->offset));
+				ast_json_array_append(j_rows, j_tmp);
+			}
+		}
+		j_win = ast_json_object_create();
+		ast_json_object_set(j_win, "frame", ast_json_integer_create(w * hop_frames));
+		ast_json_object_set(j_win, "rows", j_rows);
+		ast_json_array_append(j_res, j_win);
+	}
+	ast_free(cand);
+	ast_free(align);
+	ast_free(counts);
+	return j_res;
+}
+
 /* ---- live channels: the dialplan application's recording without the /tmp WAV -------------
  * application_handler.c:152-185 records `duration` ms of the channel's voice frames
  * (record_voice, :248-312) into /tmp/tiresias-UUID.wav and searches that file. A channel keeps the

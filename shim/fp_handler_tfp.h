@@ -82,6 +82,22 @@ struct ast_json* fp_search_fingerprint_timeline(const char* context, const char*
 struct ast_json* fp_search_fingerprint_aligned(const char* context, const char* filename, const int coefs,
 		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
 
+/* New: sliding aligned search. fp_search_fingerprint_timeline's array (src/fp_handler.c:367-374 per
+ * window), each row with where in the clip its window lies: "aligned_count", "offset", "first_frame"
+ * and "last_frame" as fp_search_fingerprint_aligned words them, window-relative (window frame x lies at
+ * clip frame x + offset), and "clip_start_frame" = frame - offset, the recording frame at which clip
+ * frame 0 lies. clip_start_frame is equal across the windows of one occurrence of a clip wherever the
+ * occurrence's offset is the only one attaining the window's aligned_count, so a caller joins the
+ * windows into "the announcement runs from recording frame A to B, from clip frame C on". A window
+ * that fits the clip equally well in an earlier place reports the earlier one (the smallest offset
+ * wins): join on the value most windows of a stretch agree on, and prefer windows of 48 frames or
+ * more, since max1 of 8 kHz audio spans about 1 dB and short windows tie often.
+ * The file is fingerprinted once and every row aligned on the GPU that holds its clip. NULL and the
+ * empty array as for the timeline call. */
+struct ast_json* fp_search_fingerprint_timeline_aligned(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int window_frames,
+		const int hop_frames, const int max_results, const bool in_context);
+
 /* New: a live channel, for the dialplan application's record loop (application_handler.c:152-185,
  * record_voice :248-312) without the /tmp WAV round trip. Open one per call with max_ms >= the
  * recording's duration, push every voice frame's SLIN samples as it is read (160 per 20 ms frame
