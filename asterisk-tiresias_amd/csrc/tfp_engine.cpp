@@ -32,6 +32,7 @@
 #include "tfp_scope.hpp"
 #include "tfp_slide.hpp"
 #include "tfp_slide_align.hpp"
+#include "tfp_trace.hpp"
 #include "tfp_synth.hpp"
 #include "tfp_tables.hpp"
 #include "tfp_tolcache.hpp"
@@ -300,6 +301,10 @@ struct tfp_engine {
   // batches / entries aligned so far by form
   DevBuf sa_runs, sa_steps, sa_nb;
   int64_t n_sa_batches = 0, n_sa_slid = 0, n_sa_direct = 0;
+  // diagonal trace (trace_core): the launch's requests and results (the boxes are aligned search's),
+  // and the batches that launched the kernel / the requests it computed so far
+  DevBuf trace_reqs, trace_out;
+  int64_t n_trace_batches = 0, n_traces = 0;
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   int32_t class_ku_max = 10;  // TFP_VOTE_CLASS_MAX: pattern-class vote up to this many used keys (-1: always the GEMM)
@@ -2345,6 +2350,100 @@ int slide_align_core(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec
   return TFP_OK;
 }
 
+// ---- diagonal trace and occurrence search (tfp_trace.hpp, tfp_occur.hpp) ----
+static_assert(sizeof(tfp_trace) == sizeof(TraceOut), "tfp_occur.hpp and the public header agree");
+
+// out[i] = the trace of reqs[i] over recording reqs[i].recording of fo[0 .. nrec] (checked by the
+// caller to lie in range). A clip id of -1 gives a zeroed row, any other id that names no live clip
+// TFP_E_NOENT before anything is written; a request that covers no frame is answered here. The rest
+// go to the kernel in one launch, after boxes() has put the recordings' frame boxes into
+// e->align_boxes (called only then). The clips' rows are read where they lie in the staging arrays,
+// as align_core reads them.
+template <class Boxes>
+int trace_core(tfp_engine* e, const std::vector<int64_t>& fo, const tfp_trace_req* reqs, int64_t n, int32_t max_gap,
+               const tfp_search_params* P, Boxes boxes, tfp_trace* out, hipStream_t s) {
+  std::vector<TraceReq> work;
+  std::vector<int64_t> slot;
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t id = reqs[i].clip_id;
+    if (id == -1) continue;
+    if (id < 0 || (size_t)id >= e->clips.size() || !e->clips[id].alive)
+      return fail(e, TFP_E_NOENT, "trace: clip id %d is not in the index", id);
+  }
+  if (n > INT32_MAX) return fail(e, TFP_E_CAPACITY, "trace: %lld requests", (long long)n);
+  for (int64_t i = 0; i < n; i++) {
+    out[i] = tfp_trace{0, 0, 0, 0, 0, 0};
+    if (reqs[i].clip_id == -1) continue;
+    const Clip& c = e->clips[reqs[i].clip_id];
+    const int64_t f0 = fo[reqs[i].recording], F = fo[reqs[i].recording + 1] - f0;
+    int64_t lo, hi;
+    trace_span(F, c.nrows, reqs[i].start, &lo, &hi);
+    if (hi <= lo) continue;
+    out[i].overlap = (int32_t)(hi - lo);
+    work.push_back(TraceReq{c.off, f0, (int32_t)c.nrows, (int32_t)F, reqs[i].start, 0});
+    slot.push_back(i);
+  }
+  if (work.empty()) return TFP_OK;  // nothing to trace: nothing is launched
+  int rc = boxes();
+  if (rc) return rc;
+  const size_t obytes = sizeof(TraceOut) * work.size();
+  if ((rc = upload(e, e->trace_reqs, work.data(), sizeof(TraceReq) * work.size(), s))) return rc;
+  HIPCHK(e, e->trace_out.reserve(obytes));
+  HIPCHK(e, launch_trace(e->trace_reqs.as<TraceReq>(), (int32_t)work.size(), max_gap, e->align_boxes.as<FrameBox>(),
+                         e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(), search_consts(P).coefs == 2,
+                         e->trace_out.as<TraceOut>(), s));
+  std::vector<tfp_trace> res(work.size());
+  HIPCHK(e, hipMemcpyAsync(res.data(), e->trace_out.p, obytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  for (size_t i = 0; i < work.size(); i++) out[slot[i]] = res[i];
+  e->n_trace_batches++;
+  e->n_traces += (int64_t)work.size();
+  return TFP_OK;
+}
+
+// The occurrences of a sliding aligned search's rows (cand, counts, align: nw windows of K rows,
+// the recordings' boxes still in e->align_boxes): tfp_occur.hpp's steps 2-5.
+int occur_core(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, const tfp_search_params* P, int32_t window,
+               int32_t hop, int32_t K, const tfp_candidate* cand, const int32_t* counts, const tfp_alignment* align,
+               int32_t max_gap, int32_t min_hits, tfp_occurrence* out, int64_t cap, int64_t* nocc, hipStream_t s) {
+  std::vector<OccurRow> rows;
+  int64_t j = 0;
+  for (int32_t r = 0; r < nrec; r++) {
+    const int64_t nw = slide_windows(fo[r + 1] - fo[r], window, hop);
+    for (int64_t w = 0; w < nw; w++, j++)
+      for (int32_t i = 0; i < counts[j]; i++) rows.push_back(OccurRow{r, cand[j * K + i].clip_id, w, align[j * K + i].offset});
+  }
+  const std::vector<OccurCand> cands = occur_candidates(rows, hop);
+  std::vector<tfp_trace_req> reqs(cands.size());
+  for (size_t i = 0; i < cands.size(); i++) reqs[i] = tfp_trace_req{cands[i].rec, cands[i].clip, cands[i].s, 0};
+  std::vector<tfp_trace> tr(cands.size());
+  const int rc = trace_core(e, fo, reqs.data(), (int64_t)reqs.size(), max_gap, P, [] { return TFP_OK; }, tr.data(), s);
+  if (rc) return rc;
+  const std::vector<int64_t> kept = occur_select(cands, reinterpret_cast<const TraceOut*>(tr.data()), min_hits,
+                                                 [&](int32_t c) { return e->clips[c].uuid.c_str(); });
+  *nocc = (int64_t)kept.size();
+  if (*nocc > cap)
+    return fail(e, TFP_E_CAPACITY, "occurrence search: %lld occurrences, room for %lld", (long long)*nocc, (long long)cap);
+  if (*nocc && !out) return fail(e, TFP_E_ARG, "occurrence search: NULL output");
+  for (size_t i = 0; i < kept.size(); i++) {
+    const OccurCand& c = cands[(size_t)kept[i]];
+    const tfp_trace& t = tr[(size_t)kept[i]];
+    tfp_occurrence& o = out[i];
+    memset(&o, 0, sizeof o);
+    o.recording = c.rec;
+    o.clip_id = c.clip;
+    o.clip_start_frame = c.s;
+    o.first_frame = t.seg_first;
+    o.last_frame = t.seg_last;
+    o.hits = t.seg_hits;
+    o.diagonal_hits = t.hits;
+    o.overlap = t.overlap;
+    o.windows = c.windows;
+    snprintf(o.uuid, sizeof o.uuid, "%s", e->clips[c.clip].uuid.c_str());
+  }
+  return TFP_OK;
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -3196,6 +3295,119 @@ int tfp_slide_align_stats(tfp_engine* e, int64_t* batches, int64_t* slid_entries
   if (batches) *batches = e->n_sa_batches;
   if (slid_entries) *slid_entries = e->n_sa_slid;
   if (direct_entries) *direct_entries = e->n_sa_direct;
+  return TFP_OK;
+}
+
+// ---- diagonal trace and occurrence search (tfp_trace.hpp): fp_handler.c:287-351 along one diagonal
+// of a recording against a clip's rows ----
+int tfp_trace_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec, const tfp_search_params* P,
+                    const tfp_trace_req* reqs, int64_t nreqs, int32_t max_gap, tfp_trace* out) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (nrec < 0 || nreqs < 0 || (nreqs && (!reqs || !out))) return fail(e, TFP_E_ARG, "trace: bad count or NULL array");
+  if (max_gap < 0) return fail(e, TFP_E_ARG, "trace: max_gap = %d", max_gap);
+  if (!valid_params(P)) return fail(e, TFP_E_ARG, "trace: coefs outside [1, 2]");
+  for (int32_t i = 0; i < nrec; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  for (int64_t i = 0; i < nreqs; i++)
+    if (reqs[i].recording < 0 || reqs[i].recording >= nrec)
+      return fail(e, TFP_E_ARG, "trace: recording %d of request %lld", reqs[i].recording, (long long)i);
+  if (!nreqs) return TFP_OK;
+  const std::vector<int64_t> fo = relative_offsets(qoff, nrec);
+  if (fo[nrec] > INT32_MAX) return fail(e, TFP_E_CAPACITY, "trace: %lld frames", (long long)fo[nrec]);
+  if (fo[nrec] && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
+  HIPCHK(e, hipSetDevice(e->device));
+  return trace_core(
+      e, fo, reqs, nreqs, max_gap, P,
+      [&]() -> int {  // the recordings' frame values and their boxes, once a request needs them
+        if (int rc = upload_frames(e, frames, qoff, nrec)) return rc;
+        HIPCHK(e, e->align_boxes.reserve(sizeof(FrameBox) * (fo[nrec] + 1)));
+        HIPCHK(e, launch_prep_boxes(e->q.as<double>(), fo[nrec], search_consts(P), e->align_boxes.as<FrameBox>(), nullptr, 0,
+                                    e->stream));
+        return TFP_OK;
+      },
+      out, e->stream);
+}
+
+namespace {
+// What both occurrence calls check before the sliding aligned search checks the rest.
+int occur_args(tfp_engine* e, int32_t k, int32_t max_gap, int32_t min_hits, const int64_t* nocc) {
+  if (!nocc) return fail(e, TFP_E_ARG, "occurrence search: NULL noccurrences");
+  if (max_gap < 0 || min_hits < 1) return fail(e, TFP_E_ARG, "occurrence search: max_gap = %d, min_hits = %d", max_gap, min_hits);
+  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "occurrence search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+  return TFP_OK;
+}
+
+// The sliding aligned search's own buffers for nw windows (0 when the count is out of range: the
+// search then reports it).
+struct OccurRows {
+  std::vector<tfp_candidate> cand;
+  std::vector<int32_t> counts;
+  std::vector<tfp_alignment> align;
+  int64_t cap;
+  OccurRows(int64_t nw, int32_t k) : cap(nw >= 0 && nw <= INT32_MAX ? nw : 0) {
+    cand.resize((size_t)cap * k + 1);
+    counts.resize((size_t)cap + 1);
+    align.resize((size_t)cap * k + 1);
+  }
+};
+}  // namespace
+
+int tfp_search_occurrences_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
+                                 const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes, int32_t k,
+                                 int32_t max_gap, int32_t min_hits, tfp_occurrence* out, int64_t cap, int64_t* nocc) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = occur_args(e, k, max_gap, min_hits, nocc);
+  if (rc) return rc;
+  for (int32_t i = 0; i < nrec; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  const std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0);
+  int64_t nw = 0, got = 0;
+  for (int32_t i = 0; i < nrec; i++) nw += slide_windows(fo[i + 1] - fo[i], window, hop);
+  OccurRows rows(nw, k);
+  if ((rc = tfp_search_sliding_aligned_batch(e, frames, qoff, nrec, P, window, hop, scopes, k, rows.cand.data(),
+                                             rows.counts.data(), rows.align.data(), rows.cap, &got)))
+    return rc;
+  *nocc = 0;
+  if (!got) return TFP_OK;  // no full window: no occurrence
+  // (the frame boxes are still in e->align_boxes wherever a row came back)
+  return occur_core(e, fo, nrec, P, window, hop, k, rows.cand.data(), rows.counts.data(), rows.align.data(), max_gap,
+                    min_hits, out, cap, nocc, e->stream);
+}
+
+int tfp_search_occurrences_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nrec, int32_t sr,
+                                     const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes,
+                                     int32_t k, int32_t max_gap, int32_t min_hits, tfp_occurrence* out, int64_t cap,
+                                     int64_t* nocc) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = occur_args(e, k, max_gap, min_hits, nocc);
+  if (rc) return rc;
+  for (int32_t i = 0; i < nrec; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  std::vector<int64_t> fo((size_t)std::max(nrec, 0) + 1, 0);
+  int64_t nw = 0, got = 0;
+  for (int32_t i = 0; i < nrec; i++) {
+    fo[i + 1] = fo[i] + tfp_frame_count(offsets[i + 1] - offsets[i]);
+    nw += slide_windows(fo[i + 1] - fo[i], window, hop);
+  }
+  OccurRows rows(nw, k);
+  // each recording fingerprinted once; its frame values stay in e->db and their boxes in e->align_boxes
+  if ((rc = tfp_search_sliding_aligned_pcm_batch(e, pcm, offsets, nrec, sr, P, window, hop, scopes, k, rows.cand.data(),
+                                                 rows.counts.data(), rows.align.data(), rows.cap, &got)))
+    return rc;
+  *nocc = 0;
+  if (!got) return TFP_OK;
+  return occur_core(e, fo, nrec, P, window, hop, k, rows.cand.data(), rows.counts.data(), rows.align.data(), max_gap,
+                    min_hits, out, cap, nocc, e->stream);
+}
+
+int tfp_trace_stats(tfp_engine* e, int64_t* batches, int64_t* traces) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (batches) *batches = e->n_trace_batches;
+  if (traces) *traces = e->n_traces;
   return TFP_OK;
 }
 

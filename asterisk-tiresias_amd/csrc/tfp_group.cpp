@@ -40,6 +40,7 @@
 #include "tfp_coalesce.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
+#include "tfp_occur.hpp"
 #include "tfp_rank_merge.hpp"
 #include "tfp_shardpool.hpp"
 
@@ -946,6 +947,86 @@ int tfp_group_search_sliding_aligned_batch(tfp_group* g, const tfp_frame* frames
   if (rc) return rc;
   for (size_t p = 0; p < np; p++)
     if (kept[p] >= 0) align[p] = res[g->members[kept[p]].shard][p];
+  return TFP_OK;
+}
+
+// Occurrence search on a group (tfp_occur.hpp): the rows of the sliding aligned search above, each
+// candidate (recording, clip, start) traced on the shard that holds its clip (tfp_trace_batch with
+// the shard-local clip id), then the suppression per (recording, audio_uuid) and the output order over
+// all shards' candidates. A clip is numbered by its member index here; clip_id out is its shard.
+int tfp_group_search_occurrences_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
+                                       const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes,
+                                       int32_t k, int32_t max_gap, int32_t min_hits, tfp_occurrence* out, int64_t cap,
+                                       int64_t* nocc) {
+  if (!g || !qoff) return TFP_E_ARG;
+  if (!nocc) return gfail(g, TFP_E_ARG, "occurrence search: NULL noccurrences");
+  if (max_gap < 0 || min_hits < 1)
+    return gfail(g, TFP_E_ARG, "occurrence search: max_gap = %d, min_hits = %d", max_gap, min_hits);
+  if (k < 1 || k > TFP_RANK_MAX || !valid_params(P)) return gfail(g, TFP_E_ARG, "sliding search: k or coefs out of range");
+  int32_t nw = 0;
+  int64_t got = 0;
+  if (int rc = group_slide_windows(g, qoff, nrec, false, window, hop, scopes, INT32_MAX, &got, &nw)) return rc;
+  *nocc = 0;
+  if (!nw) return TFP_OK;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);  // (the shards' clips stay as ranked until they are traced)
+  std::vector<tfp_candidate> cand((size_t)nw * k);
+  std::vector<int32_t> counts((size_t)nw);
+  std::vector<tfp_alignment> align((size_t)nw * k);
+  int rc = tfp_group_search_sliding_aligned_batch(g, frames, qoff, nrec, P, window, hop, scopes, k, cand.data(), counts.data(),
+                                                  align.data(), nw, &got);
+  if (rc) return rc;
+  std::vector<tfp::OccurRow> rows;
+  int64_t j = 0;
+  for (int32_t r = 0; r < nrec; r++) {
+    const int64_t n = tfp_sliding_windows(qoff[r + 1] - qoff[r], window, hop);
+    for (int64_t w = 0; w < n; w++, j++)
+      for (int32_t i = 0; i < counts[j]; i++)
+        rows.push_back(tfp::OccurRow{r, g->where.at(cand[j * k + i].uuid), w, align[j * k + i].offset});
+  }
+  const std::vector<tfp::OccurCand> cands = tfp::occur_candidates(rows, hop);
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<tfp_trace_req>> reqs(n);
+  std::vector<std::vector<size_t>> slot(n);
+  for (size_t i = 0; i < cands.size(); i++) {
+    const Member& mb = g->members[cands[i].clip];
+    reqs[mb.shard].push_back(tfp_trace_req{cands[i].rec, mb.id, cands[i].s, 0});
+    slot[mb.shard].push_back(i);
+  }
+  std::vector<std::vector<tfp_trace>> res(n);
+  for (int s = 0; s < n; s++) res[s].resize(reqs[s].size());
+  rc = run_all(g, [&](int s) {
+    return reqs[s].empty() ? TFP_OK
+                           : tfp_trace_batch(g->eng[s], frames, qoff, nrec, P, reqs[s].data(), (int64_t)reqs[s].size(),
+                                             max_gap, res[s].data());
+  });
+  if (rc) return rc;
+  std::vector<tfp::TraceOut> tr(cands.size());
+  static_assert(sizeof(tfp_trace) == sizeof(tfp::TraceOut), "tfp_occur.hpp and the public header agree");
+  for (int s = 0; s < n; s++)
+    for (size_t i = 0; i < slot[s].size(); i++) memcpy(&tr[slot[s][i]], &res[s][i], sizeof(tfp_trace));
+  const std::vector<int64_t> kept =
+      tfp::occur_select(cands, tr.data(), min_hits, [&](int32_t mi) { return g->members[mi].uuid.c_str(); });
+  *nocc = (int64_t)kept.size();
+  if (*nocc > cap)
+    return gfail(g, TFP_E_CAPACITY, "occurrence search: %lld occurrences, room for %lld", (long long)*nocc, (long long)cap);
+  if (*nocc && !out) return gfail(g, TFP_E_ARG, "occurrence search: NULL output");
+  for (size_t i = 0; i < kept.size(); i++) {
+    const tfp::OccurCand& c = cands[(size_t)kept[i]];
+    const tfp::TraceOut& t = tr[(size_t)kept[i]];
+    const Member& mb = g->members[c.clip];
+    tfp_occurrence& o = out[i];
+    memset(&o, 0, sizeof o);
+    o.recording = c.rec;
+    o.clip_id = mb.shard;
+    o.clip_start_frame = c.s;
+    o.first_frame = t.seg_first;
+    o.last_frame = t.seg_last;
+    o.hits = t.seg_hits;
+    o.diagonal_hits = t.hits;
+    o.overlap = t.overlap;
+    o.windows = c.windows;
+    snprintf(o.uuid, sizeof o.uuid, "%s", mb.uuid.c_str());
+  }
   return TFP_OK;
 }
 

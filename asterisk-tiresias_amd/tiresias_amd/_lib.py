@@ -55,6 +55,21 @@ class Alignment(C.Structure):
                 ("last_frame", C.c_int32)]
 
 
+class TraceReq(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("clip_id", C.c_int32), ("start", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Trace(C.Structure):
+    _fields_ = [("overlap", C.c_int32), ("hits", C.c_int32), ("segments", C.c_int32), ("seg_hits", C.c_int32),
+                ("seg_first", C.c_int32), ("seg_last", C.c_int32)]
+
+
+class Occurrence(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("clip_id", C.c_int32), ("clip_start_frame", C.c_int32),
+                ("first_frame", C.c_int32), ("last_frame", C.c_int32), ("hits", C.c_int32), ("diagonal_hits", C.c_int32),
+                ("overlap", C.c_int32), ("windows", C.c_int32), ("uuid", C.c_char * 64)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("clip", C.c_int64), ("offset", C.c_int64)]
 
@@ -179,6 +194,16 @@ _SIGS = {
     "tfp_slide_align_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
     "tfp_group_search_sliding_aligned_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32,
                                                          P, C.c_int32, P, P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_trace_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int64, C.c_int32, P]),
+    "tfp_search_occurrences_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32, P,
+                                               C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_search_occurrences_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), C.c_int32,
+                                                   C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                   C.POINTER(C.c_int64)]),
+    "tfp_trace_stats": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tfp_group_search_occurrences_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32, P,
+                                                     C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                     C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -6,7 +6,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import Alignment, Candidate, Frame, Result, SearchParams, SynthSpec, TfpError, check, lib
+from ._lib import Alignment, Candidate, Frame, Occurrence, Result, SearchParams, SynthSpec, TfpError, check, lib
 
 FRAME_DTYPE = np.dtype([("frame_idx", "<i4"), ("m1", "<i4"), ("m2", "<i4"), ("reserved", "<i4"),
                         ("q1", "<f8"), ("q2", "<f8")])
@@ -79,6 +79,9 @@ def synth_pcm(seed: int, clips, samples_per_clip: int, offsets=None) -> np.ndarr
     return out
 
 
+TRACE_KEYS = ("overlap", "hits", "segments", "seg_hits", "seg_first", "seg_last")
+
+
 def sliding_windows(nframes: int, window: int, hop: int) -> int:
     """tfp_sliding_windows: full windows of `window` frames, `hop` apart, in a recording of nframes frames."""
     return int(lib().tfp_sliding_windows(int(nframes), int(window), int(hop)))
@@ -132,6 +135,44 @@ class _SlidingCalls:
         qoffsets = np.ascontiguousarray(qoffsets, np.int64)
         return self._sliding("_search_sliding_aligned_batch", frames, qoffsets, np.diff(qoffsets), (), p, window, hop,
                              scopes, k, aligned=True)
+
+    # ---- occurrence search: which clips play in a recording, from which frame to which
+    OCCURRENCE_KEYS = ("recording", "clip_id", "clip_start_frame", "first_frame", "last_frame", "hits", "diagonal_hits",
+                       "overlap", "windows")
+
+    def _occurrences(self, name, data, offsets, head, p, window, hop, scopes, k, max_gap, min_hits):
+        nrec = len(offsets) - 1
+        if scopes is not None:
+            scopes = np.ascontiguousarray(scopes, np.int32)
+            if len(scopes) != nrec:
+                raise ValueError("one scope per recording")
+        args = (self._h, data.ctypes.data, offsets.ctypes.data, nrec, *head, C.byref(p), int(window), int(hop),
+                None if scopes is None else scopes.ctypes.data, int(k), int(max_gap), int(min_hits))
+        n, cap = C.c_int64(), 1024
+        while True:  # (TFP_E_CAPACITY names the room the list needs)
+            out = (Occurrence * cap)()
+            rc = self._fn(name)(*args, out, cap, C.byref(n))
+            if rc != -5 or n.value <= cap:
+                break
+            cap = n.value
+        self._chk(rc)
+        per = [[] for _ in range(nrec)]
+        for o in out[:n.value]:
+            row = {"audio_uuid": o.uuid.decode()}
+            row.update({f: getattr(o, f) for f in self.OCCURRENCE_KEYS})
+            per[o.recording].append(row)
+        return per
+
+    def search_occurrences_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, window: int, hop: int, k: int,
+                                 max_gap: int, min_hits: int, scopes=None):
+        """tfp_search_occurrences_batch: per recording the list of occurrence dicts (audio_uuid, clip_start_frame,
+        first_frame, last_frame, hits, diagonal_hits, overlap, windows, clip_id, recording), by first_frame: the
+        candidates (clip, w * hop - offset) of search_sliding_aligned_batch's rows, each traced along its own
+        diagonal over the whole recording and thinned by non-maximum suppression."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        return self._occurrences("_search_occurrences_batch", frames, qoffsets, (), p, window, hop, scopes, k, max_gap,
+                                 min_hits)
 
 
 class _ScopedCalls:
@@ -487,6 +528,34 @@ class Engine(_ScopedCalls, _SlidingCalls):
         offsets = np.ascontiguousarray(offsets, np.int64)
         return self._sliding("_search_sliding_aligned_pcm_batch", pcm, offsets, [frame_count(n) for n in np.diff(offsets)],
                              (int(sample_rate),), p, window, hop, scopes, k, aligned=True)
+
+    # ---- diagonal trace and occurrence search
+    def trace_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, reqs, max_gap: int):
+        """tfp_trace_batch: reqs = [(recording, clip_id, start), ...]; per request a dict (overlap, hits, segments,
+        seg_hits, seg_first, seg_last) of the clip laid on the recording with its frame 0 at recording frame start."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        r = np.zeros((len(reqs), 4), np.int32)
+        if len(reqs):
+            r[:, :3] = np.asarray(reqs, np.int64).reshape(-1, 3)
+        out = np.zeros((max(1, len(reqs)), 6), np.int32)
+        self._chk(lib().tfp_trace_batch(self._h, frames.ctypes.data, qoffsets.ctypes.data, len(qoffsets) - 1, C.byref(p),
+                                        r.ctypes.data, len(reqs), int(max_gap), out.ctypes.data))
+        return [dict(zip(TRACE_KEYS, map(int, row))) for row in out[:len(reqs)]]
+
+    def search_occurrences_pcm_batch(self, pcm, offsets, p: SearchParams, window: int, hop: int, k: int, max_gap: int,
+                                     min_hits: int, scopes=None, sample_rate: int = 8000):
+        """tfp_search_occurrences_pcm_batch: search_occurrences_batch over each recording's own fingerprint."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        return self._occurrences("_search_occurrences_pcm_batch", pcm, offsets, (int(sample_rate),), p, window, hop, scopes,
+                                 k, max_gap, min_hits)
+
+    def trace_stats(self) -> dict:
+        """tfp_trace_stats: batches that launched the trace kernel, and the requests it computed."""
+        b, n = C.c_int64(), C.c_int64()
+        self._chk(lib().tfp_trace_stats(self._h, C.byref(b), C.byref(n)))
+        return {"batches": b.value, "traces": n.value}
 
     def slide_align_stats(self) -> dict:
         """tfp_slide_align_stats: batches that reached the sliding alignment, and the entries aligned by form."""

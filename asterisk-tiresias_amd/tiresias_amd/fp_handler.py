@@ -463,3 +463,44 @@ class FpHandler:
                 infos.append(info)
             out.append({"frame": w * int(hop_frames), "rows": infos})
         return out
+
+    def fp_search_fingerprint_occurrences(self, context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high,
+                                          window_frames, hop_frames, k, max_gap, min_hits):
+        """Which clips of `context` play in the recording, and from which frame to which: the join of
+        fp_search_fingerprint_timeline_aligned's rows that call leaves to its caller, done by the engine. The
+        candidates (clip, clip_start_frame) of the first k rows of every window are each verified along their
+        own diagonal over the whole recording with the per-frame predicate of fp_handler.c:287-351, hits at
+        most max_gap frames apart forming a segment, and thinned by non-maximum suppression
+        (search_occurrences_batch). Returns one dict per occurrence, by first_frame: the clip's audio_list
+        row, frame_count (the recording's frames), match_count and hits (those of the segment), clip_start_frame,
+        first_frame, last_frame, diagonal_hits, overlap and windows. The context is mapped to a scope as
+        fp_search_fingerprint_in_context maps it. [] for bad arguments, a recording shorter than one window or
+        a context without clips."""
+        if context is None or filename is None:
+            return []
+        if coefs < 1 or coefs > DEF_AUBIO_COEFS or k < 1 or window_frames < 1 or hop_frames < 1 or max_gap < 0 or min_hits < 1:
+            return []
+        try:
+            pcm, sr = read_audio(filename)
+        except TfpError:
+            return []
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        k = min(int(k), TFP_RANK_MAX)
+        scopes = [self._scope_of(context, False)]
+        if pcm.dtype == np.float32:
+            fr = self.engine.fingerprint_f32_batch(pcm, [0, len(pcm)], sr)
+        else:
+            fr = self.engine.fingerprint_batch(pcm, [0, len(pcm)], sr)
+        occ = self.engine.search_occurrences_batch(fr, [0, len(fr)], p, window_frames, hop_frames, k, max_gap, min_hits,
+                                                   scopes)[0]
+        out = []
+        for o in occ:
+            info = self._audio_list_info(o["audio_uuid"])
+            if info is None:
+                continue
+            info["frame_count"] = len(fr)
+            info["match_count"] = o["hits"]
+            for key in ("clip_start_frame", "first_frame", "last_frame", "hits", "diagonal_hits", "overlap", "windows"):
+                info[key] = o[key]
+            out.append(info)
+        return out

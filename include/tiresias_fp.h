@@ -460,6 +460,8 @@ int tfp_align_stats(tfp_engine* eng, int64_t* batches, int64_t* pairs);
  * ((w' - w) * hop >= window); a run with one entry, and every run when 2 * hop >= window (a slid step
  * tests 2 * hop * N boxes, a window from scratch window * N), is aligned from scratch (direct), the
  * rest slid. Both give the same integers. Calls are not coalesced. */
+/* (The join itself, verified along each candidate's own diagonal over the whole recording, is
+ * tfp_search_occurrences_batch below; tfp_trace_batch is its primitive.) */
 /* The primitive (fp_handler.c:287-351 per window frame against the named clips' rows): window j of
  * the recordings (as tfp_search_sliding_batch numbers them) against clips clip_ids[j * k + i], i < k:
  * out[j * k + i]; clip_ids[nwindows * k] and out[nwindows * k]. An id of -1 gives a zeroed row; any
@@ -491,6 +493,91 @@ int tfp_search_sliding_aligned_pcm_batch(tfp_engine* eng, const int16_t* pcm, co
  * clip_ids counts once (the second row is a copy), and a clip without rows, an id of -1 and a call
  * that launches nothing count nothing. Any pointer may be NULL. */
 int tfp_slide_align_stats(tfp_engine* eng, int64_t* batches, int64_t* slid_entries, int64_t* direct_entries);
+
+/* ---- occurrences: which enrolled clips play in a recording, from which frame to which (new) --- */
+/* Sliding aligned search reports per window where its clips lie. A window that covers only the head
+ * or tail of an occurrence has few hits on the true diagonal and is often won by another one, and
+ * the smallest-diagonal tie rule of `offset` scatters spurious starts, so window rows alone give no
+ * exact extent. The calls below verify a start along its own diagonal over the whole recording with
+ * the per-frame predicate aligned search tests (fp_handler.c:287-351: hit(x, j) = recording frame x
+ * runs its SQL and clip row j is non-NULL and inside the frame's printed bounds, max1, and max2 where
+ * the clause is present). The clip's rows are read in frame order as enrolled: no tfp_index_commit is
+ * needed. Exact integers. Calls are not coalesced.
+ *
+ * Trace. A recording of F frames, a clip of N rows and start = s, the recording frame at which clip
+ * frame 0 lies (any int32: negative, or past the end). The diagonal covers the recording frames x in
+ * [lo, hi), lo = max(0, s), hi = min(F, s + N), and overlap = max(0, hi - lo). Let x_1 < ... < x_h be
+ * the frames of [lo, hi) with hit(x, x - s). A segment is a maximal run of them in which consecutive
+ * hits are at most max_gap frames apart (x_{i+1} - x_i - 1 <= max_gap; max_gap = INT32_MAX: one
+ * segment). The best segment has the most hits, among equals the smallest seg_first. seg_first and
+ * seg_last are recording frames counted from the recording's first frame. With no hit every field but
+ * overlap is 0. */
+typedef struct tfp_trace_req {
+  int32_t recording; /* index into qoffsets */
+  int32_t clip_id;   /* engine clip id; -1: a zeroed row */
+  int32_t start;     /* s */
+  int32_t reserved;
+} tfp_trace_req;
+typedef struct tfp_trace {
+  int32_t overlap;   /* frames of the recording the clip covers at this start */
+  int32_t hits;      /* h */
+  int32_t segments;
+  int32_t seg_hits;  /* the best segment: its hits, first and last hitting frame */
+  int32_t seg_first;
+  int32_t seg_last;
+} tfp_trace;
+/* The primitive (fp_handler.c:287-351 per recording frame against the one clip row its diagonal
+ * meets): out[i] = the trace of reqs[i] at max_gap. clip_id = -1 gives a zeroed row; any other id out
+ * of range or of a removed clip is TFP_E_NOENT. TFP_E_ARG: a recording index outside [0, nrecordings),
+ * max_gap < 0, coefs outside [1,2], non-monotone offsets; out is untouched then. A request with
+ * overlap = 0 is answered on the host, and a call with nothing to trace launches nothing. */
+int tfp_trace_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nrecordings,
+                    const tfp_search_params* params, const tfp_trace_req* reqs, int64_t nreqs, int32_t max_gap,
+                    tfp_trace* out);
+/* Occurrences of a call with window, hop, scopes, k, max_gap >= 0 and min_hits >= 1:
+ *  1. the rows of tfp_search_sliding_aligned_batch with the same arguments (fp_handler.c:367-374 per
+ *     window, each row with its alignment);
+ *  2. the candidates are the distinct (r, clip, s = w * hop - offset) over all rows, w being the
+ *     window's index inside recording r; `windows` is the number of rows naming the candidate;
+ *  3. each candidate is traced once at max_gap, and those with seg_hits < min_hits are dropped;
+ *  4. within one (r, clip) the rest are visited by seg_hits descending, then windows descending, then
+ *     s ascending, and one is kept unless its [seg_first, seg_last] meets the interval of one already
+ *     kept (non-maximum suppression: the earlier-place ties and the partial diagonals around a real
+ *     occurrence go);
+ *  5. output order: recording ascending, first_frame ascending, hits descending, audio_uuid
+ *     descending (the tie order of fp_handler.c:367-374). */
+typedef struct tfp_occurrence {
+  int32_t recording;
+  int32_t clip_id;          /* engine clip id (group calls: the shard, as tfp_candidate) */
+  int32_t clip_start_frame; /* s: the recording frame at which clip frame 0 lies */
+  int32_t first_frame;      /* seg_first, seg_last of the candidate's trace */
+  int32_t last_frame;
+  int32_t hits;             /* seg_hits */
+  int32_t diagonal_hits;    /* h, over the whole diagonal */
+  int32_t overlap;
+  int32_t windows;
+  char uuid[64];            /* audio_uuid, NUL-terminated */
+} tfp_occurrence;
+/* fp_handler.c:367-374 per window, fp_handler.c:287-351 along each candidate's diagonal. The argument
+ * rules are tfp_search_sliding_batch's, and min_hits < 1 or max_gap < 0 is TFP_E_ARG too.
+ * *noccurrences is always set on TFP_OK and TFP_E_CAPACITY; if it exceeds cap (the entries out holds)
+ * the call returns TFP_E_CAPACITY and writes nothing else. No recordings, recordings shorter than
+ * window and an empty index give no occurrence and launch nothing. */
+int tfp_search_occurrences_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nrecordings,
+                                 const tfp_search_params* params, int32_t window, int32_t hop, const int32_t* scopes,
+                                 int32_t k, int32_t max_gap, int32_t min_hits, tfp_occurrence* out, int64_t cap,
+                                 int64_t* noccurrences);
+/* PCM in (fp_handler.c:275, each recording once; :287-374 per window; :287-351 per diagonal): the
+ * recordings as tfp_search_sliding_pcm_batch takes them. The frame values and their boxes stay on the
+ * device through the slide, the alignment and the trace. */
+int tfp_search_occurrences_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nrecordings,
+                                     int32_t sample_rate, const tfp_search_params* params, int32_t window, int32_t hop,
+                                     const int32_t* scopes, int32_t k, int32_t max_gap, int32_t min_hits,
+                                     tfp_occurrence* out, int64_t cap, int64_t* noccurrences);
+/* Batches that launched the trace kernel so far and the requests it computed (the diagonals of
+ * fp_handler.c:287-351; for an occurrence call its distinct candidates). A request answered on the
+ * host (clip_id = -1, overlap = 0) counts nothing. Either pointer may be NULL. */
+int tfp_trace_stats(tfp_engine* eng, int64_t* batches, int64_t* traces);
 
 /* ---- live channels: rolling fingerprint + match (configs[4]) --------------------------
  * The dialplan app records `duration` ms of a channel to a WAV and searches it
@@ -605,6 +692,15 @@ int tfp_group_search_sliding_aligned_batch(tfp_group* g, const tfp_frame* frames
                                            int32_t hop, const int32_t* scopes, int32_t k, tfp_candidate* out,
                                            int32_t* counts, tfp_alignment* align, int64_t cap_windows,
                                            int64_t* nwindows);
+/* tfp_search_occurrences_batch on a group (fp_handler.c:367-374 per window, fp_handler.c:287-351 per
+ * diagonal): the rows of tfp_group_search_sliding_aligned_batch, each candidate traced on the shard
+ * that holds its clip (tfp_trace_batch with the shard-local clip id), the suppression per (recording,
+ * audio_uuid) and the output order over all shards. clip_id is the shard. A failing shard fails the
+ * call. */
+int tfp_group_search_occurrences_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets,
+                                       int32_t nrecordings, const tfp_search_params* params, int32_t window, int32_t hop,
+                                       const int32_t* scopes, int32_t k, int32_t max_gap, int32_t min_hits,
+                                       tfp_occurrence* out, int64_t cap, int64_t* noccurrences);
 /* tfp_search_pcm_gather and the coalescing of concurrent calls (as for one engine) on a group: the
  * channel threads' batch-1 searches through the shim run as shared batches on every GPU. */
 int tfp_group_search_pcm_gather(tfp_group* g, const int16_t* const* pcms, const int64_t* nsamples, int32_t nqueries,

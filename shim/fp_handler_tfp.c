@@ -1201,6 +1201,104 @@ struct ast_json* fp_search_fingerprint_timeline_aligned(const char* context, con
 	return j_res;
 }
 
+/* New: which clips of `context` play in the recording, and from which frame to which: the join of
+ * fp_search_fingerprint_timeline_aligned's rows that call leaves to its caller, done by the engines
+ * (tfp_group_search_occurrences_batch). The candidates (clip, clip_start_frame) of the first k rows
+ * (src/fp_handler.c:367-374) of every window are each verified along their own diagonal over the whole
+ * recording with the per-frame predicate of src/fp_handler.c:287-351, hits at most max_gap frames apart
+ * forming a segment, and thinned by non-maximum suppression. A JSON array, by first_frame, of the clips'
+ * audio_list rows with "frame_count" (the recording's frames), "match_count" and "hits" (those of the
+ * segment), "clip_start_frame", "first_frame", "last_frame", "diagonal_hits", "overlap" and "windows". The context
+ * is mapped to a scope as fp_search_fingerprint_in_context maps it. NULL for bad arguments or a failed
+ * search; the empty array where nothing plays. */
+struct ast_json* fp_search_fingerprint_occurrences(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int window_frames,
+		const int hop_frames, const int k, const int max_gap, const int min_hits)
+{
+	int16_t* pcm;
+	float* x;
+	int64_t cap, ns, off[2], qoff[2] = {0, 0}, nf = 0, room = 64, got = 0, i;
+	int32_t sr, scope;
+	int rc, rows;
+	tfp_search_params p;
+	tfp_occurrence* occ = NULL;
+	tfp_frame* fr;
+	tfp_result r;
+	struct ast_json* j_res;
+	struct ast_json* j_tmp;
+
+	if((filename == NULL) || (k < 1) || (window_frames < 1) || (hop_frames < 1) || (max_gap < 0) || (min_hits < 1)) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	if(search_params(&p, context, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	if(read_audio(filename, &pcm, &cap, &x, &ns, &sr) != 0) {
+		return NULL;
+	}
+	rows = k > TFP_RANK_MAX ? TFP_RANK_MAX : k;
+	off[0] = 0;
+	off[1] = ns;
+	nf = tfp_frame_count(ns); /* ast_json_array_size(j_fprints), fp_handler.c:286 */
+	scope = scope_of_context(context, false);
+	fr = ast_calloc(nf > 0 ? nf : 1, sizeof(*fr));
+	if(fr == NULL) {
+		rc = TFP_E_NOMEM;
+	}
+	else if(pcm != NULL) {
+		rc = tfp_group_fingerprint_batch(g_tfp, pcm, off, 1, sr, fr, nf, &qoff[1]);
+	}
+	else {
+		rc = tfp_group_fingerprint_f32_batch(g_tfp, x, off, 1, sr, fr, nf, &qoff[1]);
+	}
+	while(rc == TFP_OK) { /* (a list longer than the room: once more with the room it names) */
+		occ = ast_calloc(room, sizeof(*occ));
+		if(occ == NULL) {
+			rc = TFP_E_NOMEM;
+			break;
+		}
+		rc = tfp_group_search_occurrences_batch(g_tfp, fr, qoff, 1, &p, window_frames, hop_frames, &scope, rows, max_gap,
+				min_hits, occ, room, &got);
+		if((rc != TFP_E_CAPACITY) || (got <= room)) {
+			break;
+		}
+		ast_free(occ);
+		occ = NULL;
+		room = got;
+		rc = TFP_OK;
+	}
+	ast_free(fr);
+	pcm_put(pcm, cap);
+	ast_free(x);
+	if(rc != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not search %s: %s\n", filename, tfp_group_last_error(g_tfp));
+		ast_free(occ);
+		return NULL;
+	}
+	j_res = ast_json_array_create();
+	for(i = 0; i < got; i++) {
+		memset(&r, 0, sizeof(r));
+		r.found = 1;
+		r.match_count = occ[i].hits;
+		r.frame_count = (int32_t)nf;
+		snprintf(r.uuid, sizeof(r.uuid), "%s", occ[i].uuid);
+		j_tmp = search_result(&r); /* an occurrence whose audio_list entry is missing is skipped */
+		if(j_tmp != NULL) {
+			ast_json_object_set(j_tmp, "clip_start_frame", ast_json_integer_create(occ[i].clip_start_frame));
+			ast_json_object_set(j_tmp, "first_frame", ast_json_integer_create(occ[i].first_frame));
+			ast_json_object_set(j_tmp, "last_frame", ast_json_integer_create(occ[i].last_frame));
+			ast_json_object_set(j_tmp, "hits", ast_json_integer_create(occ[i].hits));
+			ast_json_object_set(j_tmp, "diagonal_hits", ast_json_integer_create(occ[i].diagonal_hits));
+			ast_json_object_set(j_tmp, "overlap", ast_json_integer_create(occ[i].overlap));
+			ast_json_object_set(j_tmp, "windows", ast_json_integer_create(occ[i].windows));
+			ast_json_array_append(j_res, j_tmp);
+		}
+	}
+	ast_free(occ);
+	return j_res;
+}
+
 /* ---- live channels: the dialplan application's recording without the /tmp WAV -------------
  * application_handler.c:152-185 records `duration` ms of the channel's voice frames
  * (record_voice, :248-312) into /tmp/tiresias-UUID.wav and searches that file. A channel keeps the

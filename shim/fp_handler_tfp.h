@@ -98,6 +98,20 @@ struct ast_json* fp_search_fingerprint_timeline_aligned(const char* context, con
 		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int window_frames,
 		const int hop_frames, const int max_results, const bool in_context);
 
+/* New: occurrence search. Which clips of `context` play in the recording, and from which frame to
+ * which: the join the timeline call above leaves to its caller, done by the engines. Every candidate
+ * (clip, clip_start_frame) named by the first k rows (src/fp_handler.c:367-374) of a window is verified
+ * along its own diagonal over the whole recording with the per-frame predicate of
+ * src/fp_handler.c:287-351; hits at most max_gap frames apart form a segment, a candidate's best segment
+ * needs min_hits hits, and overlapping candidates of one clip are thinned to the best. A JSON array, by
+ * "first_frame", of the clips' audio_list rows with "frame_count" (the recording's frames),
+ * "match_count" (= "hits"), "clip_start_frame", "first_frame", "last_frame" (recording frames), "hits", "diagonal_hits", "overlap"
+ * and "windows". The context is a scope, as for fp_search_fingerprint_in_context. NULL for bad
+ * arguments; the empty array where nothing plays or the recording is shorter than a window. */
+struct ast_json* fp_search_fingerprint_occurrences(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int window_frames,
+		const int hop_frames, const int k, const int max_gap, const int min_hits);
+
 /* New: a live channel, for the dialplan application's record loop (application_handler.c:152-185,
  * record_voice :248-312) without the /tmp WAV round trip. Open one per call with max_ms >= the
  * recording's duration, push every voice frame's SLIN samples as it is read (160 per 20 ms frame
