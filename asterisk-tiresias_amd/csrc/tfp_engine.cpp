@@ -988,6 +988,13 @@ int merge_index(tfp_engine* e, const std::vector<int32_t>& rank, const MergeBrea
   return TFP_OK;
 }
 
+// A live clip's tie-break key is in [0, INT32_MAX] (tiresias_fp.h): the packed result key carries it
+// as its unsigned low half, where a negative key would outrank every other clip's.
+int fail_negative_key(tfp_engine* e, int32_t clip, int32_t k) {
+  return fail(e, TFP_E_ARG, "tie-break key %d given to live clip %s: keys lie in [0, 2^31 - 1]", k,
+              e->clips[clip].uuid.c_str());
+}
+
 int full_index(tfp_engine* e);
 
 int delta_update(tfp_engine* e);
@@ -1037,6 +1044,7 @@ int rebuild(tfp_engine* e) {
       return fail(e, TFP_E_ARG, "clip %s was added after tfp_index_set_tiebreak: set the tie-break keys again",
                   e->clips[clip].uuid.c_str());
     const int32_t k = e->tiebreak_override[clip];
+    if (k < 0) return fail_negative_key(e, clip, k);
     if (!key_col.emplace(k, (int32_t)r).second) return fail(e, TFP_E_ARG, "tie-break key %d given to two live clips", k);
     tiekey[r] = k;
   }
@@ -1231,7 +1239,7 @@ int delta_update(tfp_engine* e) {
         return fail(e, TFP_E_ARG, "clip %s was added after tfp_index_set_tiebreak: set the tie-break keys again",
                     e->clips[clip].uuid.c_str());
       *k = e->tiebreak_override[clip];
-      return TFP_OK;
+      return *k < 0 ? fail_negative_key(e, clip, *k) : TFP_OK;
     };
     // the main columns' keys: only when the override changed for them (or their device copy was
     // lost to a larger buffer); otherwise the delta's clips alone (O(new clips), round 6)

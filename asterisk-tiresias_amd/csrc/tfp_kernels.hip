@@ -1760,9 +1760,10 @@ hipError_t launch_build_A(const double* d_q, SearchConsts sc, const int64_t* d_q
 // buffer: a clip's score for query q is the sum of q's counts over the keys whose boxes hold a row
 // of the clip, so it depends only on that key set (the clip's pattern, Ku bits). Per pattern only
 // the greatest column matters (a tie goes to the greatest uuid), so the vote is an argmax over at
-// most 2^Ku - 1 classes per query instead of over every clip. Layout: cls[2^kClassKuMax] int32
-// (greatest column + 1 per pattern, 0 = none); a clip's pattern comes from the cached key-presence
-// bitsets (launch_key_bits), one bit per used key.
+// most 2^Ku - 1 classes per query instead of over every clip. Layout: cls[2^kClassKuMax] uint32
+// (greatest tie key + 1 per pattern, 0 = none: keys reach INT32_MAX, so the sum needs all 32
+// bits); a clip's pattern comes from the cached key-presence bitsets (launch_key_bits), one bit
+// per used key.
 // GEMM path: every row of Bt written whole from the cached key bitsets (one thread per clip,
 // 16-byte stores), so nothing needs clearing first and the work does not grow with the boxes'
 // rows. Against clearing plus marking the boxes' rows (scattered 2-byte stores): 42 -> 33 us at
@@ -1821,20 +1822,21 @@ __global__ __launch_bounds__(256) void build_B_kernel(const uint32_t* __restrict
 constexpr int kClassMaxBlocks = 64;
 __device__ void class_max_block(int blk, int nblk, int32_t Ku, const uint32_t* __restrict__ mask,
                                 const uint32_t* __restrict__ bits, int32_t C, const int32_t* __restrict__ tiekey,
-                                _Float16* __restrict__ Bt, int32_t* best, int32_t* kk) {
-  for (int i = threadIdx.x; i < (1 << kClassKuMax); i += blockDim.x) best[i] = 0;
+                                _Float16* __restrict__ Bt, uint32_t* best, int32_t* kk) {
+  for (int i = threadIdx.x; i < (1 << kClassKuMax); i += blockDim.x) best[i] = 0u;
   if (threadIdx.x == 0) {  // the used keys, ascending (= columns kc)
     int n = 0;
     for (int w = 0; w < kKeyRange / 32 && n < Ku; w++)
       for (uint32_t m = mask[w]; m && n < Ku; m &= m - 1u) kk[n++] = 32 * w + __builtin_ctz(m);
   }
   __syncthreads();
-  int32_t* cls = reinterpret_cast<int32_t*>(Bt);
+  uint32_t* cls = reinterpret_cast<uint32_t*>(Bt);
   const int32_t W = key_bits_words(C);
   for (int64_t c = (int64_t)blk * blockDim.x + threadIdx.x; c < C; c += (int64_t)nblk * blockDim.x) {
     uint32_t pat = 0;
     for (int k = 0; k < Ku; k++) pat |= ((bits[(int64_t)kk[k] * W + (c >> 5)] >> (c & 31)) & 1u) << k;
-    if (pat) atomicMax(&best[pat], tiekey[c] + 1);  // the pattern's greatest tie key (uuid order), + 1
+    // the pattern's greatest tie key (uuid order), + 1: unsigned, a key may be INT32_MAX
+    if (pat) atomicMax(&best[pat], (uint32_t)tiekey[c] + 1u);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < (1 << kClassKuMax); i += blockDim.x)
@@ -1878,19 +1880,19 @@ __global__ __launch_bounds__(256) void class_vote_kernel(const _Float16* __restr
     if (lane == 0) best[q] = b;
     return;
   }
-  const int32_t* cls = reinterpret_cast<const int32_t*>(Bt);
+  const uint32_t* cls = reinterpret_cast<const uint32_t*>(Bt);
   int32_t cnt[kClassKuMax];
 #pragma unroll
   for (int k = 0; k < kClassKuMax; k++) cnt[k] = k < Ku ? (int32_t)(float)A[(int64_t)q * Kp + k] : 0;
   unsigned long long mine = 0;
   for (int P = lane + 1; P < (1 << Ku); P += 64) {
-    const int32_t c1 = cls[P];
+    const uint32_t c1 = cls[P];
     if (!c1) continue;
     uint32_t score = 0;
 #pragma unroll
     for (int k = 0; k < kClassKuMax; k++) score += (P >> k) & 1 ? (uint32_t)cnt[k] : 0u;
     if (!score) continue;
-    const unsigned long long key = ((unsigned long long)score << 32) | (unsigned)(c1 - 1);  // (c1 = tie key + 1)
+    const unsigned long long key = ((unsigned long long)score << 32) | (c1 - 1u);  // (c1 = tie key + 1)
     mine = key > mine ? key : mine;
   }
 #pragma unroll
@@ -2135,7 +2137,7 @@ __global__ __launch_bounds__(256) void vote_gemm_regs_kernel(const _Float16* __r
                                                               const uint32_t* __restrict__ bits, int32_t C) {
   const int32_t Kp = meta->kp;
   if (meta->cls) {  // the pattern-class path's per-pattern maxima instead of a GEMM
-    __shared__ int32_t cbest[1 << kClassKuMax];
+    __shared__ uint32_t cbest[1 << kClassKuMax];
     __shared__ int32_t ckk[kClassKuMax];
     const int blk = blockIdx.y * gridDim.x + blockIdx.x;
     const int nblk = min((int)(gridDim.x * gridDim.y), min(kClassMaxBlocks, (C + 255) / 256));

@@ -216,7 +216,15 @@ int tfp_sweep_stats(tfp_engine* eng, int64_t* bins, int64_t* library, int64_t* r
  * this engine's uuids). keys[clip_id] must order like the uuids across all shards and be
  * distinct over live clips. A clip added after this call has no key: the next search (or
  * tfp_index_commit) fails with TFP_E_ARG until the keys are set again; nclip_ids = 0 clears
- * the override. */
+ * the override.
+ *
+ * The keys' contract (the same for tfp_index_update_tiebreak): the keys of live clips lie in
+ * [0, INT32_MAX] (both ends included: a result is count << 32 | key with the key as its unsigned low
+ * half, and every search form is exact over that whole range), they are distinct, and they order like
+ * the uuids. A live clip with a negative key, or two live clips with one key, fail the next index
+ * update (tfp_index_commit or a search) with TFP_E_ARG and a message that names the key, on the full
+ * build and on the index delta's path alike. Keys given to clip ids that are not live (removed
+ * clips) are ignored, whatever their value: a device group passes -1 for those. */
 int tfp_index_set_tiebreak(tfp_engine* eng, const int32_t* keys, int32_t nclip_ids);
 /* The override's keys of clip ids [first_clip_id, first_clip_id + n) only (new in round 6): a device
  * group gives each clip enrolled since the last update its key without re-sending every clip's

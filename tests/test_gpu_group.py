@@ -307,3 +307,100 @@ def test_group_enrolment_is_o_new_clips(oracle, tfp_lib):
         assert found > nadd
     finally:
         g.close()
+
+
+def test_group_tie_keys_over_the_whole_key_range(oracle, tfp_lib):
+    """Single-clip enrolments that use up the tie-key gaps (csrc/tfp_group.cpp, insert_live): uuids
+    that keep sorting last halve the gap below 2^31 until a clip gets key 2^31 - 1 and the next one
+    respaces; uuids that keep sorting first go down to key 0 and the respace below it; then 32 clips
+    between two adjacent uuids with the same first 8 hex digits. Some new clips copy an earlier clip's
+    rows (a tie decided by the uuid, across shards). After every add a batch of 16 queries (each
+    shard's pattern-class vote: at most 5 distinct keys) and a batch of 3 (the small vote), both with
+    a query for the newest clip and one for a tied pair, == the oracle over the live rows.
+
+    Rows as _dense_db's (keys 16-18; the first three rows of a clip lie inside the 0.001 boxes), and
+    one row per clip on a key of its own, 30 + its number. A query takes frames from its clip's rows
+    inside the boxes, so the clip matches every frame and ties with every clip that has those keys:
+    the greatest uuid wins, which in the first phase is the newest clip with the greatest key so far.
+    The queries for the newest clip and the tied pair also take the clip's own key, which only the
+    clip and its copies have: in the second phase the newest clip, with the smallest key, wins it."""
+    import test_gpu_index as tgi
+    rng = np.random.default_rng(3131)
+    data = []
+    for n, (m1, m2) in enumerate(tgi._dense_db(rng, 200, 30)):
+        data.append((np.append(m1, (30 + n) * 1_000_000 + int(rng.integers(-900, 900))).astype(np.int32),
+                     np.append(m2, int(rng.integers(0, 30_000_000))).astype(np.int32)))
+    near = np.arange(3)  # (_dense_db: rows [0, nrow // 10) are within 0.0009 of their key)
+    lo_pair, hi_pair = "80000000-0000-4000-8000-000000000000", "80000000-0000-4000-8000-0000000000ff"
+    first = ["%x0000000-0000-4000-8000-%012x" % (h, h) for h in (3, 5, 7, 9, 0xb, 0xd)] + [lo_pair, hi_pair]
+    old = os.environ.get("TFP_INDEX_DELTA")
+    os.environ["TFP_INDEX_DELTA"] = "1"  # (test knob: the index delta at this DB size too)
+    try:
+        g = tfp_lib.Group([0, 0])
+    finally:
+        if old is None:
+            del os.environ["TFP_INDEX_DELTA"]
+        else:
+            os.environ["TFP_INDEX_DELTA"] = old
+    live, order = {}, []  # uuid -> rows; uuids in order of addition
+    p = tfp_lib.params(1, 0.001)
+    state = {"n": 0, "tied": None}
+
+    def add(u, phase):
+        n = state["n"]
+        rows = data[n]
+        if n % 4 == 1:  # a copy of an earlier clip's rows under this uuid
+            src = order[int(rng.integers(len(order)))]
+            rows = live[src]
+            state["tied"] = src
+        g.index_add(u, *rows)
+        live[u] = rows
+        order.append(u)
+        state["n"] = n + 1
+        for nq in (16, 3):
+            srcs = [u, state["tied"]] + [order[int(i)] for i in rng.integers(0, len(order), nq - 2)]
+            q = []
+            for i, s in enumerate(srcs):
+                m1, m2 = live[s]
+                sel = rng.choice(np.append(near, len(m1) - 1) if i < 2 else near, 25)
+                if i < 2:
+                    sel[0] = len(m1) - 1  # (at least one frame on the clip's own key)
+                q.append(np.stack([np.round(m1[sel] / 1e6) + 0.4, m2[sel] / 1e6], axis=1))  # (trunc(q1) = the row's key)
+            qdb = np.concatenate(q)
+            qoff = np.arange(nq + 1, dtype=np.int64) * 25
+            exp = _oracle_search(oracle, live, qdb[:, 0], qdb[:, 1], qoff, p)
+            # the construction: the greatest uuid among the clips with the same rows, every frame matched
+            same = [[v for v in order if live[v] is live[s]] for s in srcs[:2]]
+            assert len(same[1]) >= 2 and [exp[0], exp[1]] == [(max(same[0]), 25), (max(same[1]), 25)]
+            fr = np.zeros(len(qdb), tfp_lib.FRAME_DTYPE)
+            fr["q1"], fr["q2"] = qdb[:, 0], qdb[:, 1]
+            got = _pairs(g.search_batch(fr, qoff, p)[0])
+            bad = [(i, srcs[i], got[i], exp[i]) for i in range(nq) if got[i] != exp[i]]
+            assert not bad, (phase, "add %d" % n, u, "batch of %d" % nq, bad[:4])
+
+    try:
+        foff = np.arange(len(first) + 1, dtype=np.int64) * 31
+        g.index_add_batch(first, foff, np.concatenate([data[c][0] for c in range(len(first) - 1)] + [data[0][0]]),
+                          np.concatenate([data[c][1] for c in range(len(first) - 1)] + [data[0][1]]))
+        for c, u in enumerate(first):
+            live[u] = data[c] if c < len(first) - 1 else data[0]  # (hi_pair: a copy of the first clip's rows)
+            order.append(u)
+        state["n"], state["tied"] = len(first), first[0]
+        g.index_commit()
+
+        def until_respace(phase, uuid_of):
+            r0 = g.tiebreak_stats()["respaces"]
+            for j in range(64):
+                add(uuid_of(j), phase)
+                if g.tiebreak_stats()["respaces"] > r0:
+                    return j + 1
+            raise AssertionError("%s: no respace in 64 adds" % phase)
+
+        up = until_respace("increasing", lambda j: "f0000000-0000-4000-8000-%012x" % j)
+        down = until_respace("decreasing", lambda j: "0%07x-0000-4000-8000-%012x" % (0xfffffff - j, j))
+        assert up > 20 and down > 20  # (a gap of 2^31 / (clips + 1) halves about that often)
+        for j in range(32):
+            add("80000000-0000-4000-8000-0000000000%02x" % (j + 1), "between")
+        assert g.index_stats()[1] == len(live) == len(first) + up + down + 32
+    finally:
+        g.close()
