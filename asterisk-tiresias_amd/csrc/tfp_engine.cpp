@@ -29,6 +29,7 @@
 #include "tfp_kernels.hpp"
 #include "tfp_math.hpp"
 #include "tfp_rank.hpp"
+#include "tfp_census.hpp"
 #include "tfp_scope.hpp"
 #include "tfp_slide.hpp"
 #include "tfp_slide_align.hpp"
@@ -283,9 +284,16 @@ struct tfp_engine {
   // per-column scope table built from them, the batch's per-query scopes; the table stands for
   // index version scope_version until a scope changes (scope_dirty)
   DevBuf scope_clip, scope_colclip, scope_table, scope_q;
+  std::unordered_map<int32_t, int64_t> scope_pop;  // scope -> live clips, as of the table's build (the census's bin 0)
+  int64_t scope_live = 0;                          // live clips
   uint64_t scope_version = 0;
   bool scope_dirty = true;
   int64_t n_scope_vote = 0, n_scope_general = 0, n_scope_builds = 0;
+  // match census (tfp_census.hpp): the batch's bins [nq][nbins] with the vote form's bad flag after
+  // them, their pinned copy, and the batches each form served
+  DevBuf census_hist;
+  HostBuf census_pin;
+  int64_t n_census_vote = 0, n_census_general = 0;
   // sliding search (tfp_slide.hpp): the recordings' key slots, the launch's runs, the general form's
   // window starts and gathered frame values, and the batches / windows served so far
   DevBuf slide_slots, slide_runs, slide_wsrc, slide_q;
@@ -1830,7 +1838,15 @@ int ensure_scope_table(tfp_engine* e, hipStream_t s) {
   std::vector<int32_t> cc((size_t)std::max(Cp, 1), -1), cs(std::max<size_t>(e->clips.size(), 1), 0);
   std::copy(e->col_clip.begin(), e->col_clip.end(), cc.begin());  // (col_clip.size() <= ncols)
   for (size_t j = 0; j < e->delta.clip.size(); j++) cc[(size_t)e->delta.col0 + j] = e->delta.clip[j];
-  for (size_t i = 0; i < e->clips.size(); i++) cs[i] = e->clips[i].scope;
+  e->scope_pop.clear();
+  e->scope_live = 0;
+  for (size_t i = 0; i < e->clips.size(); i++) {
+    cs[i] = e->clips[i].scope;
+    if (e->clips[i].alive) {
+      e->scope_pop[cs[i]]++;
+      e->scope_live++;
+    }
+  }
   HIPCHK(e, e->scope_colclip.reserve_grow(sizeof(int32_t) * cc.size()));
   HIPCHK(e, e->scope_clip.reserve_grow(sizeof(int32_t) * cs.size()));
   HIPCHK(e, e->scope_table.reserve_grow(sizeof(int32_t) * cc.size()));
@@ -1961,6 +1977,142 @@ int rank_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_
   }
   if ((rc = consolidate(e)) || (rc = rank_general(e, qo, nq, d_q, sc, K, scopes, keys, s))) return rc;
   (scopes ? e->n_scope_general : e->n_rank_general)++;
+  return TFP_OK;
+}
+
+// ---- match census (tfp_census.hpp): hist[q * nbins + c] = the clips of scopes[q] with count c >= 1
+
+// The vote form (coefs = 1): *bad when a frame's key lies outside the vote range (bins undefined).
+int census_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
+                const int32_t* scopes, int32_t nbins, int32_t* hist, bool* bad, hipStream_t s) {
+  const int32_t C = e->ncols;
+  int rc;
+  if ((rc = ensure_qoff(e, qo, s)) || (rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s)) ||
+      (rc = ensure_scopes(e, scopes, nq, s)))
+    return rc;
+  const size_t n = (size_t)nq * nbins;
+  HIPCHK(e, e->census_hist.reserve(sizeof(int32_t) * (n + 1)));
+  HIPCHK(e, e->census_pin.reserve(sizeof(int32_t) * (n + 1)));
+  int32_t* d_hist = e->census_hist.as<int32_t>();
+  HIPCHK(e, hipMemsetAsync(d_hist, 0, sizeof(int32_t) * (n + 1), s));  // the bins and the bad flag after them
+  for (int64_t q0 = 0; q0 < nq; q0 += 65535) {  // (the launch grid's second dimension)
+    const int32_t m = (int32_t)std::min<int64_t>(65535, nq - q0);
+    HIPCHK(e, launch_census_vote(d_q, e->qoff.as<int64_t>() + q0, e->scope_q.as<int32_t>() + q0, m, sc,
+                                 e->tc.ranges.active().key_bits.as<uint32_t>(), C, e->scope_table.as<int32_t>(), nbins,
+                                 d_hist + q0 * nbins, d_hist + n, s));
+  }
+  HIPCHK(e, hipMemcpyAsync(e->census_pin.p, d_hist, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  const int32_t* h = e->census_pin.as<int32_t>();
+  *bad = h[n] != 0;
+  if (!*bad) std::copy(h, h + n, hist);
+  return TFP_OK;
+}
+
+// The general form (any coefs / tolerance / key), over the sorted rows of the merged index.
+int census_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
+                   const int32_t* scopes, int32_t nbins, int32_t* hist, hipStream_t s) {
+  const int32_t C = e->ncols;
+  const int64_t R = e->nrows, nf = qo[nq];
+  if (C <= 0 || R <= 0) return TFP_OK;  // an empty index: no count above 0
+  int rc;
+  if ((rc = ensure_qoff(e, qo, s))) return rc;
+  HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (nf + 1)));
+  HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->boxes.as<FrameBox>(), nullptr, 0, s));
+  if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_cells(e, sc.tole, s))) return rc;
+  CellCache* cells = &e->tc.cells.active();
+  int64_t chunk;
+  if ((rc = ensure_scan_scratch(e, nq, C, &chunk, s))) return rc;
+  if (cells->valid && cells->ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
+    (void)hipGetLastError();
+    cells->invalidate();  // every frame takes the row scan
+  }
+  if ((rc = ensure_scopes(e, scopes, nq, s))) return rc;
+  const size_t n = (size_t)nq * nbins;
+  HIPCHK(e, e->census_hist.reserve(sizeof(int32_t) * (n + 1)));
+  HIPCHK(e, e->census_pin.reserve(sizeof(int32_t) * (n + 1)));
+  int32_t* d_hist = e->census_hist.as<int32_t>();
+  HIPCHK(e, hipMemsetAsync(d_hist, 0, sizeof(int32_t) * n, s));
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int32_t m = (int32_t)std::min<int64_t>(chunk, nq - q0);
+    HIPCHK(e, launch_scan_touched(e->boxes.as<FrameBox>(), e->qoff.as<int64_t>(), qo.data(), (int32_t)q0, m,
+                                  e->m1s.as<int32_t>(), e->m2s.as<int32_t>(), e->cols.as<int32_t>(), R, cells, C,
+                                  e->stamp.as<int32_t>(), e->score.as<int32_t>(), e->touched.as<int32_t>(),
+                                  e->tcnt.as<int32_t>(), s));
+    HIPCHK(e, launch_census_final((int32_t)q0, m, e->scope_q.as<int32_t>(), e->scope_table.as<int32_t>(), C,
+                                  e->stamp.as<int32_t>(), e->score.as<int32_t>(), e->touched.as<int32_t>(),
+                                  e->tcnt.as<int32_t>(), nbins, d_hist, s));
+  }
+  HIPCHK(e, hipMemcpyAsync(e->census_pin.p, d_hist, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (the scan's scratch is free for the next call)
+  const int32_t* h = e->census_pin.as<int32_t>();
+  std::copy(h, h + n, hist);
+  return TFP_OK;
+}
+
+// Shaped like rank_core (the same forms, the same rule for a live index delta); scopes[nq] holds a
+// scope per query. On return hist[nq][nbins] is complete: bin 0 of a query is its scope's live
+// clips (row-less ones included, removed ones not) minus the clips the kernels counted.
+int census_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_q, const tfp_search_params* P,
+                const int32_t* scopes, int32_t nbins, int32_t* hist, hipStream_t s) {
+  int rc = rebuild(e);  // synchronous on e->stream
+  if (rc) return rc;
+  const SearchConsts sc = search_consts(P);
+  std::vector<int64_t> qo(h_qoff, h_qoff + nq + 1);
+  for (auto& v : qo) v -= h_qoff[0];
+  std::fill(hist, hist + (size_t)nq * nbins, 0);
+  bool done = qo[nq] == 0;  // no frame: every live clip has count 0, and nothing is launched
+  if (!done && sc.coefs == 1) {
+    if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
+    if (e->ncols <= 0 || e->nrows + e->delta.rows <= 0) {
+      done = true;  // no row: the same
+    } else {
+      bool bad = false;
+      if ((rc = census_vote(e, qo, nq, d_q, sc, scopes, nbins, hist, &bad, s))) return rc;
+      if (!bad) {
+        e->n_census_vote++;
+        done = true;
+      }
+    }
+  }
+  if (!done) {
+    if ((rc = consolidate(e)) || (rc = census_general(e, qo, nq, d_q, sc, scopes, nbins, hist, s))) return rc;
+    e->n_census_general++;
+  }
+  // the scopes' live-clip populations, counted from e->clips when the scope table was built: current
+  // after this (a no-op unless the index or a scope changed since), so a census does no per-clip work
+  if ((rc = ensure_scope_table(e, s))) return rc;
+  for (int32_t i = 0; i < nq; i++) {
+    int32_t* row = hist + (size_t)i * nbins;
+    int64_t n = 0;
+    if (scopes[i] == kScopeAny) n = e->scope_live;
+    else if (const auto it = e->scope_pop.find(scopes[i]); it != e->scope_pop.end()) n = it->second;
+    row[0] = (int32_t)(n - tfp_census_at_least(row, nbins, 1));
+  }
+  return TFP_OK;
+}
+
+// The arguments every census entry point checks (as scope_args); fills sv with a scope per query.
+int census_args(tfp_engine* e, const tfp_search_params* P, int32_t nq, const int32_t* scopes, const void* need_bins,
+                std::vector<int32_t>& sv) {
+  if (nq < 0 || !need_bins) return fail(e, TFP_E_ARG, "census: bad query count or NULL need_bins");
+  if (!valid_params(P)) return fail(e, TFP_E_ARG, "census: coefs outside [1, 2]");
+  sv.assign((size_t)nq, kScopeAny);
+  for (int32_t i = 0; scopes && i < nq; i++) {
+    if (scopes[i] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "census: scope %d of query %d", scopes[i], i);
+    sv[i] = scopes[i];
+  }
+  return TFP_OK;
+}
+
+// *need_bins = the longest query's frames + 1; TFP_E_CAPACITY when nbins is below it.
+int census_bins(tfp_engine* e, const int64_t* off, int32_t nq, int32_t nbins, const int32_t* hist, int32_t* need_bins) {
+  int64_t need = 1;
+  for (int32_t i = 0; i < nq; i++) need = std::max<int64_t>(need, off[i + 1] - off[i] + 1);
+  if (need > INT32_MAX) return fail(e, TFP_E_ARG, "census: a query of %lld frames", (long long)need - 1);
+  *need_bins = (int32_t)need;
+  if (nbins < need) return fail(e, TFP_E_CAPACITY, "census: %d bins, the longest query needs %lld", nbins, (long long)need);
+  if (nq && !hist) return fail(e, TFP_E_ARG, "census: hist is NULL");
   return TFP_OK;
 }
 
@@ -3154,6 +3306,70 @@ int tfp_scope_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batch
   if (vote_batches) *vote_batches = e->n_scope_vote;
   if (general_batches) *general_batches = e->n_scope_general;
   if (table_builds) *table_builds = e->n_scope_builds;
+  return TFP_OK;
+}
+
+// ---- match census (tfp_census.hpp): fp_handler.c:367-374's rows counted by count(*) ---------
+static_assert(kCensusLdsBins >= 2, "bin 0 is the host's");
+
+int64_t tfp_census_at_least(const int32_t* hist_row, int32_t nbins, int32_t count) {
+  if (!hist_row) return 0;
+  int64_t n = 0;
+  for (int32_t c = count <= 0 ? 0 : count; c < nbins; c++) n += hist_row[c];
+  return n;
+}
+
+int tfp_census_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq, const tfp_search_params* P,
+                     const int32_t* scopes, int32_t nbins, int32_t* hist, int32_t* need_bins) {
+  if (!e || !qoff) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  std::vector<int32_t> sv;
+  int rc = census_args(e, P, nq, scopes, need_bins, sv);
+  if (rc) return rc;
+  for (int32_t i = 0; i < nq; i++)
+    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  if (nq && qoff[nq] > qoff[0] && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
+  if ((rc = census_bins(e, qoff, nq, nbins, hist, need_bins)) || !nq) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
+  return census_core(e, qoff, nq, e->q.as<double>(), P, sv.data(), nbins, hist, e->stream);
+}
+
+int tfp_census_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                         const tfp_search_params* P, const int32_t* scopes, int32_t nbins, int32_t* hist,
+                         int32_t* need_bins) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  std::vector<int32_t> sv;
+  int rc = census_args(e, P, nq, scopes, need_bins, sv);
+  if (rc) return rc;
+  for (int32_t i = 0; i < nq; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  if (!pcm && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
+  std::vector<const void*> ptrs;
+  std::vector<int64_t> lens;
+  split_offsets(pcm, sizeof(int16_t), offsets, nq, &ptrs, &lens);
+  std::vector<int64_t> foff(nq + 1, 0);
+  for (int32_t i = 0; i < nq; i++) foff[i + 1] = foff[i] + tfp_frame_count(lens[i]);
+  if ((rc = census_bins(e, foff.data(), nq, nbins, hist, need_bins)) || !nq) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  if (foff[nq] > 0) {  // the frame values stay on the device (e->db)
+    int64_t nf;
+    if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nq, sr, &nf, nullptr, P->coefs == 2))) return rc;
+  }
+  rc = census_core(e, foff.data(), nq, e->db.as<double>(), P, sv.data(), nbins, hist, e->stream);
+  if (foff[nq] > 0) {
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
+    e->stage_pending = false;
+  }
+  return rc;
+}
+
+int tfp_census_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (vote_batches) *vote_batches = e->n_census_vote;
+  if (general_batches) *general_batches = e->n_census_general;
   return TFP_OK;
 }
 

@@ -813,6 +813,55 @@ int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const in
   });
 }
 
+// Match census on a group (tfp_census.hpp): each shard's census of its own clips runs on its worker
+// and the rows are summed on the host, bin 0 (the shard's live clips of the scope with count 0)
+// included. A clip lies on one shard, so the sum is exact.
+namespace {
+int group_census(tfp_group* g, int32_t nq, const tfp_search_params* P, const int32_t* scopes, int32_t nbins, int32_t* hist,
+                 int32_t* need_bins, const std::function<int(int, int32_t*, int32_t*)>& census) {
+  if (nq < 0 || !need_bins) return gfail(g, TFP_E_ARG, "census: bad query count or NULL need_bins");
+  if (!valid_params(P)) return gfail(g, TFP_E_ARG, "census: coefs outside [1, 2]");
+  for (int32_t i = 0; scopes && i < nq; i++)
+    if (scopes[i] < TFP_SCOPE_ANY) return gfail(g, TFP_E_ARG, "census: scope %d of query %d", scopes[i], i);
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  int rc = refresh_ranks(g);
+  if (rc) return rc;
+  const int n = (int)g->eng.size();
+  const size_t per = (size_t)std::max(nq, 1) * (size_t)std::max(nbins, 1);
+  std::vector<std::vector<int32_t>> res(n, std::vector<int32_t>(per, 0));
+  std::vector<int32_t> need(n, 0);
+  // (every shard sees the same queries: all return TFP_E_CAPACITY with the same need_bins, or none)
+  rc = run_all(g, [&](int s) { return census(s, res[s].data(), &need[s]); });
+  if (rc && rc != TFP_E_CAPACITY) return rc;
+  *need_bins = need[0];
+  if (rc) return rc;
+  if (nq && !hist) return gfail(g, TFP_E_ARG, "census: hist is NULL");
+  for (size_t i = 0; i < (size_t)nq * nbins; i++) {
+    int64_t sum = 0;
+    for (int s = 0; s < n; s++) sum += res[s][i];
+    hist[i] = (int32_t)sum;
+  }
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_group_census_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoff, int32_t nq, const tfp_search_params* P,
+                           const int32_t* scopes, int32_t nbins, int32_t* hist, int32_t* need_bins) {
+  if (!g || !qoff) return TFP_E_ARG;
+  return group_census(g, nq, P, scopes, nbins, hist, need_bins, [&](int s, int32_t* h, int32_t* nb) {
+    return tfp_census_batch(g->eng[s], frames, qoff, nq, P, scopes, nbins, h, nb);
+  });
+}
+
+int tfp_group_census_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+                               const tfp_search_params* P, const int32_t* scopes, int32_t nbins, int32_t* hist,
+                               int32_t* need_bins) {
+  if (!g || !offsets) return TFP_E_ARG;
+  return group_census(g, nq, P, scopes, nbins, hist, need_bins, [&](int s, int32_t* h, int32_t* nb) {
+    return tfp_census_pcm_batch(g->eng[s], pcm, offsets, nq, sr, P, scopes, nbins, h, nb);
+  });
+}
+
 // Sliding search on a group (tfp_slide.hpp): every shard slides over every recording, and per window
 // the shards' rows merge as a query's do (group_rank, a window in a query's place).
 namespace {

@@ -174,6 +174,15 @@ _SIGS = {
     "tfp_group_search_scoped_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P, P]),
     "tfp_group_search_scoped_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32,
                                                     P, P]),
+    "tfp_census_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P, C.POINTER(C.c_int32)]),
+    "tfp_census_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P,
+                                       C.POINTER(C.c_int32)]),
+    "tfp_census_stats": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tfp_census_at_least": (C.c_int64, [P, C.c_int32, C.c_int32]),
+    "tfp_group_census_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P,
+                                         C.POINTER(C.c_int32)]),
+    "tfp_group_census_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P,
+                                             C.POINTER(C.c_int32)]),
     "tfp_sliding_windows": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "tfp_search_sliding_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), C.c_int32, C.c_int32, P, C.c_int32,
                                            P, P, C.c_int64, C.POINTER(C.c_int64)]),

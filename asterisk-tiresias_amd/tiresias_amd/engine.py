@@ -220,7 +220,47 @@ class _ScopedCalls:
         return Engine._candidates(out, counts, nq, k)
 
 
-class Engine(_ScopedCalls, _SlidingCalls):
+def census_at_least(hist_row, count: int) -> int:
+    """tfp_census_at_least: the clips of one census row with count >= `count` (bin 0 only for count <= 0)."""
+    row = np.ascontiguousarray(hist_row, np.int32)
+    return int(lib().tfp_census_at_least(row.ctypes.data, len(row), int(count)))
+
+
+class _CensusCalls:
+    """The match census, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*), as _ScopedCalls."""
+
+    def _census(self, name, data, offsets, nframes, head, p, scopes, nbins):
+        nq = len(offsets) - 1
+        if scopes is not None:
+            scopes = np.ascontiguousarray(scopes, np.int32)
+            if len(scopes) != nq:
+                raise ValueError("one scope per query")
+        if nbins is None:
+            nbins = max([int(n) for n in nframes], default=0) + 1
+        hist = np.zeros((nq, int(nbins)), np.int32)
+        need = C.c_int32()
+        self._chk(self._fn(name)(self._h, data.ctypes.data, offsets.ctypes.data, nq, *head, C.byref(p),
+                                 None if scopes is None else scopes.ctypes.data, int(nbins), hist.ctypes.data,
+                                 C.byref(need)))
+        return hist
+
+    def census_batch(self, frames: np.ndarray, qoffsets, p: SearchParams, scopes=None, nbins=None) -> np.ndarray:
+        """tfp_census_batch: int32[nq, nbins], hist[q, c] = the live clips of scopes[q] (None: every clip)
+        whose count for query q is c, as search_scoped_batch would report it were k unbounded; bin 0
+        holds the scope's clips with no hit. nbins None: the longest query's frames + 1."""
+        frames = np.ascontiguousarray(frames, FRAME_DTYPE)
+        qoffsets = np.ascontiguousarray(qoffsets, np.int64)
+        return self._census("_census_batch", frames, qoffsets, np.diff(qoffsets), (), p, scopes, nbins)
+
+    def census_pcm_batch(self, pcm, offsets, p: SearchParams, scopes=None, nbins=None, sample_rate: int = 8000) -> np.ndarray:
+        """tfp_census_pcm_batch: census_batch of the recordings' frames, fingerprinted on the device."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        return self._census("_census_pcm_batch", pcm, offsets, [frame_count(int(n)) for n in np.diff(offsets)],
+                            (int(sample_rate),), p, scopes, nbins)
+
+
+class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
     """One engine per GPU (tfp_engine)."""
     _PFX = "tfp"
 
@@ -575,6 +615,12 @@ class Engine(_ScopedCalls, _SlidingCalls):
         self._chk(lib().tfp_scope_stats(self._h, C.byref(v), C.byref(g), C.byref(t)))
         return {"vote_batches": v.value, "general_batches": g.value, "table_builds": t.value}
 
+    def census_stats(self) -> dict:
+        """tfp_census_stats: census batches served by the vote form and by the general form."""
+        v, g = C.c_int64(), C.c_int64()
+        self._chk(lib().tfp_census_stats(self._h, C.byref(v), C.byref(g)))
+        return {"vote_batches": v.value, "general_batches": g.value}
+
     def slide_stats(self) -> dict:
         """tfp_slide_stats: sliding batches by form, and the windows they held."""
         v, g, w = C.c_int64(), C.c_int64(), C.c_int64()
@@ -674,7 +720,7 @@ class Plan:
             self._h = C.c_void_p()
 
 
-class Group(_ScopedCalls, _SlidingCalls):
+class Group(_ScopedCalls, _SlidingCalls, _CensusCalls):
     """tfp_group: one engine per listed device (a device may repeat), the enrolled clips sharded
     over them, searches combined on the host (tiresias_fp.h, device groups)."""
     _PFX = "tfp_group"

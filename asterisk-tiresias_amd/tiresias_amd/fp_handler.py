@@ -353,6 +353,44 @@ class FpHandler:
             out.append(info)
         return out
 
+    def fp_search_fingerprint_census(self, context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high):
+        """fp_search_fingerprint_in_context's winner with how it stands against every other clip of
+        `context`: the rows of the result query (fp_handler.c:367-374) counted by count(*)
+        (tfp_census_batch), which the application's ratio test (application_handler.c:180-203) cannot
+        see from the first row. A dict: winner (that call's first row, or None), frame_count,
+        population (the context's clips), clips_at_or_above (clips whose count reaches the winner's,
+        the winner included), clips_tied (count equal to the winner's) and histogram ([[count, clips],
+        ...], non-zero bins only, counts descending). None for bad arguments or an unreadable file."""
+        if context is None or filename is None:
+            return None
+        if coefs < 1 or coefs > DEF_AUBIO_COEFS:
+            return None
+        try:
+            pcm, sr = read_audio(filename)
+        except TfpError:
+            return None
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        scope = [self._scope_of(context, False)]
+        if pcm.dtype == np.float32:
+            fr = self.engine.fingerprint_f32_batch(pcm, [0, len(pcm)], sr)
+            rows, frame_count = self.engine.search_scoped_batch(fr, [0, len(fr)], p, scope, 1)[0], len(fr)
+            hist = self.engine.census_batch(fr, [0, len(fr)], p, scope)[0]
+        else:
+            rows = self.engine.search_scoped_pcm_batch(pcm, [0, len(pcm)], p, scope, 1, sr)[0]
+            frame_count = frame_count_of(len(pcm))
+            hist = self.engine.census_pcm_batch(pcm, [0, len(pcm)], p, scope, None, sr)[0]
+        winner, top = None, 0
+        if rows:
+            top = rows[0]["match_count"]
+            winner = self._audio_list_info(rows[0]["audio_uuid"])
+            if winner is not None:
+                winner["frame_count"] = frame_count
+                winner["match_count"] = top
+        return {"winner": winner, "frame_count": frame_count, "population": int(hist.sum()),
+                "clips_at_or_above": int(hist[top:].sum()) if top > 0 else 0,
+                "clips_tied": int(hist[top]) if top > 0 else 0,
+                "histogram": [[c, int(hist[c])] for c in range(len(hist) - 1, -1, -1) if hist[c]]}
+
     def fp_search_fingerprint_aligned(self, context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high,
                                       max_results):
         """fp_search_fingerprint_candidates' rows, each with where in the clip the recording lies:

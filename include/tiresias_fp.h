@@ -345,6 +345,45 @@ int tfp_search_scoped_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64
  * that a scoped search follows, none per search. Any pointer may be NULL. */
 int tfp_scope_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches, int64_t* table_builds);
 
+/* ---- match census: how every clip's count is distributed, per query (new) ---------------- */
+/* Every search above returns the head of the result query (fp_handler.c:367-374): the winner, or up
+ * to TFP_RANK_MAX rows. The census says how those rows stand against the rest of the catalog: per
+ * query, the exact number of clips of the query's scope at each count(*), which is the reference's
+ * own SQL one level up,
+ *   select c, count(*) from (select count(*) c from temp group by audio_uuid) group by c
+ * over the temp table of fp_handler.c:287-351 (with the context predicate of tfp_search_scoped_batch
+ * at :308-314 for a scope >= 0). A clip's count is exactly the match_count tfp_search_scoped_batch
+ * would report for it were k unbounded: the same coefs, tolerance < 0, ignore filters and NULL rules.
+ *
+ * hist[q * nbins + c], 1 <= c <= F_q (the query's frames): live clips of scope scopes[q] with count
+ * c. hist[q * nbins + 0]: live clips of the scope with count 0, row-less clips included, removed
+ * clips not (the scope's live clips minus the other bins). hist[q * nbins + c] = 0 for c > F_q. A
+ * scope no live clip has, and an empty index, give an all-zero row. The application's ratio test
+ * (application_handler.c:180-203) reads off it how many clips reach the winner's count, how many tie
+ * with it and how many lie within a margin of it. Rows of index shards add up bin by bin. */
+/* fp_handler.c:287-374 per query, counted by count(*) instead of read from the top. scopes[nqueries]
+ * (TFP_SCOPE_ANY or >= 0), or NULL for TFP_SCOPE_ANY everywhere. *need_bins always receives
+ * max_q F_q + 1; if nbins is below it the call returns TFP_E_CAPACITY and writes nothing else.
+ * TFP_E_ARG: coefs outside [1,2], a scope below -1, non-monotone offsets, NULL need_bins. Calls are
+ * not coalesced. */
+int tfp_census_batch(tfp_engine* eng, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                     const tfp_search_params* params, const int32_t* scopes, int32_t nbins, int32_t* hist,
+                     int32_t* need_bins);
+/* PCM in (fp_handler.c:275), census out (:287-374 counted by count(*)): the queries as
+ * tfp_search_scoped_pcm_batch takes them; query q has tfp_frame_count(samples) frames. The frame
+ * values stay on the device between the fingerprint and the census. */
+int tfp_census_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries, int32_t sample_rate,
+                         const tfp_search_params* params, const int32_t* scopes, int32_t nbins, int32_t* hist,
+                         int32_t* need_bins);
+/* Census batches served so far by the vote form (coefs = 1, every key in range: the counts of
+ * fp_handler.c:367-374 from the key bitsets) and by the general form (every other batch, counted
+ * over the sorted rows). Either pointer may be NULL. */
+int tfp_census_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches);
+/* Clips with count(*) >= count in one census row (fp_handler.c:367-374: the rows down to that
+ * count; with the winner's match_count, application_handler.c:180-203, the winner and its ties):
+ * the sum of hist_row[c] for c >= count, bin 0 excluded unless count <= 0. Host-only. */
+int64_t tfp_census_at_least(const int32_t* hist_row, int32_t nbins, int32_t count);
+
 /* ---- sliding search: the ranked rows of every window of a long recording (new) ------------- */
 /* The reference records a fixed `duration` ms (default 3000) and searches that one window
  * (application_handler.c:152-185, fp_handler.c:275-374). A caller with a whole call recording wants
@@ -674,6 +713,15 @@ int tfp_group_search_scoped_batch(tfp_group* g, const tfp_frame* frames, const i
 int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
                                       int32_t sample_rate, const tfp_search_params* params, const int32_t* scopes,
                                       int32_t k, tfp_candidate* out, int32_t* counts);
+/* Census on a group (fp_handler.c:287-374 counted by count(*), as tfp_census_batch): every shard
+ * takes the census of its own clips and the rows are summed bin by bin, bin 0 included. A clip lies
+ * on one shard, so the sum is exact. The arguments and rules as the engine calls'. */
+int tfp_group_census_batch(tfp_group* g, const tfp_frame* frames, const int64_t* qoffsets, int32_t nqueries,
+                           const tfp_search_params* params, const int32_t* scopes, int32_t nbins, int32_t* hist,
+                           int32_t* need_bins);
+int tfp_group_census_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                               int32_t sample_rate, const tfp_search_params* params, const int32_t* scopes, int32_t nbins,
+                               int32_t* hist, int32_t* need_bins);
 /* Sliding search on a group (fp_handler.c:367-374 read to row k for every window,
  * application_handler.c:152-185 moved along the recording): every shard slides over every recording,
  * and per window the shards' rows merge as tfp_group_search_ranked_batch's do; clip_id is the shard;

@@ -926,6 +926,106 @@ struct ast_json* fp_search_fingerprint_in_context(const char* context, const cha
 	return search_candidates(context, filename, coefs, tolerance, freq_ignore_low, freq_ignore_high, max_results, true);
 }
 
+/* New: the match census. fp_search_fingerprint_in_context's winner with how it stands against every
+ * other clip of `context`: the result query (fp_handler.c:367-374) lists one row per clip with a
+ * non-zero count, and the census is those rows counted by count(*) ("select c, count(*) from (select
+ * count(*) c from temp group by audio_uuid) group by c", tfp_group_census_pcm_batch), which the
+ * application's ratio test (application_handler.c:180-203) cannot see from the first row. A JSON
+ * object: "winner" (fp_search_fingerprint_in_context's first object, or null), "frame_count",
+ * "population" (the context's clips), "clips_at_or_above" (clips whose count reaches the winner's,
+ * the winner included), "clips_tied" (count equal to the winner's) and "histogram" ([[count, clips],
+ * ...], non-zero bins only, counts descending, count 0 last). NULL for bad arguments or a failed call. */
+struct ast_json* fp_search_fingerprint_census(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high)
+{
+	int16_t* pcm;
+	float* x;
+	int64_t cap, ns, off[2], nf = 0;
+	int32_t sr, count = 0, scope, nbins, need = 0, c, top = 0;
+	int32_t* hist;
+	int rc;
+	tfp_search_params p;
+	tfp_candidate cand;
+	tfp_result r;
+	struct ast_json* j_res;
+	struct ast_json* j_hist;
+	struct ast_json* j_tmp;
+
+	if(filename == NULL) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	if(search_params(&p, context, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	if(read_audio(filename, &pcm, &cap, &x, &ns, &sr) != 0) {
+		return NULL;
+	}
+	off[0] = 0;
+	off[1] = ns;
+	nf = tfp_frame_count(ns); /* ast_json_array_size(j_fprints), fp_handler.c:286 */
+	nbins = (int32_t)nf + 1;
+	hist = ast_calloc(nbins, sizeof(*hist));
+	scope = scope_of_context(context, false);
+	if(hist == NULL) {
+		rc = TFP_E_NOMEM;
+	}
+	else if(pcm != NULL) {
+		rc = tfp_group_search_scoped_pcm_batch(g_tfp, pcm, off, 1, sr, &p, &scope, 1, &cand, &count);
+		if(rc == TFP_OK) {
+			rc = tfp_group_census_pcm_batch(g_tfp, pcm, off, 1, sr, &p, &scope, nbins, hist, &need);
+		}
+	}
+	else {
+		/* audio tfp_wav_decode refuses (fp32 hop values): its frames, then the frames forms */
+		tfp_frame* fr = ast_calloc(nf > 0 ? nf : 1, sizeof(*fr));
+		int64_t qoff[2] = {0, 0};
+		rc = fr ? tfp_group_fingerprint_f32_batch(g_tfp, x, off, 1, sr, fr, nf, &qoff[1]) : TFP_E_NOMEM;
+		if(rc == TFP_OK) {
+			rc = tfp_group_search_scoped_batch(g_tfp, fr, qoff, 1, &p, &scope, 1, &cand, &count);
+		}
+		if(rc == TFP_OK) {
+			rc = tfp_group_census_batch(g_tfp, fr, qoff, 1, &p, &scope, nbins, hist, &need);
+		}
+		ast_free(fr);
+	}
+	pcm_put(pcm, cap);
+	ast_free(x);
+	if(rc != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not take the census of %s: %s\n", filename, tfp_group_last_error(g_tfp));
+		ast_free(hist);
+		return NULL;
+	}
+	j_res = ast_json_object_create();
+	j_tmp = NULL;
+	if(count > 0) {
+		memset(&r, 0, sizeof(r));
+		r.found = 1;
+		r.match_count = top = cand.match_count;
+		r.frame_count = (int32_t)nf;
+		snprintf(r.uuid, sizeof(r.uuid), "%s", cand.uuid);
+		j_tmp = search_result(&r); /* NULL: the row's audio_list entry is missing */
+	}
+	ast_json_object_set(j_res, "winner", j_tmp ? j_tmp : ast_json_null());
+	ast_json_object_set(j_res, "frame_count", ast_json_integer_create(nf));
+	ast_json_object_set(j_res, "population", ast_json_integer_create(tfp_census_at_least(hist, nbins, 0)));
+	ast_json_object_set(j_res, "clips_at_or_above", ast_json_integer_create(top > 0 ? tfp_census_at_least(hist, nbins, top) : 0));
+	ast_json_object_set(j_res, "clips_tied", ast_json_integer_create(top > 0 ? hist[top] : 0));
+	j_hist = ast_json_array_create();
+	for(c = nbins - 1; c >= 0; c--) {
+		if(hist[c] == 0) {
+			continue;
+		}
+		j_tmp = ast_json_array_create();
+		ast_json_array_append(j_tmp, ast_json_integer_create(c));
+		ast_json_array_append(j_tmp, ast_json_integer_create(hist[c]));
+		ast_json_array_append(j_hist, j_tmp);
+	}
+	ast_json_object_set(j_res, "histogram", j_hist);
+	ast_free(hist);
+	return j_res;
+}
+
 /* New: fp_search_fingerprint_candidates for every window of a long recording. The reference records
  * a fixed duration and searches that one window (application_handler.c:152-185, fp_handler.c:275-374);
  * this returns a JSON array with one object per full window of window_frames frames, hop_frames

@@ -60,6 +60,19 @@ struct ast_json* fp_search_fingerprint_candidates(const char* context, const cha
 struct ast_json* fp_search_fingerprint_in_context(const char* context, const char* filename, const int coefs,
 		const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int max_results);
 
+/* New: match census. The result query (src/fp_handler.c:367-374) lists one row per clip with a
+ * non-zero count; every call above reads its head, and none says how the head stands against the
+ * rest of the catalog, which on 8 kHz audio (max1 spans about 1 dB) is the missing half of the
+ * application's decision (src/application_handler.c:180-203): a count of 80/94 that three clips reach
+ * is not one that 4,000 clips reach. This returns, for the clips enrolled in `context` (a scope, as for
+ * fp_search_fingerprint_in_context), a JSON object: "winner" (that call's first object, or null),
+ * "frame_count", "population" (the context's clips), "clips_at_or_above" (clips whose count reaches
+ * the winner's, the winner included), "clips_tied" (count equal to the winner's, the winner included)
+ * and "histogram" ([[count, clips], ...]: the exact number of clips at each count, non-zero bins only,
+ * counts descending, so count 0 comes last). NULL: bad arguments or an unreadable file. */
+struct ast_json* fp_search_fingerprint_census(const char* context, const char* filename, const int coefs,
+		const double tolerance, const int freq_ignore_low, const int freq_ignore_high);
+
 /* New: sliding search. The reference records a fixed duration and searches that one window
  * (src/application_handler.c:152-185, src/fp_handler.c:275-374). This searches every full window of
  * window_frames frames (256 samples each), hop_frames apart, of a longer recording, fingerprinting it
