@@ -315,6 +315,7 @@ struct tfp_engine {
   int64_t n_trace_batches = 0, n_traces = 0;
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
+  FpLaunchStats fpstats;  // fingerprint launches so far per kernel (tfp_fingerprint_stats)
   int32_t class_ku_max = 10;  // TFP_VOTE_CLASS_MAX: pattern-class vote up to this many used keys (-1: always the GEMM)
   bool dbg_vote = false;      // TFP_DEBUG_VOTE: log the vote path's shape per batch
   bool dbg_index = false;     // TFP_DEBUG_INDEX: log each index update's phases (host ms)
@@ -644,11 +645,12 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
   if (f32)
     HIPCHK(e, launch_fingerprint_f32(e->fpcfg, T, static_cast<const float*>(d_pcm), d_sbeg, d_send, d_foff, d_toff, d_tclip,
                                      toff[nclips], e->micro.as<int32_t>(), e->db.as<double>(), e->stream,
-                                     exact_q ? e->logfix : LogFix{}));
+                                     exact_q ? e->logfix : LogFix{}, &e->fpstats));
   else
     HIPCHK(e, launch_fingerprint(e->fpcfg, T, fx, tile_frames, static_cast<const int16_t*>(d_pcm), d_sbeg, d_send, d_foff,
                                  d_toff, d_tclip, toff[nclips], nf, e->micro.as<int32_t>(), e->db.as<double>(),
-                                 e->stream, exact_q ? e->logfix : LogFix{}, nclips == 1 && sbeg[0] == 0 ? send[0] : -1));
+                                 e->stream, exact_q ? e->logfix : LogFix{}, &e->fpstats,
+                                 nclips == 1 && sbeg[0] == 0 ? send[0] : -1));
   *nframes_out = nf;
   if (foff_out) *foff_out = foff;
   return TFP_OK;
@@ -2799,7 +2801,7 @@ int tfp_fingerprint_device(tfp_engine* e, const tfp_plan* p, const int16_t* d_pc
   hipStream_t s = stream ? (hipStream_t)stream : e->stream;
   HIPCHK(e, launch_fingerprint(e->fpcfg, T, fx && !p->long_clip, p->tile_frames, d_pcm, p->d_soff.as<int64_t>(), p->d_soff.as<int64_t>() + 1,
                                p->d_foff.as<int64_t>(), p->d_toff.as<int32_t>(),
-                               p->d_tclip.as<int32_t>(), p->ntiles, p->nframes, d_micro, d_db, s, e->logfix));
+                               p->d_tclip.as<int32_t>(), p->ntiles, p->nframes, d_micro, d_db, s, e->logfix, &e->fpstats));
   return TFP_OK;
 }
 
@@ -3247,6 +3249,17 @@ int tfp_rank_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batche
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (vote_batches) *vote_batches = e->n_rank_vote;
   if (general_batches) *general_batches = e->n_rank_general;
+  return TFP_OK;
+}
+
+int tfp_fingerprint_stats(tfp_engine* e, int64_t* small8k, int64_t* throughput8k, int64_t* generic_i16,
+                          int64_t* generic_f32) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (small8k) *small8k = e->fpstats.small8k;
+  if (throughput8k) *throughput8k = e->fpstats.throughput8k;
+  if (generic_i16) *generic_i16 = e->fpstats.generic_i16;
+  if (generic_f32) *generic_f32 = e->fpstats.generic_f32;
   return TFP_OK;
 }
 
@@ -3775,7 +3788,7 @@ int tfp_search_device(tfp_engine* e, const tfp_plan* p, const int16_t* d_pcm, co
   HIPCHK(e, launch_fingerprint(e->fpcfg, T, fx && !p->long_clip, p->tile_frames, d_pcm, p->d_soff.as<int64_t>(), p->d_soff.as<int64_t>() + 1,
                                p->d_foff.as<int64_t>(), p->d_toff.as<int32_t>(),
                                p->d_tclip.as<int32_t>(), p->ntiles, p->nframes, e->micro.as<int32_t>(),
-                               e->db.as<double>(), s, P->coefs == 2 ? e->logfix : LogFix{}));
+                               e->db.as<double>(), s, P->coefs == 2 ? e->logfix : LogFix{}, &e->fpstats));
   std::vector<unsigned long long> keys;
   return search_core(e, p->foff.data(), p->nclips, e->db.as<double>(), P, keys,
                      reinterpret_cast<unsigned long long*>(d_keys), s);
@@ -3866,6 +3879,86 @@ int tfp_stream_reset(tfp_stream* st, int32_t ch) {
   return TFP_OK;
 }
 
+// The windows ring[c][wpos .. wpos + W) of the channels `act`, staged for one fingerprint launch:
+// the tile choice and, in the stream's mapped pinned buffer (read in place by the kernels), room
+// for pcm_bytes of a tick's samples followed by the windows' layout (sbeg, send, foff, toff, tclip).
+struct StreamWindows {
+  const DspTables* tables = nullptr;
+  bool fx = false;
+  int32_t tile = 0, ntiles = 0;
+  int64_t nframes = 0;
+  char* h = nullptr;        // the staging buffer (host view): the tick's samples go to its start
+  const char* d = nullptr;  // ... and its device view
+  size_t o_sb = 0, o_se = 0, o_fo = 0, o_to = 0, o_tc = 0;  // byte offsets of the layout arrays
+};
+
+// Stages the layout of the windows of `act` (in that order, window i's frames at [i F, (i + 1) F))
+// at ring position wpos. An upload and its hand-off to the first kernel cost ~16 us a tick, hence
+// the mapped buffer; the previous launch's kernels must be done reading it. Caller holds e->mu.
+static int stream_stage_windows(tfp_stream* st, size_t pcm_bytes, const std::vector<int32_t>& act, int64_t wpos,
+                                StreamWindows* w, std::vector<int64_t>& fov) {
+  tfp_engine* e = st->eng;
+  int rc;
+  if ((rc = ensure_tables(e, st->sr, &w->tables, &w->fx))) return rc;
+  const int32_t na = (int32_t)act.size();
+  const int64_t F = tfp_frame_count(st->W);
+  w->tile = fp_tile_frames(e->fpcfg, w->fx, false, false);
+  const int32_t tiles = (int32_t)((F + w->tile - 1) / w->tile);
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_pcm = al(pcm_bytes), b_sb = al(sizeof(int64_t) * na), b_fo = al(sizeof(int64_t) * (na + 1)),
+               b_to = al(sizeof(int32_t) * (na + 1)), b_tc = al(sizeof(int32_t) * (size_t)na * tiles);
+  const size_t total = b_pcm + 2 * b_sb + b_fo + b_to + b_tc;
+  if (st->stage_pending) HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, st->stage_h.reserve(total, hipHostMallocMapped | hipHostMallocCoherent));
+  if (st->stage_h.p != st->stage_host) {
+    HIPCHK(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&st->stage_dev), st->stage_h.p, 0));
+    st->stage_host = st->stage_h.p;
+  }
+  w->h = st->stage_h.as<char>();
+  w->d = st->stage_dev;
+  w->o_sb = b_pcm;
+  w->o_se = w->o_sb + b_sb;
+  w->o_fo = w->o_se + b_sb;
+  w->o_to = w->o_fo + b_fo;
+  w->o_tc = w->o_to + b_to;
+  int64_t* sb = reinterpret_cast<int64_t*>(w->h + w->o_sb);
+  int64_t* se = reinterpret_cast<int64_t*>(w->h + w->o_se);
+  int64_t* fo = reinterpret_cast<int64_t*>(w->h + w->o_fo);
+  int32_t* to = reinterpret_cast<int32_t*>(w->h + w->o_to);
+  int32_t* tc = reinterpret_cast<int32_t*>(w->h + w->o_tc);
+  for (int32_t i = 0; i < na; i++) {
+    sb[i] = (int64_t)act[i] * 2 * st->W + wpos;
+    se[i] = sb[i] + st->W;
+    fo[i] = (int64_t)i * F;
+    to[i] = i * tiles;
+    for (int32_t t = 0; t < tiles; t++) tc[(size_t)i * tiles + t] = i;
+  }
+  fo[na] = (int64_t)na * F;
+  to[na] = na * tiles;
+  w->ntiles = to[na];
+  w->nframes = fo[na];
+  st->stage_pending = true;
+  fov.assign(fo, fo + na + 1);  // (the pinned buffer is rewritten by the next staging)
+  return TFP_OK;
+}
+
+// Fingerprints the staged windows in place in the ring: micro-units into the engine's buffer, frame
+// values into d_db (nullptr: the engine's buffer), corrected by lf (LogFix{}: truncation-exact only).
+static int stream_fingerprint_windows(tfp_stream* st, const StreamWindows& w, double* d_db, const LogFix& lf) {
+  tfp_engine* e = st->eng;
+  if (!w.ntiles) return TFP_OK;
+  HIPCHK(e, e->micro.reserve(sizeof(int32_t) * 2 * (w.nframes + 1)));
+  if (!d_db) HIPCHK(e, e->db.reserve(sizeof(double) * 2 * (w.nframes + 1)));
+  HIPCHK(e, launch_fingerprint(e->fpcfg, w.tables, w.fx, w.tile, st->ring.as<int16_t>(),
+                               reinterpret_cast<const int64_t*>(w.d + w.o_sb),
+                               reinterpret_cast<const int64_t*>(w.d + w.o_se),
+                               reinterpret_cast<const int64_t*>(w.d + w.o_fo),
+                               reinterpret_cast<const int32_t*>(w.d + w.o_to),
+                               reinterpret_cast<const int32_t*>(w.d + w.o_tc), w.ntiles, w.nframes,
+                               e->micro.as<int32_t>(), d_db ? d_db : e->db.as<double>(), e->stream, lf, &e->fpstats));
+  return TFP_OK;
+}
+
 // One tick into a stream: the samples into the ring, then (match) the windows that are full after
 // it fingerprinted into d_db (frame values, 2 doubles per frame; nullptr: the engine's buffer) at
 // window i's frames [i F, (i + 1) F). act = their channels, in channel order. Caller holds e->mu.
@@ -3886,61 +3979,18 @@ static int stream_tick(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_
   *F_out = F;
   if (d_db && (int64_t)na * F > cap_frames) return fail(e, TFP_E_ARG, "stream tick: %d windows of %lld frames past %lld", na,
                                                         (long long)F, (long long)cap_frames);
-  const DspTables* Tb;
-  bool fx = false;
-  if ((rc = ensure_tables(e, st->sr, &Tb, &fx))) return rc;
-  const int32_t tile = fp_tile_frames(e->fpcfg, fx, false, false);
-  const int32_t tiles = (int32_t)((F + tile - 1) / tile);
-  // One mapped pinned buffer per tick, read in place by the kernels: the tick's samples, then the
-  // windows' layout (sbeg, send, foff, toff, tclip). An upload and its hand-off to the first
-  // kernel cost ~16 us a tick. The previous tick's kernels must be done reading the buffer.
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_pcm = al(sizeof(int16_t) * (size_t)st->nch * T), b_sb = al(sizeof(int64_t) * na),
-               b_fo = al(sizeof(int64_t) * (na + 1)), b_to = al(sizeof(int32_t) * (na + 1)),
-               b_tc = al(sizeof(int32_t) * (size_t)na * tiles);
-  const size_t total = b_pcm + 2 * b_sb + b_fo + b_to + b_tc;
-  if (st->stage_pending) HIPCHK(e, hipStreamSynchronize(e->stream));
-  HIPCHK(e, st->stage_h.reserve(total, hipHostMallocMapped | hipHostMallocCoherent));
-  if (st->stage_h.p != st->stage_host) {
-    HIPCHK(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&st->stage_dev), st->stage_h.p, 0));
-    st->stage_host = st->stage_h.p;
-  }
-  char* h = st->stage_h.as<char>();
-  memcpy(h, pcm, sizeof(int16_t) * (size_t)st->nch * T);
-  int64_t* sb = reinterpret_cast<int64_t*>(h + b_pcm);
-  int64_t* se = reinterpret_cast<int64_t*>(h + b_pcm + b_sb);
-  int64_t* fo = reinterpret_cast<int64_t*>(h + b_pcm + 2 * b_sb);
-  int32_t* to = reinterpret_cast<int32_t*>(h + b_pcm + 2 * b_sb + b_fo);
-  int32_t* tc = reinterpret_cast<int32_t*>(h + b_pcm + 2 * b_sb + b_fo + b_to);
-  for (int32_t i = 0; i < na; i++) {
-    sb[i] = (int64_t)act[i] * 2 * st->W + wpos;
-    se[i] = sb[i] + st->W;
-    fo[i] = (int64_t)i * F;
-    to[i] = i * tiles;
-    for (int32_t t = 0; t < tiles; t++) tc[(size_t)i * tiles + t] = i;
-  }
-  fo[na] = (int64_t)na * F;
-  to[na] = na * tiles;
-  st->stage_pending = true;
-  const char* d = st->stage_dev;
-  hipLaunchKernelGGL(stream_scatter_kernel, dim3(1024), dim3(256), 0, e->stream, reinterpret_cast<const int16_t*>(d), T,
+  // One mapped pinned buffer per tick: the tick's samples, then the windows' layout.
+  const size_t pcm_bytes = sizeof(int16_t) * (size_t)st->nch * T;
+  StreamWindows w;
+  if ((rc = stream_stage_windows(st, pcm_bytes, act, wpos, &w, fov))) return rc;
+  memcpy(w.h, pcm, pcm_bytes);
+  hipLaunchKernelGGL(stream_scatter_kernel, dim3(1024), dim3(256), 0, e->stream, reinterpret_cast<const int16_t*>(w.d), T,
                      st->W, st->wpos, st->nch, st->ring.as<int16_t>());
   HIPCHK(e, hipGetLastError());
   st->wpos = wpos;
   for (auto& f : st->filled) f = std::min<int64_t>(st->W, f + T);
-  fov.assign(fo, fo + na + 1);  // (the pinned buffer is rewritten next tick)
   if (!na) return TFP_OK;
-  HIPCHK(e, e->micro.reserve(sizeof(int32_t) * 2 * (fo[na] + 1)));
-  if (!d_db) HIPCHK(e, e->db.reserve(sizeof(double) * 2 * (fo[na] + 1)));
-  const int64_t* d_sb = reinterpret_cast<const int64_t*>(d + b_pcm);
-  HIPCHK(e, launch_fingerprint(e->fpcfg, Tb, fx, tile, st->ring.as<int16_t>(), d_sb,
-                               reinterpret_cast<const int64_t*>(d + b_pcm + b_sb),
-                               reinterpret_cast<const int64_t*>(d + b_pcm + 2 * b_sb),
-                               reinterpret_cast<const int32_t*>(d + b_pcm + 2 * b_sb + b_fo),
-                               reinterpret_cast<const int32_t*>(d + b_pcm + 2 * b_sb + b_fo + b_to), to[na], fo[na],
-                               e->micro.as<int32_t>(), d_db ? d_db : e->db.as<double>(), e->stream,
-                               P->coefs == 2 ? e->logfix : LogFix{}));
-  return TFP_OK;
+  return stream_fingerprint_windows(st, w, d_db, P->coefs == 2 ? e->logfix : LogFix{});
 }
 
 int tfp_stream_push(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_search_params* P, tfp_result* out) {
@@ -3983,6 +4033,28 @@ int tfp_internal_stream_fp(tfp_stream* st, const int16_t* pcm, int32_t T, const 
   st->stage_pending = false;
   *nact = (int32_t)a.size();
   if (match) std::copy(a.begin(), a.end(), act);
+  return TFP_OK;
+}
+
+int tfp_stream_window_frames(tfp_stream* st, int32_t ch, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!st || ch < 0 || ch >= st->nch || !nframes) return TFP_E_ARG;
+  tfp_engine* e = st->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  *nframes = 0;
+  if (st->filled[ch] < st->W) return TFP_OK;  // no full window yet
+  const int64_t F = tfp_frame_count(st->W);
+  *nframes = F;
+  if (!out || cap < F) return fail(e, TFP_E_ARG, "stream window: %lld frames past %lld", (long long)F, (long long)cap);
+  HIPCHK(e, hipSetDevice(e->device));
+  // the window where it lies in the ring, by stream_tick's own staging and launch (exact q values)
+  const std::vector<int32_t> act(1, ch);
+  std::vector<int64_t> fov;
+  StreamWindows w;
+  int rc = stream_stage_windows(st, 0, act, st->wpos, &w, fov);
+  if (rc) return rc;
+  if ((rc = stream_fingerprint_windows(st, w, nullptr, e->logfix))) return rc;
+  if ((rc = copy_frames_out(e, F, fov, out))) return rc;
+  st->stage_pending = false;  // copy_frames_out waited for e->stream
   return TFP_OK;
 }
 

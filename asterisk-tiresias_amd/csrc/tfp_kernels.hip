@@ -1412,7 +1412,8 @@ hipError_t fp_launch_config(int device, FpLaunchCfg* cfg) {
 hipError_t launch_fingerprint(const FpLaunchCfg& cfg, const DspTables* d_tables, bool fixed8k, int32_t tile_frames,
                               const int16_t* d_pcm, const int64_t* d_sbeg, const int64_t* d_send, const int64_t* d_foff,
                               const int32_t* d_toff, const int32_t* d_tclip, int32_t ntiles, int64_t nframes,
-                              int32_t* d_micro, double* d_db, hipStream_t s, const LogFix& fx, int64_t single_ns) {
+                              int32_t* d_micro, double* d_db, hipStream_t s, const LogFix& fx, FpLaunchStats* stats,
+                              int64_t single_ns) {
   const bool v8 = fixed8k && (tile_frames == 4 || !cfg.force_generic);
   if (v8 ? !(tile_frames == 4 || tile_frames == kTile8k) : tile_frames != kFramesPerBlock) return hipErrorInvalidValue;
   if (ntiles <= 0) return hipSuccess;
@@ -1425,9 +1426,11 @@ hipError_t launch_fingerprint(const FpLaunchCfg& cfg, const DspTables* d_tables,
     if (tile_frames == 4) {  // fingerprint8k_kernel<1> finishes its own tail
       hipLaunchKernelGGL(fingerprint8k_kernel<1>, dim3(grid), dim3(kBlockThreads), 0, s, d_tables, d_pcm, d_sbeg, d_send,
                          d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, cfg.rare_thr, fx, single_ns);
+      if (stats) stats->small8k++;
     } else {
       hipLaunchKernelGGL(fingerprint8k_kernel<kTile8k / 4>, dim3(grid), dim3(64 * kBW8), 0, s, d_tables, d_pcm, d_sbeg,
                          d_send, d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, cfg.rare_thr, fx, single_ns);
+      if (stats) stats->throughput8k++;
       // (each HIP call overwrites the last error: a failed launch must be caught before the next one)
       if (const hipError_t le = hipGetLastError(); le != hipSuccess) return le;
       const int64_t nv = 2 * nframes;
@@ -1439,19 +1442,21 @@ hipError_t launch_fingerprint(const FpLaunchCfg& cfg, const DspTables* d_tables,
   }
   hipLaunchKernelGGL(fingerprint_kernel<int16_t>, dim3(grid), dim3(kBlockThreads), 0, s, d_tables, d_pcm, d_sbeg, d_send,
                      d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, fx);
+  if (stats) stats->generic_i16++;
   return hipGetLastError();
 }
 
 hipError_t launch_fingerprint_f32(const FpLaunchCfg& cfg, const DspTables* d_tables, const float* d_x,
                                   const int64_t* d_sbeg, const int64_t* d_send, const int64_t* d_foff,
                                   const int32_t* d_toff, const int32_t* d_tclip, int32_t ntiles, int32_t* d_micro,
-                                  double* d_db, hipStream_t s, const LogFix& fx) {
+                                  double* d_db, hipStream_t s, const LogFix& fx, FpLaunchStats* stats) {
   if (ntiles <= 0) return hipSuccess;
   if (cfg.grid_cap_f32 <= 0) return hipErrorInvalidValue;
   const int want = (ntiles + kBlockWaves - 1) / kBlockWaves;
   const int grid = want < cfg.grid_cap_f32 ? want : cfg.grid_cap_f32;
   hipLaunchKernelGGL(fingerprint_kernel<float>, dim3(grid), dim3(kBlockThreads), 0, s, d_tables, d_x, d_sbeg, d_send,
                      d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, fx);
+  if (stats) stats->generic_f32++;
   return hipGetLastError();
 }
 

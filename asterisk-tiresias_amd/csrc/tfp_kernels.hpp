@@ -87,6 +87,14 @@ struct FpLaunchCfg {
   bool force_generic = false;    // TFP_GENERIC=1: the generic kernel at 8 kHz too (tests)
   float rare_thr = 0x1p-98f;     // TFP_RARE_THR_LOG2=n: bins with 0 < |S|^2 < 2^n take the spec-order path (tests)
 };
+// Launches issued so far per fingerprint kernel (tfp_fingerprint_stats): counted by launch_fingerprint /
+// launch_fingerprint_f32 in the branch that issues the kernel, so the count is what ran.
+struct FpLaunchStats {
+  int64_t small8k = 0;       // fingerprint8k_kernel<1> (4-frame tiles)
+  int64_t throughput8k = 0;  // fingerprint8k_kernel<kTile8k / 4> + finish_db_kernel
+  int64_t generic_i16 = 0;   // fingerprint_kernel<int16_t>
+  int64_t generic_f32 = 0;   // fingerprint_kernel<float>
+};
 // Fills cfg for `device` (occupancy queries + the test knobs from the environment).
 hipError_t fp_launch_config(int device, FpLaunchCfg* cfg);
 inline int32_t fp_tile_frames(const FpLaunchCfg& cfg, bool fixed8k, bool f32, bool small) {
@@ -102,8 +110,9 @@ bool DspTables_fixed8k(const DspTables& t);
 hipError_t launch_fingerprint(const FpLaunchCfg& cfg, const DspTables* d_tables, bool fixed8k, int32_t tile_frames,
                               const int16_t* d_pcm, const int64_t* d_sbeg, const int64_t* d_send, const int64_t* d_foff,
                               const int32_t* d_toff, const int32_t* d_tclip, int32_t ntiles, int64_t nframes,
-                              int32_t* d_micro, double* d_db, hipStream_t s, const LogFix& fx,
+                              int32_t* d_micro, double* d_db, hipStream_t s, const LogFix& fx, FpLaunchStats* stats,
                               int64_t single_ns = -1);
+// stats (may be nullptr): the issued kernel's counter is incremented (a launch of no tiles counts nothing).
 // single_ns >= 0 (8 kHz kernel): the batch is one clip of single_ns samples at d_pcm[0], frames from
 // 0, so the kernel takes its tile bounds from the argument instead of a chain of layout loads
 // (batch-1: the first PCM request goes out at the kernel's first instruction).
@@ -114,7 +123,7 @@ hipError_t launch_fingerprint(const FpLaunchCfg& cfg, const DspTables* d_tables,
 hipError_t launch_fingerprint_f32(const FpLaunchCfg& cfg, const DspTables* d_tables, const float* d_x,
                                   const int64_t* d_sbeg, const int64_t* d_send, const int64_t* d_foff,
                                   const int32_t* d_toff, const int32_t* d_tclip, int32_t ntiles, int32_t* d_micro,
-                                  double* d_db, hipStream_t s, const LogFix& fx);
+                                  double* d_db, hipStream_t s, const LogFix& fx, FpLaunchStats* stats);
 
 hipError_t launch_synth(const SynthSpecDev* d_specs, int32_t nclips, int64_t spc, int16_t* d_out, hipStream_t s);
 

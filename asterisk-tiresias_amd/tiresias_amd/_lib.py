@@ -120,6 +120,8 @@ _SIGS = {
     "tfp_stream_destroy": (None, [P]),
     "tfp_stream_reset": (C.c_int, [P, C.c_int32]),
     "tfp_stream_push": (C.c_int, [P, P, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_stream_window_frames": (C.c_int, [P, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_fingerprint_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 4),
     "tfp_synth_pcm": (C.c_int, [P, C.c_int32, C.c_int64, P]),
     "tfp_synth_pcm_device": (C.c_int, [P, P, C.c_int32, C.c_int64, P, P]),
     "tfp_synchronize": (C.c_int, [P, P]),

@@ -335,6 +335,12 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
                                                   out.ctypes.data, n, C.byref(got)))
         return out[:n]
 
+    def fingerprint_stats(self) -> dict:
+        """tfp_fingerprint_stats: fingerprint kernel launches so far, by kernel."""
+        v = [C.c_int64() for _ in range(4)]
+        self._chk(lib().tfp_fingerprint_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("small8k", "throughput8k", "generic_i16", "generic_f32"), (x.value for x in v)))
+
     # ---- index ----------------------------------------------------------------------
     def index_add(self, uuid: str, m1, m2) -> int:
         m1 = np.ascontiguousarray(m1, np.int32)
@@ -670,6 +676,7 @@ class Stream:
         eng._chk(lib().tfp_stream_create(eng.handle, int(nchannels), int(sample_rate), int(window_samples),
                                          C.byref(self._h)))
         self.nchannels = nchannels
+        self.window_samples = int(window_samples)
         self._res = (Result * nchannels)()
         eng._streams.add(self)
 
@@ -686,6 +693,14 @@ class Stream:
             return None
         return [None if not r.found else {"audio_uuid": r.uuid.decode(), "match_count": r.match_count,
                                           "frame_count": r.frame_count} for r in self._res]
+
+    def window_frames(self, channel: int) -> np.ndarray:
+        """tfp_stream_window_frames: the frames of the channel's current window (0 frames until it is full)."""
+        n = frame_count(self.window_samples)
+        out = np.zeros(max(n, 1), FRAME_DTYPE)
+        got = C.c_int64()
+        self._eng._chk(lib().tfp_stream_window_frames(self._h, int(channel), out.ctypes.data, n, C.byref(got)))
+        return out[:got.value]
 
     def close(self):
         # tfp_stream_destroy uses the engine: a stream outliving its engine's close() was already

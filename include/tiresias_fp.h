@@ -157,6 +157,13 @@ void tfp_plan_destroy(tfp_plan* plan);
 int64_t tfp_plan_frames(const tfp_plan* plan);
 int tfp_fingerprint_device(tfp_engine* eng, const tfp_plan* plan, const int16_t* d_pcm, int32_t* d_micro,
                            double* d_db, void* stream);
+/* Fingerprint kernel launches so far, by kernel and from every entry point (host batches, plans,
+ * the search-from-PCM forms, stream ticks and window read-outs): the small 8 kHz launch (4-frame
+ * tiles, batches of few frames), the throughput 8 kHz launch, and the generic kernel over int16 and
+ * over fp32 samples (other sample rates, fp32 input). Counted where the kernel is issued; a call
+ * with no frames launches nothing. Any pointer may be NULL. */
+int tfp_fingerprint_stats(tfp_engine* eng, int64_t* small8k, int64_t* throughput8k, int64_t* generic_i16,
+                          int64_t* generic_f32);
 
 /* ---- enrolled index: the audio_fingerprint table (fp_handler.c:713-753) ------------- */
 /* Append one clip's rows (create_audio_fingerprint_info). m1/m2 in micro-units. */
@@ -643,6 +650,12 @@ int tfp_stream_reset(tfp_stream* st, int32_t channel);
  * ingest. out[nchannels] receives each channel's result when params != NULL. */
 int tfp_stream_push(tfp_stream* st, const int16_t* pcm, int32_t tick_samples, const tfp_search_params* params,
                     tfp_result* out);
+/* The frames of `channel`'s most recent window_samples, as tfp_fingerprint_pcm returns them for a
+ * recording of exactly those samples (exact q values), fingerprinted where they lie in the stream's
+ * ring by the launch a tick uses. *nframes = 0 (nothing written) while the channel's history is not
+ * full. Changes nothing a later push or read-out sees. TFP_E_ARG for a channel outside
+ * [0, nchannels) or cap below the window's frame count (*nframes then holds it). */
+int tfp_stream_window_frames(tfp_stream* st, int32_t channel, tfp_frame* out, int64_t cap, int64_t* nframes);
 
 /* ---- device groups: the node's GPUs behind one index (new in round 3) -------------------
  * The module's enrolled DB sharded over one engine per listed device (the reference

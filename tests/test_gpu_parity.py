@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from fp_util import assert_frames_equal as _assert_frames_equal
+from fp_util import assert_only_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -46,24 +48,6 @@ def _pcm_cases():
         "tiny": rng.integers(-2, 3, 9000).astype(np.int16),
     }
     return cases
-
-
-def _assert_frames_equal(fr, micro, db):
-    assert len(fr) == len(micro)
-    bad = (fr["m1"] != micro[:, 0]) | (fr["m2"] != micro[:, 1])
-    if bad.any():
-        i = np.nonzero(bad)[0]
-        print("mismatching frames:", len(i), "of", len(fr), "first:", i[:10])
-        print("gpu q1,q2:", fr["q1"][i[:5]], fr["q2"][i[:5]])
-        print("cpu q1,q2:", db[i[:5], 0], db[i[:5], 1])
-    assert np.array_equal(fr["m1"], micro[:, 0]), np.nonzero(fr["m1"] != micro[:, 0])
-    assert np.array_equal(fr["m2"], micro[:, 1]), np.nonzero(fr["m2"] != micro[:, 1])
-    # q: the frame values are glibc's 10*log10|c| bit for bit (tfp_math.hpp LogFix); a NaN is a
-    # NaN whatever its payload (x86 and gfx950 make different default NaNs)
-    for k, col in (("q1", 0), ("q2", 1)):
-        a, b = fr[k], db[:, col]
-        same = (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
-        assert same.all(), np.nonzero(~same)
 
 
 @pytest.mark.parametrize("name", list(_pcm_cases().keys()))
@@ -120,17 +104,22 @@ def _sparse_cases(nclips=256, n=4096, seed=21):
 
 def test_fingerprint_sparse_and_cancelling_spectra_bit_exact(engine, oracle):
     """The throughput launch and the small launch on spectra full of exact zeros and rounding
-    residues (the rare-bin test and both elements of every conjugate pair)."""
-    clips = _sparse_cases()
+    residues (the rare-bin test and both elements of every conjugate pair). 320 clips of 16 frames
+    are past the small launch's batch size; the launch counter says which kernel each call ran."""
+    clips = _sparse_cases(nclips=320)
     flat = np.concatenate(clips)
     off = np.concatenate([[0], np.cumsum([len(c) for c in clips])]).astype(np.int64)
+    st = engine.fingerprint_stats()
     fr = engine.fingerprint_batch(flat, off)
+    assert_only_kernel(engine, st, "throughput8k", "the batch became a small one: grow nclips")
     micro, db = oracle.fingerprint_batch(flat, off, nthreads=8)
     _assert_frames_equal(fr, micro, db)
+    st = engine.fingerprint_stats()
     for c in clips[:10]:
         fr1 = engine.fingerprint(c)
         _, db1, micro1 = oracle.fingerprint(c)
         _assert_frames_equal(fr1, micro1, db1)
+    assert_only_kernel(engine, st, "small8k")
 
 
 def test_fingerprint_ragged_batch_equals_single(engine, tfp_lib):
@@ -363,18 +352,32 @@ def test_fp_handler_mirror_end_to_end(tmp_path, oracle, tfp_lib):
 def test_fingerprint_kernel_variants_bit_exact(engine, oracle, tfp_lib, knob):
     """The 8 kHz kernel's other paths against the oracle: the generic kernel (TFP_GENERIC=1), and
     the real split's spec-order slow path taken by every non-zero bin (TFP_RARE_THR_LOG2=100;
-    in production only bins with 0 < |S|^2 < 2^-98 take it)."""
-    pcm = tfp_lib.synth_pcm(SEED_DB, range(6), 80000)
+    in production only bins with 0 < |S|^2 < 2^-98 take it) in the throughput kernel and, on the
+    batch's small head, in the small kernel. 16 synthetic clips are past the small launch's batch
+    size; the launch counter says which kernel each call ran."""
+    pcm = tfp_lib.synth_pcm(SEED_DB, range(16), 80000)
     flat = np.concatenate([pcm.reshape(-1)] + list(_pcm_cases().values()))
-    lens = [80000] * 6 + [len(v) for v in _pcm_cases().values()]
+    lens = [80000] * 16 + [len(v) for v in _pcm_cases().values()]
     off = np.concatenate([[0], np.cumsum(lens)])
     micro, db = oracle.fingerprint_batch(flat, off, nthreads=8)
+    # the first 6 clips and the edge cases: the batch this test ran before it was enlarged (small)
+    flat_s = np.concatenate([pcm[:6].reshape(-1)] + list(_pcm_cases().values()))
+    off_s = np.concatenate([[0], np.cumsum(lens[:6] + lens[16:])])
     eng = _engine_with(tfp_lib, {knob[0]: knob[1]})  # knobs are read once, at engine creation
     try:
+        st = eng.fingerprint_stats()
         fr = eng.fingerprint_batch(flat, off)
+        assert_only_kernel(eng, st, "generic_i16" if knob[0] == "TFP_GENERIC" else "throughput8k",
+                           "the batch became a small one: add clips")
+        st = eng.fingerprint_stats()
+        fr_s = eng.fingerprint_batch(flat_s, off_s)
+        if knob[0] == "TFP_RARE_THR_LOG2":
+            assert_only_kernel(eng, st, "small8k")
     finally:
         eng.close()
     _assert_frames_equal(fr, micro, db)
+    nf6, nf16 = 6 * 313, 16 * 313
+    _assert_frames_equal(fr_s, np.concatenate([micro[:nf6], micro[nf16:]]), np.concatenate([db[:nf6], db[nf16:]]))
 
 
 @pytest.mark.parametrize("tol,low,high", [(0.001, -1, -1), (0.1, 100, 3400), (0.45, -1, -1), (-1.0, 300, -1)])
