@@ -24,6 +24,7 @@
 #include "../../include/tiresias_fp.h"
 #include "tfp_align.hpp"
 #include "tfp_coalesce.hpp"
+#include "tfp_g711.hpp"
 #include "tfp_index.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
@@ -313,6 +314,8 @@ struct tfp_engine {
   // and the batches that launched the kernel / the requests it computed so far
   DevBuf trace_reqs, trace_out;
   int64_t n_trace_batches = 0, n_traces = 0;
+  DevBuf g711_codes;  // a large G.711 batch's codes, expanded into pcm
+  int64_t n_g711_expand = 0, n_g711_stream = 0, n_g711_codes = 0;  // tfp_g711_stats
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   FpLaunchStats fpstats;  // fingerprint launches so far per kernel (tfp_fingerprint_stats)
@@ -484,14 +487,25 @@ const char* engine_host_ptr(tfp_engine* e, const void* p, size_t n) {
   return slot.second + (reinterpret_cast<uintptr_t>(p) - base);
 }
 
+// A batch of G.711 codes laid end to end (clip c = lens[c] codes, in order) and their law.
+struct G711Src {
+  const uint8_t* codes;
+  int32_t law;
+};
+
 // Fingerprint host samples (int16 PCM, or with f32 the fp32 values aubio_source produced):
 // clip c is the lens[c] samples at ptrs[c] (the clips may lie anywhere: a coalesced batch gathers
 // the queries of several callers); leaves micro/db on the device in e->micro / e->db.
 // exact_q: the frame values (e->db) equal glibc's 10*log10|c| bit for bit (LogFix lookups); a
 // coefs = 1 search needs only their truncation, which is exact either way.
+// g711: the clips are G.711 codes laid end to end at g711->codes (ptrs is not read). The codes go to
+// the device at one byte per sample and g711_expand_kernel writes their int16 into e->pcm; from
+// there on (layout, tile choice, launch) the call is the int16 call of the same lengths.
 int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens, bool f32, int32_t nclips, int32_t sr,
-                     int64_t* nframes_out, std::vector<int64_t>* foff_out, bool exact_q = true) {
+                     int64_t* nframes_out, std::vector<int64_t>* foff_out, bool exact_q = true,
+                     const G711Src* g711 = nullptr) {
   const size_t ss = f32 ? sizeof(float) : sizeof(int16_t);
+  const size_t hs = g711 ? sizeof(uint8_t) : ss;  // bytes per sample as the host hands them over
   const DspTables* T;
   bool fx = false;
   int rc = ensure_tables(e, sr, &T, &fx);
@@ -528,11 +542,11 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
   int64_t ns = 0;
   for (int32_t c = 0; c < nclips; c++) {
     ns += lens[c];
-    if (c + 1 < nclips && static_cast<const char*>(ptrs[c]) + ss * lens[c] != ptrs[c + 1]) contiguous = false;
+    if (!g711 && c + 1 < nclips && static_cast<const char*>(ptrs[c]) + ss * lens[c] != ptrs[c + 1]) contiguous = false;
   }
   std::vector<int64_t> sbeg(nclips + 1, 0), send(nclips + 1, 0);
   const char* base_dev = nullptr;
-  bool in_place = ns > 0 && (small || !contiguous);
+  bool in_place = !g711 && ns > 0 && (small || !contiguous);
   if (in_place) {
     std::vector<const char*> dv(nclips, nullptr);
     for (int32_t c = 0; c < nclips && in_place; c++) {
@@ -555,7 +569,7 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     }
   }
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_pcm = in_place ? 0 : al(ss * ns), b_sb = al(sizeof(int64_t) * nclips),
+  const size_t b_pcm = in_place ? 0 : al(hs * ns), b_sb = al(sizeof(int64_t) * nclips),
                b_fo = al(sizeof(int64_t) * foff.size()), b_to = al(sizeof(int32_t) * toff.size()),
                b_tc = al(sizeof(int32_t) * tclip.size());
   const size_t lay = 2 * b_sb + b_fo + b_to + b_tc, total = b_pcm + lay;
@@ -568,7 +582,7 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
   };
   auto pack_samples = [&](char* h) {
     if (contiguous) {
-      if (ns) memcpy(h, ptrs[0], ss * ns);
+      if (ns) memcpy(h, g711 ? static_cast<const void*>(g711->codes) : ptrs[0], hs * ns);
       return;
     }
     for (int32_t c = 0; c < nclips; c++)
@@ -622,6 +636,9 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     if ((rc = upload(e, e->soff, hl.data(), lay))) return rc;
     if (in_place) {
       d_pcm = base_dev;
+    } else if (g711) {
+      if ((rc = upload(e, e->g711_codes, g711->codes, hs * ns))) return rc;
+      d_pcm = e->g711_codes.p;
     } else {
       HIPCHK(e, e->pcm.reserve(ss * ns));
       if (contiguous) {
@@ -636,6 +653,14 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     }
     lay_d = e->soff.as<char>();
     HIPCHK(e, hipStreamSynchronize(e->stream));  // (hl is released on return)
+  }
+  if (g711 && ns) {
+    // d_pcm holds the codes so far (staging, or g711_codes): their int16 into the device PCM buffer
+    HIPCHK(e, e->pcm.reserve(ss * ns));
+    HIPCHK(e, launch_g711_expand(static_cast<const uint8_t*>(d_pcm), ns, g711->law, e->pcm.as<int16_t>(), e->stream));
+    e->n_g711_expand++;
+    e->n_g711_codes += ns;
+    d_pcm = e->pcm.p;
   }
   const int64_t* d_sbeg = reinterpret_cast<const int64_t*>(lay_d);
   const int64_t* d_send = reinterpret_cast<const int64_t*>(lay_d + b_sb);
@@ -2710,8 +2735,9 @@ void tfp_host_free(void* p) {
 }
 
 namespace {
+// law >= 0: pcm holds G.711 codes of that law (one byte per sample) instead of int16.
 int fingerprint_batch_impl(tfp_engine* e, const void* pcm, bool f32, const int64_t* offsets, int32_t nclips,
-                           int32_t sr, tfp_frame* out, int64_t cap, int64_t* nframes) {
+                           int32_t sr, tfp_frame* out, int64_t cap, int64_t* nframes, int32_t law = -1) {
   if (!e) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!offsets || nclips < 0 || !nframes || (!pcm && nclips && offsets[nclips] > offsets[0]))
@@ -2728,12 +2754,29 @@ int fingerprint_batch_impl(tfp_engine* e, const void* pcm, bool f32, const int64
   std::vector<int64_t> foff;
   std::vector<const void*> ptrs;
   std::vector<int64_t> lens;
-  split_offsets(pcm, f32 ? sizeof(float) : sizeof(int16_t), offsets, nclips, &ptrs, &lens);
-  int rc = fingerprint_host(e, ptrs.data(), lens.data(), f32, nclips, sr, &nf, &foff);
+  split_offsets(pcm, law >= 0 ? sizeof(uint8_t) : f32 ? sizeof(float) : sizeof(int16_t), offsets, nclips, &ptrs, &lens);
+  const G711Src g{static_cast<const uint8_t*>(ptrs[0]), law};
+  int rc = fingerprint_host(e, ptrs.data(), lens.data(), f32, nclips, sr, &nf, &foff, true, law >= 0 ? &g : nullptr);
   if (rc) return rc;
   return copy_frames_out(e, nf, foff, out);
 }
 }  // namespace
+
+int tfp_fingerprint_g711_batch(tfp_engine* e, const uint8_t* codes, const int64_t* offsets, int32_t nclips, int32_t law,
+                               int32_t sr, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!e) return TFP_E_ARG;
+  if (!g711_law_ok(law)) return fail(e, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  return fingerprint_batch_impl(e, codes, false, offsets, nclips, sr, out, cap, nframes, law);
+}
+
+int tfp_g711_stats(tfp_engine* e, int64_t* expand_launches, int64_t* stream_launches, int64_t* codes) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (expand_launches) *expand_launches = e->n_g711_expand;
+  if (stream_launches) *stream_launches = e->n_g711_stream;
+  if (codes) *codes = e->n_g711_codes;
+  return TFP_OK;
+}
 
 int tfp_fingerprint_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nclips, int32_t sr,
                           tfp_frame* out, int64_t cap, int64_t* nframes) {
@@ -3651,7 +3694,7 @@ int tfp_trace_stats(tfp_engine* e, int64_t* batches, int64_t* traces) {
 namespace {
 // One search over host samples, the queries given as (pointer, samples); no coalescing.
 int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* lens, int32_t nq, bool f32, int32_t sr,
-                       const tfp_search_params* P, tfp_result* out) {
+                       const tfp_search_params* P, tfp_result* out, const G711Src* g711 = nullptr) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   std::vector<int64_t> foff(nq + 1, 0);
@@ -3663,7 +3706,7 @@ int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* le
   std::vector<unsigned long long> keys(nq, 0ull);
   if (valid_params(P) && nq && foff[nq] > 0) {
     int64_t nf;
-    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2);
+    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2, g711);
     if (rc) return rc;
     if ((rc = search_core(e, foff.data(), nq, e->db.as<double>(), P, keys, nullptr, e->stream))) return rc;
     e->stage_pending = false;  // search_core waited for e->stream (keys on the host)
@@ -3720,6 +3763,41 @@ int tfp_search_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offse
 int tfp_search_f32_batch(tfp_engine* e, const float* x, const int64_t* offsets, int32_t nq, int32_t sr,
                          const tfp_search_params* P, tfp_result* out) {
   return search_samples_impl(e, x, true, offsets, nq, sr, P, out);
+}
+
+// (also tfp_internal.hpp: a device group's per-shard call) Not coalesced: the coalescer gathers
+// callers' queries by pointer for the in-place read of int16 buffers; codes are expanded from one
+// flat array, and gathering several callers' arrays into one would add a host copy per call.
+int tfp_internal_search_g711(tfp_engine* e, const uint8_t* codes, const int64_t* offsets, int32_t nq, int32_t law,
+                             int32_t sr, const tfp_search_params* P, tfp_result* out) {
+  if (!e || !offsets || nq < 0 || !out) return TFP_E_ARG;
+  if (!g711_law_ok(law)) return fail(e, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  for (int32_t i = 0; i < nq; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  if (!codes && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "codes are NULL");
+  std::vector<int64_t> lens(nq);
+  for (int32_t i = 0; i < nq; i++) lens[i] = offsets[i + 1] - offsets[i];
+  const G711Src g{nq ? codes + offsets[0] : codes, law};
+  return search_gather_impl(e, nullptr, lens.data(), nq, false, sr, P, out, &g);
+}
+
+// (tfp_internal.hpp) codes already on this engine's device into int16 there, on `stream`: a device
+// group's query-sharded batch expands each shard's share in front of tfp_fingerprint_device.
+int tfp_internal_g711_expand_device(tfp_engine* e, const uint8_t* d_codes, int64_t n, int32_t law, int16_t* d_pcm,
+                                    void* stream) {
+  if (!e || n < 0 || !g711_law_ok(law)) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!n) return TFP_OK;
+  HIPCHK(e, launch_g711_expand(d_codes, n, law, d_pcm, (hipStream_t)stream));
+  e->n_g711_expand++;
+  e->n_g711_codes += n;
+  return TFP_OK;
+}
+
+int tfp_search_g711_batch(tfp_engine* e, const uint8_t* codes, const int64_t* offsets, int32_t nq, int32_t law, int32_t sr,
+                          const tfp_search_params* P, tfp_result* out) {
+  return tfp_internal_search_g711(e, codes, offsets, nq, law, sr, P, out);
 }
 
 int tfp_search_pcm_gather(tfp_engine* e, const int16_t* const* pcms, const int64_t* nsamples, int32_t nq, int32_t sr,
@@ -3962,7 +4040,9 @@ static int stream_fingerprint_windows(tfp_stream* st, const StreamWindows& w, do
 // One tick into a stream: the samples into the ring, then (match) the windows that are full after
 // it fingerprinted into d_db (frame values, 2 doubles per frame; nullptr: the engine's buffer) at
 // window i's frames [i F, (i + 1) F). act = their channels, in channel order. Caller holds e->mu.
-static int stream_tick(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_search_params* P, double* d_db,
+// law < 0: pcm is int16[nch][T]; else G.711 codes uint8[nch][T] of that law, expanded by the scatter
+// itself on their way into the ring (the ring is int16 either way; no extra pass or launch).
+static int stream_tick(tfp_stream* st, const void* pcm, int32_t law, int32_t T, const tfp_search_params* P, double* d_db,
                        int64_t cap_frames, std::vector<int32_t>& act, int64_t* F_out, std::vector<int64_t>& fov) {
   const bool match = P && valid_params(P);
   tfp_engine* e = st->eng;
@@ -3980,20 +4060,29 @@ static int stream_tick(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_
   if (d_db && (int64_t)na * F > cap_frames) return fail(e, TFP_E_ARG, "stream tick: %d windows of %lld frames past %lld", na,
                                                         (long long)F, (long long)cap_frames);
   // One mapped pinned buffer per tick: the tick's samples, then the windows' layout.
-  const size_t pcm_bytes = sizeof(int16_t) * (size_t)st->nch * T;
+  const size_t pcm_bytes = (law < 0 ? sizeof(int16_t) : sizeof(uint8_t)) * (size_t)st->nch * T;
   StreamWindows w;
   if ((rc = stream_stage_windows(st, pcm_bytes, act, wpos, &w, fov))) return rc;
   memcpy(w.h, pcm, pcm_bytes);
-  hipLaunchKernelGGL(stream_scatter_kernel, dim3(1024), dim3(256), 0, e->stream, reinterpret_cast<const int16_t*>(w.d), T,
-                     st->W, st->wpos, st->nch, st->ring.as<int16_t>());
-  HIPCHK(e, hipGetLastError());
+  if (law < 0) {
+    hipLaunchKernelGGL(stream_scatter_kernel, dim3(1024), dim3(256), 0, e->stream, reinterpret_cast<const int16_t*>(w.d), T,
+                       st->W, st->wpos, st->nch, st->ring.as<int16_t>());
+    HIPCHK(e, hipGetLastError());
+  } else {
+    HIPCHK(e, launch_stream_scatter_g711(reinterpret_cast<const uint8_t*>(w.d), T, st->W, st->wpos, st->nch, law,
+                                         st->ring.as<int16_t>(), e->stream));
+    e->n_g711_stream++;
+    e->n_g711_codes += (int64_t)st->nch * T;
+  }
   st->wpos = wpos;
   for (auto& f : st->filled) f = std::min<int64_t>(st->W, f + T);
   if (!na) return TFP_OK;
   return stream_fingerprint_windows(st, w, d_db, P->coefs == 2 ? e->logfix : LogFix{});
 }
 
-int tfp_stream_push(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_search_params* P, tfp_result* out) {
+// tfp_stream_push (law < 0, int16 samples) and tfp_stream_push_g711 (codes of that law).
+static int stream_push_impl(tfp_stream* st, const void* pcm, int32_t law, int32_t T, const tfp_search_params* P,
+                            tfp_result* out) {
   if (!st || !pcm || T <= 0 || T > st->W || (P && !out)) return TFP_E_ARG;
   tfp_engine* e = st->eng;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
@@ -4001,7 +4090,7 @@ int tfp_stream_push(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_sea
   std::vector<int32_t> act;
   std::vector<int64_t> fov;
   int64_t F = 0;
-  int rc = stream_tick(st, pcm, T, P, nullptr, 0, act, &F, fov);
+  int rc = stream_tick(st, pcm, law, T, P, nullptr, 0, act, &F, fov);
   if (rc) return rc;
   if (!P) return TFP_OK;
   for (int32_t c = 0; c < st->nch; c++) {
@@ -4019,15 +4108,28 @@ int tfp_stream_push(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_sea
   return TFP_OK;
 }
 
-int tfp_internal_stream_fp(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_search_params* P, double* d_db,
+int tfp_stream_push(tfp_stream* st, const int16_t* pcm, int32_t T, const tfp_search_params* P, tfp_result* out) {
+  return stream_push_impl(st, pcm, -1, T, P, out);
+}
+
+int tfp_stream_push_g711(tfp_stream* st, const uint8_t* codes, int32_t T, int32_t law, const tfp_search_params* P,
+                         tfp_result* out) {
+  if (!st) return TFP_E_ARG;
+  if (!g711_law_ok(law)) return fail(st->eng, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  return stream_push_impl(st, codes, law, T, P, out);
+}
+
+int tfp_internal_stream_fp(tfp_stream* st, const void* pcm, int32_t law, int32_t T, const tfp_search_params* P, double* d_db,
                            int64_t cap_frames, int32_t* act, int32_t* nact, int64_t* frames_per_window) {
   const bool match = P && valid_params(P);
-  if (!st || !pcm || T <= 0 || T > st->W || !nact || !frames_per_window || (match && (!d_db || !act))) return TFP_E_ARG;
+  if (!st || !pcm || T <= 0 || T > st->W || !nact || !frames_per_window || (match && (!d_db || !act)) ||
+      (law >= 0 && !g711_law_ok(law)))
+    return TFP_E_ARG;
   tfp_engine* e = st->eng;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   std::vector<int32_t> a;
   std::vector<int64_t> fov;
-  int rc = stream_tick(st, pcm, T, P, d_db, cap_frames, a, frames_per_window, fov);
+  int rc = stream_tick(st, pcm, law, T, P, d_db, cap_frames, a, frames_per_window, fov);
   if (rc) return rc;
   HIPCHK(e, hipStreamSynchronize(e->stream));  // the values are read by other devices' streams next
   st->stage_pending = false;

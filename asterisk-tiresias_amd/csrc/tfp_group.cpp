@@ -38,6 +38,7 @@
 
 #include "../../include/tiresias_fp.h"
 #include "tfp_coalesce.hpp"
+#include "tfp_g711.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
 #include "tfp_occur.hpp"
@@ -56,11 +57,12 @@ struct Member {
 // Device buffers of the query-sharded batch path, one set per shard.
 struct ShardBufs {
   void* pcm = nullptr;      // this shard's queries (int16)
+  void* codes = nullptr;    // ... as G.711 codes, expanded into pcm (tfp_group_search_g711_batch)
   void* micro = nullptr;    // their stored values (unused by the search, written by the kernel)
   void* q = nullptr;        // the whole batch's frame values (2 doubles per frame)
   void* keys = nullptr;     // per-query keys
   void* sfp = nullptr;      // split streams: this shard's channels' window values of the tick
-  size_t b_pcm = 0, b_micro = 0, b_q = 0, b_keys = 0, b_sfp = 0;
+  size_t b_pcm = 0, b_codes = 0, b_micro = 0, b_q = 0, b_keys = 0, b_sfp = 0;
   hipStream_t stream = nullptr;
   hipEvent_t fp_done = nullptr;
   tfp_plan* plan = nullptr;  // this shard's share of the last batch shape (k queries of qn samples)
@@ -110,7 +112,7 @@ struct tfp_group {
     delete pool;
     for (size_t s = 0; s < bufs.size(); s++) {
       (void)hipSetDevice(dev[s]);
-      for (void* p : {bufs[s].pcm, bufs[s].micro, bufs[s].q, bufs[s].keys, bufs[s].sfp})
+      for (void* p : {bufs[s].pcm, bufs[s].codes, bufs[s].micro, bufs[s].q, bufs[s].keys, bufs[s].sfp})
         if (p) (void)hipFree(p);
       if (bufs[s].fp_done) (void)hipEventDestroy(bufs[s].fp_done);
       tfp_plan_destroy(bufs[s].plan);
@@ -311,8 +313,10 @@ int add_members(tfp_group* g, int32_t s, int32_t n, const char* const* uuids) {
 }
 
 // Query-sharded batch over host int16 PCM of equal-length queries: shard s fingerprints its share,
-// the frame values are exchanged, every shard searches the whole batch.
-int search_sharded(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
+// the frame values are exchanged, every shard searches the whole batch. law >= 0: pcm holds G.711
+// codes of that law instead; a shard copies its share at one byte per sample and expands it on its
+// device in front of the same fingerprint launch.
+int search_sharded(tfp_group* g, const void* pcm, int32_t law, const int64_t* offsets, int32_t nq, int32_t sr,
                    const tfp_search_params* P, tfp_result* out) {
   const int n = (int)g->eng.size();
   const int64_t qn = offsets[1] - offsets[0];
@@ -335,9 +339,19 @@ int search_sharded(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int
         grow(&b.keys, &b.b_keys, sizeof(unsigned long long) * (size_t)(nq + 1)) != hipSuccess)
       return TFP_E_NOMEM;
     if (!k) return hipEventRecord(b.fp_done, b.stream) == hipSuccess ? TFP_OK : TFP_E_HIP;
-    if (hipMemcpyAsync(b.pcm, pcm + offsets[share[s]] - offsets[0], sizeof(int16_t) * (size_t)(k * qn),
-                       hipMemcpyHostToDevice, b.stream) != hipSuccess)
-      return TFP_E_HIP;
+    if (law < 0) {
+      // (offsets index the caller's buffer, as in every other form: query i lies at pcm + offsets[i])
+      if (hipMemcpyAsync(b.pcm, (const int16_t*)pcm + offsets[share[s]], sizeof(int16_t) * (size_t)(k * qn),
+                         hipMemcpyHostToDevice, b.stream) != hipSuccess)
+        return TFP_E_HIP;
+    } else {
+      if (grow(&b.codes, &b.b_codes, (size_t)(k * qn + 1)) != hipSuccess) return TFP_E_NOMEM;
+      if (hipMemcpyAsync(b.codes, (const uint8_t*)pcm + offsets[share[s]], (size_t)(k * qn), hipMemcpyHostToDevice,
+                         b.stream) != hipSuccess)
+        return TFP_E_HIP;
+      const int r = tfp_internal_g711_expand_device(g->eng[s], (const uint8_t*)b.codes, k * qn, law, (int16_t*)b.pcm, b.stream);
+      if (r) return r;
+    }
     if (!b.plan || b.plan_k != k || b.plan_qn != qn || b.plan_sr != sr) {
       std::vector<int64_t> off(k + 1);
       for (int32_t i = 0; i <= k; i++) off[i] = qn * i;
@@ -465,8 +479,9 @@ tfp_engine* tfp_group_engine(tfp_group* g, int32_t shard) {
 }
 
 namespace {
+// law >= 0: x holds G.711 codes of that law (each shard expands its clips on its device).
 int group_fingerprint(tfp_group* g, const void* x, bool f32, const int64_t* offsets, int32_t nclips, int32_t sr,
-                      tfp_frame* out, int64_t cap, int64_t* nframes) {
+                      tfp_frame* out, int64_t cap, int64_t* nframes, int32_t law = -1) {
   if (!g || !offsets || nclips < 0 || !nframes) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(g->mu);
   const int n = (int)g->eng.size();
@@ -488,6 +503,9 @@ int group_fingerprint(tfp_group* g, const void* x, bool f32, const int64_t* offs
     const int32_t a = cut[s], b = cut[s + 1];
     if (a >= b) return TFP_OK;
     int64_t got = 0;
+    if (law >= 0)
+      return tfp_fingerprint_g711_batch(g->eng[s], (const uint8_t*)x, offsets + a, b - a, law, sr, out + foff[a],
+                                        foff[b] - foff[a], &got);
     return f32 ? tfp_fingerprint_f32_batch(g->eng[s], (const float*)x, offsets + a, b - a, sr, out + foff[a],
                                            foff[b] - foff[a], &got)
                : tfp_fingerprint_batch(g->eng[s], (const int16_t*)x, offsets + a, b - a, sr, out + foff[a],
@@ -504,6 +522,13 @@ int tfp_group_fingerprint_batch(tfp_group* g, const int16_t* pcm, const int64_t*
 int tfp_group_fingerprint_f32_batch(tfp_group* g, const float* x, const int64_t* offsets, int32_t nclips, int32_t sr,
                                     tfp_frame* out, int64_t cap, int64_t* nframes) {
   return group_fingerprint(g, x, true, offsets, nclips, sr, out, cap, nframes);
+}
+
+int tfp_group_fingerprint_g711_batch(tfp_group* g, const uint8_t* codes, const int64_t* offsets, int32_t nclips, int32_t law,
+                                     int32_t sr, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!g) return TFP_E_ARG;
+  if (!tfp::g711_law_ok(law)) return gfail(g, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  return group_fingerprint(g, codes, false, offsets, nclips, sr, out, cap, nframes, law);
 }
 
 int tfp_group_index_add(tfp_group* g, const char* uuid, const int32_t* m1, const int32_t* m2, int32_t nframes) {
@@ -1134,7 +1159,7 @@ int group_search_samples(tfp_group* g, const void* x, bool f32, const int64_t* o
   if (!f32 && n > 1 && equal && nq >= 64 * n && offsets[1] > offsets[0] && valid_params(P)) {
     std::lock_guard<std::recursive_mutex> lk(g->mu);
     const int rc = refresh_ranks(g);
-    return rc ? rc : search_sharded(g, (const int16_t*)x, offsets, nq, sr, P, out);
+    return rc ? rc : search_sharded(g, x, -1, offsets, nq, sr, P, out);
   }
   const size_t ss = f32 ? sizeof(float) : sizeof(int16_t);
   std::vector<const void*> ptrs(nq);
@@ -1155,6 +1180,31 @@ int tfp_group_search_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* 
 int tfp_group_search_f32_batch(tfp_group* g, const float* x, const int64_t* offsets, int32_t nq, int32_t sr,
                                const tfp_search_params* P, tfp_result* out) {
   return group_search_samples(g, x, true, offsets, nq, sr, P, out);
+}
+
+// Codes in: throughput batches of equal-length queries are query-sharded as the int16 form's are
+// (each shard expands and fingerprints its share, the frame values are exchanged); every other batch
+// is expanded and fingerprinted by every shard. Not coalesced (as tfp_search_g711_batch).
+int tfp_group_search_g711_batch(tfp_group* g, const uint8_t* codes, const int64_t* offsets, int32_t nq, int32_t law,
+                                int32_t sr, const tfp_search_params* P, tfp_result* out) {
+  if (!g || !offsets || nq < 0 || !out) return TFP_E_ARG;
+  if (!tfp::g711_law_ok(law)) return gfail(g, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  for (int32_t i = 0; i < nq; i++)
+    if (offsets[i + 1] < offsets[i]) return gfail(g, TFP_E_ARG, "offsets not monotone");
+  if (!codes && nq && offsets[nq] > offsets[0]) return gfail(g, TFP_E_ARG, "codes are NULL");
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  int rc = refresh_ranks(g);
+  if (rc) return rc;
+  const int n = (int)g->eng.size();
+  bool equal = nq > 0;
+  for (int32_t i = 0; i < nq && equal; i++) equal = offsets[i + 1] - offsets[i] == offsets[1] - offsets[0];
+  if (n > 1 && equal && nq >= 64 * n && offsets[1] > offsets[0] && valid_params(P))
+    return search_sharded(g, codes, law, offsets, nq, sr, P, out);
+  std::vector<std::vector<tfp_result>> res(n, std::vector<tfp_result>(std::max(nq, 1)));
+  rc = run_all(g, [&](int s) { return tfp_internal_search_g711(g->eng[s], codes, offsets, nq, law, sr, P, res[s].data()); });
+  if (rc) return rc;
+  combine(g, res, nq, out);
+  return TFP_OK;
 }
 
 int tfp_group_search_pcm_gather(tfp_group* g, const int16_t* const* pcms, const int64_t* nsamples, int32_t nq,
@@ -1226,14 +1276,18 @@ namespace {
 // full windows into its sfp buffer; (2) every shard gathers all shards' window values in shard
 // order (hipMemcpyPeerAsync; a device copy when a device repeats) and matches them against its
 // clips; (3) per window, the greatest key over the shards.
-int split_stream_push(tfp_group_stream* st, const int16_t* pcm, int32_t T, const tfp_search_params* P, tfp_result* out) {
+// law < 0: pcm is int16[nch][T]; else G.711 codes uint8[nch][T] (the shards' rows are regrouped as
+// bytes and each shard's scatter expands them).
+int split_stream_push(tfp_group_stream* st, const void* pcm, int32_t law, int32_t T, const tfp_search_params* P,
+                      tfp_result* out) {
   tfp_group* g = st->g;
   const int n = (int)g->eng.size();
+  const size_t row = (law < 0 ? sizeof(int16_t) : sizeof(uint8_t)) * (size_t)T;  // bytes of a channel's tick
   for (int s = 0; s < n; s++) {
     const auto& ch = st->chans[s];
-    st->tick[s].resize(ch.size() * (size_t)T);
+    st->tick[s].resize((ch.size() * row + 1) / sizeof(int16_t));
     for (size_t j = 0; j < ch.size(); j++)
-      memcpy(st->tick[s].data() + j * T, pcm + (size_t)ch[j] * T, sizeof(int16_t) * (size_t)T);
+      memcpy(reinterpret_cast<char*>(st->tick[s].data()) + j * row, static_cast<const char*>(pcm) + (size_t)ch[j] * row, row);
   }
   const bool match = valid_params(P);
   const int64_t F = tfp_frame_count(st->W);
@@ -1245,7 +1299,7 @@ int split_stream_push(tfp_group_stream* st, const int16_t* pcm, int32_t T, const
     const int64_t cap = (int64_t)st->chans[s].size() * F;
     if (match && grow(&b.sfp, &b.b_sfp, sizeof(double) * 2 * (size_t)(cap + 1)) != hipSuccess) return TFP_E_NOMEM;
     int64_t fw = 0;
-    return tfp_internal_stream_fp(st->st[s], st->tick[s].data(), T, match ? P : nullptr, (double*)b.sfp, cap,
+    return tfp_internal_stream_fp(st->st[s], st->tick[s].data(), law, T, match ? P : nullptr, (double*)b.sfp, cap,
                                   st->act[s].data(), &st->nact[s], &fw);
   });
   if (rc || !P) return rc;
@@ -1296,18 +1350,36 @@ int split_stream_push(tfp_group_stream* st, const int16_t* pcm, int32_t T, const
 
 }  // namespace
 
-int tfp_group_stream_push(tfp_group_stream* st, const int16_t* pcm, int32_t tick, const tfp_search_params* P,
-                          tfp_result* out) {
+namespace {
+int group_stream_push(tfp_group_stream* st, const void* pcm, int32_t law, int32_t tick, const tfp_search_params* P,
+                      tfp_result* out) {
   if (!st || !pcm || tick <= 0 || (P && !out)) return TFP_E_ARG;
   tfp_group* g = st->g;
   std::lock_guard<std::recursive_mutex> lk(g->mu);
   int rc = P ? refresh_ranks(g) : TFP_OK;
   if (rc) return rc;
-  if (st->split) return split_stream_push(st, pcm, tick, P, out);
-  rc = run_all(g, [&](int s) { return tfp_stream_push(st->st[s], pcm, tick, P, P ? st->res[s].data() : nullptr); });
+  if (st->split) return split_stream_push(st, pcm, law, tick, P, out);
+  rc = run_all(g, [&](int s) {
+    tfp_result* r = P ? st->res[s].data() : nullptr;
+    return law < 0 ? tfp_stream_push(st->st[s], (const int16_t*)pcm, tick, P, r)
+                   : tfp_stream_push_g711(st->st[s], (const uint8_t*)pcm, tick, law, P, r);
+  });
   if (rc || !P) return rc;
   combine(g, st->res, st->nch, out);
   return TFP_OK;
+}
+}  // namespace
+
+int tfp_group_stream_push(tfp_group_stream* st, const int16_t* pcm, int32_t tick, const tfp_search_params* P,
+                          tfp_result* out) {
+  return group_stream_push(st, pcm, -1, tick, P, out);
+}
+
+int tfp_group_stream_push_g711(tfp_group_stream* st, const uint8_t* codes, int32_t tick, int32_t law,
+                               const tfp_search_params* P, tfp_result* out) {
+  if (!st) return TFP_E_ARG;
+  if (!tfp::g711_law_ok(law)) return gfail(st->g, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  return group_stream_push(st, codes, law, tick, P, out);
 }
 
 }  // extern "C"

@@ -82,8 +82,19 @@ __attribute__((visibility("hidden"))) int tfp_internal_search_gather(tfp_engine*
 // full after it fingerprinted into d_db (this engine's device; window i at frames [i F, (i+1) F),
 // at most cap_frames) and their channels into act[*nact]. Returns after the values are written:
 // a device group copies them to its other shards (tfp_group_stream_push, split channels).
-__attribute__((visibility("hidden"))) int tfp_internal_stream_fp(tfp_stream* st, const int16_t* pcm, int32_t T,
+// law < 0: pcm is int16[nch][T]; TFP_G711_ULAW / TFP_G711_ALAW: uint8 codes[nch][T] of that law.
+__attribute__((visibility("hidden"))) int tfp_internal_stream_fp(tfp_stream* st, const void* pcm, int32_t law, int32_t T,
                                                                  const tfp_search_params* P, double* d_db,
                                                                  int64_t cap_frames, int32_t* act, int32_t* nact,
                                                                  int64_t* frames_per_window);
+// tfp_search_g711_batch without the public name: a device group's per-shard search over codes.
+__attribute__((visibility("hidden"))) int tfp_internal_search_g711(tfp_engine* e, const uint8_t* codes,
+                                                                   const int64_t* offsets, int32_t nq, int32_t law,
+                                                                   int32_t sr, const tfp_search_params* P,
+                                                                   tfp_result* out);
+// G.711 codes on the engine's device into int16 there (g711_expand_kernel on `stream`), counted in
+// tfp_g711_stats: a query-sharded group batch expands each shard's share of the codes.
+__attribute__((visibility("hidden"))) int tfp_internal_g711_expand_device(tfp_engine* e, const uint8_t* d_codes,
+                                                                          int64_t n, int32_t law, int16_t* d_pcm,
+                                                                          void* stream);
 }

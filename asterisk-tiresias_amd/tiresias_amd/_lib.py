@@ -44,6 +44,8 @@ class Result(C.Structure):
 TFP_RANK_MAX = 32
 TFP_SCOPE_ANY = -1  # a scoped query over every clip
 TFP_SLIDE_RUN = 32  # sliding search: consecutive windows one GPU block scores in turn
+TFP_G711_ULAW = 0   # G.711 laws of the code entry points
+TFP_G711_ALAW = 1
 
 
 class Candidate(C.Structure):
@@ -88,6 +90,20 @@ _SIGS = {
     "tfp_wav_read": (C.c_int, [C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "tfp_wav_decode_f32": (C.c_int, [P, C.c_int64, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "tfp_wav_read_f32": (C.c_int, [C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "tfp_g711_decode": (C.c_int, [P, C.c_int64, C.c_int32, P]),
+    "tfp_wav_decode_g711": (C.c_int, [P, C.c_int64, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32)]),
+    "tfp_wav_read_g711": (C.c_int, [C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32)]),
+    "tfp_fingerprint_g711_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                             C.POINTER(C.c_int64)]),
+    "tfp_search_g711_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_stream_push_g711": (C.c_int, [P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_g711_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
+    "tfp_group_fingerprint_g711_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                   C.POINTER(C.c_int64)]),
+    "tfp_group_search_g711_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_group_stream_push_g711": (C.c_int, [P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_fingerprint_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
     "tfp_search_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_fingerprint_pcm": (C.c_int, [P, P, C.c_int64, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),

@@ -61,6 +61,38 @@ def read_wav_f32(path: str) -> tuple[np.ndarray, int]:
     return _wav(lambda x, cap, n, sr: lib().tfp_wav_read_f32(p, x, cap, n, sr), np.float32)
 
 
+ULAW, ALAW = 0, 1  # TFP_G711_ULAW, TFP_G711_ALAW
+
+
+def decode_g711(codes, law: int) -> np.ndarray:
+    """tfp_g711_decode: G.711 codes -> the int16 aubio_source reads them as (table[code]; exact)."""
+    codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
+    pcm = np.empty(len(codes), np.int16)
+    check(lib().tfp_g711_decode(codes.ctypes.data, len(codes), int(law), pcm.ctypes.data))
+    return pcm
+
+
+def _wav_g711(call) -> tuple[np.ndarray, int, int]:
+    n, sr, law = C.c_int64(), C.c_int32(), C.c_int32()
+    check(call(None, 0, C.byref(n), C.byref(sr), C.byref(law)))
+    codes = np.empty(n.value, np.uint8)
+    check(call(codes.ctypes.data, n.value, C.byref(n), C.byref(sr), C.byref(law)))
+    return codes, sr.value, law.value
+
+
+def decode_wav_g711(data: bytes) -> tuple[np.ndarray, int, int]:
+    """tfp_wav_decode_g711: RIFF/WAVE bytes of a mono mu-law / A-law file -> (codes, native rate, law).
+    TfpError(TFP_E_FORMAT) for every other file."""
+    buf = C.create_string_buffer(bytes(data), len(data))
+    return _wav_g711(lambda c, cap, n, sr, law: lib().tfp_wav_decode_g711(buf, len(data), c, cap, n, sr, law))
+
+
+def read_wav_g711(path: str) -> tuple[np.ndarray, int, int]:
+    """tfp_wav_read_g711: decode_wav_g711 of a file."""
+    p = path.encode()
+    return _wav_g711(lambda c, cap, n, sr, law: lib().tfp_wav_read_g711(p, c, cap, n, sr, law))
+
+
 def synth_specs(seed: int, clips, offsets=None):
     clips = list(clips)
     offsets = [0] * len(clips) if offsets is None else list(offsets)
@@ -335,6 +367,25 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
                                                   out.ctypes.data, n, C.byref(got)))
         return out[:n]
 
+    def fingerprint_g711_batch(self, codes: np.ndarray, offsets, law: int, sample_rate: int = 8000) -> np.ndarray:
+        """tfp_fingerprint_g711_batch: fingerprint_batch over G.711 codes, expanded on the GPU; the
+        frames equal fingerprint_batch(decode_g711(codes, law)) bit for bit."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nclips = len(offsets) - 1
+        n = sum(frame_count(int(offsets[i + 1] - offsets[i])) for i in range(nclips))
+        out = np.zeros(max(n, 1), FRAME_DTYPE)
+        got = C.c_int64()
+        self._chk(lib().tfp_fingerprint_g711_batch(self._h, codes.ctypes.data, offsets.ctypes.data, nclips, int(law),
+                                                   sample_rate, out.ctypes.data, n, C.byref(got)))
+        return out[:n]
+
+    def g711_stats(self) -> dict:
+        """tfp_g711_stats: batch expansion launches, code stream ticks and the codes they took."""
+        v = [C.c_int64() for _ in range(3)]
+        self._chk(lib().tfp_g711_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("expand_launches", "stream_launches", "codes"), (x.value for x in v)))
+
     def fingerprint_stats(self) -> dict:
         """tfp_fingerprint_stats: fingerprint kernel launches so far, by kernel."""
         v = [C.c_int64() for _ in range(4)]
@@ -449,6 +500,16 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
         res = (Result * max(1, nq))()
         self._chk(lib().tfp_search_pcm_batch(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, sample_rate,
                                              C.byref(p), res))
+        return self._results(res, nq)
+
+    def search_g711_batch(self, codes: np.ndarray, offsets, law: int, p: SearchParams, sample_rate: int = 8000):
+        """tfp_search_g711_batch: search_pcm_batch over G.711 codes, expanded on the GPU."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq = len(offsets) - 1
+        res = (Result * max(1, nq))()
+        self._chk(lib().tfp_search_g711_batch(self._h, codes.ctypes.data, offsets.ctypes.data, nq, int(law), sample_rate,
+                                              C.byref(p), res))
         return self._results(res, nq)
 
     def search_f32_batch(self, x: np.ndarray, offsets, p: SearchParams, sample_rate: int = 8000):
@@ -694,6 +755,18 @@ class Stream:
         return [None if not r.found else {"audio_uuid": r.uuid.decode(), "match_count": r.match_count,
                                           "frame_count": r.frame_count} for r in self._res]
 
+    def push_g711(self, codes: np.ndarray, law: int, p: SearchParams = None):
+        """codes uint8[nchannels, tick] of one law -> as push (the scatter into the ring expands them)."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        assert codes.shape[0] == self.nchannels
+        self._eng._chk(lib().tfp_stream_push_g711(self._h, codes.ctypes.data, codes.shape[1], int(law),
+                                                  C.byref(p) if p is not None else None,
+                                                  self._res if p is not None else None))
+        if p is None:
+            return None
+        return [None if not r.found else {"audio_uuid": r.uuid.decode(), "match_count": r.match_count,
+                                          "frame_count": r.frame_count} for r in self._res]
+
     def window_frames(self, channel: int) -> np.ndarray:
         """tfp_stream_window_frames: the frames of the channel's current window (0 frames until it is full)."""
         n = frame_count(self.window_samples)
@@ -808,6 +881,17 @@ class Group(_ScopedCalls, _SlidingCalls, _CensusCalls):
                                                     out.ctypes.data, n, C.byref(got)))
         return out[:n]
 
+    def fingerprint_g711_batch(self, codes, offsets, law: int, sample_rate: int = 8000) -> np.ndarray:
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nclips = len(offsets) - 1
+        n = sum(frame_count(int(offsets[i + 1] - offsets[i])) for i in range(nclips))
+        out = np.zeros(max(n, 1), FRAME_DTYPE)
+        got = C.c_int64()
+        self._chk(lib().tfp_group_fingerprint_g711_batch(self._h, codes.ctypes.data, offsets.ctypes.data, nclips, int(law),
+                                                         sample_rate, out.ctypes.data, n, C.byref(got)))
+        return out[:n]
+
     def index_add(self, uuid: str, m1, m2):
         m1 = np.ascontiguousarray(m1, np.int32)
         m2 = np.ascontiguousarray(m2, np.int32)
@@ -861,6 +945,15 @@ class Group(_ScopedCalls, _SlidingCalls, _CensusCalls):
         res = (Result * max(1, nq))()
         self._chk(lib().tfp_group_search_pcm_batch(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, sample_rate,
                                                    C.byref(p), res))
+        return Engine._results(res, nq)
+
+    def search_g711_batch(self, codes, offsets, law: int, p: SearchParams, sample_rate: int = 8000):
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq = len(offsets) - 1
+        res = (Result * max(1, nq))()
+        self._chk(lib().tfp_group_search_g711_batch(self._h, codes.ctypes.data, offsets.ctypes.data, nq, int(law),
+                                                    sample_rate, C.byref(p), res))
         return Engine._results(res, nq)
 
     def search_f32_batch(self, x, offsets, p: SearchParams, sample_rate: int = 8000):
@@ -934,6 +1027,17 @@ class GroupStream:
         self._g._chk(lib().tfp_group_stream_push(self._h, pcm.ctypes.data, pcm.shape[1],
                                                  C.byref(p) if p is not None else None,
                                                  self._res if p is not None else None))
+        if p is None:
+            return None
+        return [None if not r.found else {"audio_uuid": r.uuid.decode(), "match_count": r.match_count,
+                                          "frame_count": r.frame_count} for r in self._res]
+
+    def push_g711(self, codes: np.ndarray, law: int, p: SearchParams = None):
+        codes = np.ascontiguousarray(codes, np.uint8)
+        assert codes.shape[0] == self.nchannels
+        self._g._chk(lib().tfp_group_stream_push_g711(self._h, codes.ctypes.data, codes.shape[1], int(law),
+                                                      C.byref(p) if p is not None else None,
+                                                      self._res if p is not None else None))
         if p is None:
             return None
         return [None if not r.found else {"audio_uuid": r.uuid.decode(), "match_count": r.match_count,

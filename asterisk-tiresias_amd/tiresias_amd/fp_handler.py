@@ -27,7 +27,8 @@ import numpy as np
 
 from . import dbio
 from ._lib import TFP_RANK_MAX, TfpError
-from .engine import Engine, frame_count as frame_count_of, params, read_wav, read_wav_f32
+from .engine import (ALAW, ULAW, Engine, decode_g711, frame_count as frame_count_of, params, read_wav, read_wav_f32,
+                     read_wav_g711)
 
 TFP_E_FORMAT = -8
 
@@ -42,16 +43,43 @@ def read_wav_mono16(filename: str):
     return read_wav(filename)
 
 
-def read_audio(filename: str):
-    """aubio_source's mono hop values of a WAV file: int16 PCM (tfp_wav_read) when they are int16
-    steps (8/16-bit mono), else the fp32 values (tfp_wav_read_f32: multichannel mean, 24/32-bit,
-    float). Raises TfpError (TFP_E_NOENT, TFP_E_FORMAT for non-WAV / unsupported encodings)."""
+# Headerless Asterisk sound files, told by their extension: G.711 codes, mono at 8 kHz (new
+# behaviour: aubio cannot open these, so the reference skips them).
+RAW_G711_EXT = {".ulaw": ULAW, ".ul": ULAW, ".mu": ULAW, ".alaw": ALAW, ".al": ALAW}
+
+
+def read_audio_codes(filename: str):
+    """A file as the enrolment takes it: (samples, rate, law). law None: int16 PCM (tfp_wav_read) or,
+    failing that, fp32 hop values (tfp_wav_read_f32); law ULAW / ALAW: the uint8 codes of a G.711 WAV
+    (tfp_wav_read_g711, tried between the two) or of a headerless .ulaw / .alaw file, for the code
+    entry points. Raises TfpError (TFP_E_NOENT, TFP_E_FORMAT)."""
+    law = RAW_G711_EXT.get(os.path.splitext(filename)[1].lower())
+    if law is not None:
+        try:
+            with open(filename, "rb") as f:
+                return np.frombuffer(f.read(), np.uint8), 8000, law
+        except OSError as e:
+            raise TfpError(-4, "cannot open %s" % filename) from e
     try:
-        return read_wav(filename)
+        return read_wav(filename) + (None,)
     except TfpError as e:
         if e.code != TFP_E_FORMAT:
             raise
-    return read_wav_f32(filename)
+    try:
+        return read_wav_g711(filename)
+    except TfpError as e:
+        if e.code != TFP_E_FORMAT:
+            raise
+    return read_wav_f32(filename) + (None,)
+
+
+def read_audio(filename: str):
+    """aubio_source's mono hop values of a file: int16 PCM (tfp_wav_read) when they are int16 steps
+    (8/16-bit mono), the int16 expansion of G.711 codes (a mu-law / A-law WAV, or a headerless
+    .ulaw / .alaw file: table[code], expanded on the host), else the fp32 values (tfp_wav_read_f32:
+    multichannel mean, 24/32-bit, float). Raises TfpError (TFP_E_NOENT, TFP_E_FORMAT)."""
+    x, sr, law = read_audio_codes(filename)
+    return (x if law is None else decode_g711(x, law)), sr
 
 
 def write_wav_mono16(filename: str, pcm: np.ndarray, sample_rate: int = 8000):
@@ -201,7 +229,9 @@ class FpHandler:
             return False
         return True
 
-    def _fingerprint(self, samples: np.ndarray, offsets, sr: int):
+    def _fingerprint(self, samples: np.ndarray, offsets, sr: int, law=None):
+        if law is not None:
+            return self.engine.fingerprint_g711_batch(samples, offsets, law, sr)
         if samples.dtype == np.float32:
             return self.engine.fingerprint_f32_batch(samples, offsets, sr)
         return self.engine.fingerprint_batch(samples, offsets, sr)
@@ -212,8 +242,9 @@ class FpHandler:
         The reference scans the context's directory (alphasort, without "." and "..") and calls
         fp_craete_audio_list_info per file, skipping files that fail. Here the same catalog rows
         are written in the same order and with the same per-context MD5 dedup (also among the
-        files of this scan). The fingerprints of all new files are computed by one
-        tfp_fingerprint_batch call per sample rate and enrolled by one tfp_index_add_batch."""
+        files of this scan). The fingerprints of all new files are computed by one fingerprint
+        call per sample rate and kind (int16, fp32, or G.711 codes of one law, which go to the GPU
+        as codes) and enrolled by one tfp_index_add_batch."""
         ctx = self.fp_get_context_list_info(context) if context is not None else None
         if ctx is None or ctx["directory"] is None:
             return False
@@ -233,19 +264,20 @@ class FpHandler:
                                             (context, h)).fetchone():
                 continue  # already enrolled
             try:
-                pcm, sr = read_audio(path)
+                pcm, sr, law = read_audio_codes(path)
             except TfpError:
                 continue
             uuid = self.fp_generate_uuid()
             self.db.execute("insert into audio_list(uuid, name, context, hash) values (?, ?, ?, ?);",
                             (uuid, os.path.basename(path), context, h))
             seen.add(h)
-            new.append((uuid, pcm, sr))
-        for sr, dt in sorted({(n[2], n[1].dtype.str) for n in new}):
-            group = [n for n in new if n[2] == sr and n[1].dtype.str == dt]
+            new.append((uuid, pcm, sr, law))
+        for sr, dt, law in sorted({(n[2], n[1].dtype.str, -1 if n[3] is None else n[3]) for n in new}):
+            law = None if law < 0 else law
+            group = [n for n in new if n[2] == sr and n[1].dtype.str == dt and n[3] == law]
             lens = [len(n[1]) for n in group]
             off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-            fr = self._fingerprint(np.concatenate([n[1] for n in group]), off, sr)
+            fr = self._fingerprint(np.concatenate([n[1] for n in group]), off, sr, law)
             foff = np.concatenate([[0], np.cumsum([(n + 255) // 256 for n in lens])]).astype(np.int64)
             self.engine.index_add_batch([n[0] for n in group], foff, fr["m1"], fr["m2"])
             self.engine.index_set_scope([n[0] for n in group], [self._scope_of(context, True)] * len(group))

@@ -130,6 +130,32 @@ int tfp_wav_decode_f32(const void* bytes, int64_t nbytes, float* x, int64_t cap,
                        int32_t* sample_rate);
 int tfp_wav_read_f32(const char* path, float* x, int64_t cap, int64_t* nsamples, int32_t* sample_rate);
 
+/* ---- G.711 ingest: mu-law / A-law codes, one byte per sample (new) ----------------------- */
+/* Telephony audio is G.711: a channel's native payload, Asterisk's .ulaw / .alaw prompt files, WAVs
+ * with format tag 6 or 7. libsndfile, the backend of new_aubio_source (fp_handler.c:604), hands
+ * aubio_source_do (fp_handler.c:633) exactly table[code] / 32768 for such a file, table being the
+ * 16-bit expansion libsndfile, Asterisk and Python's audioop share. That is the value the int16
+ * paths compute from the int16 table[code], so a fingerprint from codes equals the fingerprint of
+ * the expanded int16 bit for bit, for all 256 codes of both laws: exact, no tolerance. The code
+ * forms below move one byte per sample to the GPU and expand there, in front of the unchanged
+ * fingerprint kernels. Any law other than these two is TFP_E_ARG everywhere. */
+enum { TFP_G711_ULAW = 0, TFP_G711_ALAW = 1 };
+/* codes[n] -> pcm[n], the expansion aubio_source reads (fp_handler.c:604, :633): mu-law range
+ * +-32124 (0x7F and 0xFF both 0), A-law +-32256. n = 0 is TFP_OK; a NULL pointer with n > 0 or a
+ * bad law is TFP_E_ARG. Host-only. The search forms without a code twin (ranked, scoped, census,
+ * sliding, aligned, occurrences) take the output of this call through their pcm form. */
+int tfp_g711_decode(const uint8_t* codes, int64_t n, int32_t law, int16_t* pcm);
+/* RIFF/WAVE -> the codes as stored, for the files new_aubio_source opens through libsndfile
+ * (fp_handler.c:604, :633): mono, 8-bit, format tag 6 (A-law) or 7 (mu-law), or EXTENSIBLE with
+ * that sub-format; *law receives TFP_G711_ALAW / TFP_G711_ULAW. Everything else (PCM, float, more
+ * than one channel, bits != 8, a block align that is not 1) is TFP_E_FORMAT with a reason. The
+ * size query (codes == NULL, cap 0), TFP_E_CAPACITY, unpatched data sizes and truncated files as
+ * tfp_wav_decode. tfp_wav_decode and tfp_wav_decode_f32 keep refusing tags 6 and 7. Host-only. */
+int tfp_wav_decode_g711(const void* bytes, int64_t nbytes, uint8_t* codes, int64_t cap, int64_t* nsamples,
+                        int32_t* sample_rate, int32_t* law);
+int tfp_wav_read_g711(const char* path, uint8_t* codes, int64_t cap, int64_t* nsamples, int32_t* sample_rate,
+                      int32_t* law);
+
 /* ---- fingerprinting: create_audio_fingerprints (fp_handler.c:577-671) -------------- */
 /* One clip of mono int16 PCM at its native rate (DEF_AUBIO_SAMPLERATE 0, :37). */
 int tfp_fingerprint_pcm(tfp_engine* eng, const int16_t* pcm, int64_t nsamples, int32_t sample_rate,
@@ -143,6 +169,18 @@ int tfp_fingerprint_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* of
  * the frames equal tfp_fingerprint_batch's on s. */
 int tfp_fingerprint_f32_batch(tfp_engine* eng, const float* x, const int64_t* offsets, int32_t nclips,
                               int32_t sample_rate, tfp_frame* out, int64_t cap, int64_t* nframes);
+/* The same over G.711 codes (aubio_source on a mu-law / A-law file, fp_handler.c:604, :633):
+ * offsets[nclips+1] index into codes, the outputs are tfp_fingerprint_batch's. The frames equal
+ * tfp_fingerprint_batch on tfp_g711_decode(codes) bit for bit. The codes are copied to the GPU (1 B
+ * per sample), expanded there by one launch, and fingerprinted by the launch an int16 batch of the
+ * same lengths takes (tfp_fingerprint_stats counts it alike). */
+int tfp_fingerprint_g711_batch(tfp_engine* eng, const uint8_t* codes, const int64_t* offsets, int32_t nclips,
+                               int32_t law, int32_t sample_rate, tfp_frame* out, int64_t cap, int64_t* nframes);
+/* G.711 expansion on the GPU so far (aubio_source's table[code], fp_handler.c:604, :633): launches of
+ * the batch expansion (fingerprint and search calls over codes; a group's query-sharded batches),
+ * stream ticks whose scatter expanded codes, and the codes they took. Counted where the kernels are
+ * issued. Any pointer may be NULL. */
+int tfp_g711_stats(tfp_engine* eng, int64_t* expand_launches, int64_t* stream_launches, int64_t* codes);
 
 /* Device-resident batches (inputs already in HBM; used by the benchmark and by callers that
  * keep PCM on the GPU). A plan uploads the clip layout once. d_micro receives 2 int32 per
@@ -252,6 +290,12 @@ int tfp_search_pcm_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* off
 /* The same over fp32 hop values (tfp_wav_decode_f32). */
 int tfp_search_f32_batch(tfp_engine* eng, const float* x, const int64_t* offsets, int32_t nqueries,
                          int32_t sample_rate, const tfp_search_params* params, tfp_result* out);
+/* The same over G.711 codes (fp_handler.c:604, :633 on a mu-law / A-law recording, then :275 +
+ * :287-374): the results equal tfp_search_pcm_batch on tfp_g711_decode(codes). Not coalesced: the
+ * coalescer gathers its callers' int16 buffers by pointer, and joining several callers' code arrays
+ * would cost a host copy each, so a call runs serialised per engine like every other call. */
+int tfp_search_g711_batch(tfp_engine* eng, const uint8_t* codes, const int64_t* offsets, int32_t nqueries,
+                          int32_t law, int32_t sample_rate, const tfp_search_params* params, tfp_result* out);
 /* Queries in separate buffers (new in round 4): query i is the nsamples[i] int16 samples at pcms[i].
  * The results equal tfp_search_pcm_batch's over the same queries laid end to end. Samples inside
  * tfp_host_alloc buffers are read in place wherever they lie (one per channel recording, say).
@@ -650,6 +694,12 @@ int tfp_stream_reset(tfp_stream* st, int32_t channel);
  * ingest. out[nchannels] receives each channel's result when params != NULL. */
 int tfp_stream_push(tfp_stream* st, const int16_t* pcm, int32_t tick_samples, const tfp_search_params* params,
                     tfp_result* out);
+/* The same tick as G.711 codes[nchannels][tick_samples] (a channel's native payload; aubio_source's
+ * table[code], fp_handler.c:604, :633): the codes are expanded on their way into the ring by the
+ * launch that scatters them, so a tick has the launches of an int16 tick and half its bytes. The
+ * ring is int16 either way: int16, mu-law and A-law ticks may follow one another in any order. */
+int tfp_stream_push_g711(tfp_stream* st, const uint8_t* codes, int32_t tick_samples, int32_t law,
+                         const tfp_search_params* params, tfp_result* out);
 /* The frames of `channel`'s most recent window_samples, as tfp_fingerprint_pcm returns them for a
  * recording of exactly those samples (exact q values), fingerprinted where they lie in the stream's
  * ring by the launch a tick uses. *nframes = 0 (nothing written) while the channel's history is not
@@ -784,6 +834,17 @@ void tfp_group_stream_destroy(tfp_group_stream* st);
 int tfp_group_stream_reset(tfp_group_stream* st, int32_t channel);
 int tfp_group_stream_push(tfp_group_stream* st, const int16_t* pcm, int32_t tick_samples,
                           const tfp_search_params* params, tfp_result* out);
+/* G.711 codes on a group (aubio_source's table[code], fp_handler.c:604, :633; as the engine calls):
+ * a fingerprint batch's clips are expanded by the shard that fingerprints them; a search batch is
+ * expanded by every shard, or, where an int16 batch would be query-sharded, each shard expands and
+ * fingerprints its share and the frame values are exchanged as for int16; a stream tick's codes go
+ * to the shards as bytes and each shard's scatter expands them. Not coalesced. */
+int tfp_group_fingerprint_g711_batch(tfp_group* g, const uint8_t* codes, const int64_t* offsets, int32_t nclips,
+                                     int32_t law, int32_t sample_rate, tfp_frame* out, int64_t cap, int64_t* nframes);
+int tfp_group_search_g711_batch(tfp_group* g, const uint8_t* codes, const int64_t* offsets, int32_t nqueries,
+                                int32_t law, int32_t sample_rate, const tfp_search_params* params, tfp_result* out);
+int tfp_group_stream_push_g711(tfp_group_stream* st, const uint8_t* codes, int32_t tick_samples, int32_t law,
+                               const tfp_search_params* params, tfp_result* out);
 
 /* ---- deterministic synthetic PCM (benchmark / test data; identical host and device) -- */
 /* One spec per clip: samples s of clip = synth(seed, clip, offset + s). */

@@ -16,6 +16,7 @@
  * Every tfp_group_* call is serialised per group, so the channel threads need no lock here. */
 #include "asterisk.h"
 
+#include <ctype.h>
 #include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -319,23 +320,92 @@ static void pcm_pool_drain(void)
 	pthread_mutex_unlock(&g_pool_lock);
 }
 
-/* aubio_source (fp_handler.c:37,604,633): a WAV's mono hop values at its own rate — int16 PCM for
- * 8/16-bit mono (every Asterisk recording; in a pooled pcm_get buffer of *cap samples), else
- * (TFP_E_FORMAT) the fp32 values (multichannel mean, 24/32-bit, float). Exactly one of *pcm / *x
- * is set; release with pcm_put(*pcm, *cap) and ast_free(*x). */
+/* New behaviour (aubio cannot open these, so the reference skips them): a headerless Asterisk
+ * sound file is told by its extension, G.711 codes, mono at 8 kHz: .ulaw / .ul / .mu are mu-law,
+ * .alaw / .al are A-law. The law, or -1 for every other name. */
+static int raw_g711_law(const char* filename)
+{
+	static const struct { const char* ext; int law; } known[] = {
+		{"ulaw", TFP_G711_ULAW}, {"ul", TFP_G711_ULAW}, {"mu", TFP_G711_ULAW}, {"alaw", TFP_G711_ALAW}, {"al", TFP_G711_ALAW}};
+	const char* dot = filename ? strrchr(filename, '.') : NULL;
+	size_t k, i;
+
+	if(dot == NULL || strchr(dot, '/') != NULL) {
+		return -1;
+	}
+	for(k = 0; k < sizeof(known) / sizeof(known[0]); k++) {
+		for(i = 0; known[k].ext[i] != '\0' && tolower((unsigned char)dot[1 + i]) == known[k].ext[i]; i++) {
+		}
+		if(known[k].ext[i] == '\0' && dot[1 + i] == '\0') {
+			return known[k].law;
+		}
+	}
+	return -1;
+}
+
+/* The G.711 codes of a file as stored, with tfp_wav_read_g711's conventions (codes == NULL: the
+ * size query): a headerless file by its extension (raw_g711_law), else a mu-law / A-law WAV. */
+static int read_g711(const char* filename, uint8_t* codes, int64_t cap, int64_t* ns, int32_t* sr, int32_t* law)
+{
+	const int raw = raw_g711_law(filename);
+	FILE* fp;
+	long size;
+	size_t got;
+
+	if(raw < 0) {
+		return tfp_wav_read_g711(filename, codes, cap, ns, sr, law);
+	}
+	fp = fopen(filename, "rb");
+	if(fp == NULL) {
+		return TFP_E_NOENT;
+	}
+	if(fseek(fp, 0, SEEK_END) != 0 || (size = ftell(fp)) < 0) {
+		fclose(fp);
+		return TFP_E_NOENT;
+	}
+	*ns = size;
+	*sr = 8000;
+	*law = raw;
+	if(codes == NULL || cap < size) {
+		fclose(fp);
+		return codes == NULL ? TFP_OK : TFP_E_CAPACITY;
+	}
+	rewind(fp);
+	got = fread(codes, 1, (size_t)size, fp);
+	fclose(fp);
+	return got == (size_t)size ? TFP_OK : TFP_E_NOENT;
+}
+
+/* aubio_source (fp_handler.c:37,604,633): a file's mono hop values at its own rate — int16 PCM for
+ * 8/16-bit mono (every Asterisk recording; in a pooled pcm_get buffer of *cap samples), then the
+ * int16 expansion of G.711 codes (a mu-law / A-law WAV, or a headerless file; tfp_g711_decode on
+ * the host: file searches are not hot), else (TFP_E_FORMAT) the fp32 values (multichannel mean,
+ * 24/32-bit, float). Exactly one of *pcm / *x is set; release with pcm_put(*pcm, *cap) and
+ * ast_free(*x). */
 static int read_audio(const char* filename, int16_t** pcm, int64_t* cap, float** x, int64_t* ns, int32_t* sr)
 {
+	const bool raw = raw_g711_law(filename) >= 0;
+	int32_t law = -1;
 	int rc;
 
 	*pcm = NULL;
 	*cap = 0;
 	*x = NULL;
-	rc = tfp_wav_read(filename, NULL, 0, ns, sr);
+	rc = raw ? TFP_E_FORMAT : tfp_wav_read(filename, NULL, 0, ns, sr);
 	if(rc == TFP_OK) {
 		*pcm = pcm_get(*ns ? *ns : 1, cap);
 		rc = *pcm ? tfp_wav_read(filename, *pcm, *cap, ns, sr) : TFP_E_NOMEM;
 	}
-	else if(rc == TFP_E_FORMAT && (rc = tfp_wav_read_f32(filename, NULL, 0, ns, sr)) == TFP_OK) {
+	else if(rc == TFP_E_FORMAT && (rc = read_g711(filename, NULL, 0, ns, sr, &law)) == TFP_OK) {
+		uint8_t* codes = ast_malloc(*ns ? (size_t)*ns : 1);
+		*pcm = pcm_get(*ns ? *ns : 1, cap);
+		rc = (codes && *pcm) ? read_g711(filename, codes, *ns, ns, sr, &law) : TFP_E_NOMEM;
+		if(rc == TFP_OK) {
+			rc = tfp_g711_decode(codes, *ns, law, *pcm);
+		}
+		ast_free(codes);
+	}
+	else if(!raw && rc == TFP_E_FORMAT && (rc = tfp_wav_read_f32(filename, NULL, 0, ns, sr)) == TFP_OK) {
 		*x = ast_malloc(sizeof(float) * (*ns ? *ns : 1));
 		rc = *x ? tfp_wav_read_f32(filename, *x, *ns, ns, sr) : TFP_E_NOMEM;
 	}
@@ -460,20 +530,24 @@ bool fp_craete_audio_list_info(const char* context, const char* filename)
  * alphasort). fp_create_audio_list_infos takes the whole list: the catalog rows are written in
  * the same order with the same per-context MD5 dedup (a file repeated within the list counts as
  * already enrolled), and the audio of all new files is fingerprinted by one tfp_group_fingerprint_batch
- * (per sample rate and sample format, and per ENROL_BATCH_SAMPLES) and indexed by one
- * tfp_group_index_add_batch, instead of a GPU round trip per file. */
-#define ENROL_GROUPS 4
+ * (per sample rate and sample kind, and per ENROL_BATCH_SAMPLES) and indexed by one
+ * tfp_group_index_add_batch, instead of a GPU round trip per file. The kinds: int16 PCM, fp32 hop
+ * values, and G.711 codes of one law (a directory of .ulaw prompts is one
+ * tfp_group_fingerprint_g711_batch per flush: the codes go to the GPU as they are). */
+enum { ENROL_I16 = 0, ENROL_F32 = 1, ENROL_G711 = 2 };
+#define ENROL_GROUPS 6
 #define ENROL_BATCH_SAMPLES ((int64_t)1 << 27) /* 256 MB of int16 per batch */
 
 typedef struct {
 	int32_t sr;
-	bool f32;
+	int kind;          /* ENROL_* */
+	int32_t law;       /* ENROL_G711: TFP_G711_ULAW / TFP_G711_ALAW */
 	int n, cap;
 	int* file;         /* index into the caller's list */
 	char** uuid;
 	int64_t* off;      /* [n + 1] sample offsets */
 	int64_t scap;      /* samples allocated */
-	void* x;           /* int16 PCM or fp32 hop values */
+	void* x;           /* int16 PCM, fp32 hop values or uint8 G.711 codes */
 } enrol_group;
 
 static void group_reset(enrol_group* g)
@@ -522,8 +596,9 @@ static int group_flush(const char* context, enrol_group* g, bool* ok)
 	uu = ast_malloc(sizeof(char*) * g->n);
 	rc = TFP_E_NOMEM;
 	if(rows && m1 && m2 && foff && uu) {
-		rc = g->f32 ? tfp_group_fingerprint_f32_batch(g_tfp, (const float*)g->x, g->off, g->n, g->sr, rows, nf, &got)
-		            : tfp_group_fingerprint_batch(g_tfp, (const int16_t*)g->x, g->off, g->n, g->sr, rows, nf, &got);
+		rc = g->kind == ENROL_F32 ? tfp_group_fingerprint_f32_batch(g_tfp, (const float*)g->x, g->off, g->n, g->sr, rows, nf, &got)
+		   : g->kind == ENROL_G711 ? tfp_group_fingerprint_g711_batch(g_tfp, (const uint8_t*)g->x, g->off, g->n, g->law, g->sr, rows, nf, &got)
+		   : tfp_group_fingerprint_batch(g_tfp, (const int16_t*)g->x, g->off, g->n, g->sr, rows, nf, &got);
 	}
 	if(rc != TFP_OK) {
 		ast_log(LOG_ERROR, "Could not fingerprint %d files: %s\n", g->n, tfp_group_last_error(g_tfp));
@@ -589,10 +664,10 @@ static int group_flush(const char* context, enrol_group* g, bool* ok)
 /* appends file f's audio (ns samples at rate sr) to g; false on allocation or read errors */
 static bool group_add(enrol_group* g, int f, const char* filename, char* uuid, int64_t ns)
 {
-	const size_t ss = g->f32 ? sizeof(float) : sizeof(int16_t);
+	const size_t ss = g->kind == ENROL_F32 ? sizeof(float) : g->kind == ENROL_G711 ? sizeof(uint8_t) : sizeof(int16_t);
 	const int64_t at = g->off[g->n];
 	int64_t got = 0;
-	int32_t sr = 0;
+	int32_t sr = 0, law = g->law;
 	int rc;
 	if(g->n + 1 >= g->cap) {
 		int nc = g->cap ? 2 * g->cap : 64;
@@ -620,9 +695,10 @@ static bool group_add(enrol_group* g, int f, const char* filename, char* uuid, i
 		g->x = nx;
 		g->scap = nc;
 	}
-	rc = g->f32 ? tfp_wav_read_f32(filename, (float*)g->x + at, ns, &got, &sr)
-	            : tfp_wav_read(filename, (int16_t*)g->x + at, ns, &got, &sr);
-	if(rc != TFP_OK || got != ns || sr != g->sr) {
+	rc = g->kind == ENROL_F32 ? tfp_wav_read_f32(filename, (float*)g->x + at, ns, &got, &sr)
+	   : g->kind == ENROL_G711 ? read_g711(filename, (uint8_t*)g->x + at, ns, &got, &sr, &law)
+	   : tfp_wav_read(filename, (int16_t*)g->x + at, ns, &got, &sr);
+	if(rc != TFP_OK || got != ns || sr != g->sr || law != g->law) {
 		return false;
 	}
 	g->file[g->n] = f;
@@ -664,8 +740,8 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
 		char* uuid;
 		int ret;
 		int64_t ns = 0;
-		int32_t sr = 0;
-		bool f32 = false;
+		int32_t sr = 0, law = -1;
+		int kind = ENROL_I16;
 		enrol_group* g = NULL;
 
 		char existing[64] = "";
@@ -700,10 +776,17 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
 		if(made[i] != NULL) {
 			memcpy(made[i], uuid, strlen(uuid) + 1);
 		}
-		/* aubio_source at the native rate: int16 PCM, else the fp32 hop values (read_audio) */
-		if(tfp_wav_read(f, NULL, 0, &ns, &sr) != TFP_OK) {
-			f32 = true;
-			if(tfp_wav_read_f32(f, NULL, 0, &ns, &sr) != TFP_OK) {
+		/* aubio_source at the native rate: int16 PCM, then G.711 codes, else the fp32 hop values
+		 * (read_audio's order; a headerless G.711 file is nothing else) */
+		if(raw_g711_law(f) >= 0 || tfp_wav_read(f, NULL, 0, &ns, &sr) != TFP_OK) {
+			if(read_g711(f, NULL, 0, &ns, &sr, &law) == TFP_OK) {
+				kind = ENROL_G711;
+			}
+			else if(raw_g711_law(f) < 0 && tfp_wav_read_f32(f, NULL, 0, &ns, &sr) == TFP_OK) {
+				kind = ENROL_F32;
+				law = -1;
+			}
+			else {
 				ast_log(LOG_WARNING, "Could not read %s: %s\n", f, tfp_engine_last_error(NULL));
 				ast_log(LOG_NOTICE, "Could not create audio fingerprint info.\n");
 				fpc_delete_audio_list_info(uuid);
@@ -712,7 +795,7 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
 			}
 		}
 		for(k = 0; k < ENROL_GROUPS; k++) {
-			if(groups[k].off != NULL && groups[k].sr == sr && groups[k].f32 == f32) {
+			if(groups[k].off != NULL && groups[k].sr == sr && groups[k].kind == kind && groups[k].law == law) {
 				g = &groups[k];
 				break;
 			}
@@ -729,7 +812,8 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
 			}
 			g = &groups[k];
 			g->sr = sr;
-			g->f32 = f32;
+			g->kind = kind;
+			g->law = law;
 			g->off = ast_calloc(1, sizeof(int64_t));
 			if(g->off == NULL) {
 				fpc_delete_audio_list_info(uuid);
@@ -1453,6 +1537,23 @@ bool fp_channel_push(fp_channel* ch, const int16_t* slin, int nsamples)
 		}
 	}
 	ch->n += nsamples;
+	return true;
+}
+
+bool fp_channel_push_g711(fp_channel* ch, const uint8_t* payload, int nsamples, int law)
+{
+	int16_t slin[512];
+	int at;
+
+	if(ch == NULL || nsamples < 0 || (nsamples > 0 && payload == NULL) || (law != TFP_G711_ULAW && law != TFP_G711_ALAW)) {
+		return false;
+	}
+	for(at = 0; at < nsamples; at += 512) {
+		const int n = nsamples - at < 512 ? nsamples - at : 512;
+		if(tfp_g711_decode(payload + at, n, law, slin) != TFP_OK || fp_channel_push(ch, slin, n) == false) {
+			return false;
+		}
+	}
 	return true;
 }
 

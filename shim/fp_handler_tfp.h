@@ -135,6 +135,11 @@ struct ast_json* fp_search_fingerprint_occurrences(const char* context, const ch
 typedef struct fp_channel fp_channel;
 fp_channel* fp_channel_open(int sample_rate, int max_ms);
 bool fp_channel_push(fp_channel* ch, const int16_t* slin, int nsamples);
+/* New: the same for a channel whose native format is G.711 (160 payload bytes per 20 ms frame):
+ * law is TFP_G711_ULAW or TFP_G711_ALAW. The codes are expanded into the channel's SLIN buffer
+ * (tfp_g711_decode: the int16 aubio_source reads a mu-law / A-law file as, fp_handler.c:604, :633),
+ * so the search equals fp_channel_push of the expanded samples. SLIN and G.711 pushes may mix. */
+bool fp_channel_push_g711(fp_channel* ch, const uint8_t* payload, int nsamples, int law);
 void fp_channel_reset(fp_channel* ch);
 struct ast_json* fp_channel_search(fp_channel* ch, const char* context, const int coefs, const double tolerance,
 		const int freq_ignore_low, const int freq_ignore_high);
