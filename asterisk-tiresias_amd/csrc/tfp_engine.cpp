@@ -15,6 +15,7 @@
 #include <numeric>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -28,6 +29,7 @@
 #include "tfp_index.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
+#include "tfp_live.hpp"
 #include "tfp_math.hpp"
 #include "tfp_rank.hpp"
 #include "tfp_census.hpp"
@@ -4159,6 +4161,343 @@ int tfp_stream_window_frames(tfp_stream* st, int32_t ch, tfp_frame* out, int64_t
   st->stage_pending = false;  // copy_frames_out waited for e->stream
   return TFP_OK;
 }
+
+// ---- live calls (tfp_live.hpp) -------------------------------------------------------------
+
+struct tfp_live {
+  tfp_engine* eng = nullptr;
+  int32_t nch = 0, sr = 0;
+  int64_t max_samples = 0, Fmax = 0;  // Fmax: frames of a full history
+  std::vector<int64_t> samples;       // per channel: samples since its last reset
+  std::vector<int64_t> added;         // ... and final frames its count row holds
+  DevBuf hist, q, counts, bad, dstage, part, keys, gq, gfoff;
+  int64_t count_cols = 0;             // the row width counts is laid out for (live_count_cols), 0: none yet
+  HostBuf stage_h, keys_pin;          // a push's tick + descriptors; the rows' keys and the bad flag read back
+  hipEvent_t stage_ev = nullptr;      // the upload of stage_h
+  bool stage_pending = false;
+  // what the count table was built for: any index update, the resolved tolerance, both ignore thresholds
+  bool stamp_valid = false;
+  uint64_t stamp_version = 0;
+  SearchConsts stamp_sc{};
+  int64_t n_incremental = 0, n_general = 0, n_rebuilds = 0, n_fp_frames = 0, n_added = 0;
+  ~tfp_live() {
+    if (stage_ev) (void)hipEventDestroy(stage_ev);
+  }
+};
+
+int tfp_live_create(tfp_engine* e, int32_t nch, int32_t sr, int64_t max_samples, tfp_live** out) {
+  if (!e || !out) return TFP_E_ARG;
+  *out = nullptr;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (nch <= 0 || nch > 65535) return fail(e, TFP_E_ARG, "live calls: %d channels outside [1, 65535]", nch);
+  if (!live_capacity_ok(max_samples))
+    return fail(e, TFP_E_ARG, "live calls: max_samples %lld outside [1, %lld]", (long long)max_samples,
+                (long long)kLiveMaxSamples);
+  HIPCHK(e, hipSetDevice(e->device));
+  const DspTables* T;
+  int rc = ensure_tables(e, sr, &T);
+  if (rc) return rc;
+  std::unique_ptr<tfp_live> lv(new tfp_live());
+  lv->eng = e;
+  lv->nch = nch;
+  lv->sr = sr;
+  lv->max_samples = max_samples;
+  lv->Fmax = live_frames(max_samples);
+  lv->samples.assign(nch, 0);
+  lv->added.assign(nch, 0);
+  // (neither needs clearing: a push reads only samples and frame values that a push has written)
+  if (lv->hist.reserve(sizeof(int16_t) * (size_t)nch * max_samples) != hipSuccess ||
+      lv->q.reserve(sizeof(double) * 2 * (size_t)nch * lv->Fmax) != hipSuccess ||
+      lv->bad.reserve(sizeof(int32_t)) != hipSuccess)
+    return fail(e, TFP_E_NOMEM, "live calls: %d channels of %lld samples", nch, (long long)max_samples);
+  HIPCHK(e, hipMemsetAsync(lv->bad.p, 0, sizeof(int32_t), e->stream));
+  HIPCHK(e, hipEventCreateWithFlags(&lv->stage_ev, hipEventDisableTiming));
+  *out = lv.release();
+  return TFP_OK;
+}
+
+void tfp_live_destroy(tfp_live* lv) {
+  if (!lv) return;
+  {
+    std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+    (void)hipSetDevice(lv->eng->device);
+    (void)hipStreamSynchronize(lv->eng->stream);  // the last push's kernels and copies
+  }
+  delete lv;
+}
+
+int tfp_live_reset(tfp_live* lv, int32_t ch) {
+  if (!lv || ch >= lv->nch) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  const int32_t c0 = ch < 0 ? 0 : ch, c1 = ch < 0 ? lv->nch : ch + 1;
+  if (lv->count_cols)  // a new call starts with an empty count row
+    HIPCHK(e, hipMemsetAsync(lv->counts.as<uint16_t>() + (size_t)c0 * lv->count_cols, 0,
+                             sizeof(uint16_t) * (size_t)(c1 - c0) * lv->count_cols, e->stream));
+  for (int32_t c = c0; c < c1; c++) lv->samples[c] = lv->added[c] = 0;
+  return TFP_OK;
+}
+
+int tfp_live_samples(tfp_live* lv, int32_t ch, int64_t* nsamples) {
+  if (!lv || ch < 0 || ch >= lv->nch || !nsamples) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  *nsamples = lv->samples[ch];
+  return TFP_OK;
+}
+
+int tfp_live_stats(tfp_live* lv, int64_t* incremental_pushes, int64_t* general_pushes, int64_t* rebuilds,
+                   int64_t* frames_fingerprinted, int64_t* frames_added) {
+  if (!lv) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  if (incremental_pushes) *incremental_pushes = lv->n_incremental;
+  if (general_pushes) *general_pushes = lv->n_general;
+  if (rebuilds) *rebuilds = lv->n_rebuilds;
+  if (frames_fingerprinted) *frames_fingerprinted = lv->n_fp_frames;
+  if (frames_added) *frames_added = lv->n_added;
+  return TFP_OK;
+}
+
+namespace {
+
+bool live_stamp_holds(const tfp_live* lv, const SearchConsts& sc) {
+  const SearchConsts& t = lv->stamp_sc;
+  return lv->stamp_valid && lv->stamp_version == lv->eng->index_version && t.tole == sc.tole && t.has_low == sc.has_low &&
+         t.has_high == sc.has_high && (!sc.has_low || t.thr_low == sc.thr_low) && (!sc.has_high || t.thr_high == sc.thr_high);
+}
+
+// The exact fallback: every channel's frames so far, the tail included, as one query of the scoped
+// search core (which merges a live index delta where its form needs that). Caller holds e->mu and
+// waits for the stream.
+int live_general(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K,
+                 std::vector<unsigned long long>& keys) {
+  tfp_engine* e = lv->eng;
+  const int32_t nch = lv->nch;
+  std::vector<int64_t> foff(nch + 1, 0);
+  int64_t max_n = 0;
+  for (int32_t c = 0; c < nch; c++) {
+    const int64_t n = live_frames(lv->samples[c]);
+    foff[c + 1] = foff[c] + n;
+    max_n = std::max(max_n, n);
+  }
+  keys.assign((size_t)nch * K, 0ull);
+  if (!foff[nch]) return TFP_OK;
+  int rc = upload(e, lv->gfoff, foff.data(), sizeof(int64_t) * foff.size());
+  if (rc) return rc;
+  HIPCHK(e, lv->gq.reserve(sizeof(double) * 2 * (size_t)(foff[nch] + 1)));
+  HIPCHK(e, launch_live_gather(lv->q.as<double>(), lv->Fmax, lv->gfoff.as<int64_t>(), nch, max_n, lv->gq.as<double>(),
+                               e->stream));
+  return rank_core(e, foff.data(), nch, lv->gq.as<double>(), P, K, scopes, keys, e->stream);
+}
+
+}  // namespace
+
+int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* nsamples, const tfp_search_params* P,
+                  const int32_t* scopes, int32_t K, tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
+  if (!lv) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  const int32_t nch = lv->nch;
+  if (!pcm || T <= 0) return fail(e, TFP_E_ARG, "live push: NULL samples or tick_samples %d", T);
+  if (P) {
+    if (!out || !counts) return fail(e, TFP_E_ARG, "live push: NULL output");
+    if (K < 1 || K > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "live push: k = %d outside [1, %d]", K, TFP_RANK_MAX);
+    for (int32_t c = 0; scopes && c < nch; c++)
+      if (scopes[c] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "live push: scope %d of channel %d", scopes[c], c);
+  }
+  for (int32_t c = 0; nsamples && c < nch; c++)
+    if (nsamples[c] < 0 || nsamples[c] > T)
+      return fail(e, TFP_E_ARG, "live push: nsamples[%d] = %d outside [0, %d]", c, nsamples[c], T);
+  for (int32_t c = 0; c < nch; c++)  // all or nothing: no channel has taken a sample yet
+    if (lv->samples[c] + (nsamples ? nsamples[c] : T) > lv->max_samples)
+      return fail(e, TFP_E_CAPACITY, "live push: channel %d past %lld samples", c, (long long)lv->max_samples);
+  HIPCHK(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  int rc;
+  const bool match = P && valid_params(P);  // fp_handler.c:247-250: bad params -> empty rows
+  // The index and the table's stamp first: a failure here leaves the call uningested.
+  SearchConsts sc{};
+  bool vote = false, rebuild_table = false;
+  if (match) {
+    if ((rc = rebuild(e))) return rc;
+    sc = search_consts(P);
+    if (sc.coefs == 1) {
+      if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
+      if (e->ncols > 0 && e->nrows + e->delta.rows > 0) {
+        if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s)) || (rc = ensure_scope_table(e, s))) return rc;
+        vote = true;
+        rebuild_table = !live_stamp_holds(lv, sc);
+      }
+    }
+  }
+  const int32_t C = e->ncols;
+  const int64_t Cpad = vote ? live_count_cols(C) : 0;
+  // The push's plan: per channel its descriptor; per channel with new samples one clip to
+  // fingerprint and one copy of its kept frames; per channel with newly final frames one add.
+  std::vector<LiveChan> chan(nch);
+  std::vector<int32_t> act;
+  std::vector<LivePlan> plans;
+  for (int32_t c = 0; c < nch; c++) {
+    const int32_t n = nsamples ? nsamples[c] : T;
+    chan[c].s_old = lv->samples[c];
+    chan[c].n_new = n;
+    chan[c].scope = scopes ? scopes[c] : TFP_SCOPE_ANY;
+    chan[c].tail = live_tail_frame(lv->samples[c] + n);
+    if (n > 0) {
+      act.push_back(c);
+      plans.push_back(live_plan(lv->samples[c], n));
+    }
+  }
+  const int32_t na = (int32_t)act.size();
+  const DspTables* tables = nullptr;
+  bool fx = false;
+  if ((rc = ensure_tables(e, lv->sr, &tables, &fx))) return rc;
+  int64_t nf16 = 0, max_frames = 0;
+  for (const LivePlan& p : plans) {
+    nf16 += (p.clip_frames + 15) / 16;
+    max_frames = std::max(max_frames, p.clip_frames);
+  }
+  // 4-frame wave tiles for a small batch (fingerprint_host's rule) and for a tick's worth per channel
+  const bool small = fx && (nf16 <= 256 || max_frames <= 4);
+  const int32_t tile = fp_tile_frames(e->fpcfg, fx, false, small);
+  std::vector<int64_t> sbeg(std::max(na, 1)), send(std::max(na, 1)), foff(na + 1, 0);
+  std::vector<int32_t> toff(na + 1, 0), tclip;
+  std::vector<LiveCopy> copies(std::max(na, 1));
+  for (int32_t i = 0; i < na; i++) {
+    const LivePlan& p = plans[i];
+    sbeg[i] = (int64_t)act[i] * lv->max_samples + p.clip_beg;
+    send[i] = (int64_t)act[i] * lv->max_samples + p.s_new;
+    foff[i + 1] = foff[i] + p.clip_frames;
+    toff[i + 1] = toff[i] + (int32_t)((p.clip_frames + tile - 1) / tile);
+    copies[i] = LiveCopy{foff[i] + p.drop, (int64_t)act[i] * lv->Fmax + p.f0, p.keep};
+  }
+  tclip.assign(std::max<int32_t>(toff[na], 1), 0);
+  for (int32_t i = 0; i < na; i++)
+    for (int32_t t = toff[i]; t < toff[i + 1]; t++) tclip[t] = i;
+  std::vector<LiveAdd> adds;
+  int64_t add_frames = 0;
+  if (vote)
+    for (int32_t c = 0; c < nch; c++) {
+      const int64_t from = rebuild_table ? 0 : lv->added[c], to = live_final_frames(lv->samples[c] + chan[c].n_new);
+      if (to > from) {
+        adds.push_back(LiveAdd{c, (int32_t)from, (int32_t)to, 0});
+        add_frames += to - from;
+      }
+    }
+  // One pinned buffer, one upload: the tick, then the descriptors.
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_pcm = al(sizeof(int16_t) * (size_t)nch * T), b_chan = al(sizeof(LiveChan) * nch),
+               b_sb = al(sizeof(int64_t) * sbeg.size()), b_fo = al(sizeof(int64_t) * foff.size()),
+               b_to = al(sizeof(int32_t) * toff.size()), b_tc = al(sizeof(int32_t) * tclip.size()),
+               b_cp = al(sizeof(LiveCopy) * copies.size()), b_add = al(sizeof(LiveAdd) * std::max<size_t>(adds.size(), 1));
+  const size_t o_chan = b_pcm, o_sb = o_chan + b_chan, o_se = o_sb + b_sb, o_fo = o_se + b_sb, o_to = o_fo + b_fo,
+               o_tc = o_to + b_to, o_cp = o_tc + b_tc, o_add = o_cp + b_cp, total = o_add + b_add;
+  if (lv->stage_pending) HIPCHK(e, hipEventSynchronize(lv->stage_ev));  // the last push's upload has read stage_h
+  lv->stage_pending = false;
+  HIPCHK(e, lv->stage_h.reserve(total));
+  HIPCHK(e, lv->dstage.reserve(total));
+  char* h = lv->stage_h.as<char>();
+  memcpy(h, pcm, sizeof(int16_t) * (size_t)nch * T);
+  memcpy(h + o_chan, chan.data(), sizeof(LiveChan) * nch);
+  memcpy(h + o_sb, sbeg.data(), sizeof(int64_t) * sbeg.size());
+  memcpy(h + o_se, send.data(), sizeof(int64_t) * send.size());
+  memcpy(h + o_fo, foff.data(), sizeof(int64_t) * foff.size());
+  memcpy(h + o_to, toff.data(), sizeof(int32_t) * toff.size());
+  memcpy(h + o_tc, tclip.data(), sizeof(int32_t) * tclip.size());
+  memcpy(h + o_cp, copies.data(), sizeof(LiveCopy) * copies.size());
+  if (!adds.empty()) memcpy(h + o_add, adds.data(), sizeof(LiveAdd) * adds.size());
+  const int64_t nf = foff[na];
+  HIPCHK(e, e->micro.reserve(sizeof(int32_t) * 2 * (nf + 1)));
+  HIPCHK(e, e->db.reserve(sizeof(double) * 2 * (nf + 1)));
+  if (rebuild_table) HIPCHK(e, lv->counts.reserve(sizeof(uint16_t) * (size_t)nch * Cpad));
+  const size_t nkeys = P ? (size_t)nch * K : 0;
+  if (vote) {
+    HIPCHK(e, lv->part.reserve(sizeof(unsigned long long) * (size_t)nch * rank_vote_blocks(C) * K));
+    HIPCHK(e, lv->keys.reserve(sizeof(unsigned long long) * nkeys));
+    HIPCHK(e, lv->keys_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  }
+  // From here on the call ingests.
+  HIPCHK(e, hipMemcpyAsync(lv->dstage.p, h, total, hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipEventRecord(lv->stage_ev, s));
+  lv->stage_pending = true;
+  const char* d = lv->dstage.as<char>();
+  const LiveChan* d_chan = reinterpret_cast<const LiveChan*>(d + o_chan);
+  // 1: scatter
+  HIPCHK(e, launch_live_scatter(reinterpret_cast<const int16_t*>(d), T, d_chan, nch, lv->max_samples, lv->hist.as<int16_t>(), s));
+  // 2: fingerprint only what changed (exact frame values: the kept history serves coefs = 2 as well,
+  // and a coefs = 1 key is their truncation either way), then the kept frames into the history
+  if (na) {
+    HIPCHK(e, launch_fingerprint(e->fpcfg, tables, fx, tile, lv->hist.as<int16_t>(), reinterpret_cast<const int64_t*>(d + o_sb),
+                                 reinterpret_cast<const int64_t*>(d + o_se), reinterpret_cast<const int64_t*>(d + o_fo),
+                                 reinterpret_cast<const int32_t*>(d + o_to), reinterpret_cast<const int32_t*>(d + o_tc),
+                                 toff[na], nf, e->micro.as<int32_t>(), e->db.as<double>(), s, e->logfix, &e->fpstats));
+    int64_t max_keep = 0;
+    for (const LivePlan& p : plans) max_keep = std::max(max_keep, p.keep);
+    HIPCHK(e, launch_live_store(e->db.as<double>(), reinterpret_cast<const LiveCopy*>(d + o_cp), na, max_keep,
+                                lv->q.as<double>(), s));
+  }
+  for (int32_t c = 0; c < nch; c++) lv->samples[c] += chan[c].n_new;
+  lv->n_fp_frames += nf;
+  if (!P) return TFP_OK;
+  memset(out, 0, sizeof(tfp_candidate) * nkeys);
+  for (int32_t c = 0; c < nch; c++) {
+    counts[c] = 0;
+    if (frame_counts) frame_counts[c] = (int32_t)live_frames(lv->samples[c]);
+  }
+  if (!match) return TFP_OK;
+  std::vector<unsigned long long> keys(nkeys, 0ull);
+  if (sc.coefs == 1 && !vote) {  // an empty index: no row
+    lv->n_incremental++;
+    return TFP_OK;
+  }
+  if (vote) {
+    // 3: add the newly final frames (after a stamp mismatch: all of them, into a zeroed table)
+    if (rebuild_table) {
+      HIPCHK(e, hipMemsetAsync(lv->counts.p, 0, sizeof(uint16_t) * (size_t)nch * Cpad, s));
+      HIPCHK(e, hipMemsetAsync(lv->bad.p, 0, sizeof(int32_t), s));
+      std::fill(lv->added.begin(), lv->added.end(), 0);
+      lv->count_cols = Cpad;
+      lv->stamp_valid = true;
+      lv->stamp_version = e->index_version;
+      lv->stamp_sc = sc;
+      lv->n_rebuilds++;
+    }
+    const uint32_t* d_bits = e->tc.ranges.active().key_bits.as<uint32_t>();
+    HIPCHK(e, launch_live_add(lv->q.as<double>(), lv->Fmax, reinterpret_cast<const LiveAdd*>(d + o_add), (int32_t)adds.size(),
+                              sc, d_bits, C, lv->counts.as<uint16_t>(), lv->bad.as<int32_t>(), s));
+    for (const LiveAdd& a : adds) lv->added[a.ch] = a.fend;
+    lv->n_added += add_frames;
+    // 4: select
+    HIPCHK(e, launch_live_select(lv->q.as<double>(), lv->Fmax, d_chan, nch, sc, d_bits, C, lv->counts.as<uint16_t>(),
+                                 e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
+                                 lv->part.as<unsigned long long>(), lv->keys.as<unsigned long long>(), lv->bad.as<int32_t>(), s));
+    unsigned long long* hk = lv->keys_pin.as<unsigned long long>();
+    HIPCHK(e, hipMemcpyAsync(hk, lv->keys.p, sizeof(unsigned long long) * nkeys, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(hk + nkeys, lv->bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    lv->stage_pending = false;
+    // A frame's key is trunc(10 log10|c|) of a finite DCT coefficient of int16 samples, or 0 where
+    // the value is not finite (frame_key): |key| <= 459 (kKeyOffset), so no int16 input reaches an
+    // out-of-range key. The route stays: the table then holds frames it could not add, so it is
+    // dropped, and this and every later push of such a call take the general form.
+    if (!(uint32_t)hk[nkeys]) {
+      std::copy(hk, hk + nkeys, keys.begin());
+      fill_candidates(e, keys, nch, K, out, counts);
+      lv->n_incremental++;
+      return TFP_OK;
+    }
+    lv->stamp_valid = false;
+  }
+  std::vector<int32_t> any;
+  if (!scopes) any.assign(nch, TFP_SCOPE_ANY);
+  if ((rc = live_general(lv, P, scopes ? scopes : any.data(), K, keys))) return rc;
+  HIPCHK(e, hipStreamSynchronize(s));  // (live_general returns before any wait when no channel has a frame)
+  lv->stage_pending = false;
+  fill_candidates(e, keys, nch, K, out, counts);
+  lv->n_general++;
+  return TFP_OK;
+}
+
 
 int tfp_synth_pcm(const tfp_synth_spec* specs, int32_t nclips, int64_t spc, int16_t* out) {
   if (nclips < 0 || spc < 0 || (nclips && (!specs || !out))) return TFP_E_ARG;

@@ -1382,4 +1382,105 @@ int tfp_group_stream_push_g711(tfp_group_stream* st, const uint8_t* codes, int32
   return group_stream_push(st, codes, law, tick, P, out);
 }
 
+// ---- live calls on a group (tfp_live.hpp): every shard keeps every channel ------------------------
+
+struct tfp_group_live {
+  tfp_group* g = nullptr;
+  std::vector<tfp_live*> lv;     // one per shard
+  int32_t nch = 0;
+  int64_t max_samples = 0;
+  std::vector<int64_t> samples;  // per channel, as every shard counts them (the capacity check before any shard is told)
+};
+
+int tfp_group_live_create(tfp_group* g, int32_t nch, int32_t sr, int64_t max_samples, tfp_group_live** out) {
+  if (!g || !out) return TFP_E_ARG;
+  *out = nullptr;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  tfp_group_live* gl = new tfp_group_live();
+  gl->g = g;
+  gl->nch = nch;
+  gl->max_samples = max_samples;
+  gl->lv.assign(g->eng.size(), nullptr);
+  const int rc = run_all(g, [&](int s) { return tfp_live_create(g->eng[s], nch, sr, max_samples, &gl->lv[s]); });
+  if (rc) {
+    for (auto* p : gl->lv) tfp_live_destroy(p);
+    delete gl;
+    return rc;
+  }
+  gl->samples.assign(nch, 0);
+  *out = gl;
+  return TFP_OK;
+}
+
+void tfp_group_live_destroy(tfp_group_live* gl) {
+  if (!gl) return;
+  for (auto* p : gl->lv) tfp_live_destroy(p);
+  delete gl;
+}
+
+int tfp_group_live_reset(tfp_group_live* gl, int32_t ch) {
+  if (!gl || ch >= gl->nch) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(gl->g->mu);
+  const int rc = run_all(gl->g, [&](int s) { return tfp_live_reset(gl->lv[s], ch); });
+  if (rc) return rc;
+  for (int32_t c = ch < 0 ? 0 : ch; c < (ch < 0 ? gl->nch : ch + 1); c++) gl->samples[c] = 0;
+  return TFP_OK;
+}
+
+int tfp_group_live_samples(tfp_group_live* gl, int32_t ch, int64_t* nsamples) {
+  if (!gl || ch < 0 || ch >= gl->nch || !nsamples) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(gl->g->mu);
+  *nsamples = gl->samples[ch];
+  return TFP_OK;
+}
+
+int tfp_group_live_stats(tfp_group_live* gl, int32_t shard, int64_t* incremental_pushes, int64_t* general_pushes,
+                         int64_t* rebuilds, int64_t* frames_fingerprinted, int64_t* frames_added) {
+  if (!gl || shard < 0 || (size_t)shard >= gl->lv.size()) return TFP_E_ARG;
+  return tfp_live_stats(gl->lv[shard], incremental_pushes, general_pushes, rebuilds, frames_fingerprinted, frames_added);
+}
+
+int tfp_group_live_push(tfp_group_live* gl, const int16_t* pcm, int32_t T, const int32_t* nsamples,
+                        const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                        int32_t* frame_counts) {
+  if (!gl) return TFP_E_ARG;
+  tfp_group* g = gl->g;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  const int32_t nch = gl->nch;
+  if (!pcm || T <= 0) return gfail(g, TFP_E_ARG, "live push: NULL samples or tick_samples %d", T);
+  for (int32_t c = 0; nsamples && c < nch; c++)
+    if (nsamples[c] < 0 || nsamples[c] > T)
+      return gfail(g, TFP_E_ARG, "live push: nsamples[%d] = %d outside [0, %d]", c, nsamples[c], T);
+  if (P) {
+    if (!out || !counts) return gfail(g, TFP_E_ARG, "live push: NULL output");
+    if (k < 1 || k > TFP_RANK_MAX) return gfail(g, TFP_E_ARG, "live push: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+    if (scopes)
+      if (int rc = group_scope_args(g, scopes, nch)) return rc;
+  }
+  for (int32_t c = 0; c < nch; c++)  // before any shard is told: a capacity failure leaves every shard unchanged
+    if (gl->samples[c] + (nsamples ? nsamples[c] : T) > gl->max_samples)
+      return gfail(g, TFP_E_CAPACITY, "live push: channel %d past %lld samples", c, (long long)gl->max_samples);
+  int rc;
+  if (P && valid_params(P)) {
+    // each shard's first k rows of every channel, merged as scoped search's (shard 0 reports the frame counts)
+    rc = group_rank(g, nch, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+      return tfp_live_push(gl->lv[s], pcm, T, nsamples, P, scopes, k, o, c, s == 0 ? frame_counts : nullptr);
+    });
+  } else {
+    // ingest only; with invalid params the rows come out empty (fp_handler.c:247-250)
+    std::vector<tfp_candidate> o(P ? (size_t)nch * k : 0);
+    std::vector<int32_t> cn(P ? nch : 0);
+    rc = run_all(g, [&](int s) {
+      return tfp_live_push(gl->lv[s], pcm, T, nsamples, s == 0 ? P : nullptr, scopes, k, o.data(), cn.data(), frame_counts);
+    });
+    if (!rc && P) {
+      memset(out, 0, sizeof(tfp_candidate) * (size_t)nch * k);
+      memset(counts, 0, sizeof(int32_t) * nch);
+    }
+  }
+  if (rc) return rc;
+  for (int32_t c = 0; c < nch; c++) gl->samples[c] += nsamples ? nsamples[c] : T;
+  return TFP_OK;
+}
+
 }  // extern "C"

@@ -1,0 +1,218 @@
+// tfp_live.hip — live calls (tfp_live.hpp): the kernels of a push around the existing fingerprint
+// launch. live_scatter_kernel: the tick's samples to the end of each channel's history.
+// live_store_kernel: the fingerprinted frames' values into the channels' frame histories (the
+// lead-in frame dropped). live_add_kernel: the key bitset rows of the newly final frames added to the
+// channels' count rows. live_select_kernel: scope_vote_kernel's selection (tfp_scope.hip) with the
+// score read from the count row plus the provisional tail frame's bit, instead of summed over the
+// query's keys; its partial lists go through ranked search's merge (launch_rank_merge).
+// live_gather_kernel: the frame histories laid end to end for the general form.
+//
+// The count row is what a push moves (2 bytes per column, read and written once per push however
+// many frames it adds, against 1 bit per column and frame of bitset), so a thread owns 8 columns:
+// one 16-byte load and store of counts, consecutive lanes on consecutive 16 bytes, and the 8 bits
+// from the bitset word that 4 neighbouring lanes share. The 16-bit counts are added in pairs as
+// 32-bit words: a count never exceeds the channel's final frames (<= 65535, kLiveMaxSamples), so no
+// carry crosses.
+#include <hip/hip_runtime.h>
+
+#include "tfp_live.hpp"
+
+namespace tfp {
+
+namespace {
+
+constexpr int kLiveAddCols = 8 * 256;  // columns per live_add block (8 per thread)
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long key) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned long long o = __shfl_xor(key, off, 64);
+    key = o > key ? o : key;
+  }
+  return key;
+}
+
+__device__ __forceinline__ bool in_scope(int32_t qs, int32_t cs) { return qs == kScopeAny || cs == qs; }
+
+__global__ __launch_bounds__(256) void live_scatter_kernel(const int16_t* __restrict__ tick, int32_t T,
+                                                           const LiveChan* __restrict__ chan, int32_t nch,
+                                                           int64_t max_samples, int16_t* __restrict__ hist) {
+  const int64_t n = (int64_t)nch * T;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = i / T, t = i % T;
+    const int64_t at = chan[c].s_old + t;
+    if (t < chan[c].n_new && at < max_samples) hist[c * max_samples + at] = tick[i];
+  }
+}
+
+__global__ __launch_bounds__(256) void live_store_kernel(const double* __restrict__ db, const LiveCopy* __restrict__ cp,
+                                                         double* __restrict__ q) {
+  const LiveCopy c = cp[blockIdx.y];
+  const double2* src = reinterpret_cast<const double2*>(db) + c.src;
+  double2* dst = reinterpret_cast<double2*>(q) + c.dst;
+  for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < c.n; f += (int64_t)gridDim.x * 256) dst[f] = src[f];
+}
+
+__global__ __launch_bounds__(256) void live_add_kernel(const double* __restrict__ q, int64_t Fmax,
+                                                       const LiveAdd* __restrict__ adds, SearchConsts sc,
+                                                       const uint32_t* __restrict__ bits, int32_t W, int64_t Cpad,
+                                                       uint16_t* __restrict__ counts, int32_t* __restrict__ bad) {
+  const LiveAdd a = adds[blockIdx.y];
+  const int64_t c8 = 8 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
+  if (c8 >= Cpad) return;  // (Cpad is a multiple of 128: a thread's 8 columns lie inside the row or outside it)
+  const double* qc = q + 2 * (int64_t)a.ch * Fmax;
+  uint4* row = reinterpret_cast<uint4*>(counts + (int64_t)a.ch * Cpad + c8);
+  uint4 v = *row;
+  const uint32_t* col = bits + (c8 >> 5);
+  const int sh = (int)(c8 & 31);
+  bool out_of_range = false;
+  for (int32_t f = a.fbeg; f < a.fend; f++) {  // the same frame and key in every lane
+    int32_t k = 0;
+    if (!frame_key(qc, f, sc, k)) continue;
+    const int64_t idx = (int64_t)k + kKeyOffset;
+    if (idx < 0 || idx >= kKeyRange) {
+      out_of_range = true;
+      continue;
+    }
+    const uint32_t b = col[idx * W] >> sh;  // bit j: column c8 + j
+    v.x += (b & 1u) | ((b & 2u) << 15);
+    v.y += ((b >> 2) & 1u) | ((b & 8u) << 13);
+    v.z += ((b >> 4) & 1u) | ((b & 32u) << 11);
+    v.w += ((b >> 6) & 1u) | ((b & 128u) << 9);
+  }
+  *row = v;
+  if (out_of_range && blockIdx.x == 0 && threadIdx.x == 0) *bad = 1;
+}
+
+__global__ __launch_bounds__(256) void live_select_kernel(const double* __restrict__ q, int64_t Fmax,
+                                                          const LiveChan* __restrict__ chan, SearchConsts sc,
+                                                          const uint32_t* __restrict__ bits, int32_t C, int32_t W,
+                                                          int64_t Cpad, const uint16_t* __restrict__ counts,
+                                                          const int32_t* __restrict__ tiekey,
+                                                          const int32_t* __restrict__ table, int32_t K,
+                                                          unsigned long long* __restrict__ part, int32_t* __restrict__ bad) {
+  static_assert(4 * 256 == kRankVoteCols, "4 columns per thread");
+  __shared__ unsigned long long wmax[2][4];
+  const int ch = blockIdx.y, blk = blockIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const LiveChan lc = chan[ch];
+  // this thread's columns in scope, as scope_vote_kernel reads them (one 16-byte load of the table)
+  const int c4 = 4 * (blk * 256 + threadIdx.x);
+  uint32_t in = 0;
+  if (c4 < C) {
+    const int4 s4 = *reinterpret_cast<const int4*>(table + c4);
+    in = (in_scope(lc.scope, s4.x) ? 1u : 0u) | (in_scope(lc.scope, s4.y) ? 2u : 0u) | (in_scope(lc.scope, s4.z) ? 4u : 0u) |
+         (in_scope(lc.scope, s4.w) ? 8u : 0u);
+#pragma unroll
+    for (int j = 1; j < 4; j++)
+      if (c4 + j >= C) in &= ~(1u << j);
+  }
+  // the provisional tail frame's bitset row (-1: no tail, or its SQL does not run)
+  int slot = -1;
+  if (lc.tail >= 0) {
+    int32_t k = 0;
+    if (frame_key(q + 2 * (int64_t)ch * Fmax, lc.tail, sc, k)) {
+      const int64_t idx = (int64_t)k + kKeyOffset;
+      if (idx < 0 || idx >= kKeyRange) {
+        if (threadIdx.x == 0) *bad = 1;  // (every writer stores 1)
+      } else {
+        slot = (int)idx;
+      }
+    }
+  }
+  uint32_t score[4] = {0, 0, 0, 0};
+  if (in) {  // (in != 0 implies c4 < C <= Cpad; c4 is a multiple of 4: an aligned 8-byte load of 4 counts)
+    const uint2 cv = *reinterpret_cast<const uint2*>(counts + (int64_t)ch * Cpad + c4);
+    const uint32_t tb = slot >= 0 ? bits[(int64_t)slot * W + (c4 >> 5)] >> (c4 & 31) : 0u;
+    score[0] = (cv.x & 0xffffu) + (tb & 1u);
+    score[1] = (cv.x >> 16) + ((tb >> 1) & 1u);
+    score[2] = (cv.y & 0xffffu) + ((tb >> 2) & 1u);
+    score[3] = (cv.y >> 16) + ((tb >> 3) & 1u);
+  }
+  unsigned long long mine[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    mine[j] = (((in >> j) & 1u) && score[j] > 0) ? ((unsigned long long)score[j] << 32) | (uint32_t)tiekey[c4 + j] : 0ull;
+  unsigned long long* out = part + ((int64_t)ch * gridDim.x + blk) * K;
+  unsigned long long prev = ~0ull;
+  for (int r = 0; r < K; r++) {
+    unsigned long long key = 0ull;
+#pragma unroll
+    for (int j = 0; j < 4; j++) key = (mine[j] < prev && mine[j] > key) ? mine[j] : key;
+    key = wave_max_u64(key);
+    if (lane == 0) wmax[r & 1][wv] = key;
+    __syncthreads();  // (wmax[r & 1] is next written two rounds on, after the barrier of round r + 1)
+    key = wmax[r & 1][0];
+#pragma unroll
+    for (int i = 1; i < 4; i++) key = wmax[r & 1][i] > key ? wmax[r & 1][i] : key;
+    if (threadIdx.x == 0) out[r] = key;
+    prev = key;  // (0: no key is below it, the remaining rounds give 0)
+  }
+}
+
+__global__ __launch_bounds__(256) void live_gather_kernel(const double* __restrict__ q, int64_t Fmax,
+                                                          const int64_t* __restrict__ foff, double* __restrict__ out) {
+  const int ch = blockIdx.y;
+  const int64_t f0 = foff[ch], n = foff[ch + 1] - f0;
+  const double2* src = reinterpret_cast<const double2*>(q) + (int64_t)ch * Fmax;
+  double2* dst = reinterpret_cast<double2*>(out) + f0;
+  for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < n; f += (int64_t)gridDim.x * 256) dst[f] = src[f];
+}
+
+inline unsigned copy_blocks(int64_t max_n) {
+  const int64_t g = (max_n + 255) / 256;
+  return (unsigned)(g < 1 ? 1 : (g > 64 ? 64 : g));
+}
+
+}  // namespace
+
+hipError_t launch_live_scatter(const int16_t* d_tick, int32_t T, const LiveChan* d_chan, int32_t nch, int64_t max_samples,
+                               int16_t* d_hist, hipStream_t s) {
+  const int64_t n = (int64_t)nch * T;
+  if (n <= 0) return hipSuccess;
+  const int64_t g = (n + 255) / 256;
+  hipLaunchKernelGGL(live_scatter_kernel, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, d_tick, T, d_chan, nch,
+                     max_samples, d_hist);
+  return hipGetLastError();
+}
+
+hipError_t launch_live_store(const double* d_db, const LiveCopy* d_cp, int32_t ncopy, int64_t max_n, double* d_q,
+                             hipStream_t s) {
+  if (ncopy <= 0) return hipSuccess;
+  if (ncopy > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_store_kernel, dim3(copy_blocks(max_n), ncopy), dim3(256), 0, s, d_db, d_cp, d_q);
+  return hipGetLastError();
+}
+
+hipError_t launch_live_add(const double* d_q, int64_t Fmax, const LiveAdd* d_add, int32_t nadd, SearchConsts sc,
+                           const uint32_t* d_bits, int32_t C, uint16_t* d_counts, int32_t* d_bad, hipStream_t s) {
+  if (nadd <= 0) return hipSuccess;
+  if (C <= 0 || nadd > 65535) return hipErrorInvalidValue;
+  const int64_t Cpad = live_count_cols(C);
+  hipLaunchKernelGGL(live_add_kernel, dim3((unsigned)((Cpad + kLiveAddCols - 1) / kLiveAddCols), nadd), dim3(256), 0, s, d_q,
+                     Fmax, d_add, sc, d_bits, key_bits_words(C), Cpad, d_counts, d_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_live_select(const double* d_q, int64_t Fmax, const LiveChan* d_chan, int32_t nch, SearchConsts sc,
+                              const uint32_t* d_bits, int32_t C, const uint16_t* d_counts, const int32_t* d_tiekey,
+                              const int32_t* d_table, int32_t K, unsigned long long* d_part, unsigned long long* d_keys,
+                              int32_t* d_bad, hipStream_t s) {
+  if (nch <= 0) return hipSuccess;
+  if (K < 1 || K > kRankMax || C <= 0 || nch > 65535) return hipErrorInvalidValue;
+  const int32_t nb = rank_vote_blocks(C);
+  hipLaunchKernelGGL(live_select_kernel, dim3(nb, nch), dim3(256), 0, s, d_q, Fmax, d_chan, sc, d_bits, C, key_bits_words(C),
+                     live_count_cols(C), d_counts, d_tiekey, d_table, K, d_part, d_bad);
+  const hipError_t err = hipGetLastError();
+  return err != hipSuccess ? err : launch_rank_merge(d_part, nch, nb * K, K, d_keys, s);
+}
+
+hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, int32_t nch, int64_t max_n,
+                              double* d_out, hipStream_t s) {
+  if (nch <= 0) return hipSuccess;
+  if (nch > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_gather_kernel, dim3(copy_blocks(max_n), nch), dim3(256), 0, s, d_q, Fmax, d_foff, d_out);
+  return hipGetLastError();
+}
+
+}  // namespace tfp

@@ -1,0 +1,71 @@
+// tfp_live.hpp — live calls: the scoped rows (tfp_scope.hpp) of each call so far, after every push,
+// with the per-clip counts carried from push to push.
+//
+// The dialplan application records a channel from the start of the call and searches the recording
+// among its context's clips (application_handler.c:152-185, record_voice :248-312; fp_handler.c:287-374
+// with the context predicate at :308-314, doc/dialplan_application.rst:11). A recording anchored at
+// the call's start only grows: its frames [0, floor(S / 256)) are final (tfp_live_plan.hpp). For
+// coefs = 1 a clip's count is the sum over the query frames of one bit of the key bitsets
+// (launch_key_bits: bits[key][column]), so a channel keeps a row of 16-bit counts over the index
+// columns, a push adds the bitset rows of its newly final frames to it, and the rows are selected
+// from count + the provisional tail frame's bit. Everything else (coefs = 2, a key outside the vote
+// range) runs the scoped search core over the kept frame values: exact, not incremental.
+//
+// Per live object, on the device: the int16 history [nchannels][max_samples]; the frame values
+// [nchannels][Fmax] (2 doubles per frame, Fmax = ceil(max_samples / 256), the provisional tail
+// included); the count table uint16 [nchannels][Cpad], Cpad = 32 key_bits_words(C) columns in the
+// scope table's layout (main columns, then the delta's). The channels' sample counts and added-frame
+// counts are kept by the host and travel with each push's descriptors.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "tfp_kernels.hpp"
+#include "tfp_live_plan.hpp"
+#include "tfp_rank.hpp"
+#include "tfp_scope.hpp"
+
+namespace tfp {
+
+// Per channel and push (uploaded with the tick).
+struct LiveChan {
+  int64_t s_old;  // samples before the push
+  int64_t tail;   // the provisional frame after the push, -1 when every frame is final (or none)
+  int32_t n_new;  // samples of this push: tick[c][0, n_new)
+  int32_t scope;  // the channel's scope of a searching push
+};
+// Frame values db[src, src + n) -> the frame history at frame dst (a flat index: channel * Fmax + frame).
+struct LiveCopy {
+  int64_t src, dst, n;
+};
+// Final frames [fbeg, fend) of channel ch to add to its count row.
+struct LiveAdd {
+  int32_t ch, fbeg, fend, pad;
+};
+
+inline int64_t live_count_cols(int32_t C) { return (int64_t)key_bits_words(C) * 32; }  // Cpad: a multiple of 128
+
+// tick[nch][T] -> hist[c][s_old, s_old + n_new) per channel (the host has checked s_old + n_new <= max_samples).
+hipError_t launch_live_scatter(const int16_t* d_tick, int32_t T, const LiveChan* d_chan, int32_t nch, int64_t max_samples,
+                               int16_t* d_hist, hipStream_t s);
+// The ncopy copies of d_cp (each at most max_n frames).
+hipError_t launch_live_store(const double* d_db, const LiveCopy* d_cp, int32_t ncopy, int64_t max_n, double* d_q,
+                             hipStream_t s);
+// counts[ch][col] += bits[key(frame)][col] for the frames of each of the nadd entries, in frame order
+// (a frame whose SQL does not run adds nothing). One workgroup owns 2,048 columns of one channel:
+// no atomics. *d_bad is set (never cleared) when a key lies outside [-512, 511].
+hipError_t launch_live_add(const double* d_q, int64_t Fmax, const LiveAdd* d_add, int32_t nadd, SearchConsts sc,
+                           const uint32_t* d_bits, int32_t C, uint16_t* d_counts, int32_t* d_bad, hipStream_t s);
+// d_keys[ch * K + r] = row r of channel ch: the r-th greatest (count + tail bit) << 32 | tie key over
+// the columns of scope d_chan[ch].scope with a non-zero score. d_part: nch * rank_vote_blocks(C) * K
+// keys of scratch. *d_bad as above (the tail's key).
+hipError_t launch_live_select(const double* d_q, int64_t Fmax, const LiveChan* d_chan, int32_t nch, SearchConsts sc,
+                              const uint32_t* d_bits, int32_t C, const uint16_t* d_counts, const int32_t* d_tiekey,
+                              const int32_t* d_table, int32_t K, unsigned long long* d_part, unsigned long long* d_keys,
+                              int32_t* d_bad, hipStream_t s);
+// The channels' frame values laid end to end for the general form: channel c's frames
+// [0, d_foff[c + 1] - d_foff[c]) at d_out frame d_foff[c] (at most max_n frames per channel).
+hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, int32_t nch, int64_t max_n,
+                              double* d_out, hipStream_t s);
+
+}  // namespace tfp

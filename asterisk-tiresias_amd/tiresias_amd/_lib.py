@@ -138,6 +138,18 @@ _SIGS = {
     "tfp_stream_push": (C.c_int, [P, P, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_stream_window_frames": (C.c_int, [P, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
     "tfp_fingerprint_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 4),
+    "tfp_live_create": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(P)]),
+    "tfp_live_destroy": (None, [P]),
+    "tfp_live_reset": (C.c_int, [P, C.c_int32]),
+    "tfp_live_push": (C.c_int, [P, P, C.c_int32, P, C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_live_samples": (C.c_int, [P, C.c_int32, C.POINTER(C.c_int64)]),
+    "tfp_live_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 5),
+    "tfp_group_live_create": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(P)]),
+    "tfp_group_live_destroy": (None, [P]),
+    "tfp_group_live_reset": (C.c_int, [P, C.c_int32]),
+    "tfp_group_live_push": (C.c_int, [P, P, C.c_int32, P, C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_group_live_samples": (C.c_int, [P, C.c_int32, C.POINTER(C.c_int64)]),
+    "tfp_group_live_stats": (C.c_int, [P, C.c_int32] + [C.POINTER(C.c_int64)] * 5),
     "tfp_synth_pcm": (C.c_int, [P, C.c_int32, C.c_int64, P]),
     "tfp_synth_pcm_device": (C.c_int, [P, P, C.c_int32, C.c_int64, P, P]),
     "tfp_synchronize": (C.c_int, [P, P]),

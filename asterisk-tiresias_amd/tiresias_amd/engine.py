@@ -789,6 +789,76 @@ class Stream:
             pass
 
 
+class _LiveCalls:
+    """Live calls (tfp_live / tfp_group_live): the same calls on an Engine's and on a Group's object."""
+
+    def _open(self, owner, nchannels: int, max_samples: int, sample_rate: int):
+        self._owner = owner
+        self._h = C.c_void_p()
+        owner._chk(self._fn("_create")(owner.handle, int(nchannels), int(sample_rate), int(max_samples), C.byref(self._h)))
+        self.nchannels = int(nchannels)
+        self.max_samples = int(max_samples)
+        owner._streams.add(self)
+
+    def _fn(self, name):
+        return getattr(lib(), self._PFX + name)
+
+    def reset(self, channel: int = -1):
+        """A new call on `channel` (< 0: every channel) starts empty."""
+        self._owner._chk(self._fn("_reset")(self._h, int(channel)))
+
+    def samples(self, channel: int) -> int:
+        n = C.c_int64()
+        self._owner._chk(self._fn("_samples")(self._h, int(channel), C.byref(n)))
+        return n.value
+
+    def push(self, pcm: np.ndarray, p: SearchParams = None, scopes=None, k: int = 1, nsamples=None):
+        """pcm int16[nchannels, tick]; channel c takes its first nsamples[c] samples (None: the whole tick).
+        p None: ingest only, returns None. Else (rows, frame_counts): per channel the first k rows of the
+        scoped search of its call so far (scopes None: TFP_SCOPE_ANY) and its frame count."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        assert pcm.ndim == 2 and pcm.shape[0] == self.nchannels
+        n, k = self.nchannels, int(k)
+        ns = None if nsamples is None else np.ascontiguousarray(nsamples, np.int32)
+        sc = None if scopes is None else np.ascontiguousarray(scopes, np.int32)
+        if (ns is not None and len(ns) != n) or (sc is not None and len(sc) != n):
+            raise ValueError("one entry per channel")
+        out, counts, fc = (Candidate * max(1, n * max(k, 1)))(), (C.c_int32 * n)(), (C.c_int32 * n)()
+        self._owner._chk(self._fn("_push")(self._h, pcm.ctypes.data, pcm.shape[1], None if ns is None else ns.ctypes.data,
+                                           C.byref(p) if p is not None else None, None if sc is None else sc.ctypes.data,
+                                           k, out, counts, fc))
+        if p is None:
+            return None
+        return Engine._candidates(out, counts, n, k), list(fc)
+
+    def close(self):
+        # the destroy call uses the owner: an object outliving its owner's close() was destroyed by it
+        if self._h and self._owner._h:
+            self._fn("_destroy")(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Live(_LiveCalls):
+    """tfp_live: every channel's call so far on one engine, the per-clip counts carried from push to push."""
+    _PFX = "tfp_live"
+
+    def __init__(self, eng: Engine, nchannels: int, max_samples: int, sample_rate: int = 8000):
+        self._open(eng, nchannels, max_samples, sample_rate)
+
+    def stats(self) -> dict:
+        """tfp_live_stats: searching pushes by form, count-table rebuilds, frames fingerprinted and added."""
+        v = [C.c_int64() for _ in range(5)]
+        self._owner._chk(lib().tfp_live_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("incremental_pushes", "general_pushes", "rebuilds", "frames_fingerprinted", "frames_added"),
+                        (x.value for x in v)))
+
+
 class Plan:
     def __init__(self, eng: Engine, offsets, sample_rate: int = 8000):
         offsets = np.ascontiguousarray(offsets, np.int64)
@@ -1053,3 +1123,21 @@ class GroupStream:
             self.close()
         except Exception:
             pass
+
+
+class GroupLive(_LiveCalls):
+    """tfp_group_live: live calls matched against every shard of a Group (every shard keeps every channel)."""
+    _PFX = "tfp_group_live"
+
+    def __init__(self, g: Group, nchannels: int, max_samples: int, sample_rate: int = 8000):
+        self._open(g, nchannels, max_samples, sample_rate)
+
+    def stats(self) -> list:
+        """tfp_group_live_stats: each shard's tfp_live_stats, in shard order."""
+        res = []
+        for shard in range(len(self._owner.devices)):
+            v = [C.c_int64() for _ in range(5)]
+            self._owner._chk(lib().tfp_group_live_stats(self._h, shard, *[C.byref(x) for x in v]))
+            res.append(dict(zip(("incremental_pushes", "general_pushes", "rebuilds", "frames_fingerprinted",
+                                 "frames_added"), (x.value for x in v))))
+        return res

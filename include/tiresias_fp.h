@@ -707,6 +707,59 @@ int tfp_stream_push_g711(tfp_stream* st, const uint8_t* codes, int32_t tick_samp
  * [0, nchannels) or cap below the window's frame count (*nframes then holds it). */
 int tfp_stream_window_frames(tfp_stream* st, int32_t channel, tfp_frame* out, int64_t cap, int64_t* nframes);
 
+/* ---- live calls: the scoped rows of each call so far, counts carried from push to push (new) ----
+ * The dialplan application answers a channel, records `duration` ms of it from the start of the call
+ * and asks which clip of its context the recording matches (application_handler.c:152-185,
+ * record_voice :248-312; doc/dialplan_application.rst:11). A live object keeps every channel's
+ * recording so far on the GPU, anchored at the start of the call: after a searching push the rows of
+ * channel c are what tfp_search_scoped_pcm_batch returns for one query holding exactly the S_c samples
+ * the channel has taken since its last reset (fp_handler.c:287-374 with the context predicate at
+ * :308-314), with the same params, scope and k, row for row (match_count, uuid, clip_id), and
+ * frame_counts[c] = tfp_frame_count(S_c); a channel with S_c = 0 has counts[c] = 0 and
+ * frame_counts[c] = 0. This holds after every push, for every interleaving of pushes and resets,
+ * across index updates and across changes of params or scope between pushes. So the caller can ask
+ * after every 20 ms frame what the application asks once at the end, and stop recording as soon as
+ * the winner's margin suffices.
+ *
+ * Frame f of a recording reads samples [256 (f - 1), 256 (f + 1)), so with S samples in, frames
+ * [0, floor(S / 256)) never change again: a push fingerprints only the frames its samples complete
+ * or touch, and for coefs = 1 adds each newly final frame's key bitset row to the channel's row of
+ * per-clip counts; the rows are selected from those counts plus the provisional last frame's bit.
+ * The counts are rebuilt from the kept frame values when the index, the resolved tolerance or an
+ * ignore threshold has changed since they were built (a change of scope or k needs no rebuild).
+ * coefs = 2 runs the scoped search over the kept frame values: exact, not incremental. Calls take the
+ * engine's mutex, as the stream calls do, and are not coalesced. */
+typedef struct tfp_live tfp_live;
+/* max_samples: the longest call kept (record_voice's duration, application_handler.c:248-312),
+ * 1 <= max_samples <= 65535 * 256 so that a count fits 16 bits; anything else is TFP_E_ARG. */
+int tfp_live_create(tfp_engine* eng, int32_t nchannels, int32_t sample_rate, int64_t max_samples, tfp_live** out);
+void tfp_live_destroy(tfp_live* lv); /* before tfp_engine_destroy of its engine */
+/* A new call on `channel` (< 0: every channel) starts empty (application_handler.c:152-185: one
+ * recording per tiresias_exec). */
+int tfp_live_reset(tfp_live* lv, int32_t channel);
+/* pcm[nchannels][tick_samples] (host): channel c takes its first nsamples[c] samples,
+ * 0 <= nsamples[c] <= tick_samples, 0 = an idle channel; nsamples NULL = tick_samples for every
+ * channel (record_voice's frame loop, application_handler.c:248-312). A push that would take any
+ * channel past max_samples returns TFP_E_CAPACITY and ingests nothing, for any channel.
+ * params NULL: ingest only, the out pointers are ignored. Else the search follows
+ * (fp_handler.c:287-374 with the context predicate at :308-314): scopes[nchannels], each
+ * TFP_SCOPE_ANY or >= 0 (NULL: TFP_SCOPE_ANY everywhere; below -1 is TFP_E_ARG); 1 <= k <=
+ * TFP_RANK_MAX; out[nchannels * k] and counts[nchannels] as tfp_search_scoped_batch writes them,
+ * entries past counts[c] zeroed; frame_counts[nchannels] may be NULL. Invalid params (coefs outside
+ * [1, 2]) ingest and give empty rows, as tfp_stream_push does (fp_handler.c:247-250). */
+int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t tick_samples, const int32_t* nsamples,
+                  const tfp_search_params* params, const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                  int32_t* frame_counts);
+/* Samples `channel` has taken since its last reset (record_voice's running length,
+ * application_handler.c:248-312). */
+int tfp_live_samples(tfp_live* lv, int32_t channel, int64_t* nsamples);
+/* Searching pushes served from the carried counts and by the general form (the rows of
+ * fp_handler.c:367-374 either way), rebuilds of the count table, frames given to the fingerprint
+ * kernels (the lead-in frames included) and final frames added to count rows (a rebuild adds every
+ * final frame again). Any pointer may be NULL. */
+int tfp_live_stats(tfp_live* lv, int64_t* incremental_pushes, int64_t* general_pushes, int64_t* rebuilds,
+                   int64_t* frames_fingerprinted, int64_t* frames_added);
+
 /* ---- device groups: the node's GPUs behind one index (new in round 3) -------------------
  * The module's enrolled DB sharded over one engine per listed device (the reference
  * has one SQLite DB, fp_handler.c:30): each clip lives on one engine (the one holding the fewest
@@ -834,6 +887,23 @@ void tfp_group_stream_destroy(tfp_group_stream* st);
 int tfp_group_stream_reset(tfp_group_stream* st, int32_t channel);
 int tfp_group_stream_push(tfp_group_stream* st, const int16_t* pcm, int32_t tick_samples,
                           const tfp_search_params* params, tfp_result* out);
+/* Live calls on a group (tfp_live_*; application_handler.c:152-185, :248-312): every shard keeps
+ * every channel's call so far, as replicated group streams do, and returns its first k rows per push
+ * over its own clips; the rows merge as tfp_group_search_scoped_batch's do (fp_handler.c:367-374 with
+ * the context predicate at :308-314 over all shards). clip_id is the shard. A failing shard fails the
+ * call; a capacity failure (TFP_E_CAPACITY) leaves every shard unchanged. */
+typedef struct tfp_group_live tfp_group_live;
+int tfp_group_live_create(tfp_group* g, int32_t nchannels, int32_t sample_rate, int64_t max_samples, tfp_group_live** out);
+void tfp_group_live_destroy(tfp_group_live* lv);
+int tfp_group_live_reset(tfp_group_live* lv, int32_t channel);
+int tfp_group_live_push(tfp_group_live* lv, const int16_t* pcm, int32_t tick_samples, const int32_t* nsamples,
+                        const tfp_search_params* params, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                        int32_t* counts, int32_t* frame_counts);
+int tfp_group_live_samples(tfp_group_live* lv, int32_t channel, int64_t* nsamples);
+/* tfp_live_stats of shard `shard`'s object (every shard serves every push, over its own clips'
+ * columns of fp_handler.c:367-374's rows). */
+int tfp_group_live_stats(tfp_group_live* lv, int32_t shard, int64_t* incremental_pushes, int64_t* general_pushes,
+                         int64_t* rebuilds, int64_t* frames_fingerprinted, int64_t* frames_added);
 /* G.711 codes on a group (aubio_source's table[code], fp_handler.c:604, :633; as the engine calls):
  * a fingerprint batch's clips are expanded by the shard that fingerprints them; a search batch is
  * expanded by every shard, or, where an int16 batch would be query-sharded, each shard expands and
