@@ -4180,6 +4180,10 @@ struct tfp_live {
   uint64_t stamp_version = 0;
   SearchConsts stamp_sc{};
   int64_t n_incremental = 0, n_general = 0, n_rebuilds = 0, n_fp_frames = 0, n_added = 0;
+  // a verdict's candidate table and the columns' staged rows it was built from; cand_builds: the
+  // engine's scope-table build it follows (-1: none yet)
+  DevBuf cand, cand_rows;
+  int64_t cand_builds = -1;
   ~tfp_live() {
     if (stage_ev) (void)hipEventDestroy(stage_ev);
   }
@@ -4290,16 +4294,56 @@ int live_general(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes
   return rank_core(e, foff.data(), nch, lv->gq.as<double>(), P, K, scopes, keys, e->stream);
 }
 
-}  // namespace
+// The verdict's candidate table (launch_live_candidates) for the current index and scopes: rebuilt
+// when the scope table was (an index update or a scope change), else it stands. Caller holds e->mu and
+// has run ensure_scope_table.
+int ensure_live_candidates(tfp_live* lv, hipStream_t s) {
+  tfp_engine* e = lv->eng;
+  if (lv->cand_builds == e->n_scope_builds) return TFP_OK;
+  const int32_t Cp = scope_table_cols(e->ncols);
+  std::vector<LiveColRows> rows((size_t)std::max(Cp, 1), LiveColRows{0, 0});
+  auto put = [&](size_t col, int32_t clip) {
+    if (clip >= 0 && e->clips[clip].alive) rows[col] = LiveColRows{e->clips[clip].off, e->clips[clip].nrows};
+  };
+  for (size_t c = 0; c < e->col_clip.size(); c++) put(c, e->col_clip[c]);
+  for (size_t j = 0; j < e->delta.clip.size(); j++) put((size_t)e->delta.col0 + j, e->delta.clip[j]);
+  HIPCHK(e, lv->cand_rows.reserve(sizeof(LiveColRows) * rows.size()));
+  HIPCHK(e, lv->cand.reserve(sizeof(int32_t) * rows.size()));
+  HIPCHK(e, hipMemcpyAsync(lv->cand_rows.p, rows.data(), sizeof(LiveColRows) * rows.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(e, launch_live_candidates(e->st_m1.as<int32_t>(), lv->cand_rows.as<LiveColRows>(), e->scope_table.as<int32_t>(),
+                                   e->ncols, lv->cand.as<int32_t>(), s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (rows is released on return)
+  lv->cand_builds = e->n_scope_builds;
+  return TFP_OK;
+}
 
-int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* nsamples, const tfp_search_params* P,
-                  const int32_t* scopes, int32_t K, tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
-  if (!lv) return TFP_E_ARG;
+// What tfp_live_verdict asks of the shared body instead of a push's rows: per channel the planned
+// length in, the two greatest candidate keys of launch_live_verdict out (0: none), and whether a key
+// lay outside the vote range (the keys are then zeroed: nothing can be said).
+struct LiveVerdictReq {
+  const int64_t* total;
+  unsigned long long* keys;  // [nch * 2]
+  bool bad;
+};
+
+// The body of every live call. A push: tick[nch][T] is int16 (law < 0) or G.711 codes of that law
+// (uint8), the only difference between tfp_live_push and tfp_live_push_g711. A verdict (vd set):
+// no tick, T = 0, every channel idle; the count rows are brought up to date as a searching push of
+// no samples does, and launch_live_verdict takes launch_live_select's place.
+// What a verdict skips, each by the guard an idle push already takes: the tick's copy (0 bytes), the
+// scatter (nch * T = 0), the fingerprint plan, launch and store (no channel has new samples, na = 0),
+// the sample counters (n_new = 0). What it runs: the index and stamp checks, the candidate table, the
+// one upload of descriptors (chan for the adds' bookkeeping, adds, its own LiveVerdictChan), the
+// rebuild memsets and launch_live_add where frames are owed, launch_live_verdict, the read-back.
+// K is the rows per channel read back: the caller's k for a push, 2 (leader, rival) for a verdict.
+int live_step(tfp_live* lv, const void* pcm, int32_t law, int32_t T, const int32_t* nsamples, const tfp_search_params* P,
+              const int32_t* scopes, int32_t K, tfp_candidate* out, int32_t* counts, int32_t* frame_counts,
+              LiveVerdictReq* vd) {
   tfp_engine* e = lv->eng;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   const int32_t nch = lv->nch;
-  if (!pcm || T <= 0) return fail(e, TFP_E_ARG, "live push: NULL samples or tick_samples %d", T);
-  if (P) {
+  if (!vd && (!pcm || T <= 0)) return fail(e, TFP_E_ARG, "live push: NULL samples or tick_samples %d", T);
+  if (P && !vd) {
     if (!out || !counts) return fail(e, TFP_E_ARG, "live push: NULL output");
     if (K < 1 || K > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "live push: k = %d outside [1, %d]", K, TFP_RANK_MAX);
     for (int32_t c = 0; scopes && c < nch; c++)
@@ -4325,6 +4369,7 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
       if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
       if (e->ncols > 0 && e->nrows + e->delta.rows > 0) {
         if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s)) || (rc = ensure_scope_table(e, s))) return rc;
+        if (vd && (rc = ensure_live_candidates(lv, s))) return rc;
         vote = true;
         rebuild_table = !live_stamp_holds(lv, sc);
       }
@@ -4337,6 +4382,12 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
   std::vector<LiveChan> chan(nch);
   std::vector<int32_t> act;
   std::vector<LivePlan> plans;
+  std::vector<LiveVerdictChan> vchan(vd ? nch : 0);
+  for (int32_t c = 0; vd && c < nch; c++) {
+    vchan[c].tail = live_tail_frame(lv->samples[c]);
+    vchan[c].scope = scopes ? scopes[c] : TFP_SCOPE_ANY;
+    vchan[c].complete = lv->samples[c] == vd->total[c] ? 1 : 0;
+  }
   for (int32_t c = 0; c < nch; c++) {
     const int32_t n = nsamples ? nsamples[c] : T;
     chan[c].s_old = lv->samples[c];
@@ -4386,18 +4437,21 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
     }
   // One pinned buffer, one upload: the tick, then the descriptors.
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_pcm = al(sizeof(int16_t) * (size_t)nch * T), b_chan = al(sizeof(LiveChan) * nch),
+  const size_t tick_bytes = (law < 0 ? sizeof(int16_t) : sizeof(uint8_t)) * (size_t)nch * T;  // (a verdict: none)
+  const size_t b_pcm = al(tick_bytes), b_chan = al(sizeof(LiveChan) * nch),
                b_sb = al(sizeof(int64_t) * sbeg.size()), b_fo = al(sizeof(int64_t) * foff.size()),
                b_to = al(sizeof(int32_t) * toff.size()), b_tc = al(sizeof(int32_t) * tclip.size()),
-               b_cp = al(sizeof(LiveCopy) * copies.size()), b_add = al(sizeof(LiveAdd) * std::max<size_t>(adds.size(), 1));
+               b_cp = al(sizeof(LiveCopy) * copies.size()), b_add = al(sizeof(LiveAdd) * std::max<size_t>(adds.size(), 1)),
+               b_vch = al(sizeof(LiveVerdictChan) * vchan.size());
   const size_t o_chan = b_pcm, o_sb = o_chan + b_chan, o_se = o_sb + b_sb, o_fo = o_se + b_sb, o_to = o_fo + b_fo,
-               o_tc = o_to + b_to, o_cp = o_tc + b_tc, o_add = o_cp + b_cp, total = o_add + b_add;
+               o_tc = o_to + b_to, o_cp = o_tc + b_tc, o_add = o_cp + b_cp, o_vch = o_add + b_add, total = o_vch + b_vch;
   if (lv->stage_pending) HIPCHK(e, hipEventSynchronize(lv->stage_ev));  // the last push's upload has read stage_h
   lv->stage_pending = false;
   HIPCHK(e, lv->stage_h.reserve(total));
   HIPCHK(e, lv->dstage.reserve(total));
   char* h = lv->stage_h.as<char>();
-  memcpy(h, pcm, sizeof(int16_t) * (size_t)nch * T);
+  if (tick_bytes) memcpy(h, pcm, tick_bytes);
+  if (vd) memcpy(h + o_vch, vchan.data(), sizeof(LiveVerdictChan) * nch);
   memcpy(h + o_chan, chan.data(), sizeof(LiveChan) * nch);
   memcpy(h + o_sb, sbeg.data(), sizeof(int64_t) * sbeg.size());
   memcpy(h + o_se, send.data(), sizeof(int64_t) * send.size());
@@ -4410,6 +4464,7 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
   HIPCHK(e, e->micro.reserve(sizeof(int32_t) * 2 * (nf + 1)));
   HIPCHK(e, e->db.reserve(sizeof(double) * 2 * (nf + 1)));
   if (rebuild_table) HIPCHK(e, lv->counts.reserve(sizeof(uint16_t) * (size_t)nch * Cpad));
+  if (vd) K = 2;  // the leader and the rival
   const size_t nkeys = P ? (size_t)nch * K : 0;
   if (vote) {
     HIPCHK(e, lv->part.reserve(sizeof(unsigned long long) * (size_t)nch * rank_vote_blocks(C) * K));
@@ -4422,8 +4477,15 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
   lv->stage_pending = true;
   const char* d = lv->dstage.as<char>();
   const LiveChan* d_chan = reinterpret_cast<const LiveChan*>(d + o_chan);
-  // 1: scatter
-  HIPCHK(e, launch_live_scatter(reinterpret_cast<const int16_t*>(d), T, d_chan, nch, lv->max_samples, lv->hist.as<int16_t>(), s));
+  // 1: scatter (codes are expanded on their way into the int16 history: everything after is one path)
+  if (law < 0) {
+    HIPCHK(e, launch_live_scatter(reinterpret_cast<const int16_t*>(d), T, d_chan, nch, lv->max_samples, lv->hist.as<int16_t>(), s));
+  } else {
+    HIPCHK(e, launch_live_scatter_g711(reinterpret_cast<const uint8_t*>(d), T, d_chan, nch, law, lv->max_samples,
+                                       lv->hist.as<int16_t>(), s));
+    e->n_g711_stream++;
+    for (int32_t c = 0; c < nch; c++) e->n_g711_codes += chan[c].n_new;
+  }
   // 2: fingerprint only what changed (exact frame values: the kept history serves coefs = 2 as well,
   // and a coefs = 1 key is their truncation either way), then the kept frames into the history
   if (na) {
@@ -4439,10 +4501,16 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
   for (int32_t c = 0; c < nch; c++) lv->samples[c] += chan[c].n_new;
   lv->n_fp_frames += nf;
   if (!P) return TFP_OK;
-  memset(out, 0, sizeof(tfp_candidate) * nkeys);
-  for (int32_t c = 0; c < nch; c++) {
-    counts[c] = 0;
-    if (frame_counts) frame_counts[c] = (int32_t)live_frames(lv->samples[c]);
+  if (vd) {
+    std::fill(vd->keys, vd->keys + nkeys, 0ull);
+    vd->bad = false;
+    if (!vote) return TFP_OK;  // an empty index: no candidate
+  } else {
+    memset(out, 0, sizeof(tfp_candidate) * nkeys);
+    for (int32_t c = 0; c < nch; c++) {
+      counts[c] = 0;
+      if (frame_counts) frame_counts[c] = (int32_t)live_frames(lv->samples[c]);
+    }
   }
   if (!match) return TFP_OK;
   std::vector<unsigned long long> keys(nkeys, 0ull);
@@ -4467,10 +4535,16 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
                               sc, d_bits, C, lv->counts.as<uint16_t>(), lv->bad.as<int32_t>(), s));
     for (const LiveAdd& a : adds) lv->added[a.ch] = a.fend;
     lv->n_added += add_frames;
-    // 4: select
-    HIPCHK(e, launch_live_select(lv->q.as<double>(), lv->Fmax, d_chan, nch, sc, d_bits, C, lv->counts.as<uint16_t>(),
-                                 e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
-                                 lv->part.as<unsigned long long>(), lv->keys.as<unsigned long long>(), lv->bad.as<int32_t>(), s));
+    // 4: select (a verdict: its own selection over the candidate table)
+    if (vd)
+      HIPCHK(e, launch_live_verdict(lv->q.as<double>(), lv->Fmax, reinterpret_cast<const LiveVerdictChan*>(d + o_vch), nch, sc,
+                                    d_bits, C, lv->counts.as<uint16_t>(), e->tiekey.as<int32_t>(), lv->cand.as<int32_t>(),
+                                    lv->part.as<unsigned long long>(), lv->keys.as<unsigned long long>(),
+                                    lv->bad.as<int32_t>(), s));
+    else
+      HIPCHK(e, launch_live_select(lv->q.as<double>(), lv->Fmax, d_chan, nch, sc, d_bits, C, lv->counts.as<uint16_t>(),
+                                   e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
+                                   lv->part.as<unsigned long long>(), lv->keys.as<unsigned long long>(), lv->bad.as<int32_t>(), s));
     unsigned long long* hk = lv->keys_pin.as<unsigned long long>();
     HIPCHK(e, hipMemcpyAsync(hk, lv->keys.p, sizeof(unsigned long long) * nkeys, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(hk + nkeys, lv->bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -4481,12 +4555,20 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
     // out-of-range key. The route stays: the table then holds frames it could not add, so it is
     // dropped, and this and every later push of such a call take the general form.
     if (!(uint32_t)hk[nkeys]) {
+      if (vd) {
+        std::copy(hk, hk + nkeys, vd->keys);
+        return TFP_OK;
+      }
       std::copy(hk, hk + nkeys, keys.begin());
       fill_candidates(e, keys, nch, K, out, counts);
       lv->n_incremental++;
       return TFP_OK;
     }
     lv->stamp_valid = false;
+    if (vd) {  // nothing can be said of counts the table could not take
+      vd->bad = true;
+      return TFP_OK;
+    }
   }
   std::vector<int32_t> any;
   if (!scopes) any.assign(nch, TFP_SCOPE_ANY);
@@ -4495,6 +4577,76 @@ int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* ns
   lv->stage_pending = false;
   fill_candidates(e, keys, nch, K, out, counts);
   lv->n_general++;
+  return TFP_OK;
+}
+
+// A verdict's arguments (tiresias_fp.h): nothing is written and nothing brought up to date on failure.
+int live_verdict_args(tfp_live* lv, const int64_t* total, const tfp_search_params* P, const int32_t* scopes) {
+  char msg[160];
+  if (!live_verdict_args_ok(total, P ? &P->coefs : nullptr, scopes, lv->samples.data(), lv->nch, lv->max_samples, msg, sizeof msg))
+    return fail(lv->eng, TFP_E_ARG, "%s", msg);
+  return TFP_OK;
+}
+
+}  // namespace
+
+int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* nsamples, const tfp_search_params* P,
+                  const int32_t* scopes, int32_t K, tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
+  if (!lv) return TFP_E_ARG;
+  return live_step(lv, pcm, -1, T, nsamples, P, scopes, K, out, counts, frame_counts, nullptr);
+}
+
+int tfp_live_push_g711(tfp_live* lv, const uint8_t* codes, int32_t T, int32_t law, const int32_t* nsamples,
+                       const tfp_search_params* P, const int32_t* scopes, int32_t K, tfp_candidate* out, int32_t* counts,
+                       int32_t* frame_counts) {
+  if (!lv) return TFP_E_ARG;
+  if (!g711_law_ok(law)) return fail(lv->eng, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  return live_step(lv, codes, law, T, nsamples, P, scopes, K, out, counts, frame_counts, nullptr);
+}
+
+int tfp_internal_live_verdict_keys(tfp_live* lv, const int64_t* total, const tfp_search_params* P, const int32_t* scopes,
+                                   unsigned long long* keys, int32_t* bad) {
+  if (!lv || !keys || !bad) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  int rc = live_verdict_args(lv, total, P, scopes);
+  if (rc) return rc;
+  LiveVerdictReq vd{total, keys, false};
+  if ((rc = live_step(lv, nullptr, -1, 0, nullptr, P, scopes, 2, nullptr, nullptr, nullptr, &vd))) return rc;
+  *bad = vd.bad ? 1 : 0;
+  return TFP_OK;
+}
+
+int tfp_live_verdict(tfp_live* lv, const int64_t* total, const tfp_search_params* P, const int32_t* scopes,
+                     struct tfp_live_verdict* out) {
+  if (!lv || !out) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  const int32_t nch = lv->nch;
+  std::vector<unsigned long long> keys((size_t)nch * 2, 0ull);
+  int32_t bad = 0;
+  const int rc = tfp_internal_live_verdict_keys(lv, total, P, scopes, keys.data(), &bad);
+  if (rc) return rc;
+  std::vector<struct tfp_live_verdict> res(nch);  // copied out on success: every failure leaves out untouched
+  for (int32_t c = 0; c < nch; c++) {
+    const LiveVerdictRule r = live_verdict_rule(bad ? 0ull : keys[2 * c], bad ? 0ull : keys[2 * c + 1], lv->samples[c], total[c]);
+    struct tfp_live_verdict& v = res[c];
+    memset(&v, 0, sizeof v);
+    v.remaining = r.remaining;
+    v.complete = r.complete;
+    v.decided = r.decided;
+    const unsigned long long side[2] = {r.leader, r.rival};  // (a rival's packed key may be 0: count 0, tie key 0)
+    for (int i = 0; i < 2; i++) {
+      if (!(i ? r.has_rival : r.has_leader)) continue;
+      const int32_t clip = clip_of_col(e, col_of_key(e, (int32_t)(uint32_t)(side[i] & 0xffffffffu)));
+      if (clip < 0) return fail(e, TFP_E_HIP, "live verdict: tie-break key %u names no clip", (unsigned)(side[i] & 0xffffffffu));
+      tfp_candidate& cd = i ? v.rival : v.leader;
+      cd.match_count = (int32_t)(side[i] >> 32);
+      cd.clip_id = clip;
+      snprintf(cd.uuid, sizeof cd.uuid, "%s", e->clips[clip].uuid.c_str());
+      (i ? v.has_rival : v.has_leader) = 1;
+    }
+  }
+  std::copy(res.begin(), res.end(), out);
   return TFP_OK;
 }
 

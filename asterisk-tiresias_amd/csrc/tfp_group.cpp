@@ -41,6 +41,7 @@
 #include "tfp_g711.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
+#include "tfp_live_plan.hpp"
 #include "tfp_occur.hpp"
 #include "tfp_rank_merge.hpp"
 #include "tfp_shardpool.hpp"
@@ -1440,10 +1441,20 @@ int tfp_group_live_stats(tfp_group_live* gl, int32_t shard, int64_t* incremental
   return tfp_live_stats(gl->lv[shard], incremental_pushes, general_pushes, rebuilds, frames_fingerprinted, frames_added);
 }
 
-int tfp_group_live_push(tfp_group_live* gl, const int16_t* pcm, int32_t T, const int32_t* nsamples,
-                        const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
-                        int32_t* frame_counts) {
-  if (!gl) return TFP_E_ARG;
+}  // extern "C"
+
+namespace {
+// One shard's push: int16 samples (law < 0) or G.711 codes of that law.
+int shard_live_push(tfp_live* lv, const void* pcm, int32_t law, int32_t T, const int32_t* nsamples, const tfp_search_params* P,
+                    const int32_t* scopes, int32_t k, tfp_candidate* o, int32_t* c, int32_t* frame_counts) {
+  return law < 0 ? tfp_live_push(lv, (const int16_t*)pcm, T, nsamples, P, scopes, k, o, c, frame_counts)
+                 : tfp_live_push_g711(lv, (const uint8_t*)pcm, T, law, nsamples, P, scopes, k, o, c, frame_counts);
+}
+
+// tfp_group_live_push (law < 0) and tfp_group_live_push_g711: the tick's source is the only difference.
+int group_live_push(tfp_group_live* gl, const void* pcm, int32_t law, int32_t T, const int32_t* nsamples,
+                    const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                    int32_t* frame_counts) {
   tfp_group* g = gl->g;
   std::lock_guard<std::recursive_mutex> lk(g->mu);
   const int32_t nch = gl->nch;
@@ -1464,14 +1475,14 @@ int tfp_group_live_push(tfp_group_live* gl, const int16_t* pcm, int32_t T, const
   if (P && valid_params(P)) {
     // each shard's first k rows of every channel, merged as scoped search's (shard 0 reports the frame counts)
     rc = group_rank(g, nch, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
-      return tfp_live_push(gl->lv[s], pcm, T, nsamples, P, scopes, k, o, c, s == 0 ? frame_counts : nullptr);
+      return shard_live_push(gl->lv[s], pcm, law, T, nsamples, P, scopes, k, o, c, s == 0 ? frame_counts : nullptr);
     });
   } else {
     // ingest only; with invalid params the rows come out empty (fp_handler.c:247-250)
     std::vector<tfp_candidate> o(P ? (size_t)nch * k : 0);
     std::vector<int32_t> cn(P ? nch : 0);
     rc = run_all(g, [&](int s) {
-      return tfp_live_push(gl->lv[s], pcm, T, nsamples, s == 0 ? P : nullptr, scopes, k, o.data(), cn.data(), frame_counts);
+      return shard_live_push(gl->lv[s], pcm, law, T, nsamples, s == 0 ? P : nullptr, scopes, k, o.data(), cn.data(), frame_counts);
     });
     if (!rc && P) {
       memset(out, 0, sizeof(tfp_candidate) * (size_t)nch * k);
@@ -1480,6 +1491,75 @@ int tfp_group_live_push(tfp_group_live* gl, const int16_t* pcm, int32_t T, const
   }
   if (rc) return rc;
   for (int32_t c = 0; c < nch; c++) gl->samples[c] += nsamples ? nsamples[c] : T;
+  return TFP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tfp_group_live_push(tfp_group_live* gl, const int16_t* pcm, int32_t T, const int32_t* nsamples,
+                        const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                        int32_t* frame_counts) {
+  if (!gl) return TFP_E_ARG;
+  return group_live_push(gl, pcm, -1, T, nsamples, P, scopes, k, out, counts, frame_counts);
+}
+
+int tfp_group_live_push_g711(tfp_group_live* gl, const uint8_t* codes, int32_t T, int32_t law, const int32_t* nsamples,
+                             const tfp_search_params* P, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                             int32_t* counts, int32_t* frame_counts) {
+  if (!gl) return TFP_E_ARG;
+  if (!tfp::g711_law_ok(law)) return gfail(gl->g, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
+  return group_live_push(gl, codes, law, T, nsamples, P, scopes, k, out, counts, frame_counts);
+}
+
+int tfp_group_live_verdict(tfp_group_live* gl, const int64_t* total, const tfp_search_params* P, const int32_t* scopes,
+                           struct tfp_live_verdict* out) {
+  if (!gl || !out) return TFP_E_ARG;
+  tfp_group* g = gl->g;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  const int32_t nch = gl->nch;
+  // before any shard is told: a refused call brings no shard's count rows up to date
+  char msg[160];
+  if (!tfp::live_verdict_args_ok(total, P ? &P->coefs : nullptr, scopes, gl->samples.data(), nch, gl->max_samples, msg, sizeof msg))
+    return gfail(g, TFP_E_ARG, "%s", msg);
+  int rc = refresh_ranks(g);
+  if (rc) return rc;
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<unsigned long long>> keys(n, std::vector<unsigned long long>((size_t)nch * 2, 0ull));
+  std::vector<int32_t> bad(n, 0);
+  rc = run_all(g, [&](int s) { return tfp_internal_live_verdict_keys(gl->lv[s], total, P, scopes, keys[s].data(), &bad[s]); });
+  if (rc) return rc;
+  const bool any_bad = std::any_of(bad.begin(), bad.end(), [](int32_t b) { return b != 0; });
+  std::vector<struct tfp_live_verdict> res(nch);  // copied out on success: every failure leaves out untouched
+  for (int32_t c = 0; c < nch; c++) {
+    unsigned long long top[2] = {0ull, 0ull};  // the two greatest of the shards' keys (distinct: the tie keys are)
+    for (int s = 0; s < n && !any_bad; s++)
+      for (int r = 0; r < 2; r++) {
+        const unsigned long long k = keys[s][(size_t)c * 2 + r];
+        if (k > top[0]) top[1] = top[0], top[0] = k;
+        else if (k > top[1]) top[1] = k;
+      }
+    const tfp::LiveVerdictRule r = tfp::live_verdict_rule(top[0], top[1], gl->samples[c], total[c]);
+    struct tfp_live_verdict& v = res[c];
+    memset(&v, 0, sizeof v);
+    v.remaining = r.remaining;
+    v.complete = r.complete;
+    v.decided = r.decided;
+    const unsigned long long side[2] = {r.leader, r.rival};
+    for (int i = 0; i < 2; i++) {
+      if (!(i ? r.has_rival : r.has_leader)) continue;
+      const auto it = g->key2member.find((int32_t)(uint32_t)(side[i] & 0xffffffffu));
+      if (it == g->key2member.end())
+        return gfail(g, TFP_E_HIP, "live verdict: tie-break key %u names no clip", (unsigned)(side[i] & 0xffffffffu));
+      const Member& mb = g->members[it->second];
+      tfp_candidate& cd = i ? v.rival : v.leader;
+      cd.match_count = (int32_t)(side[i] >> 32);
+      cd.clip_id = mb.shard;
+      snprintf(cd.uuid, sizeof cd.uuid, "%s", mb.uuid.c_str());
+      (i ? v.has_rival : v.has_leader) = 1;
+    }
+  }
+  std::copy(res.begin(), res.end(), out);
   return TFP_OK;
 }
 

@@ -97,4 +97,11 @@ __attribute__((visibility("hidden"))) int tfp_internal_search_g711(tfp_engine* e
 __attribute__((visibility("hidden"))) int tfp_internal_g711_expand_device(tfp_engine* e, const uint8_t* d_codes,
                                                                           int64_t n, int32_t law, int16_t* d_pcm,
                                                                           void* stream);
+// tfp_live_verdict before the rule: keys[nchannels * 2], per channel the two greatest candidate keys
+// ((base count << 32 | tie key) + 1, 0: none) over this engine's own columns, zeroed with *bad = 1
+// when a frame's key lay outside the vote range. A device group takes the top 2 of its shards' keys
+// (they carry the group-wide tie keys) and applies the rule once.
+__attribute__((visibility("hidden"))) int tfp_internal_live_verdict_keys(tfp_live* lv, const int64_t* total_samples,
+                                                                         const tfp_search_params* P, const int32_t* scopes,
+                                                                         unsigned long long* keys, int32_t* bad);
 }

@@ -6,6 +6,9 @@
 // score read from the count row plus the provisional tail frame's bit, instead of summed over the
 // query's keys; its partial lists go through ranked search's merge (launch_rank_merge).
 // live_gather_kernel: the frame histories laid end to end for the general form.
+// live_scatter_g711_kernel: live_scatter_kernel over G.711 codes, expanded by tfp_g711.hpp's map.
+// live_verdict_kernel: the two greatest candidates per channel for tfp_live_verdict, a count of 0
+// included, over the candidate table live_candidates_kernel derives from the scope table.
 //
 // The count row is what a push moves (2 bytes per column, read and written once per push however
 // many frames it adds, against 1 bit per column and frame of bitset), so a thread owns 8 columns:
@@ -42,6 +45,19 @@ __global__ __launch_bounds__(256) void live_scatter_kernel(const int16_t* __rest
     const int64_t c = i / T, t = i % T;
     const int64_t at = chan[c].s_old + t;
     if (t < chan[c].n_new && at < max_samples) hist[c * max_samples + at] = tick[i];
+  }
+}
+
+// live_scatter_kernel over codes: 1 B per sample in, the int16 of tfp_g711.hpp's map into the history.
+template <int LAW>
+__global__ __launch_bounds__(256) void live_scatter_g711_kernel(const uint8_t* __restrict__ tick, int32_t T,
+                                                                const LiveChan* __restrict__ chan, int32_t nch,
+                                                                int64_t max_samples, int16_t* __restrict__ hist) {
+  const int64_t n = (int64_t)nch * T;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = i / T, t = i % T;
+    const int64_t at = chan[c].s_old + t;
+    if (t < chan[c].n_new && at < max_samples) hist[c * max_samples + at] = (int16_t)g711_expand<LAW>(tick[i]);
   }
 }
 
@@ -150,6 +166,91 @@ __global__ __launch_bounds__(256) void live_select_kernel(const double* __restri
   }
 }
 
+// The verdict's selection: live_select_kernel's loads and reduction with three differences. A column
+// is a candidate when it is in scope and its candidate-table entry is not kScopeNone (TFP_SCOPE_ANY
+// does not admit a column without a clip, nor one whose clip has no row); a candidate with score 0
+// keeps a key, ((score << 32) | tie key) + 1 (tie keys reach INT32_MAX and scores 65535: the + 1
+// stays inside the low word, and 0 is left for "no column"); the tail frame's bit counts only for a
+// channel flagged complete. The top 2 per block, then launch_rank_merge with K = 2.
+__global__ __launch_bounds__(256) void live_verdict_kernel(const double* __restrict__ q, int64_t Fmax,
+                                                           const LiveVerdictChan* __restrict__ chan, SearchConsts sc,
+                                                           const uint32_t* __restrict__ bits, int32_t C, int32_t W,
+                                                           int64_t Cpad, const uint16_t* __restrict__ counts,
+                                                           const int32_t* __restrict__ tiekey,
+                                                           const int32_t* __restrict__ cand,
+                                                           unsigned long long* __restrict__ part, int32_t* __restrict__ bad) {
+  static_assert(4 * 256 == kRankVoteCols, "4 columns per thread");
+  __shared__ unsigned long long wmax[2][4];
+  const int ch = blockIdx.y, blk = blockIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const LiveVerdictChan lc = chan[ch];
+  const int c4 = 4 * (blk * 256 + threadIdx.x);
+  uint32_t in = 0;
+  if (c4 < C) {  // (the table holds scope_table_cols(C) entries: the 16-byte load stays inside it)
+    const int4 s4 = *reinterpret_cast<const int4*>(cand + c4);
+    in = ((s4.x != kScopeNone && in_scope(lc.scope, s4.x)) ? 1u : 0u) | ((s4.y != kScopeNone && in_scope(lc.scope, s4.y)) ? 2u : 0u) |
+         ((s4.z != kScopeNone && in_scope(lc.scope, s4.z)) ? 4u : 0u) | ((s4.w != kScopeNone && in_scope(lc.scope, s4.w)) ? 8u : 0u);
+#pragma unroll
+    for (int j = 1; j < 4; j++)
+      if (c4 + j >= C) in &= ~(1u << j);
+  }
+  // a complete channel's provisional tail frame: its bitset row (-1: none, or its SQL does not run)
+  int slot = -1;
+  if (lc.complete && lc.tail >= 0) {
+    int32_t k = 0;
+    if (frame_key(q + 2 * (int64_t)ch * Fmax, lc.tail, sc, k)) {
+      const int64_t idx = (int64_t)k + kKeyOffset;
+      if (idx < 0 || idx >= kKeyRange) {
+        if (threadIdx.x == 0) *bad = 1;  // (every writer stores 1)
+      } else {
+        slot = (int)idx;
+      }
+    }
+  }
+  uint32_t score[4] = {0, 0, 0, 0};
+  if (in) {  // (in != 0 implies c4 < C <= Cpad; c4 is a multiple of 4: an aligned 8-byte load of 4 counts)
+    const uint2 cv = *reinterpret_cast<const uint2*>(counts + (int64_t)ch * Cpad + c4);
+    const uint32_t tb = slot >= 0 ? bits[(int64_t)slot * W + (c4 >> 5)] >> (c4 & 31) : 0u;
+    score[0] = (cv.x & 0xffffu) + (tb & 1u);
+    score[1] = (cv.x >> 16) + ((tb >> 1) & 1u);
+    score[2] = (cv.y & 0xffffu) + ((tb >> 2) & 1u);
+    score[3] = (cv.y >> 16) + ((tb >> 3) & 1u);
+  }
+  unsigned long long mine[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    mine[j] = ((in >> j) & 1u) ? (((unsigned long long)score[j] << 32) | (uint32_t)tiekey[c4 + j]) + 1ull : 0ull;
+  unsigned long long* out = part + ((int64_t)ch * gridDim.x + blk) * 2;
+  unsigned long long prev = ~0ull;
+  for (int r = 0; r < 2; r++) {
+    unsigned long long key = 0ull;
+#pragma unroll
+    for (int j = 0; j < 4; j++) key = (mine[j] < prev && mine[j] > key) ? mine[j] : key;
+    key = wave_max_u64(key);
+    if (lane == 0) wmax[r][wv] = key;
+    __syncthreads();
+    key = wmax[r][0];
+#pragma unroll
+    for (int i = 1; i < 4; i++) key = wmax[r][i] > key ? wmax[r][i] : key;
+    if (threadIdx.x == 0) out[r] = key;
+    prev = key;  // (0: no key is below it, the second round gives 0)
+  }
+}
+
+// One wave per column: any staged row of the column's clip with a non-NULL max1.
+__global__ __launch_bounds__(256) void live_candidates_kernel(const int32_t* __restrict__ m1,
+                                                              const LiveColRows* __restrict__ rows,
+                                                              const int32_t* __restrict__ table, int32_t Cp,
+                                                              int32_t* __restrict__ cand) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= Cp) return;  // (a whole wave leaves: c is the same in all its lanes)
+  const LiveColRows r = rows[c];
+  bool has = false;
+  for (int64_t i = lane; i < r.n && !has; i += 64) has = m1[r.off + i] != kLiveNullM1;
+  const bool any = __any(has);
+  if (lane == 0) cand[c] = any ? table[c] : kScopeNone;
+}
+
 __global__ __launch_bounds__(256) void live_gather_kernel(const double* __restrict__ q, int64_t Fmax,
                                                           const int64_t* __restrict__ foff, double* __restrict__ out) {
   const int ch = blockIdx.y;
@@ -174,6 +275,41 @@ hipError_t launch_live_scatter(const int16_t* d_tick, int32_t T, const LiveChan*
   hipLaunchKernelGGL(live_scatter_kernel, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, d_tick, T, d_chan, nch,
                      max_samples, d_hist);
   return hipGetLastError();
+}
+
+hipError_t launch_live_scatter_g711(const uint8_t* d_tick, int32_t T, const LiveChan* d_chan, int32_t nch, int32_t law,
+                                    int64_t max_samples, int16_t* d_hist, hipStream_t s) {
+  if (!g711_law_ok(law)) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)nch * T;
+  if (n <= 0) return hipSuccess;
+  const int64_t g = (n + 255) / 256;
+  const dim3 grid((unsigned)(g > 1024 ? 1024 : g));
+  if (law == kG711Alaw)
+    hipLaunchKernelGGL(live_scatter_g711_kernel<kG711Alaw>, grid, dim3(256), 0, s, d_tick, T, d_chan, nch, max_samples, d_hist);
+  else
+    hipLaunchKernelGGL(live_scatter_g711_kernel<kG711Ulaw>, grid, dim3(256), 0, s, d_tick, T, d_chan, nch, max_samples, d_hist);
+  return hipGetLastError();
+}
+
+hipError_t launch_live_candidates(const int32_t* d_m1, const LiveColRows* d_rows, const int32_t* d_table, int32_t C,
+                                  int32_t* d_cand, hipStream_t s) {
+  if (C <= 0) return hipSuccess;
+  const int32_t Cp = scope_table_cols(C);
+  hipLaunchKernelGGL(live_candidates_kernel, dim3((unsigned)((Cp + 3) / 4)), dim3(256), 0, s, d_m1, d_rows, d_table, Cp, d_cand);
+  return hipGetLastError();
+}
+
+hipError_t launch_live_verdict(const double* d_q, int64_t Fmax, const LiveVerdictChan* d_chan, int32_t nch, SearchConsts sc,
+                               const uint32_t* d_bits, int32_t C, const uint16_t* d_counts, const int32_t* d_tiekey,
+                               const int32_t* d_cand, unsigned long long* d_part, unsigned long long* d_keys,
+                               int32_t* d_bad, hipStream_t s) {
+  if (nch <= 0) return hipSuccess;
+  if (C <= 0 || nch > 65535) return hipErrorInvalidValue;
+  const int32_t nb = rank_vote_blocks(C);
+  hipLaunchKernelGGL(live_verdict_kernel, dim3(nb, nch), dim3(256), 0, s, d_q, Fmax, d_chan, sc, d_bits, C, key_bits_words(C),
+                     live_count_cols(C), d_counts, d_tiekey, d_cand, d_part, d_bad);
+  const hipError_t err = hipGetLastError();
+  return err != hipSuccess ? err : launch_rank_merge(d_part, nch, nb * 2, 2, d_keys, s);
 }
 
 hipError_t launch_live_store(const double* d_db, const LiveCopy* d_cp, int32_t ncopy, int64_t max_n, double* d_q,

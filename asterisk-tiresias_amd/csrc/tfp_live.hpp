@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tfp_g711.hpp"
 #include "tfp_kernels.hpp"
 #include "tfp_live_plan.hpp"
 #include "tfp_rank.hpp"
@@ -43,11 +44,41 @@ struct LiveAdd {
   int32_t ch, fbeg, fend, pad;
 };
 
+// Per channel and verdict (launch_live_verdict): a descriptor of its own, a push's LiveChan stays as it is.
+struct LiveVerdictChan {
+  int64_t tail;      // the provisional frame of the samples so far, -1 when every frame is final (or none)
+  int32_t scope;     // the channel's scope
+  int32_t complete;  // 1: the recording has its planned length, the tail's bit counts; 0: final frames only
+};
+// A column's clip in the staging rows (launch_live_candidates): rows [off, off + n), n = 0 without a clip.
+struct LiveColRows {
+  int64_t off;
+  int64_t n;
+};
+constexpr int32_t kLiveNullM1 = INT32_MIN;  // a staged row with a NULL max1: it matches no frame
+
 inline int64_t live_count_cols(int32_t C) { return (int64_t)key_bits_words(C) * 32; }  // Cpad: a multiple of 128
 
 // tick[nch][T] -> hist[c][s_old, s_old + n_new) per channel (the host has checked s_old + n_new <= max_samples).
 hipError_t launch_live_scatter(const int16_t* d_tick, int32_t T, const LiveChan* d_chan, int32_t nch, int64_t max_samples,
                                int16_t* d_hist, hipStream_t s);
+// The same with G.711 codes tick[nch][T] (1 B per sample) of law kG711Ulaw / kG711Alaw, expanded by
+// tfp_g711.hpp's map on their way into the int16 history.
+hipError_t launch_live_scatter_g711(const uint8_t* d_tick, int32_t T, const LiveChan* d_chan, int32_t nch, int32_t law,
+                                    int64_t max_samples, int16_t* d_hist, hipStream_t s);
+// The verdict's candidate table over scope_table_cols(C) columns: d_cand[c] = d_table[c] (the scope
+// table) where column c's clip has a staged row with a non-NULL max1 (d_m1[off, off + n) of d_rows[c]),
+// else kScopeNone: a clip without such a row can never score, so it is no candidate.
+hipError_t launch_live_candidates(const int32_t* d_m1, const LiveColRows* d_rows, const int32_t* d_table, int32_t C,
+                                  int32_t* d_cand, hipStream_t s);
+// d_keys[ch * 2 + r], r = 0, 1: the two greatest of ((count << 32 | tie key) + 1) over the columns of
+// scope d_chan[ch].scope whose d_cand entry is not kScopeNone, a count of 0 included (0: no such
+// column). count = the count row's entry, plus the tail frame's bit for a complete channel only.
+// d_part: nch * rank_vote_blocks(C) * 2 keys of scratch. *d_bad as launch_live_select (the tail's key).
+hipError_t launch_live_verdict(const double* d_q, int64_t Fmax, const LiveVerdictChan* d_chan, int32_t nch, SearchConsts sc,
+                               const uint32_t* d_bits, int32_t C, const uint16_t* d_counts, const int32_t* d_tiekey,
+                               const int32_t* d_cand, unsigned long long* d_part, unsigned long long* d_keys,
+                               int32_t* d_bad, hipStream_t s);
 // The ncopy copies of d_cp (each at most max_n frames).
 hipError_t launch_live_store(const double* d_db, const LiveCopy* d_cp, int32_t ncopy, int64_t max_n, double* d_q,
                              hipStream_t s);

@@ -52,6 +52,12 @@ class Candidate(C.Structure):
     _fields_ = [("match_count", C.c_int32), ("clip_id", C.c_int32), ("uuid", C.c_char * 64)]
 
 
+class LiveVerdict(C.Structure):
+    """struct tfp_live_verdict: a live call's early verdict (tiresias_fp.h)."""
+    _fields_ = [("leader", Candidate), ("rival", Candidate), ("has_leader", C.c_int32), ("has_rival", C.c_int32),
+                ("remaining", C.c_int32), ("complete", C.c_int32), ("decided", C.c_int32)]
+
+
 class Alignment(C.Structure):
     _fields_ = [("aligned_count", C.c_int32), ("offset", C.c_int32), ("first_frame", C.c_int32),
                 ("last_frame", C.c_int32)]
@@ -144,6 +150,10 @@ _SIGS = {
     "tfp_live_push": (C.c_int, [P, P, C.c_int32, P, C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
     "tfp_live_samples": (C.c_int, [P, C.c_int32, C.POINTER(C.c_int64)]),
     "tfp_live_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 5),
+    "tfp_live_push_g711": (C.c_int, [P, P, C.c_int32, C.c_int32, P, C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_live_verdict": (C.c_int, [P, P, C.POINTER(SearchParams), P, P]),
+    "tfp_group_live_push_g711": (C.c_int, [P, P, C.c_int32, C.c_int32, P, C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_group_live_verdict": (C.c_int, [P, P, C.POINTER(SearchParams), P, P]),
     "tfp_group_live_create": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(P)]),
     "tfp_group_live_destroy": (None, [P]),
     "tfp_group_live_reset": (C.c_int, [P, C.c_int32]),

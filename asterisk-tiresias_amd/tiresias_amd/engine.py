@@ -6,7 +6,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import Alignment, Candidate, Frame, Occurrence, Result, SearchParams, SynthSpec, TfpError, check, lib
+from ._lib import Alignment, Candidate, Frame, LiveVerdict, Occurrence, Result, SearchParams, SynthSpec, TfpError, check, lib
 
 FRAME_DTYPE = np.dtype([("frame_idx", "<i4"), ("m1", "<i4"), ("m2", "<i4"), ("reserved", "<i4"),
                         ("q1", "<f8"), ("q2", "<f8")])
@@ -816,20 +816,48 @@ class _LiveCalls:
         """pcm int16[nchannels, tick]; channel c takes its first nsamples[c] samples (None: the whole tick).
         p None: ingest only, returns None. Else (rows, frame_counts): per channel the first k rows of the
         scoped search of its call so far (scopes None: TFP_SCOPE_ANY) and its frame count."""
-        pcm = np.ascontiguousarray(pcm, np.int16)
-        assert pcm.ndim == 2 and pcm.shape[0] == self.nchannels
+        return self._push(np.ascontiguousarray(pcm, np.int16), None, p, scopes, k, nsamples)
+
+    def push_g711(self, codes: np.ndarray, law: int, p: SearchParams = None, scopes=None, k: int = 1, nsamples=None):
+        """push over G.711 codes uint8[nchannels, tick] of TFP_G711_ULAW / TFP_G711_ALAW: the results of
+        push(g711_decode(codes, law), ...), the codes expanded on the GPU."""
+        return self._push(np.ascontiguousarray(codes, np.uint8), int(law), p, scopes, k, nsamples)
+
+    def _push(self, tick, law, p, scopes, k, nsamples):
+        assert tick.ndim == 2 and tick.shape[0] == self.nchannels
         n, k = self.nchannels, int(k)
         ns = None if nsamples is None else np.ascontiguousarray(nsamples, np.int32)
         sc = None if scopes is None else np.ascontiguousarray(scopes, np.int32)
         if (ns is not None and len(ns) != n) or (sc is not None and len(sc) != n):
             raise ValueError("one entry per channel")
         out, counts, fc = (Candidate * max(1, n * max(k, 1)))(), (C.c_int32 * n)(), (C.c_int32 * n)()
-        self._owner._chk(self._fn("_push")(self._h, pcm.ctypes.data, pcm.shape[1], None if ns is None else ns.ctypes.data,
-                                           C.byref(p) if p is not None else None, None if sc is None else sc.ctypes.data,
-                                           k, out, counts, fc))
+        rest = (None if ns is None else ns.ctypes.data, C.byref(p) if p is not None else None,
+                None if sc is None else sc.ctypes.data, k, out, counts, fc)
+        if law is None:
+            rc = self._fn("_push")(self._h, tick.ctypes.data, tick.shape[1], *rest)
+        else:
+            rc = self._fn("_push_g711")(self._h, tick.ctypes.data, tick.shape[1], law, *rest)
+        self._owner._chk(rc)
         if p is None:
             return None
         return Engine._candidates(out, counts, n, k), list(fc)
+
+    def verdict(self, total_samples, p: SearchParams, scopes=None):
+        """tfp_live_verdict: per channel a dict of leader / rival ({"audio_uuid", "match_count", "clip_id"} or
+        None), remaining, complete and decided, for calls planned to reach total_samples[c] samples."""
+        n = self.nchannels
+        tot = np.ascontiguousarray(total_samples, np.int64)
+        sc = None if scopes is None else np.ascontiguousarray(scopes, np.int32)
+        if len(tot) != n or (sc is not None and len(sc) != n):
+            raise ValueError("one entry per channel")
+        out = (LiveVerdict * n)()
+        self._owner._chk(self._fn("_verdict")(self._h, tot.ctypes.data, C.byref(p) if p is not None else None,
+                                              None if sc is None else sc.ctypes.data, out))
+
+        def cand(c, has):
+            return {"audio_uuid": c.uuid.decode(), "match_count": c.match_count, "clip_id": c.clip_id} if has else None
+        return [{"leader": cand(v.leader, v.has_leader), "rival": cand(v.rival, v.has_rival), "remaining": v.remaining,
+                 "complete": bool(v.complete), "decided": bool(v.decided)} for v in out]
 
     def close(self):
         # the destroy call uses the owner: an object outliving its owner's close() was destroyed by it

@@ -759,6 +759,61 @@ int tfp_live_samples(tfp_live* lv, int32_t channel, int64_t* nsamples);
  * final frame again). Any pointer may be NULL. */
 int tfp_live_stats(tfp_live* lv, int64_t* incremental_pushes, int64_t* general_pushes, int64_t* rebuilds,
                    int64_t* frames_fingerprinted, int64_t* frames_added);
+/* tfp_live_push over a channel's native G.711 payload: codes[nchannels][tick_samples], one byte per
+ * sample, of law TFP_G711_ULAW or TFP_G711_ALAW (any other law is TFP_E_ARG, nothing ingested). The
+ * codes cross to the GPU as bytes and the scatter expands them into the int16 history
+ * (aubio_source's table[code], fp_handler.c:604, :633), so int16, mu-law and A-law pushes of one call
+ * may follow one another in any order. Every other argument and rule is tfp_live_push's, the
+ * all-or-nothing capacity check included. Rows, counts, frame counts and every later verdict equal
+ * those of tfp_live_push on tfp_g711_decode(codes), bit for bit. tfp_g711_stats counts the scatter
+ * among its stream_launches (a tick whose scatter expanded codes) and the samples taken among codes. */
+int tfp_live_push_g711(tfp_live* lv, const uint8_t* codes, int32_t tick_samples, int32_t law, const int32_t* nsamples,
+                       const tfp_search_params* params, const int32_t* scopes, int32_t k, tfp_candidate* out,
+                       int32_t* counts, int32_t* frame_counts);
+
+/* The early verdict: when the margin suffices. record_voice records a planned `duration`
+ * (application_handler.c:163, :248-312), so with S_c samples of total_samples[c] in, the frames still
+ * to come are known: F_tot - F_fin, F_tot = tfp_frame_count(total_samples[c]), F_fin = floor(S_c / 256).
+ *
+ * Per channel: the base count of a clip is its count over the final frames [0, F_fin) while
+ * S_c < total_samples[c] (the provisional tail is left out: it can still change), and over every frame,
+ * tail included, once S_c == total_samples[c] (`complete`; then it is tfp_live_push's count).
+ * remaining = F_tot - F_fin, 0 when complete. The candidates are the enrolled, not removed clips of
+ * the channel's scope that have at least one row with a non-NULL max1 (a clip without one can never
+ * score), a base count of 0 included, ordered by (base count, tie-break key) as the rows are. The
+ * leader is the greatest candidate if its base count is >= 1 (else there is neither leader nor
+ * rival); the rival is the greatest other candidate. decided = complete, or has_leader and (no rival,
+ * or (leader count, leader key) > (rival count + remaining, rival key)); keys are distinct.
+ *
+ * decided implies that row 0 of tfp_search_scoped_pcm_batch on any recording of total_samples[c]
+ * samples that extends the S_c samples so far is the leader: the recording's frames [0, F_fin) are the
+ * final frames, so every clip's count there is its base count plus at most one per remaining frame
+ * and the leader's is at least its base count; every candidate but the leader is bounded by the
+ * rival, and a clip that is no candidate never scores. The verdict holds for the index, the params and
+ * the scope of the call that produced it.
+ *
+ * The call ingests nothing. It brings the count rows up to date exactly as a searching push of no
+ * samples would (the same check of what the rows were built for, rebuild and adds; tfp_live_stats
+ * counts the rebuild and the frames added, a verdict is not counted as a push), then one launch
+ * selects the two greatest candidates per channel. total_samples[c] < S_c or > max_samples is
+ * TFP_E_ARG naming the channel; params->coefs != 1 (the dialplan passes 1, application_handler.c:180)
+ * or a scope below -1 is TFP_E_ARG; nothing is written then. scopes NULL: TFP_SCOPE_ANY everywhere.
+ * An empty index gives no leader and decided = complete. Where a frame's key lies outside the vote
+ * range every channel comes back with no leader and decided = complete, and the count rows are
+ * dropped as a push drops them: a verdict that cannot be computed is undecided, never wrong.
+ * (The struct has no typedef: C keeps struct tags apart from function names, a typedef would clash.) */
+struct tfp_live_verdict {
+  tfp_candidate leader;   /* zeroed when has_leader == 0; match_count = its base count */
+  tfp_candidate rival;    /* zeroed when has_rival == 0;  match_count = its base count */
+  int32_t has_leader, has_rival;
+  int32_t remaining;      /* frames of the finished recording that are not final yet */
+  int32_t complete;       /* S_c == total_samples[c] */
+  int32_t decided;
+};
+/* out[nchannels]: every channel's verdict against its planned length (record_voice's duration,
+ * application_handler.c:163, :248-312). */
+int tfp_live_verdict(tfp_live* lv, const int64_t* total_samples, const tfp_search_params* params,
+                     const int32_t* scopes, struct tfp_live_verdict* out /*[nchannels]*/);
 
 /* ---- device groups: the node's GPUs behind one index (new in round 3) -------------------
  * The module's enrolled DB sharded over one engine per listed device (the reference
@@ -904,6 +959,17 @@ int tfp_group_live_samples(tfp_group_live* lv, int32_t channel, int64_t* nsample
  * columns of fp_handler.c:367-374's rows). */
 int tfp_group_live_stats(tfp_group_live* lv, int32_t shard, int64_t* incremental_pushes, int64_t* general_pushes,
                          int64_t* rebuilds, int64_t* frames_fingerprinted, int64_t* frames_added);
+/* tfp_live_push_g711 on a group: the codes go to every shard as bytes and each shard's scatter
+ * expands them (aubio_source's table[code], fp_handler.c:604, :633). */
+int tfp_group_live_push_g711(tfp_group_live* lv, const uint8_t* codes, int32_t tick_samples, int32_t law,
+                             const int32_t* nsamples, const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                             tfp_candidate* out, int32_t* counts, int32_t* frame_counts);
+/* tfp_live_verdict on a group (application_handler.c:163, :248-312): every shard selects its two
+ * greatest candidates over its own clips under the group-wide tie-break keys; the top 2 of their union
+ * (the top 2 of a union is the top 2 of the parts' top 2s) go through the rule once. clip_id is the
+ * shard. Arguments and failures as tfp_live_verdict; a failing shard fails the call. */
+int tfp_group_live_verdict(tfp_group_live* lv, const int64_t* total_samples, const tfp_search_params* params,
+                           const int32_t* scopes, struct tfp_live_verdict* out /*[nchannels]*/);
 /* G.711 codes on a group (aubio_source's table[code], fp_handler.c:604, :633; as the engine calls):
  * a fingerprint batch's clips are expanded by the shard that fingerprints them; a search batch is
  * expanded by every shard, or, where an int16 batch would be query-sharded, each shard expands and

@@ -1599,3 +1599,152 @@ void fp_channel_close(fp_channel* ch)
 		ast_free(ch);
 	}
 }
+
+/* ---- live calls: the record loop's ticks in, an exact early verdict out ---------------------
+ * record_voice (application_handler.c:248-312) reads one voice frame per channel every 20 ms for a
+ * planned `duration` (:163), and the application searches the recording in its context once it is
+ * complete (:152-185). A live object takes the frames of all its channels tick by tick
+ * (tfp_group_live_push / tfp_group_live_push_g711: the calls stay on the GPUs from their first
+ * sample) and fp_live_verdict says per channel whether the search of the finished recording is
+ * already settled (tfp_group_live_verdict). Used by one thread, the one that aggregates the tick. */
+struct fp_live {
+	tfp_group_live* lv;
+	int32_t nch, sr;
+};
+
+static int64_t samples_of_ms(int32_t sr, int ms)
+{
+	return ((int64_t)sr * ms + 999) / 1000; /* as fp_channel_open sizes its recording */
+}
+
+fp_live* fp_live_open(int nchannels, int sample_rate, int max_ms)
+{
+	fp_live* lv;
+
+	if(g_tfp == NULL || nchannels <= 0 || sample_rate <= 0 || max_ms <= 0) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	lv = ast_calloc(1, sizeof(*lv));
+	if(lv == NULL) {
+		return NULL;
+	}
+	lv->nch = nchannels;
+	lv->sr = sample_rate;
+	if(tfp_group_live_create(g_tfp, nchannels, sample_rate, samples_of_ms(sample_rate, max_ms), &lv->lv) != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not open %d live calls: %s\n", nchannels, tfp_group_last_error(g_tfp));
+		ast_free(lv);
+		return NULL;
+	}
+	return lv;
+}
+
+bool fp_live_push(fp_live* lv, const int16_t* slin, int tick_samples, const int32_t* nsamples)
+{
+	if(lv == NULL || slin == NULL || tick_samples <= 0) {
+		return false;
+	}
+	if(tfp_group_live_push(lv->lv, slin, tick_samples, nsamples, NULL, NULL, 0, NULL, NULL, NULL) != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not push a tick: %s\n", tfp_group_last_error(g_tfp));
+		return false;
+	}
+	return true;
+}
+
+bool fp_live_push_g711(fp_live* lv, const uint8_t* payload, int tick_samples, int law, const int32_t* nsamples)
+{
+	if(lv == NULL || payload == NULL || tick_samples <= 0 || (law != TFP_G711_ULAW && law != TFP_G711_ALAW)) {
+		return false;
+	}
+	if(tfp_group_live_push_g711(lv->lv, payload, tick_samples, law, nsamples, NULL, NULL, 0, NULL, NULL, NULL) != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not push a tick: %s\n", tfp_group_last_error(g_tfp));
+		return false;
+	}
+	return true;
+}
+
+struct ast_json* fp_live_verdict(fp_live* lv, const char* const* contexts, const int* duration_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high)
+{
+	tfp_search_params p;
+	struct tfp_live_verdict* v;
+	int64_t* total;
+	int32_t* scopes;
+	int32_t c;
+	int rc;
+	struct ast_json* j_res = NULL;
+
+	if(lv == NULL || contexts == NULL || duration_ms == NULL) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	for(c = 0; c < lv->nch; c++) {
+		if(contexts[c] == NULL || duration_ms[c] <= 0) {
+			ast_log(LOG_WARNING, "Wrong input parameter.\n");
+			return NULL;
+		}
+	}
+	/* coefs = 1: what the dialplan passes (application_handler.c:180), and what a verdict's counts are */
+	if(search_params(&p, contexts[0], 1, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	v = ast_calloc(lv->nch, sizeof(*v));
+	total = ast_calloc(lv->nch, sizeof(*total));
+	scopes = ast_calloc(lv->nch, sizeof(*scopes));
+	if(v != NULL && total != NULL && scopes != NULL) {
+		for(c = 0; c < lv->nch; c++) {
+			total[c] = samples_of_ms(lv->sr, duration_ms[c]);
+			scopes[c] = scope_of_context(contexts[c], false); /* as fp_search_fingerprint_in_context maps it */
+		}
+		rc = tfp_group_live_verdict(lv->lv, total, &p, scopes, v);
+		if(rc != TFP_OK) {
+			ast_log(LOG_ERROR, "Could not take the calls' verdicts: %s\n", tfp_group_last_error(g_tfp));
+		}
+		else {
+			j_res = ast_json_array_create();
+		}
+		for(c = 0; j_res != NULL && c < lv->nch; c++) {
+			struct ast_json* j_tmp = NULL;
+			int64_t ns = 0;
+			if(v[c].has_leader != 0) {
+				j_tmp = fpc_get_audio_list_info(v[c].leader.uuid); /* fp_handler.c:394-401 */
+				if(j_tmp == NULL) {
+					ast_log(LOG_ERROR, "Could not get audio list info. uuid[%s]\n", v[c].leader.uuid);
+				}
+			}
+			if(j_tmp == NULL) {
+				j_tmp = ast_json_object_create();
+			}
+			else {
+				tfp_group_live_samples(lv->lv, c, &ns);
+				ast_json_object_set(j_tmp, "frame_count", ast_json_integer_create(tfp_frame_count(ns)));
+				ast_json_object_set(j_tmp, "match_count", ast_json_integer_create(v[c].leader.match_count));
+			}
+			ast_json_object_set(j_tmp, "decided", ast_json_integer_create(v[c].decided));
+			ast_json_object_set(j_tmp, "complete", ast_json_integer_create(v[c].complete));
+			ast_json_object_set(j_tmp, "remaining", ast_json_integer_create(v[c].remaining));
+			ast_json_object_set(j_tmp, "rival_match_count",
+					ast_json_integer_create(v[c].has_rival != 0 ? v[c].rival.match_count : -1));
+			ast_json_array_append(j_res, j_tmp);
+		}
+	}
+	ast_free(v);
+	ast_free(total);
+	ast_free(scopes);
+	return j_res;
+}
+
+void fp_live_reset(fp_live* lv, int channel)
+{
+	if(lv != NULL && channel < lv->nch) {
+		tfp_group_live_reset(lv->lv, channel);
+	}
+}
+
+void fp_live_close(fp_live* lv)
+{
+	if(lv != NULL) {
+		tfp_group_live_destroy(lv->lv);
+		ast_free(lv);
+	}
+}

@@ -145,4 +145,35 @@ struct ast_json* fp_channel_search(fp_channel* ch, const char* context, const in
 		const int freq_ignore_low, const int freq_ignore_high);
 void fp_channel_close(fp_channel* ch);
 
+/* New: live calls, for a record loop that wants the application's answer as early as it is certain
+ * (application_handler.c:152-185 with the planned duration of :163; record_voice :248-312). One object
+ * holds nchannels calls on the GPUs from their first sample; the thread that gathers the channels'
+ * 20 ms frames into one tick pushes it, and asks for the verdicts when it likes. Open after fp_init
+ * with max_ms >= the longest duration; close before fp_term.
+ * fp_live_push: slin[nchannels][tick_samples], channel c takes its first nsamples[c] samples
+ * (NULL: the whole tick; 0: the channel delivered nothing). fp_live_push_g711: the same over the
+ * channels' native payload, one byte per sample, law TFP_G711_ULAW or TFP_G711_ALAW, expanded on the
+ * GPU (aubio_source's table[code], fp_handler.c:604, :633); SLIN and G.711 ticks may mix. Both only
+ * ingest. A tick that would take any channel past max_ms is refused for every channel.
+ * fp_live_verdict: contexts[nchannels] and duration_ms[nchannels] (the planned recording of each
+ * call, >= what it has taken so far); a JSON array with one object per channel holding "decided",
+ * "complete" (0 / 1), "remaining" (frames of the finished recording that can still change a count)
+ * and "rival_match_count" (the best other clip's count so far, -1: the context has no other clip
+ * that can match), and, when a clip leads, the fields of fp_search_fingerprint_info (uuid, name,
+ * context, hash, "match_count": its count over the frames that are final, every frame once complete;
+ * "frame_count": the frames so far). decided = 1 with a leader: fp_search_fingerprint_in_context on
+ * the finished recording will return this clip first, whatever audio follows; decided = 1 without:
+ * the call is complete and nothing matched. The context maps to a scope as for
+ * fp_search_fingerprint_in_context; coefs is 1, as the dialplan passes it (application_handler.c:180).
+ * NULL: bad arguments (a duration below what the channel has taken among them).
+ * fp_live_reset: a new call on `channel` (< 0: on every channel). */
+typedef struct fp_live fp_live;
+fp_live* fp_live_open(int nchannels, int sample_rate, int max_ms);
+bool fp_live_push(fp_live* lv, const int16_t* slin, int tick_samples, const int32_t* nsamples);
+bool fp_live_push_g711(fp_live* lv, const uint8_t* payload, int tick_samples, int law, const int32_t* nsamples);
+struct ast_json* fp_live_verdict(fp_live* lv, const char* const* contexts, const int* duration_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high);
+void fp_live_reset(fp_live* lv, int channel);
+void fp_live_close(fp_live* lv);
+
 #endif
