@@ -31,6 +31,7 @@
 #include "tfp_kernels.hpp"
 #include "tfp_live.hpp"
 #include "tfp_math.hpp"
+#include "tfp_query_plan.hpp"
 #include "tfp_rank.hpp"
 #include "tfp_census.hpp"
 #include "tfp_scope.hpp"
@@ -1856,6 +1857,41 @@ void fill_results(tfp_engine* e, const std::vector<unsigned long long>& keys, co
 
 bool valid_params(const tfp_search_params* P) { return P && P->coefs >= 1 && P->coefs <= 2; }
 
+// The queries' frame values (q1, q2) on the device (e->q), as the frames forms search them.
+int upload_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq) {
+  const int64_t nf = qoff[nq] - qoff[0];
+  std::vector<double> q(2 * (nf + 1));
+  for (int64_t i = 0; i < nf; i++) {
+    q[2 * i] = frames[qoff[0] + i].q1;
+    q[2 * i + 1] = frames[qoff[0] + i].q2;
+  }
+  return upload(e, e->q, q.data(), sizeof(double) * q.size());
+}
+
+// ---- the argument checks the forms share; `what` names the form in the message ----
+int check_k(tfp_engine* e, const char* what, int32_t k) {
+  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "%s: k = %d outside [1, %d]", what, k, TFP_RANK_MAX);
+  return TFP_OK;
+}
+
+int check_params(tfp_engine* e, const char* what, const tfp_search_params* P) {
+  return valid_params(P) ? TFP_OK : fail(e, TFP_E_ARG, "%s: coefs outside [1, 2]", what);
+}
+
+// scopes (or nullptr: none to check): one per `item` ("query", "recording"), TFP_SCOPE_ANY or above.
+int check_scopes(tfp_engine* e, const char* what, const int32_t* scopes, int32_t n, const char* item) {
+  for (int32_t i = 0; scopes && i < n; i++)
+    if (scopes[i] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "%s: scope %d of %s %d", what, scopes[i], item, i);
+  return TFP_OK;
+}
+
+// The caller's offsets off[0..n] never fall (tfp_query_plan.hpp); the frames forms call theirs qoffsets.
+int check_monotone(tfp_engine* e, const int64_t* off, int32_t n, bool samples) {
+  if (offsets_monotone(off, n)) return TFP_OK;
+  if (samples) return fail(e, TFP_E_ARG, "offsets not monotone");
+  return fail(e, TFP_E_ARG, "qoffsets not monotone");
+}
+
 // ---- ranked search (tfp_rank.hpp): keys[q * K + r] = row r of query q's result set, 0 past the last
 
 // The per-column scope table (tfp_scope.hpp) of the current index: built when the index version or a
@@ -1897,6 +1933,47 @@ int ensure_scopes(tfp_engine* e, const int32_t* scopes, int32_t nq, hipStream_t 
   return upload(e, e->scope_q, scopes, sizeof(int32_t) * (size_t)nq, s);
 }
 
+// The vote forms' result: nkeys keys with the bad flag after them (rank_keys, and rank_pin for the copy
+// back). vote_keys_begin reserves both and zeroes the flag; vote_keys_end copies keys and flag back, waits,
+// and fills keys unless the flag is set (*bad).
+int vote_keys_begin(tfp_engine* e, size_t nkeys, unsigned long long** d_keys, int32_t** d_bad, hipStream_t s) {
+  HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+  *d_keys = e->rank_keys.as<unsigned long long>();
+  *d_bad = reinterpret_cast<int32_t*>(*d_keys + nkeys);
+  HIPCHK(e, hipMemsetAsync(*d_bad, 0, sizeof(unsigned long long), s));
+  return TFP_OK;
+}
+
+int vote_keys_end(tfp_engine* e, size_t nkeys, std::vector<unsigned long long>& keys, bool* bad, hipStream_t s) {
+  HIPCHK(e, hipMemcpyAsync(e->rank_pin.p, e->rank_keys.p, sizeof(unsigned long long) * (nkeys + 1), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  const unsigned long long* h = e->rank_pin.as<unsigned long long>();
+  *bad = (uint32_t)h[nkeys] != 0;
+  if (!*bad) std::copy(h, h + nkeys, keys.begin());
+  return TFP_OK;
+}
+
+// The general forms' set-up over the merged index (C > 0 columns): the batch's offsets and frame boxes on
+// the device, the tolerance's ranges and clip-set cells (*cells), the scan scratch for *chunk queries at a
+// time and, with scopes, the scope table and the queries' scopes.
+int general_setup(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
+                  const int32_t* scopes, CellCache** cells, int64_t* chunk, hipStream_t s) {
+  const int64_t nf = qo[nq];
+  int rc;
+  if ((rc = ensure_qoff(e, qo, s))) return rc;
+  HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (nf + 1)));
+  HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->boxes.as<FrameBox>(), nullptr, 0, s));
+  if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_cells(e, sc.tole, s))) return rc;
+  *cells = &e->tc.cells.active();
+  if ((rc = ensure_scan_scratch(e, nq, e->ncols, chunk, s))) return rc;
+  if ((*cells)->valid && (*cells)->ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
+    (void)hipGetLastError();
+    (*cells)->invalidate();  // every frame takes the row scan
+  }
+  return scopes ? ensure_scopes(e, scopes, nq, s) : TFP_OK;
+}
+
 // The vote form (coefs = 1): *bad when a frame's key lies outside the vote range (keys undefined).
 // scopes (or nullptr): the queries' scopes, for the scoped kernels (tfp_scope.hpp).
 int rank_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
@@ -1910,11 +1987,9 @@ int rank_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const d
   chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(chunk, 65535), nq));
   const size_t nkeys = (size_t)nq * K;
   HIPCHK(e, e->rank_part.reserve(sizeof(unsigned long long) * (size_t)chunk * nb * K));
-  HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
-  HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
-  unsigned long long* d_keys = e->rank_keys.as<unsigned long long>();
-  int32_t* d_bad = reinterpret_cast<int32_t*>(d_keys + nkeys);
-  HIPCHK(e, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
+  unsigned long long* d_keys;
+  int32_t* d_bad;
+  if ((rc = vote_keys_begin(e, nkeys, &d_keys, &d_bad, s))) return rc;
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int32_t n = (int32_t)std::min<int64_t>(chunk, nq - q0);
     if (scopes)
@@ -1927,33 +2002,18 @@ int rank_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const d
                                  e->tiekey.as<int32_t>(), K, e->rank_part.as<unsigned long long>(), d_keys + q0 * K, d_bad,
                                  s));
   }
-  HIPCHK(e, hipMemcpyAsync(e->rank_pin.p, d_keys, sizeof(unsigned long long) * (nkeys + 1), hipMemcpyDeviceToHost, s));
-  HIPCHK(e, hipStreamSynchronize(s));
-  const unsigned long long* h = e->rank_pin.as<unsigned long long>();
-  *bad = (uint32_t)h[nkeys] != 0;
-  if (!*bad) std::copy(h, h + nkeys, keys.begin());
-  return TFP_OK;
+  return vote_keys_end(e, nkeys, keys, bad, s);
 }
 
 // The general form (any coefs / tolerance / key), over the sorted rows of the merged index.
 int rank_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
                  int32_t K, const int32_t* scopes, std::vector<unsigned long long>& keys, hipStream_t s) {
   const int32_t C = e->ncols;
-  const int64_t R = e->nrows, nf = qo[nq];
+  const int64_t R = e->nrows;
   if (C <= 0 || R <= 0) return TFP_OK;  // an empty index: no row
-  int rc;
-  if ((rc = ensure_qoff(e, qo, s))) return rc;
-  HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (nf + 1)));
-  HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->boxes.as<FrameBox>(), nullptr, 0, s));
-  if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_cells(e, sc.tole, s))) return rc;
-  CellCache* cells = &e->tc.cells.active();
+  CellCache* cells;
   int64_t chunk;
-  if ((rc = ensure_scan_scratch(e, nq, C, &chunk, s))) return rc;
-  if (cells->valid && cells->ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
-    (void)hipGetLastError();
-    cells->invalidate();  // every frame takes the row scan
-  }
-  if (scopes && (rc = ensure_scopes(e, scopes, nq, s))) return rc;
+  if (int rc = general_setup(e, qo, nq, d_q, sc, scopes, &cells, &chunk, s)) return rc;
   const size_t nkeys = (size_t)nq * K;
   HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
   HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
@@ -1991,8 +2051,7 @@ int rank_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_
   int rc = rebuild(e);  // synchronous on e->stream
   if (rc) return rc;
   const SearchConsts sc = search_consts(P);
-  std::vector<int64_t> qo(h_qoff, h_qoff + nq + 1);
-  for (auto& v : qo) v -= h_qoff[0];
+  const std::vector<int64_t> qo = relative_offsets(h_qoff, nq);
   keys.assign((size_t)nq * K, 0ull);
   if (sc.coefs == 1) {
     if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
@@ -2042,21 +2101,11 @@ int census_vote(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const
 int census_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const SearchConsts& sc,
                    const int32_t* scopes, int32_t nbins, int32_t* hist, hipStream_t s) {
   const int32_t C = e->ncols;
-  const int64_t R = e->nrows, nf = qo[nq];
+  const int64_t R = e->nrows;
   if (C <= 0 || R <= 0) return TFP_OK;  // an empty index: no count above 0
-  int rc;
-  if ((rc = ensure_qoff(e, qo, s))) return rc;
-  HIPCHK(e, e->boxes.reserve(sizeof(FrameBox) * (nf + 1)));
-  HIPCHK(e, launch_prep_boxes(d_q, nf, sc, e->boxes.as<FrameBox>(), nullptr, 0, s));
-  if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_cells(e, sc.tole, s))) return rc;
-  CellCache* cells = &e->tc.cells.active();
+  CellCache* cells;
   int64_t chunk;
-  if ((rc = ensure_scan_scratch(e, nq, C, &chunk, s))) return rc;
-  if (cells->valid && cells->ensure_entries(s) != hipSuccess) {  // (the cells form's candidates)
-    (void)hipGetLastError();
-    cells->invalidate();  // every frame takes the row scan
-  }
-  if ((rc = ensure_scopes(e, scopes, nq, s))) return rc;
+  if (int rc = general_setup(e, qo, nq, d_q, sc, scopes, &cells, &chunk, s)) return rc;
   const size_t n = (size_t)nq * nbins;
   HIPCHK(e, e->census_hist.reserve(sizeof(int32_t) * (n + 1)));
   HIPCHK(e, e->census_pin.reserve(sizeof(int32_t) * (n + 1)));
@@ -2087,8 +2136,7 @@ int census_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
   int rc = rebuild(e);  // synchronous on e->stream
   if (rc) return rc;
   const SearchConsts sc = search_consts(P);
-  std::vector<int64_t> qo(h_qoff, h_qoff + nq + 1);
-  for (auto& v : qo) v -= h_qoff[0];
+  const std::vector<int64_t> qo = relative_offsets(h_qoff, nq);
   std::fill(hist, hist + (size_t)nq * nbins, 0);
   bool done = qo[nq] == 0;  // no frame: every live clip has count 0, and nothing is launched
   if (!done && sc.coefs == 1) {
@@ -2121,23 +2169,20 @@ int census_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* 
   return TFP_OK;
 }
 
-// The arguments every census entry point checks (as scope_args); fills sv with a scope per query.
+// The arguments every census entry point checks; fills sv with a scope per query.
 int census_args(tfp_engine* e, const tfp_search_params* P, int32_t nq, const int32_t* scopes, const void* need_bins,
                 std::vector<int32_t>& sv) {
   if (nq < 0 || !need_bins) return fail(e, TFP_E_ARG, "census: bad query count or NULL need_bins");
-  if (!valid_params(P)) return fail(e, TFP_E_ARG, "census: coefs outside [1, 2]");
+  int rc = check_params(e, "census", P);
+  if (rc || (rc = check_scopes(e, "census", scopes, nq, "query"))) return rc;
   sv.assign((size_t)nq, kScopeAny);
-  for (int32_t i = 0; scopes && i < nq; i++) {
-    if (scopes[i] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "census: scope %d of query %d", scopes[i], i);
-    sv[i] = scopes[i];
-  }
+  if (scopes) sv.assign(scopes, scopes + nq);
   return TFP_OK;
 }
 
 // *need_bins = the longest query's frames + 1; TFP_E_CAPACITY when nbins is below it.
 int census_bins(tfp_engine* e, const int64_t* off, int32_t nq, int32_t nbins, const int32_t* hist, int32_t* need_bins) {
-  int64_t need = 1;
-  for (int32_t i = 0; i < nq; i++) need = std::max<int64_t>(need, off[i + 1] - off[i] + 1);
+  const int64_t need = census_need(off, nq);
   if (need > INT32_MAX) return fail(e, TFP_E_ARG, "census: a query of %lld frames", (long long)need - 1);
   *need_bins = (int32_t)need;
   if (nbins < need) return fail(e, TFP_E_CAPACITY, "census: %d bins, the longest query needs %lld", nbins, (long long)need);
@@ -2165,31 +2210,8 @@ void fill_candidates(tfp_engine* e, const std::vector<unsigned long long>& keys,
   }
 }
 
-int rank_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, const void* out, const void* counts) {
-  if (!e) return TFP_E_ARG;
-  if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
-  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "ranked search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
-  if (!valid_params(P)) return fail(e, TFP_E_ARG, "ranked search: coefs outside [1, 2]");
-  return TFP_OK;
-}
-
-// rank_args, and a scope per query of TFP_SCOPE_ANY or above.
-int scope_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, const int32_t* scopes, const void* out,
-               const void* counts) {
-  int rc = rank_args(e, P, k, nq, out, counts);
-  if (rc) return rc;
-  if (nq && !scopes) return fail(e, TFP_E_ARG, "scoped search: scopes is NULL");
-  for (int32_t i = 0; i < nq; i++)
-    if (scopes[i] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "scoped search: scope %d of query %d", scopes[i], i);
-  return TFP_OK;
-}
-
 // ---- sliding search (tfp_slide.hpp): keys[j * K + r] = row r of window j, 0 past the last. fo: the
 // recordings' relative frame offsets into d_q; woff: the first window of each recording.
-
-// The tolerances at which the vote form runs: those at which the key bitsets hold every column, a
-// live index delta's included (delta_tol_ok), so the vote form never needs the delta merged.
-bool slide_vote_tol(double tole) { return delta_tol_ok(tole); }
 
 // The vote form: *bad when a frame's key lies outside the vote range (keys undefined).
 int slide_vote(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, const double* d_q, const SearchConsts& sc,
@@ -2223,23 +2245,16 @@ int slide_vote(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, cons
   HIPCHK(e, e->slide_slots.reserve(sizeof(int16_t) * (size_t)(nf + 1)));
   if ((rc = upload(e, e->slide_runs, runs.data(), sizeof(SlideRun) * runs.size(), s))) return rc;
   HIPCHK(e, e->rank_part.reserve(sizeof(unsigned long long) * (size_t)maxw * nb * K));
-  HIPCHK(e, e->rank_keys.reserve(sizeof(unsigned long long) * (nkeys + 1)));
-  HIPCHK(e, e->rank_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
-  unsigned long long* d_keys = e->rank_keys.as<unsigned long long>();
-  int32_t* d_bad = reinterpret_cast<int32_t*>(d_keys + nkeys);
-  HIPCHK(e, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
+  unsigned long long* d_keys;
+  int32_t* d_bad;
+  if ((rc = vote_keys_begin(e, nkeys, &d_keys, &d_bad, s))) return rc;
   HIPCHK(e, launch_slide_keys(d_q, nf, sc, e->slide_slots.as<int16_t>(), d_bad, s));
   for (const Group& g : groups)
     HIPCHK(e, launch_slide_vote(e->slide_slots.as<int16_t>(), e->slide_runs.as<SlideRun>() + g.r0, (int32_t)(g.r1 - g.r0),
                                 (int32_t)g.n, window, hop, e->tc.ranges.active().key_bits.as<uint32_t>(), C,
                                 e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
                                 e->rank_part.as<unsigned long long>(), d_keys + g.w0 * K, s));
-  HIPCHK(e, hipMemcpyAsync(e->rank_pin.p, d_keys, sizeof(unsigned long long) * (nkeys + 1), hipMemcpyDeviceToHost, s));
-  HIPCHK(e, hipStreamSynchronize(s));
-  const unsigned long long* h = e->rank_pin.as<unsigned long long>();
-  *bad = (uint32_t)h[nkeys] != 0;
-  if (!*bad) std::copy(h, h + nkeys, keys.begin());
-  return TFP_OK;
+  return vote_keys_end(e, nkeys, keys, bad, s);
 }
 
 // The general form: the windows' frame values laid end to end in chunks of <= 256 MB, each chunk a
@@ -2284,7 +2299,9 @@ int slide_core(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, cons
   const SearchConsts sc = search_consts(P);
   const int64_t nw = woff[nrec];
   keys.assign((size_t)nw * K, 0ull);
-  if (sc.coefs == 1 && slide_vote_tol(sc.tole)) {
+  // the vote form runs at the tolerances whose key bitsets hold a live index delta's columns too, so it
+  // never needs the delta merged
+  if (sc.coefs == 1 && delta_tol_ok(sc.tole)) {
     if (e->ncols <= 0 || e->nrows + e->delta.rows <= 0) return TFP_OK;
     bool bad = false;
     if ((rc = slide_vote(e, fo, nrec, d_q, sc, window, hop, scopes, K, woff, keys, &bad, s))) return rc;
@@ -2307,14 +2324,12 @@ int slide_args(tfp_engine* e, const tfp_search_params* P, int32_t window, int32_
                int64_t cap_windows, int64_t* nwindows, std::vector<int64_t>& woff) {
   if (nrec < 0 || !nwindows) return fail(e, TFP_E_ARG, "sliding search: bad recording count or NULL nwindows");
   if (window < 1 || hop < 1) return fail(e, TFP_E_ARG, "sliding search: window = %d, hop = %d", window, hop);
-  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "sliding search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
-  if (!valid_params(P)) return fail(e, TFP_E_ARG, "sliding search: coefs outside [1, 2]");
-  for (int32_t i = 0; scopes && i < nrec; i++)
-    if (scopes[i] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "sliding search: scope %d of recording %d", scopes[i], i);
-  woff.assign((size_t)nrec + 1, 0);
-  for (int32_t i = 0; i < nrec; i++) woff[i + 1] = woff[i] + slide_windows(fo[i + 1] - fo[i], window, hop);
+  int rc = check_k(e, "sliding search", k);
+  if (rc || (rc = check_params(e, "sliding search", P)) || (rc = check_scopes(e, "sliding search", scopes, nrec, "recording")))
+    return rc;
+  woff = window_offsets(fo, nrec, window, hop);
   *nwindows = woff[nrec];
-  if (woff[nrec] > cap_windows || woff[nrec] > INT32_MAX)
+  if (!windows_fit(woff[nrec], cap_windows))
     return fail(e, TFP_E_CAPACITY, "sliding search: %lld windows, room for %lld", (long long)woff[nrec],
                 (long long)cap_windows);
   if (woff[nrec] && (!out || !counts)) return fail(e, TFP_E_ARG, "sliding search: NULL output");
@@ -2374,12 +2389,6 @@ int align_core(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const 
   e->n_align_batches++;
   e->n_align_pairs += named;
   return TFP_OK;
-}
-
-std::vector<int64_t> relative_offsets(const int64_t* off, int32_t nq) {
-  std::vector<int64_t> qo(off, off + nq + 1);
-  for (auto& v : qo) v -= off[0];
-  return qo;
 }
 
 // The candidates' clip ids as align_core takes them: -1 past counts[q].
@@ -2598,7 +2607,7 @@ int occur_core(tfp_engine* e, const std::vector<int64_t>& fo, int32_t nrec, cons
   std::vector<OccurRow> rows;
   int64_t j = 0;
   for (int32_t r = 0; r < nrec; r++) {
-    const int64_t nw = slide_windows(fo[r + 1] - fo[r], window, hop);
+    const int64_t nw = plan_windows(fo[r + 1] - fo[r], window, hop);
     for (int64_t w = 0; w < nw; w++, j++)
       for (int32_t i = 0; i < counts[j]; i++) rows.push_back(OccurRow{r, cand[j * K + i].clip_id, w, align[j * K + i].offset});
   }
@@ -2649,7 +2658,8 @@ int tfp_device_count(int32_t* count) {
   return TFP_OK;
 }
 
-int64_t tfp_frame_count(int64_t n) { return n <= 0 ? 0 : (n + TFP_HOP - 1) / TFP_HOP; }
+static_assert(kPlanHop == TFP_HOP, "tfp_query_plan.hpp and the public header agree");
+int64_t tfp_frame_count(int64_t n) { return plan_frames(n); }
 
 int tfp_engine_create(int32_t device, tfp_engine** out) {
   if (!out) return TFP_E_ARG;
@@ -2744,10 +2754,8 @@ int fingerprint_batch_impl(tfp_engine* e, const void* pcm, bool f32, const int64
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!offsets || nclips < 0 || !nframes || (!pcm && nclips && offsets[nclips] > offsets[0]))
     return fail(e, TFP_E_ARG, "bad arguments");
-  for (int32_t c = 0; c < nclips; c++)
-    if (offsets[c + 1] < offsets[c]) return fail(e, TFP_E_ARG, "offsets not monotone");
-  int64_t need = 0;
-  for (int32_t c = 0; c < nclips; c++) need += tfp_frame_count(offsets[c + 1] - offsets[c]);
+  if (int rc = check_monotone(e, offsets, nclips, true)) return rc;
+  const int64_t need = sample_frame_offsets(offsets, nclips)[nclips];
   *nframes = need;
   if (need > 0 && (!out || cap < need)) return fail(e, TFP_E_CAPACITY, "need %lld frames", (long long)need);
   if (need == 0) return TFP_OK;
@@ -3121,12 +3129,7 @@ int tfp_search_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff
   std::vector<unsigned long long> keys(nq, 0ull);
   if (valid_params(P) && nq) {  // coefs out of range: NULL for every query (fp_handler.c:247-250)
     HIPCHK(e, hipSetDevice(e->device));
-    std::vector<double> q(2 * (nf + 1));
-    for (int64_t i = 0; i < nf; i++) {
-      q[2 * i] = frames[qoff[0] + i].q1;
-      q[2 * i + 1] = frames[qoff[0] + i].q2;
-    }
-    int rc = upload(e, e->q, q.data(), sizeof(double) * q.size());
+    int rc = upload_frames(e, frames, qoff, nq);
     if (rc) return rc;
     if ((rc = search_core(e, qoff, nq, e->q.as<double>(), P, keys, nullptr, e->stream))) return rc;
   }
@@ -3144,38 +3147,74 @@ int tfp_search(tfp_engine* e, const tfp_frame* frames, int32_t nframes, const tf
 static_assert(kRankMax == TFP_RANK_MAX, "tfp_rank.hpp and the public header agree");
 
 namespace {
-// The queries' frame values (q1, q2) on the device (e->q), as the frames forms search them.
-int upload_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq) {
-  const int64_t nf = qoff[nq] - qoff[0];
-  std::vector<double> q(2 * (nf + 1));
-  for (int64_t i = 0; i < nf; i++) {
-    q[2 * i] = frames[qoff[0] + i].q1;
-    q[2 * i + 1] = frames[qoff[0] + i].q2;
-  }
-  return upload(e, e->q, q.data(), sizeof(double) * q.size());
-}
+// Where a batch's frame values come from: the caller's frames, or int16 samples fingerprinted here.
+// off[0..n] are the caller's offsets into either. Every form's body is written once over this; its
+// public entry points build the source and call the body.
+struct QuerySrc {
+  const void* data;  // query i is off[i] .. off[i + 1] of it: tfp_frame, or with samples int16 at sample rate sr
+  const int64_t* off;
+  int32_t sr;
+  bool samples;
+  bool fingerprinted = false;  // materialise() queued a fingerprint that settle() waits for
 
-// tfp_search_ranked_batch, and with align its rows' alignments (tfp_search_aligned_batch).
-// scopes (or nullptr): tfp_search_scoped_batch.
-int search_ranked_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
-                         const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align,
-                         const int32_t* scopes = nullptr) {
-  int rc = rank_args(e, P, k, nq, out, counts);
-  if (rc) return rc;
-  for (int32_t i = 0; i < nq; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
-  const int64_t nf = nq ? qoff[nq] - qoff[0] : 0;
-  if (nf && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
-  std::vector<unsigned long long> keys((size_t)nq * k, 0ull);
-  if (nq) {
-    HIPCHK(e, hipSetDevice(e->device));
-    if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
-    if ((rc = rank_core(e, qoff, nq, e->q.as<double>(), P, k, scopes, keys, e->stream))) return rc;
+  int check_offsets(tfp_engine* e, int32_t n) const { return check_monotone(e, off, n, samples); }
+  int check_data(tfp_engine* e, int64_t nframes) const {  // frames to search need their data
+    return nframes > 0 && !data ? fail(e, TFP_E_ARG, "%s", samples ? "samples are NULL" : "frames is NULL") : TFP_OK;
   }
+  // the queries' relative frame offsets (n <= 0: {0}, no offset is read)
+  std::vector<int64_t> fo(int32_t n) const { return samples ? sample_frame_offsets(off, n) : relative_offsets(off, n); }
+
+  // The frame values on the device, *d_q: frames are uploaded into e->q; samples are fingerprinted once
+  // into e->db (nothing to do without a frame). They stay there for an alignment after the search.
+  int materialise(tfp_engine* e, int32_t n, const std::vector<int64_t>& fo, const tfp_search_params* P, const double** d_q) {
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = TFP_OK;
+    if (!samples) {
+      rc = upload_frames(e, static_cast<const tfp_frame*>(data), off, n);
+    } else if (fo[n] > 0) {
+      std::vector<const void*> ptrs;
+      std::vector<int64_t> lens;
+      split_offsets(data, sizeof(int16_t), off, n, &ptrs, &lens);
+      int64_t nf;
+      rc = fingerprint_host(e, ptrs.data(), lens.data(), false, n, sr, &nf, nullptr, P->coefs == 2);
+      fingerprinted = rc == TFP_OK;
+    }
+    *d_q = samples ? e->db.as<double>() : e->q.as<double>();
+    return rc;
+  }
+
+  // After the core: the fingerprint's staging buffer is free again once the stream has drained.
+  int settle(tfp_engine* e) {
+    if (!fingerprinted) return TFP_OK;
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
+    e->stage_pending = false;
+    return TFP_OK;
+  }
+};
+
+// Ranked search (tfp_search_ranked_*_batch); with align its rows' alignments (tfp_search_aligned_*_batch),
+// scoped: scoped search (tfp_search_scoped_*_batch), a scope per query of TFP_SCOPE_ANY or above.
+int search_ranked(tfp_engine* e, QuerySrc src, int32_t nq, const tfp_search_params* P, int32_t k, tfp_candidate* out,
+                  int32_t* counts, tfp_alignment* align, bool scoped = false, const int32_t* scopes = nullptr) {
+  if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
+  int rc = check_k(e, "ranked search", k);
+  if (rc || (rc = check_params(e, "ranked search", P))) return rc;
+  if (scoped && nq && !scopes) return fail(e, TFP_E_ARG, "scoped search: scopes is NULL");
+  if ((rc = check_scopes(e, "scoped search", scopes, nq, "query")) || (rc = src.check_offsets(e, nq))) return rc;
+  const std::vector<int64_t> fo = src.fo(nq);
+  if ((rc = src.check_data(e, fo[nq]))) return rc;
+  std::vector<unsigned long long> keys((size_t)nq * k, 0ull);
+  const double* d_q = nullptr;
+  // frames run the core, hence the index build, for any query; samples only once a frame exists
+  const bool run = nq && (!src.samples || fo[nq] > 0);
+  if (run && ((rc = src.materialise(e, nq, fo, P, &d_q)) ||
+              (rc = rank_core(e, fo.data(), nq, d_q, P, k, scopes, keys, e->stream)) || (rc = src.settle(e))))
+    return rc;
   fill_candidates(e, keys, nq, k, out, counts);
-  if (align && nq)  // (the frame values are still in e->q)
-    return align_core(e, relative_offsets(qoff, nq), nq, e->q.as<double>(), P, k, candidate_ids(out, counts, nq, k).data(),
-                      align, e->stream);
+  if (align && nq) {
+    if (src.samples) memset(align, 0, sizeof(tfp_alignment) * (size_t)nq * k);  // (frames always run: align_core zeroes)
+    if (run) return align_core(e, fo, nq, d_q, P, k, candidate_ids(out, counts, nq, k).data(), align, e->stream);
+  }
   return TFP_OK;
 }
 }  // namespace
@@ -3184,7 +3223,7 @@ int tfp_search_ranked_batch(tfp_engine* e, const tfp_frame* frames, const int64_
                             const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  return search_ranked_frames(e, frames, qoff, nq, P, k, out, counts, nullptr);
+  return search_ranked(e, QuerySrc{frames, qoff, 0, false}, nq, P, k, out, counts, nullptr);
 }
 
 int tfp_search_ranked(tfp_engine* e, const tfp_frame* frames, int32_t nframes, const tfp_search_params* P, int32_t k,
@@ -3194,73 +3233,28 @@ int tfp_search_ranked(tfp_engine* e, const tfp_frame* frames, int32_t nframes, c
   return tfp_search_ranked_batch(e, frames, qoff, 1, P, k, out, count);
 }
 
-namespace {
-// tfp_search_ranked_pcm_batch, and with align its rows' alignments (tfp_search_aligned_pcm_batch):
-// the frame values stay on the device (e->db) for both.
-// scopes (or nullptr): tfp_search_scoped_pcm_batch.
-int search_ranked_pcm(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
-                      const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts, tfp_alignment* align,
-                      const int32_t* scopes = nullptr) {
-  int rc = rank_args(e, P, k, nq, out, counts);
-  if (rc) return rc;
-  for (int32_t i = 0; i < nq; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
-  if (!pcm && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
-  std::vector<const void*> ptrs;
-  std::vector<int64_t> lens;
-  split_offsets(pcm, sizeof(int16_t), offsets, nq, &ptrs, &lens);
-  std::vector<int64_t> foff(nq + 1, 0);
-  for (int32_t i = 0; i < nq; i++) foff[i + 1] = foff[i] + tfp_frame_count(lens[i]);
-  std::vector<unsigned long long> keys((size_t)nq * k, 0ull);
-  if (nq && foff[nq] > 0) {
-    HIPCHK(e, hipSetDevice(e->device));
-    int64_t nf;
-    if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nq, sr, &nf, nullptr, P->coefs == 2))) return rc;
-    if ((rc = rank_core(e, foff.data(), nq, e->db.as<double>(), P, k, scopes, keys, e->stream))) return rc;
-    HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
-    e->stage_pending = false;
-  }
-  fill_candidates(e, keys, nq, k, out, counts);
-  if (align && nq) {
-    memset(align, 0, sizeof(tfp_alignment) * (size_t)nq * k);
-    if (foff[nq] > 0)
-      return align_core(e, foff, nq, e->db.as<double>(), P, k, candidate_ids(out, counts, nq, k).data(), align, e->stream);
-  }
-  return TFP_OK;
-}
-}  // namespace
-
 int tfp_search_ranked_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
                                 const tfp_search_params* P, int32_t k, tfp_candidate* out, int32_t* counts) {
   if (!e || !offsets) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  return search_ranked_pcm(e, pcm, offsets, nq, sr, P, k, out, counts, nullptr);
+  return search_ranked(e, QuerySrc{pcm, offsets, sr, true}, nq, P, k, out, counts, nullptr);
 }
 
 // ---- aligned search (tfp_align.hpp) -------------------------------------------------------
-namespace {
-int align_args(tfp_engine* e, const tfp_search_params* P, int32_t k, int32_t nq, const void* out) {
-  if (nq < 0 || !out) return fail(e, TFP_E_ARG, "aligned search: bad query count or NULL output");
-  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "aligned search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
-  if (!valid_params(P)) return fail(e, TFP_E_ARG, "aligned search: coefs outside [1, 2]");
-  return TFP_OK;
-}
-}  // namespace
-
 int tfp_align_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq, const tfp_search_params* P,
                     const int32_t* clip_ids, int32_t k, tfp_alignment* out) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  int rc = align_args(e, P, k, nq, out);
-  if (rc) return rc;
+  if (nq < 0 || !out) return fail(e, TFP_E_ARG, "aligned search: bad query count or NULL output");
+  int rc = check_k(e, "aligned search", k);
+  if (rc || (rc = check_params(e, "aligned search", P))) return rc;
   if (nq && !clip_ids) return fail(e, TFP_E_ARG, "aligned search: clip_ids is NULL");
-  for (int32_t i = 0; i < nq; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
-  if (!nq) return TFP_OK;
-  if (qoff[nq] > qoff[0] && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
-  HIPCHK(e, hipSetDevice(e->device));
-  if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
-  return align_core(e, relative_offsets(qoff, nq), nq, e->q.as<double>(), P, k, clip_ids, out, e->stream);
+  QuerySrc src{frames, qoff, 0, false};
+  if ((rc = src.check_offsets(e, nq)) || !nq) return rc;
+  const std::vector<int64_t> fo = src.fo(nq);
+  const double* d_q;
+  if ((rc = src.check_data(e, fo[nq])) || (rc = src.materialise(e, nq, fo, P, &d_q))) return rc;
+  return align_core(e, fo, nq, d_q, P, k, clip_ids, out, e->stream);
 }
 
 int tfp_search_aligned_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
@@ -3269,7 +3263,7 @@ int tfp_search_aligned_batch(tfp_engine* e, const tfp_frame* frames, const int64
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!align) return fail(e, TFP_E_ARG, "aligned search: NULL output");
-  return search_ranked_frames(e, frames, qoff, nq, P, k, cand, counts, align);
+  return search_ranked(e, QuerySrc{frames, qoff, 0, false}, nq, P, k, cand, counts, align);
 }
 
 int tfp_search_aligned_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
@@ -3278,7 +3272,7 @@ int tfp_search_aligned_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_
   if (!e || !offsets) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!align) return fail(e, TFP_E_ARG, "aligned search: NULL output");
-  return search_ranked_pcm(e, pcm, offsets, nq, sr, P, k, cand, counts, align);
+  return search_ranked(e, QuerySrc{pcm, offsets, sr, true}, nq, P, k, cand, counts, align);
 }
 
 int tfp_align_stats(tfp_engine* e, int64_t* batches, int64_t* pairs) {
@@ -3345,8 +3339,7 @@ int tfp_search_scoped_batch(tfp_engine* e, const tfp_frame* frames, const int64_
                             int32_t* counts) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  const int rc = scope_args(e, P, k, nq, scopes, out, counts);
-  return rc ? rc : search_ranked_frames(e, frames, qoff, nq, P, k, out, counts, nullptr, scopes);
+  return search_ranked(e, QuerySrc{frames, qoff, 0, false}, nq, P, k, out, counts, nullptr, true, scopes);
 }
 
 int tfp_search_scoped_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
@@ -3354,8 +3347,7 @@ int tfp_search_scoped_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t
                                 int32_t* counts) {
   if (!e || !offsets) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  const int rc = scope_args(e, P, k, nq, scopes, out, counts);
-  return rc ? rc : search_ranked_pcm(e, pcm, offsets, nq, sr, P, k, out, counts, nullptr, scopes);
+  return search_ranked(e, QuerySrc{pcm, offsets, sr, true}, nq, P, k, out, counts, nullptr, true, scopes);
 }
 
 int tfp_scope_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches, int64_t* table_builds) {
@@ -3377,20 +3369,29 @@ int64_t tfp_census_at_least(const int32_t* hist_row, int32_t nbins, int32_t coun
   return n;
 }
 
+namespace {
+// The match census over a query source (tfp_census_*_batch).
+int census_search(tfp_engine* e, QuerySrc src, int32_t nq, const tfp_search_params* P, const int32_t* scopes, int32_t nbins,
+                  int32_t* hist, int32_t* need_bins) {
+  std::vector<int32_t> sv;
+  int rc = census_args(e, P, nq, scopes, need_bins, sv);
+  if (rc || (rc = src.check_offsets(e, nq))) return rc;
+  const std::vector<int64_t> fo = src.fo(nq);
+  if ((rc = src.check_data(e, fo[nq])) || (rc = census_bins(e, fo.data(), nq, nbins, hist, need_bins)) || !nq) return rc;
+  const double* d_q;
+  // the core runs, hence the index is built, even without a frame: bin 0 needs the scopes' populations
+  if ((rc = src.materialise(e, nq, fo, P, &d_q))) return rc;
+  rc = census_core(e, fo.data(), nq, d_q, P, sv.data(), nbins, hist, e->stream);
+  const int waited = src.settle(e);  // (after a failed core too, unlike the other forms)
+  return waited ? waited : rc;
+}
+}  // namespace
+
 int tfp_census_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq, const tfp_search_params* P,
                      const int32_t* scopes, int32_t nbins, int32_t* hist, int32_t* need_bins) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  std::vector<int32_t> sv;
-  int rc = census_args(e, P, nq, scopes, need_bins, sv);
-  if (rc) return rc;
-  for (int32_t i = 0; i < nq; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
-  if (nq && qoff[nq] > qoff[0] && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
-  if ((rc = census_bins(e, qoff, nq, nbins, hist, need_bins)) || !nq) return rc;
-  HIPCHK(e, hipSetDevice(e->device));
-  if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
-  return census_core(e, qoff, nq, e->q.as<double>(), P, sv.data(), nbins, hist, e->stream);
+  return census_search(e, QuerySrc{frames, qoff, 0, false}, nq, P, scopes, nbins, hist, need_bins);
 }
 
 int tfp_census_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t sr,
@@ -3398,29 +3399,7 @@ int tfp_census_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offse
                          int32_t* need_bins) {
   if (!e || !offsets) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  std::vector<int32_t> sv;
-  int rc = census_args(e, P, nq, scopes, need_bins, sv);
-  if (rc) return rc;
-  for (int32_t i = 0; i < nq; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
-  if (!pcm && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
-  std::vector<const void*> ptrs;
-  std::vector<int64_t> lens;
-  split_offsets(pcm, sizeof(int16_t), offsets, nq, &ptrs, &lens);
-  std::vector<int64_t> foff(nq + 1, 0);
-  for (int32_t i = 0; i < nq; i++) foff[i + 1] = foff[i] + tfp_frame_count(lens[i]);
-  if ((rc = census_bins(e, foff.data(), nq, nbins, hist, need_bins)) || !nq) return rc;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (foff[nq] > 0) {  // the frame values stay on the device (e->db)
-    int64_t nf;
-    if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nq, sr, &nf, nullptr, P->coefs == 2))) return rc;
-  }
-  rc = census_core(e, foff.data(), nq, e->db.as<double>(), P, sv.data(), nbins, hist, e->stream);
-  if (foff[nq] > 0) {
-    HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
-    e->stage_pending = false;
-  }
-  return rc;
+  return census_search(e, QuerySrc{pcm, offsets, sr, true}, nq, P, scopes, nbins, hist, need_bins);
 }
 
 int tfp_census_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches) {
@@ -3434,27 +3413,45 @@ int tfp_census_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batc
 // ---- sliding search (tfp_slide.hpp): fp_handler.c:367-374 for every window of a recording ----
 static_assert(kSlideRun == TFP_SLIDE_RUN, "tfp_slide.hpp and the public header agree");
 
-int64_t tfp_sliding_windows(int64_t nframes, int32_t window, int32_t hop) { return slide_windows(nframes, window, hop); }
+int64_t tfp_sliding_windows(int64_t nframes, int32_t window, int32_t hop) { return plan_windows(nframes, window, hop); }
+
+namespace {
+// Sliding search over a query source (tfp_search_sliding_*_batch); aligned: with each row's alignment
+// (tfp_search_sliding_aligned_*_batch), which leaves the recordings' boxes in e->align_boxes.
+int search_sliding(tfp_engine* e, QuerySrc src, int32_t nrec, const tfp_search_params* P, int32_t window, int32_t hop,
+                   const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts, bool aligned, tfp_alignment* align,
+                   int64_t cap_windows, int64_t* nwindows, const std::vector<int64_t>* checked_fo = nullptr) {
+  int rc = checked_fo ? TFP_OK : src.check_offsets(e, nrec);  // (before the other arguments, unlike the ranked forms)
+  if (rc) return rc;
+  // (nrec < 0: no offset is read, slide_args rejects the count; checked_fo: the occurrence search's, not worked out twice)
+  const std::vector<int64_t>& fo = checked_fo ? *checked_fo : src.fo(nrec);
+  std::vector<int64_t> woff;
+  if ((rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff))) return rc;
+  const int32_t nw = (int32_t)woff[nrec];
+  if (!nw) return TFP_OK;  // no full window: nothing is fingerprinted or launched
+  if (aligned) {  // (asked only once a window exists)
+    if (!align) return fail(e, TFP_E_ARG, "sliding aligned search: NULL output");
+    if ((rc = slide_align_limits(e, window))) return rc;
+  }
+  std::vector<unsigned long long> keys;
+  const double* d_q;
+  if ((rc = src.check_data(e, fo[nrec])) || (rc = src.materialise(e, nrec, fo, P, &d_q)) ||
+      (rc = slide_core(e, fo, nrec, d_q, P, window, hop, scopes, k, woff, keys, e->stream)) || (rc = src.settle(e)))
+    return rc;
+  fill_candidates(e, keys, nw, k, out, counts);
+  if (!aligned) return TFP_OK;
+  return slide_align_core(e, fo, nrec, d_q, P, window, hop, k, woff, candidate_ids(out, counts, nw, k).data(), align,
+                          e->stream);
+}
+}  // namespace
 
 int tfp_search_sliding_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
                              const tfp_search_params* P, int32_t window, int32_t hop, const int32_t* scopes, int32_t k,
                              tfp_candidate* out, int32_t* counts, int64_t cap_windows, int64_t* nwindows) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  for (int32_t i = 0; i < nrec; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
-  std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0), woff;
-  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
-  if (rc) return rc;
-  const int32_t nw = (int32_t)woff[nrec];
-  if (!nw) return TFP_OK;  // no full window: nothing is launched
-  if (!frames) return fail(e, TFP_E_ARG, "frames is NULL");
-  std::vector<unsigned long long> keys;
-  HIPCHK(e, hipSetDevice(e->device));
-  if ((rc = upload_frames(e, frames, qoff, nrec))) return rc;
-  if ((rc = slide_core(e, fo, nrec, e->q.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
-  fill_candidates(e, keys, nw, k, out, counts);
-  return TFP_OK;
+  return search_sliding(e, QuerySrc{frames, qoff, 0, false}, nrec, P, window, hop, scopes, k, out, counts, false, nullptr,
+                        cap_windows, nwindows);
 }
 
 int tfp_search_sliding_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nrec, int32_t sr,
@@ -3462,27 +3459,8 @@ int tfp_search_sliding_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_
                                  tfp_candidate* out, int32_t* counts, int64_t cap_windows, int64_t* nwindows) {
   if (!e || !offsets) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  for (int32_t i = 0; i < nrec; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
-  std::vector<const void*> ptrs;
-  std::vector<int64_t> lens;
-  if (nrec > 0) split_offsets(pcm, sizeof(int16_t), offsets, nrec, &ptrs, &lens);
-  std::vector<int64_t> fo((size_t)std::max(nrec, 0) + 1, 0), woff;
-  for (int32_t i = 0; i < nrec; i++) fo[i + 1] = fo[i] + tfp_frame_count(lens[i]);
-  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
-  if (rc) return rc;
-  const int32_t nw = (int32_t)woff[nrec];
-  if (!nw) return TFP_OK;  // no full window: nothing is fingerprinted
-  if (!pcm) return fail(e, TFP_E_ARG, "samples are NULL");
-  std::vector<unsigned long long> keys;
-  HIPCHK(e, hipSetDevice(e->device));
-  int64_t nf;  // each recording fingerprinted once, as one clip; the frame values stay in e->db
-  if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nrec, sr, &nf, nullptr, P->coefs == 2))) return rc;
-  if ((rc = slide_core(e, fo, nrec, e->db.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
-  HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
-  e->stage_pending = false;
-  fill_candidates(e, keys, nw, k, out, counts);
-  return TFP_OK;
+  return search_sliding(e, QuerySrc{pcm, offsets, sr, true}, nrec, P, window, hop, scopes, k, out, counts, false, nullptr,
+                        cap_windows, nwindows);
 }
 
 int tfp_slide_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches, int64_t* windows) {
@@ -3501,16 +3479,17 @@ int tfp_align_sliding_batch(tfp_engine* e, const tfp_frame* frames, const int64_
                             tfp_alignment* out, int64_t cap_windows, int64_t* nwindows) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  for (int32_t i = 0; i < nrec; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
-  std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0), woff;
-  int rc = slide_args(e, P, window, hop, k, nrec, nullptr, fo, out, clip_ids, cap_windows, nwindows, woff);
-  if (rc || (rc = slide_align_limits(e, window))) return rc;
+  QuerySrc src{frames, qoff, 0, false};
+  int rc = src.check_offsets(e, nrec);
+  if (rc) return rc;
+  std::vector<int64_t> fo = src.fo(nrec), woff;
+  if ((rc = slide_args(e, P, window, hop, k, nrec, nullptr, fo, out, clip_ids, cap_windows, nwindows, woff)) ||
+      (rc = slide_align_limits(e, window)))
+    return rc;
   if (!woff[nrec]) return TFP_OK;  // no full window: nothing is launched
-  if (!frames) return fail(e, TFP_E_ARG, "frames is NULL");
-  HIPCHK(e, hipSetDevice(e->device));
-  if ((rc = upload_frames(e, frames, qoff, nrec))) return rc;
-  return slide_align_core(e, fo, nrec, e->q.as<double>(), P, window, hop, k, woff, clip_ids, out, e->stream);
+  const double* d_q;
+  if ((rc = src.check_data(e, fo[nrec])) || (rc = src.materialise(e, nrec, fo, P, &d_q))) return rc;
+  return slide_align_core(e, fo, nrec, d_q, P, window, hop, k, woff, clip_ids, out, e->stream);
 }
 
 int tfp_search_sliding_aligned_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
@@ -3519,24 +3498,8 @@ int tfp_search_sliding_aligned_batch(tfp_engine* e, const tfp_frame* frames, con
                                      int64_t cap_windows, int64_t* nwindows) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  for (int32_t i = 0; i < nrec; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
-  std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0), woff;
-  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
-  if (rc) return rc;
-  const int32_t nw = (int32_t)woff[nrec];
-  if (!nw) return TFP_OK;  // no full window: nothing is launched
-  if (!align) return fail(e, TFP_E_ARG, "sliding aligned search: NULL output");
-  if ((rc = slide_align_limits(e, window))) return rc;
-  if (!frames) return fail(e, TFP_E_ARG, "frames is NULL");
-  std::vector<unsigned long long> keys;
-  HIPCHK(e, hipSetDevice(e->device));
-  if ((rc = upload_frames(e, frames, qoff, nrec))) return rc;
-  if ((rc = slide_core(e, fo, nrec, e->q.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
-  fill_candidates(e, keys, nw, k, out, counts);
-  // (the frame values are still in e->q)
-  return slide_align_core(e, fo, nrec, e->q.as<double>(), P, window, hop, k, woff, candidate_ids(out, counts, nw, k).data(),
-                          align, e->stream);
+  return search_sliding(e, QuerySrc{frames, qoff, 0, false}, nrec, P, window, hop, scopes, k, out, counts, true, align,
+                        cap_windows, nwindows);
 }
 
 int tfp_search_sliding_aligned_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nrec, int32_t sr,
@@ -3545,30 +3508,8 @@ int tfp_search_sliding_aligned_pcm_batch(tfp_engine* e, const int16_t* pcm, cons
                                          int64_t cap_windows, int64_t* nwindows) {
   if (!e || !offsets) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  for (int32_t i = 0; i < nrec; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
-  std::vector<const void*> ptrs;
-  std::vector<int64_t> lens;
-  if (nrec > 0) split_offsets(pcm, sizeof(int16_t), offsets, nrec, &ptrs, &lens);
-  std::vector<int64_t> fo((size_t)std::max(nrec, 0) + 1, 0), woff;
-  for (int32_t i = 0; i < nrec; i++) fo[i + 1] = fo[i] + tfp_frame_count(lens[i]);
-  int rc = slide_args(e, P, window, hop, k, nrec, scopes, fo, out, counts, cap_windows, nwindows, woff);
-  if (rc) return rc;
-  const int32_t nw = (int32_t)woff[nrec];
-  if (!nw) return TFP_OK;  // no full window: nothing is fingerprinted
-  if (!align) return fail(e, TFP_E_ARG, "sliding aligned search: NULL output");
-  if ((rc = slide_align_limits(e, window))) return rc;
-  if (!pcm) return fail(e, TFP_E_ARG, "samples are NULL");
-  std::vector<unsigned long long> keys;
-  HIPCHK(e, hipSetDevice(e->device));
-  int64_t nf;  // each recording fingerprinted once; the frame values stay in e->db for the slide and the alignment
-  if ((rc = fingerprint_host(e, ptrs.data(), lens.data(), false, nrec, sr, &nf, nullptr, P->coefs == 2))) return rc;
-  if ((rc = slide_core(e, fo, nrec, e->db.as<double>(), P, window, hop, scopes, k, woff, keys, e->stream))) return rc;
-  HIPCHK(e, hipStreamSynchronize(e->stream));  // (an empty index returns before any wait)
-  e->stage_pending = false;
-  fill_candidates(e, keys, nw, k, out, counts);
-  return slide_align_core(e, fo, nrec, e->db.as<double>(), P, window, hop, k, woff,
-                          candidate_ids(out, counts, nw, k).data(), align, e->stream);
+  return search_sliding(e, QuerySrc{pcm, offsets, sr, true}, nrec, P, window, hop, scopes, k, out, counts, true, align,
+                        cap_windows, nwindows);
 }
 
 int tfp_slide_align_stats(tfp_engine* e, int64_t* batches, int64_t* slid_entries, int64_t* direct_entries) {
@@ -3588,23 +3529,23 @@ int tfp_trace_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff,
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (nrec < 0 || nreqs < 0 || (nreqs && (!reqs || !out))) return fail(e, TFP_E_ARG, "trace: bad count or NULL array");
   if (max_gap < 0) return fail(e, TFP_E_ARG, "trace: max_gap = %d", max_gap);
-  if (!valid_params(P)) return fail(e, TFP_E_ARG, "trace: coefs outside [1, 2]");
-  for (int32_t i = 0; i < nrec; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
+  QuerySrc src{frames, qoff, 0, false};
+  int rc = check_params(e, "trace", P);
+  if (rc || (rc = src.check_offsets(e, nrec))) return rc;
   for (int64_t i = 0; i < nreqs; i++)
     if (reqs[i].recording < 0 || reqs[i].recording >= nrec)
       return fail(e, TFP_E_ARG, "trace: recording %d of request %lld", reqs[i].recording, (long long)i);
   if (!nreqs) return TFP_OK;
-  const std::vector<int64_t> fo = relative_offsets(qoff, nrec);
+  const std::vector<int64_t> fo = src.fo(nrec);
   if (fo[nrec] > INT32_MAX) return fail(e, TFP_E_CAPACITY, "trace: %lld frames", (long long)fo[nrec]);
-  if (fo[nrec] && !frames) return fail(e, TFP_E_ARG, "frames is NULL");
-  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = src.check_data(e, fo[nrec]))) return rc;
   return trace_core(
       e, fo, reqs, nreqs, max_gap, P,
       [&]() -> int {  // the recordings' frame values and their boxes, once a request needs them
-        if (int rc = upload_frames(e, frames, qoff, nrec)) return rc;
+        const double* d_q;
+        if (int rc = src.materialise(e, nrec, fo, P, &d_q)) return rc;
         HIPCHK(e, e->align_boxes.reserve(sizeof(FrameBox) * (fo[nrec] + 1)));
-        HIPCHK(e, launch_prep_boxes(e->q.as<double>(), fo[nrec], search_consts(P), e->align_boxes.as<FrameBox>(), nullptr, 0,
+        HIPCHK(e, launch_prep_boxes(d_q, fo[nrec], search_consts(P), e->align_boxes.as<FrameBox>(), nullptr, 0,
                                     e->stream));
         return TFP_OK;
       },
@@ -3612,14 +3553,6 @@ int tfp_trace_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff,
 }
 
 namespace {
-// What both occurrence calls check before the sliding aligned search checks the rest.
-int occur_args(tfp_engine* e, int32_t k, int32_t max_gap, int32_t min_hits, const int64_t* nocc) {
-  if (!nocc) return fail(e, TFP_E_ARG, "occurrence search: NULL noccurrences");
-  if (max_gap < 0 || min_hits < 1) return fail(e, TFP_E_ARG, "occurrence search: max_gap = %d, min_hits = %d", max_gap, min_hits);
-  if (k < 1 || k > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "occurrence search: k = %d outside [1, %d]", k, TFP_RANK_MAX);
-  return TFP_OK;
-}
-
 // The sliding aligned search's own buffers for nw windows (0 when the count is out of range: the
 // search then reports it).
 struct OccurRows {
@@ -3633,6 +3566,28 @@ struct OccurRows {
     align.resize((size_t)cap * k + 1);
   }
 };
+
+// Occurrence search over a query source (tfp_search_occurrences_*_batch): the sliding aligned search into
+// its own rows, then their occurrences.
+int search_occurrences(tfp_engine* e, QuerySrc src, int32_t nrec, const tfp_search_params* P, int32_t window, int32_t hop,
+                       const int32_t* scopes, int32_t k, int32_t max_gap, int32_t min_hits, tfp_occurrence* out, int64_t cap,
+                       int64_t* nocc) {
+  if (!nocc) return fail(e, TFP_E_ARG, "occurrence search: NULL noccurrences");
+  if (max_gap < 0 || min_hits < 1) return fail(e, TFP_E_ARG, "occurrence search: max_gap = %d, min_hits = %d", max_gap, min_hits);
+  int rc = check_k(e, "occurrence search", k);  // (the sliding aligned search checks the rest)
+  if (rc || (rc = src.check_offsets(e, nrec))) return rc;
+  const std::vector<int64_t> fo = src.fo(nrec);
+  OccurRows rows(window_offsets(fo, nrec, window, hop)[std::max(nrec, 0)], k);
+  int64_t got = 0;
+  if ((rc = search_sliding(e, src, nrec, P, window, hop, scopes, k, rows.cand.data(), rows.counts.data(), true,
+                           rows.align.data(), rows.cap, &got, &fo)))
+    return rc;
+  *nocc = 0;
+  if (!got) return TFP_OK;  // no full window: no occurrence
+  // (the frame boxes are still in e->align_boxes wherever a row came back)
+  return occur_core(e, fo, nrec, P, window, hop, k, rows.cand.data(), rows.counts.data(), rows.align.data(), max_gap,
+                    min_hits, out, cap, nocc, e->stream);
+}
 }  // namespace
 
 int tfp_search_occurrences_batch(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nrec,
@@ -3640,22 +3595,8 @@ int tfp_search_occurrences_batch(tfp_engine* e, const tfp_frame* frames, const i
                                  int32_t max_gap, int32_t min_hits, tfp_occurrence* out, int64_t cap, int64_t* nocc) {
   if (!e || !qoff) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  int rc = occur_args(e, k, max_gap, min_hits, nocc);
-  if (rc) return rc;
-  for (int32_t i = 0; i < nrec; i++)
-    if (qoff[i + 1] < qoff[i]) return fail(e, TFP_E_ARG, "qoffsets not monotone");
-  const std::vector<int64_t> fo = nrec > 0 ? relative_offsets(qoff, nrec) : std::vector<int64_t>(1, 0);
-  int64_t nw = 0, got = 0;
-  for (int32_t i = 0; i < nrec; i++) nw += slide_windows(fo[i + 1] - fo[i], window, hop);
-  OccurRows rows(nw, k);
-  if ((rc = tfp_search_sliding_aligned_batch(e, frames, qoff, nrec, P, window, hop, scopes, k, rows.cand.data(),
-                                             rows.counts.data(), rows.align.data(), rows.cap, &got)))
-    return rc;
-  *nocc = 0;
-  if (!got) return TFP_OK;  // no full window: no occurrence
-  // (the frame boxes are still in e->align_boxes wherever a row came back)
-  return occur_core(e, fo, nrec, P, window, hop, k, rows.cand.data(), rows.counts.data(), rows.align.data(), max_gap,
-                    min_hits, out, cap, nocc, e->stream);
+  return search_occurrences(e, QuerySrc{frames, qoff, 0, false}, nrec, P, window, hop, scopes, k, max_gap, min_hits, out, cap,
+                            nocc);
 }
 
 int tfp_search_occurrences_pcm_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nrec, int32_t sr,
@@ -3664,25 +3605,8 @@ int tfp_search_occurrences_pcm_batch(tfp_engine* e, const int16_t* pcm, const in
                                      int64_t* nocc) {
   if (!e || !offsets) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  int rc = occur_args(e, k, max_gap, min_hits, nocc);
-  if (rc) return rc;
-  for (int32_t i = 0; i < nrec; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
-  std::vector<int64_t> fo((size_t)std::max(nrec, 0) + 1, 0);
-  int64_t nw = 0, got = 0;
-  for (int32_t i = 0; i < nrec; i++) {
-    fo[i + 1] = fo[i] + tfp_frame_count(offsets[i + 1] - offsets[i]);
-    nw += slide_windows(fo[i + 1] - fo[i], window, hop);
-  }
-  OccurRows rows(nw, k);
-  // each recording fingerprinted once; its frame values stay in e->db and their boxes in e->align_boxes
-  if ((rc = tfp_search_sliding_aligned_pcm_batch(e, pcm, offsets, nrec, sr, P, window, hop, scopes, k, rows.cand.data(),
-                                                 rows.counts.data(), rows.align.data(), rows.cap, &got)))
-    return rc;
-  *nocc = 0;
-  if (!got) return TFP_OK;
-  return occur_core(e, fo, nrec, P, window, hop, k, rows.cand.data(), rows.counts.data(), rows.align.data(), max_gap,
-                    min_hits, out, cap, nocc, e->stream);
+  return search_occurrences(e, QuerySrc{pcm, offsets, sr, true}, nrec, P, window, hop, scopes, k, max_gap, min_hits, out,
+                            cap, nocc);
 }
 
 int tfp_trace_stats(tfp_engine* e, int64_t* batches, int64_t* traces) {
@@ -3747,8 +3671,7 @@ int search_gather_entry(tfp_engine* e, const void* const* ptrs, const int64_t* l
 int search_samples_impl(tfp_engine* e, const void* pcm, bool f32, const int64_t* offsets, int32_t nq, int32_t sr,
                         const tfp_search_params* P, tfp_result* out) {
   if (!e || !offsets || nq < 0 || !out) return TFP_E_ARG;
-  for (int32_t i = 0; i < nq; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  if (int rc = check_monotone(e, offsets, nq, true)) return rc;
   if (!pcm && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
   std::vector<const void*> ptrs;
   std::vector<int64_t> lens;
@@ -3774,8 +3697,7 @@ int tfp_internal_search_g711(tfp_engine* e, const uint8_t* codes, const int64_t*
                              int32_t sr, const tfp_search_params* P, tfp_result* out) {
   if (!e || !offsets || nq < 0 || !out) return TFP_E_ARG;
   if (!g711_law_ok(law)) return fail(e, TFP_E_ARG, "G.711 law %d is neither TFP_G711_ULAW nor TFP_G711_ALAW", law);
-  for (int32_t i = 0; i < nq; i++)
-    if (offsets[i + 1] < offsets[i]) return fail(e, TFP_E_ARG, "offsets not monotone");
+  if (int rc = check_monotone(e, offsets, nq, true)) return rc;
   if (!codes && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "codes are NULL");
   std::vector<int64_t> lens(nq);
   for (int32_t i = 0; i < nq; i++) lens[i] = offsets[i + 1] - offsets[i];
