@@ -274,6 +274,9 @@ struct tfp_engine {
   // the coefs = 2 sweep's sort path per batch (tfp_sweep_stats): the bin sort's speculative pass
   // stood, the library sort ran, a speculative pass was redone; crowd bins the bin sort copied
   int64_t n_sweep_bins = 0, n_sweep_lib = 0, n_sweep_redo = 0, n_sweep_crowd = 0;
+  // plain search's form per batch (tfp_search_path_stats): the small vote, the vote by pattern classes
+  // or by the GEMM, a vote the host had to redo (VoteMeta::ok clear), a pass of the general path
+  int64_t n_path_small = 0, n_path_class = 0, n_path_gemm = 0, n_path_redone = 0, n_path_general = 0;
   ClipOrder order;
   // scan scratch: stamp / score / touched nq x ncols int32 each, tcnt nq int32; kept all-zero
   // by the scan kernels themselves
@@ -1606,6 +1609,7 @@ int search_small(tfp_engine* e, Batch& b) {
       b.keys[i] = k;
     }
   }
+  e->n_path_small++;
   return TFP_OK;
 }
 
@@ -1642,7 +1646,11 @@ int search_vote(tfp_engine* e, Batch& b) {
   if (!b.d_keys_out && nq)
     memcpy(b.keys.data(), e->vres_pin.as<char>() + sizeof(VoteMeta), sizeof(unsigned long long) * nq);
   if (e->dbg_vote) fprintf(stderr, "[tfp] vote: nq %d Qp %d C %d ku %d kp %d ok %d\n", nq, Qp, C, hm.ku, hm.kp, hm.ok);
-  if (hm.ok) return TFP_OK;
+  if (hm.ok) {
+    (hm.cls ? e->n_path_class : e->n_path_gemm)++;
+    return TFP_OK;
+  }
+  e->n_path_redone++;
   // a count above fp16's exact range or a key outside the vote range: the scan path (over the
   // sorted rows), which needs the frames' boxes too
   if (b.has_delta) return kNeedsSorted;
@@ -1756,6 +1764,7 @@ int search_general(tfp_engine* e, Batch& b) {
       if (bins_used) e->n_sweep_crowd += info[3];
     }
     if (swept) (bins_used ? e->n_sweep_bins : e->n_sweep_lib)++;
+    e->n_path_general++;
     return TFP_OK;
   }
 }
@@ -3736,6 +3745,18 @@ int tfp_sweep_stats(tfp_engine* e, int64_t* bins, int64_t* library, int64_t* red
   if (library) *library = e->n_sweep_lib;
   if (redone) *redone = e->n_sweep_redo;
   if (crowd_bins) *crowd_bins = e->n_sweep_crowd;
+  return TFP_OK;
+}
+
+int tfp_search_path_stats(tfp_engine* e, int64_t* small, int64_t* vote_class, int64_t* vote_gemm, int64_t* vote_redone,
+                          int64_t* general) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (small) *small = e->n_path_small;
+  if (vote_class) *vote_class = e->n_path_class;
+  if (vote_gemm) *vote_gemm = e->n_path_gemm;
+  if (vote_redone) *vote_redone = e->n_path_redone;
+  if (general) *general = e->n_path_general;
   return TFP_OK;
 }
 

@@ -775,13 +775,13 @@ __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void
       t.f0 = (int64_t)b * (4 * kPasses);
       t.s0 = 0;
       t.ns = single_ns;
-      return t;
+    } else {
+      t.c = __builtin_amdgcn_readfirstlane(tclip[b]);
+      t.f0 = (int64_t)(b - toff[t.c]) * (4 * kPasses);
+      t.s0 = sbeg[t.c];
+      t.ns = send[t.c] - t.s0;
     }
-    t.c = __builtin_amdgcn_readfirstlane(tclip[b]);
-    t.f0 = (int64_t)(b - toff[t.c]) * (4 * kPasses);
-    t.s0 = sbeg[t.c];
-    t.ns = send[t.c] - t.s0;
-    if constexpr (kPairFb) {
+    if constexpr (kPairFb) {  // (a throughput launch of one long clip too: its edge tiles read through rs)
       t.rs = clip_rsrc(t.s0, t.ns);
       t.odd = (reinterpret_cast<uintptr_t>(pcm + t.s0) & 3) != 0;
     }

@@ -167,6 +167,7 @@ _SIGS = {
     "tfp_group_destroy": (None, [P]),
     "tfp_index_cache_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 7),
     "tfp_sweep_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 4),
+    "tfp_search_path_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 5),
     "tfp_group_size": (C.c_int32, [P]),
     "tfp_group_tiebreak_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
     "tfp_group_peer_stats": (C.c_int, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -452,6 +452,12 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
         self._chk(lib().tfp_sweep_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("bins", "library", "redone", "crowd"), [x.value for x in v]))
 
+    def search_path_stats(self) -> dict:
+        """tfp_search_path_stats: the plain-search batches each form served so far."""
+        v = [C.c_int64() for _ in range(5)]
+        self._chk(lib().tfp_search_path_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("small", "vote_class", "vote_gemm", "vote_redone", "general"), (x.value for x in v)))
+
     def index_cache_stats(self) -> dict:
         """The coefs = 2 clip-set caches (tfp_index_cache_stats): builds, cached hits, builds from the
         clip order, the clip order's full builds and merges, the index delta's caches and sweeps."""

@@ -257,6 +257,15 @@ int tfp_index_cache_stats(tfp_engine* eng, int64_t* cache_builds, int64_t* cache
  * for the row scan), and the crowd bins (one value: the silence floor) the bin sort copied unsorted.
  * Any pointer may be NULL. */
 int tfp_sweep_stats(tfp_engine* eng, int64_t* bins, int64_t* library, int64_t* redone, int64_t* crowd_bins);
+/* Which form served each plain-search batch so far (tfp_search*, the device forms, streams; not the
+ * ranked, scoped, census or sliding forms, which have their own counters): the small vote (up to 8
+ * queries of up to 2048 frames), the coefs = 1 vote by pattern classes and by the GEMM, votes the
+ * host redid on the general path (a per-key count above 2048, a key outside the vote range), and
+ * passes of the general path that produced the batch's results (every coefs = 2 batch, coefs = 1
+ * queries of 16384 frames and more, the redone votes). Counted in the branch that wrote the
+ * results. Any pointer may be NULL. */
+int tfp_search_path_stats(tfp_engine* eng, int64_t* small, int64_t* vote_class, int64_t* vote_gemm,
+                          int64_t* vote_redone, int64_t* general);
 /* Multi-GPU sharding: override the tie-break key of each live clip (default: its rank among
  * this engine's uuids). keys[clip_id] must order like the uuids across all shards and be
  * distinct over live clips. A clip added after this call has no key: the next search (or

@@ -80,6 +80,19 @@ def test_host_batch_takes_throughput_kernel(engine, ragged):
     assert np.array_equal(fr["frame_idx"], np.concatenate([np.arange(n) for n in np.diff(ragged.foff)]))
 
 
+@pytest.mark.parametrize("nsamples", [4100 * 256 + 77, 4097 * 256])
+def test_one_long_clip_takes_throughput_kernel(engine, oracle, tfp_lib, nsamples):
+    """One clip of more than 4096 frames (a long recording through tfp_fingerprint_pcm): the throughput
+    launch without the layout loads. Its first and last tiles read the clip through the buffer
+    resource, as any clip's do."""
+    pcm = tfp_lib.synth_pcm(0x10C6, [3], nsamples)[0]
+    st = engine.fingerprint_stats()
+    fr = engine.fingerprint(pcm)
+    assert_only_kernel(engine, st, "throughput8k", "the clip is a small batch now: lengthen it")
+    _, db, micro = oracle.fingerprint(pcm)
+    assert_frames_equal(fr, micro, db)
+
+
 def test_host_batch_head_takes_small_kernel(engine, ragged):
     st = engine.fingerprint_stats()
     fr = engine.fingerprint_batch(ragged.flat[:ragged.off[NHEAD]], ragged.off[:NHEAD + 1])
