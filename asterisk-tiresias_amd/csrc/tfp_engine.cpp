@@ -4127,6 +4127,17 @@ struct tfp_live {
   // engine's scope-table build it follows (-1: none yet)
   DevBuf cand, cand_rows;
   int64_t cand_builds = -1;
+  // the trailing window (tfp_live_window): a second count table in the layout of counts, allocated by the
+  // first window call; per channel the final frames [wbeg, wend) its row holds (empty: the row is zero);
+  // a stamp of its own, counts' fields plus the window length
+  DevBuf wcounts, wbad;
+  int64_t wcount_cols = 0;
+  std::vector<int64_t> wbeg, wend;
+  bool wstamp_valid = false;
+  uint64_t wstamp_version = 0;
+  SearchConsts wstamp_sc{};
+  int64_t wstamp_window = 0;
+  int64_t n_wslid = 0, n_wgeneral = 0, n_wrebuilds = 0, n_wadded = 0, n_wremoved = 0, n_wrestarted = 0;
   ~tfp_live() {
     if (stage_ev) (void)hipEventDestroy(stage_ev);
   }
@@ -4152,6 +4163,8 @@ int tfp_live_create(tfp_engine* e, int32_t nch, int32_t sr, int64_t max_samples,
   lv->Fmax = live_frames(max_samples);
   lv->samples.assign(nch, 0);
   lv->added.assign(nch, 0);
+  lv->wbeg.assign(nch, 0);
+  lv->wend.assign(nch, 0);
   // (neither needs clearing: a push reads only samples and frame values that a push has written)
   if (lv->hist.reserve(sizeof(int16_t) * (size_t)nch * max_samples) != hipSuccess ||
       lv->q.reserve(sizeof(double) * 2 * (size_t)nch * lv->Fmax) != hipSuccess ||
@@ -4182,7 +4195,14 @@ int tfp_live_reset(tfp_live* lv, int32_t ch) {
   if (lv->count_cols)  // a new call starts with an empty count row
     HIPCHK(e, hipMemsetAsync(lv->counts.as<uint16_t>() + (size_t)c0 * lv->count_cols, 0,
                              sizeof(uint16_t) * (size_t)(c1 - c0) * lv->count_cols, e->stream));
-  for (int32_t c = c0; c < c1; c++) lv->samples[c] = lv->added[c] = 0;
+  if (lv->wcount_cols)  // ... and with an empty window row
+    HIPCHK(e, hipMemsetAsync(lv->wcounts.as<uint16_t>() + (size_t)c0 * lv->wcount_cols, 0,
+                             sizeof(uint16_t) * (size_t)(c1 - c0) * lv->wcount_cols, e->stream));
+  for (int32_t c = c0; c < c1; c++) {
+    lv->samples[c] = lv->added[c] = 0;
+    lv->n_wremoved += lv->wend[c] - lv->wbeg[c];
+    lv->wbeg[c] = lv->wend[c] = 0;
+  }
   return TFP_OK;
 }
 
@@ -4216,24 +4236,26 @@ bool live_stamp_holds(const tfp_live* lv, const SearchConsts& sc) {
 // The exact fallback: every channel's frames so far, the tail included, as one query of the scoped
 // search core (which merges a live index delta where its form needs that). Caller holds e->mu and
 // waits for the stream.
+// window > 0 (tfp_live_window): each channel's trailing window [first, F) of them instead.
 int live_general(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K,
-                 std::vector<unsigned long long>& keys) {
+                 std::vector<unsigned long long>& keys, int64_t window = 0) {
   tfp_engine* e = lv->eng;
   const int32_t nch = lv->nch;
-  std::vector<int64_t> foff(nch + 1, 0);
+  std::vector<int64_t> foff(2 * (size_t)nch + 1, 0);  // the offsets, then the channels' first frames
   int64_t max_n = 0;
   for (int32_t c = 0; c < nch; c++) {
-    const int64_t n = live_frames(lv->samples[c]);
-    foff[c + 1] = foff[c] + n;
-    max_n = std::max(max_n, n);
+    const int64_t F = live_frames(lv->samples[c]), first = window > 0 && F > window ? F - window : 0;
+    foff[c + 1] = foff[c] + (F - first);
+    foff[nch + 1 + c] = first;
+    max_n = std::max(max_n, F - first);
   }
   keys.assign((size_t)nch * K, 0ull);
   if (!foff[nch]) return TFP_OK;
   int rc = upload(e, lv->gfoff, foff.data(), sizeof(int64_t) * foff.size());
   if (rc) return rc;
   HIPCHK(e, lv->gq.reserve(sizeof(double) * 2 * (size_t)(foff[nch] + 1)));
-  HIPCHK(e, launch_live_gather(lv->q.as<double>(), lv->Fmax, lv->gfoff.as<int64_t>(), nch, max_n, lv->gq.as<double>(),
-                               e->stream));
+  HIPCHK(e, launch_live_gather(lv->q.as<double>(), lv->Fmax, lv->gfoff.as<int64_t>(), lv->gfoff.as<int64_t>() + nch + 1, nch,
+                               max_n, lv->gq.as<double>(), e->stream));
   return rank_core(e, foff.data(), nch, lv->gq.as<double>(), P, K, scopes, keys, e->stream);
 }
 
@@ -4531,6 +4553,124 @@ int live_verdict_args(tfp_live* lv, const int64_t* total, const tfp_search_param
   return TFP_OK;
 }
 
+bool live_wstamp_holds(const tfp_live* lv, const SearchConsts& sc, int64_t window) {
+  const SearchConsts& t = lv->wstamp_sc;
+  return lv->wstamp_valid && lv->wstamp_version == lv->eng->index_version && lv->wstamp_window == window &&
+         t.tole == sc.tole && t.has_low == sc.has_low && t.has_high == sc.has_high &&
+         (!sc.has_low || t.thr_low == sc.thr_low) && (!sc.has_high || t.thr_high == sc.thr_high);
+}
+
+// The body of tfp_live_window: nothing is ingested and no frame fingerprinted. coefs = 1 over an index
+// with rows: the window table's stamp is checked (a mismatch zeroes the table and empties every range),
+// each channel's row is planned (live_window_plan) and the rows that owe frames go to the slide
+// kernel in one launch; the push's selection then reads the window table, with the tail's bit added
+// as a push adds it. One upload (descriptors), one read-back (keys and the bad flag), one wait.
+// coefs = 2, and a key outside the vote range (which drops the table), gather each channel's window of
+// kept frame values for the scoped search core. keys: nch * K, zeroed where there is no row.
+int live_window_step(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int64_t window,
+                     std::vector<unsigned long long>& keys) {
+  tfp_engine* e = lv->eng;
+  const int32_t nch = lv->nch;
+  hipStream_t s = e->stream;
+  int rc;
+  if ((rc = rebuild(e))) return rc;
+  const SearchConsts sc = search_consts(P);
+  bool vote = false;
+  if (sc.coefs == 1) {
+    if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
+    if (e->ncols > 0 && e->nrows + e->delta.rows > 0) {
+      if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s)) || (rc = ensure_scope_table(e, s))) return rc;
+      vote = true;
+    }
+  }
+  keys.assign((size_t)nch * K, 0ull);
+  if (sc.coefs == 1 && !vote) {  // an empty index: no row
+    lv->n_wslid++;
+    return TFP_OK;
+  }
+  if (vote) {
+    const int32_t C = e->ncols;
+    const int64_t Cpad = live_count_cols(C);
+    const bool holds = live_wstamp_holds(lv, sc, window);
+    std::vector<LiveChan> chan(nch);
+    std::vector<LiveSlide> slides;
+    std::vector<LiveWindowPlan> plans(nch);
+    for (int32_t c = 0; c < nch; c++) {
+      chan[c] = LiveChan{lv->samples[c], live_tail_frame(lv->samples[c]), 0, scopes ? scopes[c] : TFP_SCOPE_ANY};
+      const LiveWindowPlan& p = plans[c] = live_window_plan(lv->samples[c], window, holds, lv->wbeg[c], lv->wend[c]);
+      if (p.owes)
+        slides.push_back(LiveSlide{c, (int32_t)p.sub_beg, (int32_t)p.sub_end, (int32_t)p.add_beg, (int32_t)p.add_end, p.restart, 0, 0});
+    }
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_chan = al(sizeof(LiveChan) * nch), total = b_chan + al(sizeof(LiveSlide) * std::max<size_t>(slides.size(), 1));
+    const size_t nkeys = (size_t)nch * K;
+    if (lv->stage_pending) HIPCHK(e, hipEventSynchronize(lv->stage_ev));  // the last call's upload has read stage_h
+    lv->stage_pending = false;
+    HIPCHK(e, lv->stage_h.reserve(total));
+    HIPCHK(e, lv->dstage.reserve(total));
+    HIPCHK(e, lv->part.reserve(sizeof(unsigned long long) * (size_t)nch * rank_vote_blocks(C) * K));
+    HIPCHK(e, lv->keys.reserve(sizeof(unsigned long long) * nkeys));
+    HIPCHK(e, lv->keys_pin.reserve(sizeof(unsigned long long) * (nkeys + 1)));
+    if (!holds) {
+      HIPCHK(e, lv->wcounts.reserve(sizeof(uint16_t) * (size_t)nch * Cpad));
+      HIPCHK(e, lv->wbad.reserve(sizeof(int32_t)));
+    }
+    char* h = lv->stage_h.as<char>();
+    memcpy(h, chan.data(), sizeof(LiveChan) * nch);
+    if (!slides.empty()) memcpy(h + b_chan, slides.data(), sizeof(LiveSlide) * slides.size());
+    HIPCHK(e, hipMemcpyAsync(lv->dstage.p, h, total, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipEventRecord(lv->stage_ev, s));
+    lv->stage_pending = true;
+    if (!holds) {  // every row restarts: the table is zeroed, every range is empty
+      HIPCHK(e, hipMemsetAsync(lv->wcounts.p, 0, sizeof(uint16_t) * (size_t)nch * Cpad, s));
+      HIPCHK(e, hipMemsetAsync(lv->wbad.p, 0, sizeof(int32_t), s));
+      for (int32_t c = 0; c < nch; c++) {
+        lv->n_wremoved += lv->wend[c] - lv->wbeg[c];
+        lv->wbeg[c] = lv->wend[c] = 0;
+      }
+      lv->wcount_cols = Cpad;
+      lv->wstamp_valid = true;
+      lv->wstamp_version = e->index_version;
+      lv->wstamp_sc = sc;
+      lv->wstamp_window = window;
+      lv->n_wrebuilds++;
+    }
+    const char* d = lv->dstage.as<char>();
+    const uint32_t* d_bits = e->tc.ranges.active().key_bits.as<uint32_t>();
+    HIPCHK(e, launch_live_slide(lv->q.as<double>(), lv->Fmax, reinterpret_cast<const LiveSlide*>(d + b_chan), (int32_t)slides.size(),
+                                sc, d_bits, C, lv->wcounts.as<uint16_t>(), lv->wbad.as<int32_t>(), s));
+    for (int32_t c = 0; c < nch; c++) {
+      const LiveWindowPlan& p = plans[c];
+      lv->n_wadded += p.add_end - p.add_beg;
+      lv->n_wremoved += (p.sub_end - p.sub_beg) + p.dropped;
+      if (p.owes && p.restart) lv->n_wrestarted++;
+      lv->wbeg[c] = p.a;
+      lv->wend[c] = p.b;
+    }
+    HIPCHK(e, launch_live_select(lv->q.as<double>(), lv->Fmax, reinterpret_cast<const LiveChan*>(d), nch, sc, d_bits, C,
+                                 lv->wcounts.as<uint16_t>(), e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
+                                 lv->part.as<unsigned long long>(), lv->keys.as<unsigned long long>(), lv->wbad.as<int32_t>(), s));
+    unsigned long long* hk = lv->keys_pin.as<unsigned long long>();
+    HIPCHK(e, hipMemcpyAsync(hk, lv->keys.p, sizeof(unsigned long long) * nkeys, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(hk + nkeys, lv->wbad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    lv->stage_pending = false;
+    if (!(uint32_t)hk[nkeys]) {
+      std::copy(hk, hk + nkeys, keys.begin());
+      lv->n_wslid++;
+      return TFP_OK;
+    }
+    lv->wstamp_valid = false;  // the table holds frames it could not add: dropped, as a push drops its own
+  }
+  std::vector<int32_t> any;
+  if (!scopes) any.assign(nch, TFP_SCOPE_ANY);
+  if ((rc = live_general(lv, P, scopes ? scopes : any.data(), K, keys, window))) return rc;
+  HIPCHK(e, hipStreamSynchronize(s));  // (live_general returns before any wait when no channel has a frame)
+  lv->stage_pending = false;
+  lv->n_wgeneral++;
+  return TFP_OK;
+}
+
 }  // namespace
 
 int tfp_live_push(tfp_live* lv, const int16_t* pcm, int32_t T, const int32_t* nsamples, const tfp_search_params* P,
@@ -4593,6 +4733,78 @@ int tfp_live_verdict(tfp_live* lv, const int64_t* total, const tfp_search_params
   return TFP_OK;
 }
 
+int tfp_live_window(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int32_t window,
+                    tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames) {
+  if (!lv) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  const int32_t nch = lv->nch;
+  if (!P || !out || !counts) return fail(e, TFP_E_ARG, "live window: NULL params or output");
+  if (window < 1) return fail(e, TFP_E_ARG, "live window: window = %d frames", window);
+  if (K < 1 || K > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "live window: k = %d outside [1, %d]", K, TFP_RANK_MAX);
+  for (int32_t c = 0; scopes && c < nch; c++)
+    if (scopes[c] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "live window: scope %d of channel %d", scopes[c], c);
+  HIPCHK(e, hipSetDevice(e->device));
+  std::vector<unsigned long long> keys((size_t)nch * K, 0ull);
+  if (valid_params(P)) {  // fp_handler.c:247-250: bad params -> empty rows
+    const int rc = live_window_step(lv, P, scopes, K, window, keys);
+    if (rc) return rc;
+  }
+  fill_candidates(e, keys, nch, K, out, counts);
+  for (int32_t c = 0; c < nch; c++) {
+    const int64_t F = live_frames(lv->samples[c]), first = F > window ? F - window : 0;
+    if (frame_counts) frame_counts[c] = (int32_t)(F - first);
+    if (first_frames) first_frames[c] = (int32_t)first;
+  }
+  return TFP_OK;
+}
+
+int32_t tfp_live_window_frames(int64_t window_ms, int32_t sample_rate) {
+  const int64_t f = live_window_frames_of_ms(window_ms, sample_rate);
+  return f > INT32_MAX ? INT32_MAX : (int32_t)f;
+}
+
+int tfp_live_frames(tfp_live* lv, int32_t ch, int64_t first, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!lv || !nframes) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (ch < 0 || ch >= lv->nch) return fail(e, TFP_E_ARG, "live frames: channel %d outside [0, %d)", ch, lv->nch);
+  const int64_t F = live_frames(lv->samples[ch]);
+  if (first < 0 || first > F) return fail(e, TFP_E_ARG, "live frames: first = %lld outside [0, %lld]", (long long)first, (long long)F);
+  const int64_t n = F - first;
+  *nframes = n;
+  if (cap < n) return fail(e, TFP_E_ARG, "live frames: cap %lld below the %lld frames asked for", (long long)cap, (long long)n);
+  if (!n) return TFP_OK;
+  if (!out) return fail(e, TFP_E_ARG, "live frames: NULL output");
+  HIPCHK(e, hipSetDevice(e->device));
+  std::vector<double> d(2 * (size_t)n);
+  HIPCHK(e, hipMemcpyAsync(d.data(), lv->q.as<double>() + 2 * ((int64_t)ch * lv->Fmax + first), sizeof(double) * 2 * n,
+                           hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  lv->stage_pending = false;
+  for (int64_t f = 0; f < n; f++) {
+    out[f].frame_idx = (int32_t)(first + f);
+    out[f].m1 = micro_of_db(d[2 * f]);  // as stored (db_ctx_handler.c:479-481)
+    out[f].m2 = micro_of_db(d[2 * f + 1]);
+    out[f].reserved = 0;
+    out[f].q1 = d[2 * f];
+    out[f].q2 = d[2 * f + 1];
+  }
+  return TFP_OK;
+}
+
+int tfp_live_window_stats(tfp_live* lv, int64_t* slid_calls, int64_t* general_calls, int64_t* rebuilds, int64_t* frames_added,
+                          int64_t* frames_removed, int64_t* rows_restarted) {
+  if (!lv) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  if (slid_calls) *slid_calls = lv->n_wslid;
+  if (general_calls) *general_calls = lv->n_wgeneral;
+  if (rebuilds) *rebuilds = lv->n_wrebuilds;
+  if (frames_added) *frames_added = lv->n_wadded;
+  if (frames_removed) *frames_removed = lv->n_wremoved;
+  if (rows_restarted) *rows_restarted = lv->n_wrestarted;
+  return TFP_OK;
+}
 
 int tfp_synth_pcm(const tfp_synth_spec* specs, int32_t nclips, int64_t spc, int16_t* out) {
   if (nclips < 0 || spc < 0 || (nclips && (!specs || !out))) return TFP_E_ARG;

@@ -1563,4 +1563,48 @@ int tfp_group_live_verdict(tfp_group_live* gl, const int64_t* total, const tfp_s
   return TFP_OK;
 }
 
+// Every shard keeps every channel: each answers for its own clips from its own window table, and the
+// rows merge as a push's do. The frame counts and first frames come from the group's sample counts.
+int tfp_group_live_window(tfp_group_live* gl, const tfp_search_params* P, const int32_t* scopes, int32_t k, int32_t window,
+                          tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames) {
+  if (!gl) return TFP_E_ARG;
+  tfp_group* g = gl->g;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  const int32_t nch = gl->nch;
+  if (!P || !out || !counts) return gfail(g, TFP_E_ARG, "live window: NULL params or output");
+  if (window < 1) return gfail(g, TFP_E_ARG, "live window: window = %d frames", window);
+  if (k < 1 || k > TFP_RANK_MAX) return gfail(g, TFP_E_ARG, "live window: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+  if (scopes)
+    if (int rc = group_scope_args(g, scopes, nch)) return rc;
+  if (valid_params(P)) {
+    const int rc = group_rank(g, nch, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+      return tfp_live_window(gl->lv[s], P, scopes, k, window, o, c, nullptr, nullptr);
+    });
+    if (rc) return rc;
+  } else {  // empty rows (fp_handler.c:247-250)
+    memset(out, 0, sizeof(tfp_candidate) * (size_t)nch * k);
+    memset(counts, 0, sizeof(int32_t) * nch);
+  }
+  for (int32_t c = 0; c < nch; c++) {
+    const int64_t F = tfp::live_frames(gl->samples[c]), first = F > window ? F - window : 0;
+    if (frame_counts) frame_counts[c] = (int32_t)(F - first);
+    if (first_frames) first_frames[c] = (int32_t)first;
+  }
+  return TFP_OK;
+}
+
+int tfp_group_live_frames(tfp_group_live* gl, int32_t ch, int64_t first, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!gl || !nframes) return TFP_E_ARG;
+  tfp_group* g = gl->g;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  const int rc = tfp_live_frames(gl->lv[0], ch, first, out, cap, nframes);  // (every shard keeps the same values)
+  return rc ? gfail(g, rc, "%s", tfp_engine_last_error(g->eng[0])) : TFP_OK;
+}
+
+int tfp_group_live_window_stats(tfp_group_live* gl, int32_t shard, int64_t* slid_calls, int64_t* general_calls,
+                                int64_t* rebuilds, int64_t* frames_added, int64_t* frames_removed, int64_t* rows_restarted) {
+  if (!gl || shard < 0 || (size_t)shard >= gl->lv.size()) return TFP_E_ARG;
+  return tfp_live_window_stats(gl->lv[shard], slid_calls, general_calls, rebuilds, frames_added, frames_removed, rows_restarted);
+}
+
 }  // extern "C"

@@ -6,6 +6,8 @@
 // score read from the count row plus the provisional tail frame's bit, instead of summed over the
 // query's keys; its partial lists go through ranked search's merge (launch_rank_merge).
 // live_gather_kernel: the frame histories laid end to end for the general form.
+// live_slide_kernel: a trailing window's count rows (tfp_live_window): the key bitset rows of the
+// frames that left a channel's window subtracted from its row, those of the newly final frames added.
 // live_scatter_g711_kernel: live_scatter_kernel over G.711 codes, expanded by tfp_g711.hpp's map.
 // live_verdict_kernel: the two greatest candidates per channel for tfp_live_verdict, a count of 0
 // included, over the candidate table live_candidates_kernel derives from the scope table.
@@ -24,7 +26,8 @@ namespace tfp {
 
 namespace {
 
-constexpr int kLiveAddCols = 8 * 256;  // columns per live_add block (8 per thread)
+constexpr int kLiveAddCols = 8 * 256;  // columns per live_add / live_slide block (8 per thread)
+constexpr int kLiveSlideAhead = 4;     // bitset loads live_slide_kernel issues ahead of their use
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long key) {
 #pragma unroll
@@ -96,6 +99,68 @@ __global__ __launch_bounds__(256) void live_add_kernel(const double* __restrict_
     v.z += ((b >> 4) & 1u) | ((b & 32u) << 11);
     v.w += ((b >> 6) & 1u) | ((b & 128u) << 9);
   }
+  *row = v;
+  if (out_of_range && blockIdx.x == 0 && threadIdx.x == 0) *bad = 1;
+}
+
+// live_add_kernel's row handling for a trailing window (tfp_live_window.hpp): the frames [sub_beg, sub_end)
+// leave the row and [add_beg, add_end) enter it, with one 16-byte load and one 16-byte store of the
+// counts however many frames move; a restarting row starts from zero instead of loading. The 16-bit
+// counts are subtracted in pairs as 32-bit words: a row holds exactly the frames of its range under
+// one stamp, so every bit a leaving frame subtracts was added by that frame and no borrow crosses
+// (a leaving frame whose SQL does not run, or whose key is out of range, subtracts nothing, as it
+// added nothing). The frame and its key are the same in every lane, and the bitset loads of
+// successive frames depend on the frame values only, not on the accumulators: kLiveSlideAhead of
+// them are issued, unconditionally (a frame past the range re-reads the last one and is masked, a
+// key that does not count reads row 0), before the first is used.
+template <bool ADD>
+__device__ __forceinline__ void live_slide_side(const double* __restrict__ qc, int32_t fbeg, int32_t fend,
+                                                const SearchConsts& sc, const uint32_t* __restrict__ col, int32_t W, int sh,
+                                                uint4& v, bool& out_of_range) {
+  for (int32_t f0 = fbeg; f0 < fend; f0 += kLiveSlideAhead) {
+    uint32_t b[kLiveSlideAhead];
+    bool use[kLiveSlideAhead];
+#pragma unroll
+    for (int j = 0; j < kLiveSlideAhead; j++) {
+      const bool inside = f0 + j < fend;
+      int32_t k = 0;
+      const bool runs = frame_key(qc, inside ? f0 + j : fend - 1, sc, k);
+      const int64_t idx = (int64_t)k + kKeyOffset;
+      const bool in_range = idx >= 0 && idx < kKeyRange;
+      if (ADD && inside && runs && !in_range) out_of_range = true;
+      use[j] = inside && runs && in_range;
+      b[j] = col[(use[j] ? idx : 0) * W];
+    }
+#pragma unroll
+    for (int j = 0; j < kLiveSlideAhead; j++) {
+      const uint32_t t = use[j] ? b[j] >> sh : 0u;  // bit i: column c8 + i
+      const uint32_t x = (t & 1u) | ((t & 2u) << 15), y = ((t >> 2) & 1u) | ((t & 8u) << 13);
+      const uint32_t z = ((t >> 4) & 1u) | ((t & 32u) << 11), w = ((t >> 6) & 1u) | ((t & 128u) << 9);
+      if (ADD) {
+        v.x += x, v.y += y, v.z += z, v.w += w;
+      } else {
+        v.x -= x, v.y -= y, v.z -= z, v.w -= w;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void live_slide_kernel(const double* __restrict__ q, int64_t Fmax,
+                                                         const LiveSlide* __restrict__ slides, SearchConsts sc,
+                                                         const uint32_t* __restrict__ bits, int32_t W, int64_t Cpad,
+                                                         uint16_t* __restrict__ counts, int32_t* __restrict__ bad) {
+  const LiveSlide d = slides[blockIdx.y];
+  const int64_t c8 = 8 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
+  if (c8 >= Cpad) return;  // (Cpad is a multiple of 128: a thread's 8 columns lie inside the row or outside it)
+  const double* qc = q + 2 * (int64_t)d.ch * Fmax;
+  uint4* row = reinterpret_cast<uint4*>(counts + (int64_t)d.ch * Cpad + c8);
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (!d.restart) v = *row;  // (the same in every lane)
+  const uint32_t* col = bits + (c8 >> 5);
+  const int sh = (int)(c8 & 31);
+  bool out_of_range = false;
+  live_slide_side<false>(qc, d.sub_beg, d.sub_end, sc, col, W, sh, v, out_of_range);
+  live_slide_side<true>(qc, d.add_beg, d.add_end, sc, col, W, sh, v, out_of_range);
   *row = v;
   if (out_of_range && blockIdx.x == 0 && threadIdx.x == 0) *bad = 1;
 }
@@ -252,10 +317,11 @@ __global__ __launch_bounds__(256) void live_candidates_kernel(const int32_t* __r
 }
 
 __global__ __launch_bounds__(256) void live_gather_kernel(const double* __restrict__ q, int64_t Fmax,
-                                                          const int64_t* __restrict__ foff, double* __restrict__ out) {
+                                                          const int64_t* __restrict__ foff,
+                                                          const int64_t* __restrict__ first, double* __restrict__ out) {
   const int ch = blockIdx.y;
   const int64_t f0 = foff[ch], n = foff[ch + 1] - f0;
-  const double2* src = reinterpret_cast<const double2*>(q) + (int64_t)ch * Fmax;
+  const double2* src = reinterpret_cast<const double2*>(q) + (int64_t)ch * Fmax + (first ? first[ch] : 0);
   double2* dst = reinterpret_cast<double2*>(out) + f0;
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < n; f += (int64_t)gridDim.x * 256) dst[f] = src[f];
 }
@@ -330,6 +396,16 @@ hipError_t launch_live_add(const double* d_q, int64_t Fmax, const LiveAdd* d_add
   return hipGetLastError();
 }
 
+hipError_t launch_live_slide(const double* d_q, int64_t Fmax, const LiveSlide* d_slide, int32_t nslide, SearchConsts sc,
+                             const uint32_t* d_bits, int32_t C, uint16_t* d_counts, int32_t* d_bad, hipStream_t s) {
+  if (nslide <= 0) return hipSuccess;
+  if (C <= 0 || nslide > 65535) return hipErrorInvalidValue;
+  const int64_t Cpad = live_count_cols(C);
+  hipLaunchKernelGGL(live_slide_kernel, dim3((unsigned)((Cpad + kLiveAddCols - 1) / kLiveAddCols), nslide), dim3(256), 0, s,
+                     d_q, Fmax, d_slide, sc, d_bits, key_bits_words(C), Cpad, d_counts, d_bad);
+  return hipGetLastError();
+}
+
 hipError_t launch_live_select(const double* d_q, int64_t Fmax, const LiveChan* d_chan, int32_t nch, SearchConsts sc,
                               const uint32_t* d_bits, int32_t C, const uint16_t* d_counts, const int32_t* d_tiekey,
                               const int32_t* d_table, int32_t K, unsigned long long* d_part, unsigned long long* d_keys,
@@ -343,11 +419,11 @@ hipError_t launch_live_select(const double* d_q, int64_t Fmax, const LiveChan* d
   return err != hipSuccess ? err : launch_rank_merge(d_part, nch, nb * K, K, d_keys, s);
 }
 
-hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, int32_t nch, int64_t max_n,
-                              double* d_out, hipStream_t s) {
+hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, const int64_t* d_first, int32_t nch,
+                              int64_t max_n, double* d_out, hipStream_t s) {
   if (nch <= 0) return hipSuccess;
   if (nch > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(live_gather_kernel, dim3(copy_blocks(max_n), nch), dim3(256), 0, s, d_q, Fmax, d_foff, d_out);
+  hipLaunchKernelGGL(live_gather_kernel, dim3(copy_blocks(max_n), nch), dim3(256), 0, s, d_q, Fmax, d_foff, d_first, d_out);
   return hipGetLastError();
 }
 

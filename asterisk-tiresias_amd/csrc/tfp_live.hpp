@@ -16,6 +16,12 @@
 // included); the count table uint16 [nchannels][Cpad], Cpad = 32 key_bits_words(C) columns in the
 // scope table's layout (main columns, then the delta's). The channels' sample counts and added-frame
 // counts are kept by the host and travel with each push's descriptors.
+//
+// The trailing window (tfp_live_window, tfp_live_window.hpp) keeps a second count table in the same
+// layout, allocated by the first window call: channel c's row holds the final frames of the last
+// `window` frames of its call, moved from call to call by launch_live_slide (the rows of the frames
+// that left subtracted, those of the newly final frames added) and read by launch_live_select as a
+// push's row is. The rows' frame ranges are host state.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +29,7 @@
 #include "tfp_g711.hpp"
 #include "tfp_kernels.hpp"
 #include "tfp_live_plan.hpp"
+#include "tfp_live_window.hpp"
 #include "tfp_rank.hpp"
 #include "tfp_scope.hpp"
 
@@ -42,6 +49,13 @@ struct LiveCopy {
 // Final frames [fbeg, fend) of channel ch to add to its count row.
 struct LiveAdd {
   int32_t ch, fbeg, fend, pad;
+};
+
+// A window call's change to channel ch's row of the window count table (tfp_live_window.hpp): the
+// final frames [sub_beg, sub_end) leave it, [add_beg, add_end) enter it; restart: the row starts from
+// zero instead of from what it holds (and nothing is subtracted).
+struct LiveSlide {
+  int32_t ch, sub_beg, sub_end, add_beg, add_end, restart, pad0, pad1;
 };
 
 // Per channel and verdict (launch_live_verdict): a descriptor of its own, a push's LiveChan stays as it is.
@@ -87,6 +101,13 @@ hipError_t launch_live_store(const double* d_db, const LiveCopy* d_cp, int32_t n
 // no atomics. *d_bad is set (never cleared) when a key lies outside [-512, 511].
 hipError_t launch_live_add(const double* d_q, int64_t Fmax, const LiveAdd* d_add, int32_t nadd, SearchConsts sc,
                            const uint32_t* d_bits, int32_t C, uint16_t* d_counts, int32_t* d_bad, hipStream_t s);
+// counts[ch][col] += bits[key(frame)][col] over each entry's entering frames and -= over its leaving
+// frames (an entry with restart set starts its row from zero), live_add's shape: one workgroup owns
+// 2,048 columns of one channel, one 16-byte load and store of the row per thread, no atomics. At most
+// one entry per channel. *d_bad is set (never cleared) when an entering frame's key lies outside
+// [-512, 511].
+hipError_t launch_live_slide(const double* d_q, int64_t Fmax, const LiveSlide* d_slide, int32_t nslide, SearchConsts sc,
+                             const uint32_t* d_bits, int32_t C, uint16_t* d_counts, int32_t* d_bad, hipStream_t s);
 // d_keys[ch * K + r] = row r of channel ch: the r-th greatest (count + tail bit) << 32 | tie key over
 // the columns of scope d_chan[ch].scope with a non-zero score. d_part: nch * rank_vote_blocks(C) * K
 // keys of scratch. *d_bad as above (the tail's key).
@@ -95,8 +116,9 @@ hipError_t launch_live_select(const double* d_q, int64_t Fmax, const LiveChan* d
                               const int32_t* d_table, int32_t K, unsigned long long* d_part, unsigned long long* d_keys,
                               int32_t* d_bad, hipStream_t s);
 // The channels' frame values laid end to end for the general form: channel c's frames
-// [0, d_foff[c + 1] - d_foff[c]) at d_out frame d_foff[c] (at most max_n frames per channel).
-hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, int32_t nch, int64_t max_n,
-                              double* d_out, hipStream_t s);
+// [first, first + d_foff[c + 1] - d_foff[c]), first = d_first[c] (nullptr: 0), at d_out frame d_foff[c]
+// (at most max_n frames per channel).
+hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, const int64_t* d_first, int32_t nch,
+                              int64_t max_n, double* d_out, hipStream_t s);
 
 }  // namespace tfp

@@ -865,6 +865,36 @@ class _LiveCalls:
         return [{"leader": cand(v.leader, v.has_leader), "rival": cand(v.rival, v.has_rival), "remaining": v.remaining,
                  "complete": bool(v.complete), "decided": bool(v.decided)} for v in out]
 
+    def window(self, p: SearchParams, scopes=None, k: int = 1, window: int = 1):
+        """tfp_live_window: (rows, frame_counts, first_frames), per channel the first k rows of the scoped
+        search of the last `window` frames of its call so far (the tail included), how many frames that
+        is and the first of them. Ingests nothing."""
+        n, k = self.nchannels, int(k)
+        sc = None if scopes is None else np.ascontiguousarray(scopes, np.int32)
+        if sc is not None and len(sc) != n:
+            raise ValueError("one entry per channel")
+        out, counts = (Candidate * max(1, n * max(k, 1)))(), (C.c_int32 * n)()
+        fc, ff = (C.c_int32 * n)(), (C.c_int32 * n)()
+        self._owner._chk(self._fn("_window")(self._h, C.byref(p) if p is not None else None,
+                                             None if sc is None else sc.ctypes.data, k, int(window), out, counts, fc, ff))
+        return Engine._candidates(out, counts, n, k), list(fc), list(ff)
+
+    def frames(self, channel: int, first: int = 0, cap: int = None) -> np.ndarray:
+        """tfp_live_frames: the kept frames [first, F) of the channel's call so far (exact q values).
+        cap: the capacity handed to the call (None: what it needs)."""
+        got = C.c_int64()
+        if cap is None:
+            cap = max(frame_count(self.samples(channel)) - int(first), 0)
+        out = np.zeros(max(int(cap), 1), FRAME_DTYPE)
+        self._owner._chk(self._fn("_frames")(self._h, int(channel), int(first), out.ctypes.data, int(cap), C.byref(got)))
+        return out[:got.value]
+
+    def _window_stats(self, *lead):
+        v = [C.c_int64() for _ in range(6)]
+        self._owner._chk(self._fn("_window_stats")(self._h, *lead, *[C.byref(x) for x in v]))
+        return dict(zip(("slid_calls", "general_calls", "rebuilds", "frames_added", "frames_removed", "rows_restarted"),
+                        (x.value for x in v)))
+
     def close(self):
         # the destroy call uses the owner: an object outliving its owner's close() was destroyed by it
         if self._h and self._owner._h:
@@ -891,6 +921,10 @@ class Live(_LiveCalls):
         self._owner._chk(lib().tfp_live_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("incremental_pushes", "general_pushes", "rebuilds", "frames_fingerprinted", "frames_added"),
                         (x.value for x in v)))
+
+    def window_stats(self) -> dict:
+        """tfp_live_window_stats: window calls by form, table restarts, frames added and removed, rows restarted."""
+        return self._window_stats()
 
 
 class Plan:
@@ -1175,3 +1209,7 @@ class GroupLive(_LiveCalls):
             res.append(dict(zip(("incremental_pushes", "general_pushes", "rebuilds", "frames_fingerprinted",
                                  "frames_added"), (x.value for x in v))))
         return res
+
+    def window_stats(self) -> list:
+        """tfp_group_live_window_stats: each shard's tfp_live_window_stats, in shard order."""
+        return [self._window_stats(shard) for shard in range(len(self._owner.devices))]

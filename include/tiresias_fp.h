@@ -824,6 +824,60 @@ struct tfp_live_verdict {
 int tfp_live_verdict(tfp_live* lv, const int64_t* total_samples, const tfp_search_params* params,
                      const int32_t* scopes, struct tfp_live_verdict* out /*[nchannels]*/);
 
+/* The trailing window: the rows of the last `window` frames of each call. An announcement or a
+ * greeting that begins after an unknown stretch of ringback is diluted by its lead-in for as long as
+ * the recording stays anchored at the start of the call (application_handler.c:152-185, record_voice
+ * :248-312); the window is that recording with its start moved along.
+ *
+ * Channel c has taken S samples since its last reset: F = tfp_frame_count(S), Ff = floor(S / 256), the
+ * provisional tail is frame Ff when S % 256 != 0; first = max(0, F - window). The channel's window is
+ * frames [first, F) of the call, the tail included. Its rows are what tfp_search_scoped_batch returns
+ * for one query holding exactly the frame values of [first, F) as the live object keeps them
+ * (tfp_live_frames; fp_handler.c:287-374 with the context predicate at :308-314), with the same
+ * params, scope and k, row for row (match_count, uuid, clip_id); frame_counts[c] = F - first and
+ * first_frames[c] = first. So while F <= window the rows are tfp_live_push's, and once F >= window
+ * they are the last window of tfp_search_sliding_batch over the call's frames with that window and
+ * hop = 1. This holds after every call, for every interleaving of pushes (int16 or G.711) and resets,
+ * across index updates and across changes of params, scope, k or window between calls. A channel with
+ * S = 0 gives no rows, frame_counts = 0 and first_frames = 0; an empty index gives no rows.
+ *
+ * The call ingests nothing and fingerprints nothing (a caller pushes, ingest only or searching, and
+ * then asks). For coefs = 1 a second table of 16-bit counts, nchannels x the count row's columns,
+ * allocated by the first window call, holds per channel the sum of the key bitset rows of the
+ * window's final frames [first, Ff): a call subtracts the rows of the frames that left a channel's
+ * window and adds those of the frames that became final, or starts the row again from zero where
+ * that visits fewer frames, so it visits at most min(leaving + entering, Ff - first) frames per
+ * channel; the rows are selected from those counts plus the tail's bit. The table is restarted when
+ * the index, the resolved tolerance, an ignore threshold or `window` has changed since it was built
+ * (a change of scope or k needs no restart). coefs = 2, and a frame key outside the vote range, run
+ * the scoped search over each channel's window of kept frame values: exact, not incremental.
+ *
+ * 1 <= k <= TFP_RANK_MAX, window >= 1 (frames), scopes as tfp_live_push (NULL: TFP_SCOPE_ANY), params,
+ * out[nchannels * k] and counts[nchannels] not NULL: anything else is TFP_E_ARG and nothing is
+ * written. frame_counts and first_frames may be NULL. Invalid params (coefs outside [1, 2]) give empty
+ * rows, as a push does (fp_handler.c:247-250). */
+int tfp_live_window(tfp_live* lv, const tfp_search_params* params, const int32_t* scopes, int32_t k, int32_t window,
+                    tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames);
+/* `window` for window_ms of audio at sample_rate (the unit record_voice's duration is given in,
+ * application_handler.c:163): ceil(window_ms * sample_rate / 1000 / 256) frames, at least 1. Host-only. */
+int32_t tfp_live_window_frames(int64_t window_ms, int32_t sample_rate);
+/* The kept frame values of frames [first, F) of `channel`'s call so far, the provisional tail
+ * included (exact q values, what a push and a window search read; fp_handler.c:290, :321), as
+ * tfp_stream_window_frames reads out a stream's window. frame_idx is the frame's index in the call;
+ * m1 / m2 are the values as they would be stored. Changes nothing a later call sees. TFP_E_ARG for a
+ * channel outside [0, nchannels), first outside [0, F], or cap below F - first (*nframes then holds
+ * it). */
+int tfp_live_frames(tfp_live* lv, int32_t channel, int64_t first, tfp_frame* out, int64_t cap, int64_t* nframes);
+/* Window calls served from the window table (a coefs = 1 call over an empty index counts here too,
+ * though it builds no table and restarts nothing) and by the general form (the rows of
+ * fp_handler.c:367-374 either way), restarts of the whole table (a changed stamp), frames whose bitset
+ * rows the slide kernel added, frames that left rows (subtracted by the slide kernel, or dropped
+ * unvisited where a row restarted, a channel was reset or the table restarted: frames_added -
+ * frames_removed is what the rows hold), and rows restarted by a call. Any pointer may be NULL.
+ * tfp_live_stats is not moved by window calls. */
+int tfp_live_window_stats(tfp_live* lv, int64_t* slid_calls, int64_t* general_calls, int64_t* rebuilds,
+                          int64_t* frames_added, int64_t* frames_removed, int64_t* rows_restarted);
+
 /* ---- device groups: the node's GPUs behind one index (new in round 3) -------------------
  * The module's enrolled DB sharded over one engine per listed device (the reference
  * has one SQLite DB, fp_handler.c:30): each clip lives on one engine (the one holding the fewest
@@ -979,6 +1033,18 @@ int tfp_group_live_push_g711(tfp_group_live* lv, const uint8_t* codes, int32_t t
  * shard. Arguments and failures as tfp_live_verdict; a failing shard fails the call. */
 int tfp_group_live_verdict(tfp_group_live* lv, const int64_t* total_samples, const tfp_search_params* params,
                            const int32_t* scopes, struct tfp_live_verdict* out /*[nchannels]*/);
+/* tfp_live_window on a group (application_handler.c:152-185, :248-312 with the recording's start moved
+ * along): every shard keeps every channel, so each answers from a window table of its own over its
+ * own clips' columns, and the rows merge as tfp_group_live_push's do (fp_handler.c:367-374 with the
+ * context predicate at :308-314 over all shards). clip_id is the shard. Arguments and failures as
+ * tfp_live_window; a failing shard fails the call. tfp_group_live_frames reads shard 0's kept frame
+ * values (every shard keeps the same); tfp_group_live_window_stats is shard `shard`'s
+ * tfp_live_window_stats. */
+int tfp_group_live_window(tfp_group_live* lv, const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                          int32_t window, tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames);
+int tfp_group_live_frames(tfp_group_live* lv, int32_t channel, int64_t first, tfp_frame* out, int64_t cap, int64_t* nframes);
+int tfp_group_live_window_stats(tfp_group_live* lv, int32_t shard, int64_t* slid_calls, int64_t* general_calls,
+                                int64_t* rebuilds, int64_t* frames_added, int64_t* frames_removed, int64_t* rows_restarted);
 /* G.711 codes on a group (aubio_source's table[code], fp_handler.c:604, :633; as the engine calls):
  * a fingerprint batch's clips are expanded by the shard that fingerprints them; a search batch is
  * expanded by every shard, or, where an int16 batch would be query-sharded, each shard expands and

@@ -1734,6 +1734,83 @@ struct ast_json* fp_live_verdict(fp_live* lv, const char* const* contexts, const
 	return j_res;
 }
 
+/* The calls' trailing windows (tfp_group_live_window): per channel the first k rows of the search of
+ * the last window_ms of its call in its context, each with its catalog fields as fp_live_verdict
+ * fills the leader's (fp_handler.c:394-401), beside the window's first frame and frame count. */
+struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k)
+{
+	tfp_search_params p;
+	tfp_candidate* cand;
+	int32_t* scopes;
+	int32_t* counts;
+	int32_t* fc;
+	int32_t* ff;
+	int32_t c, i, kk;
+	int rc;
+	struct ast_json* j_res = NULL;
+
+	if(lv == NULL || contexts == NULL || window_ms <= 0 || k < 1) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	for(c = 0; c < lv->nch; c++) {
+		if(contexts[c] == NULL) {
+			ast_log(LOG_WARNING, "Wrong input parameter.\n");
+			return NULL;
+		}
+	}
+	/* coefs = 1: what the dialplan passes (application_handler.c:180), and the form whose counts slide */
+	if(search_params(&p, contexts[0], 1, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	kk = k > TFP_RANK_MAX ? TFP_RANK_MAX : k;
+	cand = ast_calloc((size_t)lv->nch * kk, sizeof(*cand));
+	scopes = ast_calloc(lv->nch, sizeof(*scopes));
+	counts = ast_calloc(lv->nch, sizeof(*counts));
+	fc = ast_calloc(lv->nch, sizeof(*fc));
+	ff = ast_calloc(lv->nch, sizeof(*ff));
+	if(cand != NULL && scopes != NULL && counts != NULL && fc != NULL && ff != NULL) {
+		for(c = 0; c < lv->nch; c++) {
+			scopes[c] = scope_of_context(contexts[c], false); /* as fp_search_fingerprint_in_context maps it */
+		}
+		rc = tfp_group_live_window(lv->lv, &p, scopes, kk, tfp_live_window_frames(window_ms, lv->sr), cand, counts, fc, ff);
+		if(rc != TFP_OK) {
+			ast_log(LOG_ERROR, "Could not search the calls' windows: %s\n", tfp_group_last_error(g_tfp));
+		}
+		else {
+			j_res = ast_json_array_create();
+		}
+		for(c = 0; j_res != NULL && c < lv->nch; c++) {
+			struct ast_json* j_ch = ast_json_object_create();
+			struct ast_json* j_rows = ast_json_array_create();
+			for(i = 0; i < counts[c]; i++) {
+				tfp_result r;
+				struct ast_json* j_tmp;
+				memset(&r, 0, sizeof(r));
+				r.found = 1;
+				r.match_count = cand[(size_t)c * kk + i].match_count;
+				r.frame_count = fc[c];
+				snprintf(r.uuid, sizeof(r.uuid), "%s", cand[(size_t)c * kk + i].uuid);
+				j_tmp = search_result(&r); /* a row whose audio_list entry is missing is skipped */
+				if(j_tmp != NULL) {
+					ast_json_array_append(j_rows, j_tmp);
+				}
+			}
+			ast_json_object_set(j_ch, "first_frame", ast_json_integer_create(ff[c]));
+			ast_json_object_set(j_ch, "frame_count", ast_json_integer_create(fc[c]));
+			ast_json_object_set(j_ch, "rows", j_rows);
+			ast_json_array_append(j_res, j_ch);
+		}
+	}
+	ast_free(cand);
+	ast_free(scopes);
+	ast_free(counts);
+	ast_free(fc);
+	ast_free(ff);
+	return j_res;
+}
+
 void fp_live_reset(fp_live* lv, int channel)
 {
 	if(lv != NULL && channel < lv->nch) {

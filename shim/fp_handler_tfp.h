@@ -166,6 +166,14 @@ void fp_channel_close(fp_channel* ch);
  * the call is complete and nothing matched. The context maps to a scope as for
  * fp_search_fingerprint_in_context; coefs is 1, as the dialplan passes it (application_handler.c:180).
  * NULL: bad arguments (a duration below what the channel has taken among them).
+ * fp_live_window: for a clip that begins after an unknown lead-in (ringback, early media), the search
+ * of the last window_ms of each call instead of the whole recording so far. contexts[nchannels]; a
+ * JSON array with one object per channel: "first_frame" and "frame_count" (the window is frames
+ * [first_frame, first_frame + frame_count) of the call, ceil(window_ms * rate / 1000 / 256) frames
+ * once the call is that long, at least 1, the unfinished last frame included) and "rows", the first
+ * k results of fp_search_fingerprint_in_context on exactly those frames, each with the fields of
+ * fp_search_fingerprint_info (uuid, name, context, hash, match_count, frame_count). It ingests
+ * nothing: push, then ask. coefs is 1. NULL: bad arguments (window_ms <= 0 or k < 1 among them).
  * fp_live_reset: a new call on `channel` (< 0: on every channel). */
 typedef struct fp_live fp_live;
 fp_live* fp_live_open(int nchannels, int sample_rate, int max_ms);
@@ -173,6 +181,8 @@ bool fp_live_push(fp_live* lv, const int16_t* slin, int tick_samples, const int3
 bool fp_live_push_g711(fp_live* lv, const uint8_t* payload, int tick_samples, int law, const int32_t* nsamples);
 struct ast_json* fp_live_verdict(fp_live* lv, const char* const* contexts, const int* duration_ms, const double tolerance,
 		const int freq_ignore_low, const int freq_ignore_high);
+struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k);
 void fp_live_reset(fp_live* lv, int channel);
 void fp_live_close(fp_live* lv);
 
