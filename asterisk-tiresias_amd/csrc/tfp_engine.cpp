@@ -4138,6 +4138,16 @@ struct tfp_live {
   SearchConsts wstamp_sc{};
   int64_t wstamp_window = 0;
   int64_t n_wslid = 0, n_wgeneral = 0, n_wrebuilds = 0, n_wadded = 0, n_wremoved = 0, n_wrestarted = 0;
+  // the aligned window (tfp_live_window_aligned), allocated by its first call and grown as needed: the
+  // rows' columns, the window frames' boxes [nchannels][stride], the pairs, launch_align's partial
+  // keys, and the results ([keys][bad flag][AlignOut], one read-back into wa_pin); the longest live
+  // clip's row count, per index version
+  DevBuf wa_cols, wa_boxes, wa_pairs, wa_part, wa_res, wa_wchan;
+  HostBuf wa_pin;
+  bool wa_nmax_valid = false;
+  uint64_t wa_nmax_version = 0;
+  int64_t wa_nmax = 0;
+  int64_t n_wa_inplace = 0, n_wa_general = 0, n_wa_pairs = 0;
   ~tfp_live() {
     if (stage_ev) (void)hipEventDestroy(stage_ev);
   }
@@ -4560,6 +4570,99 @@ bool live_wstamp_holds(const tfp_live* lv, const SearchConsts& sc, int64_t windo
          (!sc.has_low || t.thr_low == sc.thr_low) && (!sc.has_high || t.thr_high == sc.thr_high);
 }
 
+// What tfp_live_window_aligned asks of the window call's body besides the keys: out[c * K + r] = the
+// alignment of row r of channel c with the channel's window (zeros where the key is 0).
+struct LiveAlignReq {
+  std::vector<AlignOut> out;
+};
+
+// An aligned window call's sizes: per channel its window, the boxes' stride (the longest window), the
+// bands of the longest live clip against it, and the pairs per launch_align chunk.
+struct LiveAlignPlan {
+  std::vector<LiveWinChan> wchan;
+  int64_t stride = 0, max_bands = 0, chunk = 1;
+};
+
+int live_align_plan(tfp_live* lv, int32_t K, int64_t window, LiveAlignPlan& ap) {
+  tfp_engine* e = lv->eng;
+  const int32_t nch = lv->nch;
+  if (!lv->wa_nmax_valid || lv->wa_nmax_version != e->index_version) {  // (the caller has run rebuild)
+    lv->wa_nmax = 0;
+    for (const Clip& c : e->clips)
+      if (c.alive) lv->wa_nmax = std::max(lv->wa_nmax, c.nrows);
+    lv->wa_nmax_version = e->index_version;
+    lv->wa_nmax_valid = true;
+  }
+  ap.wchan.resize(nch);
+  ap.stride = 0;
+  for (int32_t c = 0; c < nch; c++) {
+    const int64_t F = live_frames(lv->samples[c]), first = F > window ? F - window : 0;
+    ap.wchan[c] = LiveWinChan{(int32_t)first, (int32_t)(F - first)};
+    ap.stride = std::max(ap.stride, F - first);
+  }
+  if (ap.stride + lv->wa_nmax > (int64_t(1) << 31))  // align_core's limit
+    return fail(e, TFP_E_CAPACITY, "live window: %lld frames against %lld rows", (long long)ap.stride, (long long)lv->wa_nmax);
+  ap.max_bands = align_bands(ap.stride, lv->wa_nmax);
+  const int64_t npairs = (int64_t)nch * K;
+  // pairs in chunks of <= 256 MB of partial keys (and of the launch grid's second dimension), as align_core
+  ap.chunk = std::max<int64_t>(1, std::min<int64_t>({(int64_t(1) << 25) / std::max<int64_t>(ap.max_bands, 1), kAlignMaxPairs, npairs}));
+  HIPCHK(e, lv->wa_cols.reserve(sizeof(int32_t) * (size_t)npairs));
+  HIPCHK(e, lv->wa_boxes.reserve(sizeof(FrameBox) * (size_t)(nch * ap.stride + 1)));
+  HIPCHK(e, lv->wa_pairs.reserve(sizeof(AlignPair) * (size_t)npairs));
+  HIPCHK(e, lv->wa_part.reserve(sizeof(unsigned long long) * (size_t)(ap.chunk * std::max<int64_t>(ap.max_bands, 1))));
+  const size_t rbytes = (sizeof(unsigned long long) + sizeof(AlignOut)) * (size_t)npairs + 8;
+  HIPCHK(e, lv->wa_res.reserve(rbytes));
+  HIPCHK(e, lv->wa_pin.reserve(rbytes));
+  return TFP_OK;
+}
+
+// The window frames' boxes from the kept frame values in place, then launch_align over the nch * K
+// pairs at wa_pairs, into d_out. Queued on s, no wait. The engine's tfp_align_stats is not moved.
+int live_align_launch(tfp_live* lv, const SearchConsts& sc, const LiveAlignPlan& ap, const LiveWinChan* d_wchan, int32_t K,
+                      AlignOut* d_out, hipStream_t s) {
+  tfp_engine* e = lv->eng;
+  const int64_t npairs = (int64_t)lv->nch * K;
+  HIPCHK(e, launch_live_window_boxes(lv->q.as<double>(), lv->Fmax, d_wchan, lv->nch, ap.stride, sc, lv->wa_boxes.as<FrameBox>(), s));
+  for (int64_t p0 = 0; p0 < npairs; p0 += ap.chunk) {
+    const int32_t n = (int32_t)std::min<int64_t>(ap.chunk, npairs - p0);
+    HIPCHK(e, launch_align(lv->wa_pairs.as<AlignPair>() + p0, n, ap.max_bands, lv->wa_boxes.as<FrameBox>(), e->st_m1.as<int32_t>(),
+                           e->st_m2.as<int32_t>(), sc.coefs == 2, lv->wa_part.as<unsigned long long>(), d_out + p0, s));
+  }
+  return TFP_OK;
+}
+
+// The general form's alignments: the rows came back from the scoped search core (keys, on the host), so
+// the pairs are built here from the clips' staging rows, uploaded with the channels' windows, and
+// aligned as the in-place form's are. Caller holds e->mu; returns after waiting for the stream.
+int live_align_general(tfp_live* lv, const SearchConsts& sc, int32_t K, int64_t window,
+                       const std::vector<unsigned long long>& keys, LiveAlignReq* al) {
+  tfp_engine* e = lv->eng;
+  hipStream_t s = e->stream;
+  const int32_t nch = lv->nch;
+  const size_t npairs = (size_t)nch * K;
+  LiveAlignPlan ap;
+  int rc = live_align_plan(lv, K, window, ap);
+  if (rc) return rc;
+  std::vector<AlignPair> pairs(npairs, AlignPair{0, 0, 0, 0});
+  for (size_t p = 0; p < npairs; p++) {
+    if (!keys[p]) continue;
+    const int32_t clip = clip_of_col(e, col_of_key(e, (int32_t)(uint32_t)(keys[p] & 0xffffffffu)));
+    if (clip < 0) return fail(e, TFP_E_HIP, "live window: tie-break key %u names no clip", (unsigned)(keys[p] & 0xffffffffu));
+    const Clip& c = e->clips[clip];
+    const LiveWinChan& w = ap.wchan[p / K];
+    if (c.nrows > 0 && w.F > 0) pairs[p] = AlignPair{c.off, (int64_t)(p / K) * ap.stride, (int32_t)c.nrows, w.F};
+  }
+  if ((rc = upload(e, lv->wa_pairs, pairs.data(), sizeof(AlignPair) * npairs)) ||
+      (rc = upload(e, lv->wa_wchan, ap.wchan.data(), sizeof(LiveWinChan) * nch)))
+    return rc;
+  AlignOut* d_out = reinterpret_cast<AlignOut*>(lv->wa_res.as<char>());
+  if ((rc = live_align_launch(lv, sc, ap, lv->wa_wchan.as<LiveWinChan>(), K, d_out, s))) return rc;
+  HIPCHK(e, hipMemcpyAsync(lv->wa_pin.p, d_out, sizeof(AlignOut) * npairs, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (pairs and ap.wchan are released on return)
+  al->out.assign(lv->wa_pin.as<AlignOut>(), lv->wa_pin.as<AlignOut>() + npairs);
+  return TFP_OK;
+}
+
 // The body of tfp_live_window: nothing is ingested and no frame fingerprinted. coefs = 1 over an index
 // with rows: the window table's stamp is checked (a mismatch zeroes the table and empties every range),
 // each channel's row is planned (live_window_plan) and the rows that owe frames go to the slide
@@ -4567,8 +4670,12 @@ bool live_wstamp_holds(const tfp_live* lv, const SearchConsts& sc, int64_t windo
 // as a push adds it. One upload (descriptors), one read-back (keys and the bad flag), one wait.
 // coefs = 2, and a key outside the vote range (which drops the table), gather each channel's window of
 // kept frame values for the scoped search core. keys: nch * K, zeroed where there is no row.
+// al (tfp_live_window_aligned): the rows' alignments as well. Served from the table, the select's keys
+// stay on the device: their columns, the window's boxes and the pairs are built there and launch_align
+// follows on the stream, so the call still has one upload, one read-back (keys, flag and alignments)
+// and one wait. The general form aligns after its rows have come back (live_align_general).
 int live_window_step(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int64_t window,
-                     std::vector<unsigned long long>& keys) {
+                     std::vector<unsigned long long>& keys, LiveAlignReq* al = nullptr) {
   tfp_engine* e = lv->eng;
   const int32_t nch = lv->nch;
   hipStream_t s = e->stream;
@@ -4580,12 +4687,15 @@ int live_window_step(tfp_live* lv, const tfp_search_params* P, const int32_t* sc
     if (!e->delta.clip.empty() && !delta_tol_ok(sc.tole) && (rc = consolidate(e))) return rc;
     if (e->ncols > 0 && e->nrows + e->delta.rows > 0) {
       if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s)) || (rc = ensure_scope_table(e, s))) return rc;
+      if (al && (rc = ensure_live_candidates(lv, s))) return rc;  // the columns' staged rows (LiveColRows)
       vote = true;
     }
   }
   keys.assign((size_t)nch * K, 0ull);
+  if (al) al->out.assign((size_t)nch * K, AlignOut{0, 0, 0, 0});
   if (sc.coefs == 1 && !vote) {  // an empty index: no row
     lv->n_wslid++;
+    if (al) lv->n_wa_inplace++;
     return TFP_OK;
   }
   if (vote) {
@@ -4601,8 +4711,11 @@ int live_window_step(tfp_live* lv, const tfp_search_params* P, const int32_t* sc
       if (p.owes)
         slides.push_back(LiveSlide{c, (int32_t)p.sub_beg, (int32_t)p.sub_end, (int32_t)p.add_beg, (int32_t)p.add_end, p.restart, 0, 0});
     }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_chan = al(sizeof(LiveChan) * nch), total = b_chan + al(sizeof(LiveSlide) * std::max<size_t>(slides.size(), 1));
+    LiveAlignPlan ap;
+    if (al && (rc = live_align_plan(lv, K, window, ap))) return rc;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_chan = up(sizeof(LiveChan) * nch), o_wchan = b_chan + up(sizeof(LiveSlide) * std::max<size_t>(slides.size(), 1)),
+                 total = o_wchan + (al ? up(sizeof(LiveWinChan) * nch) : 0);
     const size_t nkeys = (size_t)nch * K;
     if (lv->stage_pending) HIPCHK(e, hipEventSynchronize(lv->stage_ev));  // the last call's upload has read stage_h
     lv->stage_pending = false;
@@ -4618,6 +4731,7 @@ int live_window_step(tfp_live* lv, const tfp_search_params* P, const int32_t* sc
     char* h = lv->stage_h.as<char>();
     memcpy(h, chan.data(), sizeof(LiveChan) * nch);
     if (!slides.empty()) memcpy(h + b_chan, slides.data(), sizeof(LiveSlide) * slides.size());
+    if (al) memcpy(h + o_wchan, ap.wchan.data(), sizeof(LiveWinChan) * nch);
     HIPCHK(e, hipMemcpyAsync(lv->dstage.p, h, total, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipEventRecord(lv->stage_ev, s));
     lv->stage_pending = true;
@@ -4647,17 +4761,46 @@ int live_window_step(tfp_live* lv, const tfp_search_params* P, const int32_t* sc
       lv->wbeg[c] = p.a;
       lv->wend[c] = p.b;
     }
+    // (aligned: the keys go where the one read-back takes them from, [keys][bad flag][AlignOut])
+    unsigned long long* d_keys = al ? lv->wa_res.as<unsigned long long>() : lv->keys.as<unsigned long long>();
     HIPCHK(e, launch_live_select(lv->q.as<double>(), lv->Fmax, reinterpret_cast<const LiveChan*>(d), nch, sc, d_bits, C,
                                  lv->wcounts.as<uint16_t>(), e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
-                                 lv->part.as<unsigned long long>(), lv->keys.as<unsigned long long>(), lv->wbad.as<int32_t>(), s));
+                                 lv->part.as<unsigned long long>(), d_keys, lv->wbad.as<int32_t>(), s));
     unsigned long long* hk = lv->keys_pin.as<unsigned long long>();
-    HIPCHK(e, hipMemcpyAsync(hk, lv->keys.p, sizeof(unsigned long long) * nkeys, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipMemcpyAsync(hk + nkeys, lv->wbad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (al) {
+      const LiveWinChan* d_wchan = reinterpret_cast<const LiveWinChan*>(d + o_wchan);
+      int32_t* d_flag = reinterpret_cast<int32_t*>(d_keys + nkeys);
+      AlignOut* d_out = reinterpret_cast<AlignOut*>(d_keys + nkeys + 1);
+      HIPCHK(e, hipMemsetAsync(lv->wa_cols.p, 0xff, sizeof(int32_t) * nkeys, s));  // -1: no column
+      HIPCHK(e, launch_live_key_cols(d_keys, reinterpret_cast<const LiveChan*>(d), nch, K, e->tiekey.as<int32_t>(),
+                                     e->scope_table.as<int32_t>(), lv->cand_rows.as<LiveColRows>(), C, lv->wa_cols.as<int32_t>(), s));
+      HIPCHK(e, launch_live_pairs(d_keys, lv->wa_cols.as<int32_t>(), lv->cand_rows.as<LiveColRows>(), C, d_wchan, nch, K, ap.stride,
+                                  lv->wbad.as<int32_t>(), lv->wa_pairs.as<AlignPair>(), d_flag, s));
+      if ((rc = live_align_launch(lv, sc, ap, d_wchan, K, d_out, s))) return rc;
+      hk = lv->wa_pin.as<unsigned long long>();
+      HIPCHK(e, hipMemcpyAsync(hk, d_keys, (sizeof(unsigned long long) + sizeof(AlignOut)) * nkeys + 8, hipMemcpyDeviceToHost, s));
+    } else {
+      HIPCHK(e, hipMemcpyAsync(hk, lv->keys.p, sizeof(unsigned long long) * nkeys, hipMemcpyDeviceToHost, s));
+      HIPCHK(e, hipMemcpyAsync(hk + nkeys, lv->wbad.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(e, hipStreamSynchronize(s));
     lv->stage_pending = false;
     if (!(uint32_t)hk[nkeys]) {
       std::copy(hk, hk + nkeys, keys.begin());
       lv->n_wslid++;
+      if (al) {
+        // (counted before the check below: the table has moved, so the stats name the call it was)
+        lv->n_wa_inplace++;
+        for (size_t p = 0; p < nkeys; p++) lv->n_wa_pairs += keys[p] != 0;
+        const AlignOut* ho = reinterpret_cast<const AlignOut*>(hk + nkeys + 1);
+        for (size_t p = 0; p < nkeys; p++) {
+          if (!keys[p]) continue;
+          // a row has a frame that hits one of its clip's rows, so its best diagonal holds a hit
+          if (ho[p].aligned_count <= 0)
+            return fail(e, TFP_E_HIP, "live window: no staged rows found for tie-break key %u", (unsigned)(keys[p] & 0xffffffffu));
+          al->out[p] = ho[p];
+        }
+      }
       return TFP_OK;
     }
     lv->wstamp_valid = false;  // the table holds frames it could not add: dropped, as a push drops its own
@@ -4668,6 +4811,13 @@ int live_window_step(tfp_live* lv, const tfp_search_params* P, const int32_t* sc
   HIPCHK(e, hipStreamSynchronize(s));  // (live_general returns before any wait when no channel has a frame)
   lv->stage_pending = false;
   lv->n_wgeneral++;
+  if (al) {
+    if ((rc = live_align_general(lv, sc, K, window, keys, al))) return rc;
+    for (size_t p = 0; p < keys.size(); p++)
+      if (!keys[p]) al->out[p] = AlignOut{0, 0, 0, 0};
+      else lv->n_wa_pairs++;
+    lv->n_wa_general++;
+  }
   return TFP_OK;
 }
 
@@ -4733,29 +4883,67 @@ int tfp_live_verdict(tfp_live* lv, const int64_t* total, const tfp_search_params
   return TFP_OK;
 }
 
-int tfp_live_window(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int32_t window,
-                    tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames) {
-  if (!lv) return TFP_E_ARG;
+namespace {
+// tfp_live_window (align NULL, aligned false) and tfp_live_window_aligned: the same arguments, rows,
+// counts and frame ranges; the aligned call also fills align[nch * K], zeros past counts[c].
+int live_window_call(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int32_t window,
+                     tfp_candidate* out, tfp_alignment* align, bool aligned, int32_t* counts, int32_t* frame_counts,
+                     int32_t* first_frames) {
   tfp_engine* e = lv->eng;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   const int32_t nch = lv->nch;
-  if (!P || !out || !counts) return fail(e, TFP_E_ARG, "live window: NULL params or output");
+  if (!P || !out || !counts || (aligned && !align)) return fail(e, TFP_E_ARG, "live window: NULL params or output");
   if (window < 1) return fail(e, TFP_E_ARG, "live window: window = %d frames", window);
   if (K < 1 || K > TFP_RANK_MAX) return fail(e, TFP_E_ARG, "live window: k = %d outside [1, %d]", K, TFP_RANK_MAX);
   for (int32_t c = 0; scopes && c < nch; c++)
     if (scopes[c] < TFP_SCOPE_ANY) return fail(e, TFP_E_ARG, "live window: scope %d of channel %d", scopes[c], c);
   HIPCHK(e, hipSetDevice(e->device));
   std::vector<unsigned long long> keys((size_t)nch * K, 0ull);
+  LiveAlignReq al;
+  if (aligned) al.out.assign((size_t)nch * K, AlignOut{0, 0, 0, 0});
   if (valid_params(P)) {  // fp_handler.c:247-250: bad params -> empty rows
-    const int rc = live_window_step(lv, P, scopes, K, window, keys);
+    const int rc = live_window_step(lv, P, scopes, K, window, keys, aligned ? &al : nullptr);
     if (rc) return rc;
   }
   fill_candidates(e, keys, nch, K, out, counts);
+  if (aligned) {
+    memset(align, 0, sizeof(tfp_alignment) * (size_t)nch * K);
+    for (int32_t c = 0; c < nch; c++) {  // fill_candidates' walk: a key that names no clip has no row
+      int32_t n = 0;
+      for (int32_t r = 0; r < K && keys[(size_t)c * K + r]; r++) {
+        if (clip_of_col(e, col_of_key(e, (int32_t)(uint32_t)(keys[(size_t)c * K + r] & 0xffffffffu))) < 0) continue;
+        memcpy(&align[(size_t)c * K + n++], &al.out[(size_t)c * K + r], sizeof(tfp_alignment));
+      }
+    }
+  }
   for (int32_t c = 0; c < nch; c++) {
     const int64_t F = live_frames(lv->samples[c]), first = F > window ? F - window : 0;
     if (frame_counts) frame_counts[c] = (int32_t)(F - first);
     if (first_frames) first_frames[c] = (int32_t)first;
   }
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_live_window(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int32_t window,
+                    tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames) {
+  if (!lv) return TFP_E_ARG;
+  return live_window_call(lv, P, scopes, K, window, out, nullptr, false, counts, frame_counts, first_frames);
+}
+
+int tfp_live_window_aligned(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int32_t window,
+                            tfp_candidate* out, tfp_alignment* align, int32_t* counts, int32_t* frame_counts,
+                            int32_t* first_frames) {
+  if (!lv) return TFP_E_ARG;
+  return live_window_call(lv, P, scopes, K, window, out, align, true, counts, frame_counts, first_frames);
+}
+
+int tfp_live_window_aligned_stats(tfp_live* lv, int64_t* inplace_calls, int64_t* general_calls, int64_t* pairs) {
+  if (!lv) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  if (inplace_calls) *inplace_calls = lv->n_wa_inplace;
+  if (general_calls) *general_calls = lv->n_wa_general;
+  if (pairs) *pairs = lv->n_wa_pairs;
   return TFP_OK;
 }
 

@@ -1563,26 +1563,57 @@ int tfp_group_live_verdict(tfp_group_live* gl, const int64_t* total, const tfp_s
   return TFP_OK;
 }
 
-// Every shard keeps every channel: each answers for its own clips from its own window table, and the
-// rows merge as a push's do. The frame counts and first frames come from the group's sample counts.
-int tfp_group_live_window(tfp_group_live* gl, const tfp_search_params* P, const int32_t* scopes, int32_t k, int32_t window,
-                          tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames) {
-  if (!gl) return TFP_E_ARG;
+}  // extern "C"
+
+namespace {
+// tfp_group_live_window (aligned false) and tfp_group_live_window_aligned: the same arguments, rows, counts
+// and frame ranges. Every shard keeps every channel: each answers for its own clips from its own window
+// table, and the rows merge as a push's do. The frame counts and first frames come from the group's
+// sample counts. Aligned: every shard aligns its own rows (tfp_live_window_aligned), and a kept row
+// takes the alignment its shard computed for it, found by the shard-local clip id.
+int group_live_window_call(tfp_group_live* gl, const tfp_search_params* P, const int32_t* scopes, int32_t k, int32_t window,
+                           tfp_candidate* out, tfp_alignment* align, bool aligned, int32_t* counts, int32_t* frame_counts,
+                           int32_t* first_frames) {
   tfp_group* g = gl->g;
   std::lock_guard<std::recursive_mutex> lk(g->mu);
   const int32_t nch = gl->nch;
-  if (!P || !out || !counts) return gfail(g, TFP_E_ARG, "live window: NULL params or output");
+  if (!P || !out || !counts || (aligned && !align)) return gfail(g, TFP_E_ARG, "live window: NULL params or output");
   if (window < 1) return gfail(g, TFP_E_ARG, "live window: window = %d frames", window);
   if (k < 1 || k > TFP_RANK_MAX) return gfail(g, TFP_E_ARG, "live window: k = %d outside [1, %d]", k, TFP_RANK_MAX);
   if (scopes)
     if (int rc = group_scope_args(g, scopes, nch)) return rc;
+  const size_t np = (size_t)nch * k;
   if (valid_params(P)) {
-    const int rc = group_rank(g, nch, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
-      return tfp_live_window(gl->lv[s], P, scopes, k, window, o, c, nullptr, nullptr);
-    });
+    const int n = (int)g->eng.size();
+    std::vector<std::vector<tfp_alignment>> sal(aligned ? n : 0, std::vector<tfp_alignment>(np));
+    // each shard's rows as shard-local clip ids (-1 past its count): group_rank's own buffers end with it
+    std::vector<std::vector<int32_t>> sid(aligned ? n : 0, std::vector<int32_t>(np, -1));
+    std::vector<int32_t> kept;
+    const int rc = group_rank(
+        g, nch, P, k, out, counts,
+        [&](int s, tfp_candidate* o, int32_t* c) {
+          if (!aligned) return tfp_live_window(gl->lv[s], P, scopes, k, window, o, c, nullptr, nullptr);
+          const int rs = tfp_live_window_aligned(gl->lv[s], P, scopes, k, window, o, sal[s].data(), c, nullptr, nullptr);
+          for (int32_t ch = 0; !rs && ch < nch; ch++)
+            for (int32_t r = 0; r < c[ch]; r++) sid[s][(size_t)ch * k + r] = o[(size_t)ch * k + r].clip_id;
+          return rs;
+        },
+        aligned ? &kept : nullptr);
     if (rc) return rc;
+    if (aligned) memset(align, 0, sizeof(tfp_alignment) * np);
+    for (size_t p = 0; aligned && p < np; p++) {
+      if (kept[p] < 0) continue;
+      const Member& mb = g->members[kept[p]];
+      const size_t c0 = p / k * k;
+      for (size_t r = c0; r < c0 + k; r++)
+        if (sid[mb.shard][r] == mb.id) {
+          align[p] = sal[mb.shard][r];
+          break;
+        }
+    }
   } else {  // empty rows (fp_handler.c:247-250)
-    memset(out, 0, sizeof(tfp_candidate) * (size_t)nch * k);
+    memset(out, 0, sizeof(tfp_candidate) * np);
+    if (aligned) memset(align, 0, sizeof(tfp_alignment) * np);
     memset(counts, 0, sizeof(int32_t) * nch);
   }
   for (int32_t c = 0; c < nch; c++) {
@@ -1591,6 +1622,22 @@ int tfp_group_live_window(tfp_group_live* gl, const tfp_search_params* P, const 
     if (first_frames) first_frames[c] = (int32_t)first;
   }
   return TFP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tfp_group_live_window(tfp_group_live* gl, const tfp_search_params* P, const int32_t* scopes, int32_t k, int32_t window,
+                          tfp_candidate* out, int32_t* counts, int32_t* frame_counts, int32_t* first_frames) {
+  if (!gl) return TFP_E_ARG;
+  return group_live_window_call(gl, P, scopes, k, window, out, nullptr, false, counts, frame_counts, first_frames);
+}
+
+int tfp_group_live_window_aligned(tfp_group_live* gl, const tfp_search_params* P, const int32_t* scopes, int32_t k,
+                                  int32_t window, tfp_candidate* out, tfp_alignment* align, int32_t* counts,
+                                  int32_t* frame_counts, int32_t* first_frames) {
+  if (!gl) return TFP_E_ARG;
+  return group_live_window_call(gl, P, scopes, k, window, out, align, true, counts, frame_counts, first_frames);
 }
 
 int tfp_group_live_frames(tfp_group_live* gl, int32_t ch, int64_t first, tfp_frame* out, int64_t cap, int64_t* nframes) {
@@ -1605,6 +1652,12 @@ int tfp_group_live_window_stats(tfp_group_live* gl, int32_t shard, int64_t* slid
                                 int64_t* rebuilds, int64_t* frames_added, int64_t* frames_removed, int64_t* rows_restarted) {
   if (!gl || shard < 0 || (size_t)shard >= gl->lv.size()) return TFP_E_ARG;
   return tfp_live_window_stats(gl->lv[shard], slid_calls, general_calls, rebuilds, frames_added, frames_removed, rows_restarted);
+}
+
+int tfp_group_live_window_aligned_stats(tfp_group_live* gl, int32_t shard, int64_t* inplace_calls, int64_t* general_calls,
+                                        int64_t* pairs) {
+  if (!gl || shard < 0 || (size_t)shard >= gl->lv.size()) return TFP_E_ARG;
+  return tfp_live_window_aligned_stats(gl->lv[shard], inplace_calls, general_calls, pairs);
 }
 
 }  // extern "C"

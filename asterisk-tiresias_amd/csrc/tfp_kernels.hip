@@ -1554,37 +1554,7 @@ __global__ void prep_boxes_kernel(const double* __restrict__ q, int64_t n, Searc
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nzero; i += (int64_t)gridDim.x * blockDim.x)
     zero_words[i] = 0u;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const double q1 = q[2 * i], q2 = q[2 * i + 1];
-    const double v1 = __builtin_isfinite(q1) ? q1 : 0.0;  // ast_json_real_get(NULL) = 0.0
-    // (int) truncation, :290 — out of int range gives INT_MIN as x86 cvttsd2si does
-    const int32_t ki = (v1 > -2147483649.0 && v1 < 2147483648.0) ? (int32_t)v1 : INT32_MIN;
-    const double freq = (double)ki;
-    FrameBox bx;
-    bx.k = ki;
-    bx.flags = 1;
-    bx.L2 = bx.U2 = 0;
-    if (sc.has_low && freq < sc.thr_low) bx.flags = 0;
-    if (sc.has_high && freq > sc.thr_high) bx.flags = 0;
-    const double lo = freq - sc.tole, hi = freq + sc.tole;
-    if (!__builtin_isfinite(lo) || !__builtin_isfinite(hi)) bx.flags = 0;  // "%f" -> nan/inf: SQL error
-    bx.L1 = fmt6_bound(lo);
-    bx.U1 = fmt6_bound(hi);
-    if (sc.coefs == 2 && bx.flags) {
-      const double f2 = __builtin_isfinite(q2) ? q2 : 0.0;
-      bool skip = false;
-      if (sc.has_low && f2 < sc.thr_low) skip = true;
-      else if (sc.has_high && f2 > sc.thr_high) skip = true;
-      if (!skip) {
-        const double lo2 = f2 - sc.tole, hi2 = f2 + sc.tole;
-        if (!__builtin_isfinite(lo2) || !__builtin_isfinite(hi2)) bx.flags = 0;
-        else {
-          bx.L2 = fmt6_bound(lo2);
-          bx.U2 = fmt6_bound(hi2);
-          bx.flags |= 2;
-        }
-      }
-    }
-    boxes[i] = bx;
+    boxes[i] = frame_box(q[2 * i], q[2 * i + 1], sc);
   }
 }
 

@@ -11,6 +11,9 @@
 // live_scatter_g711_kernel: live_scatter_kernel over G.711 codes, expanded by tfp_g711.hpp's map.
 // live_verdict_kernel: the two greatest candidates per channel for tfp_live_verdict, a count of 0
 // included, over the candidate table live_candidates_kernel derives from the scope table.
+// live_key_cols_kernel, live_window_boxes_kernel, live_pairs_kernel: the aligned window
+// (tfp_live_window_aligned): the selected rows' columns, the window frames' boxes from the kept frame
+// values in place, and one AlignPair per (channel, row) for launch_align, all without a host trip.
 //
 // The count row is what a push moves (2 bytes per column, read and written once per push however
 // many frames it adds, against 1 bit per column and frame of bitset), so a thread owns 8 columns:
@@ -326,6 +329,81 @@ __global__ __launch_bounds__(256) void live_gather_kernel(const double* __restri
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < n; f += (int64_t)gridDim.x * 256) dst[f] = src[f];
 }
 
+// The aligned window's three kernels (tfp_live.hpp). live_key_cols_kernel: live_select_kernel's grid and
+// column loads; a block whose channel has no row (its first key is 0: the keys descend) leaves at once.
+// The channel's at most K tie keys sit in LDS, every lane reads the same one (a broadcast).
+__global__ __launch_bounds__(256) void live_key_cols_kernel(const unsigned long long* __restrict__ keys,
+                                                            const LiveChan* __restrict__ chan, int32_t K,
+                                                            const int32_t* __restrict__ tiekey,
+                                                            const int32_t* __restrict__ table,
+                                                            const LiveColRows* __restrict__ rows, int32_t C,
+                                                            int32_t* __restrict__ cols) {
+  __shared__ uint32_t want[kRankMax];
+  __shared__ int32_t nwant;
+  const int ch = blockIdx.y;
+  const unsigned long long* kc = keys + (int64_t)ch * K;
+  if (!kc[0]) return;  // (the whole block)
+  if (threadIdx.x < (unsigned)K) want[threadIdx.x] = (uint32_t)kc[threadIdx.x];
+  if (threadIdx.x == 0) {
+    int32_t n = 1;
+    while (n < K && kc[n]) n++;
+    nwant = n;
+  }
+  __syncthreads();
+  const int c4 = 4 * (blockIdx.x * 256 + threadIdx.x);
+  if (c4 >= C) return;
+  const int32_t qs = chan[ch].scope;
+  const int4 s4 = *reinterpret_cast<const int4*>(table + c4);  // (scope_table_cols(C) entries: inside the table)
+  const int32_t cs[4] = {s4.x, s4.y, s4.z, s4.w};
+  const int32_t n = nwant;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if (c4 + j >= C || !in_scope(qs, cs[j])) continue;
+    const uint32_t tk = (uint32_t)tiekey[c4 + j];
+    for (int32_t r = 0; r < n; r++)
+      if (want[r] == tk && rows[c4 + j].n > 0) cols[(int64_t)ch * K + r] = c4 + j;
+  }
+}
+
+__global__ __launch_bounds__(256) void live_window_boxes_kernel(const double* __restrict__ q, int64_t Fmax,
+                                                                const LiveWinChan* __restrict__ wchan, int64_t stride,
+                                                                SearchConsts sc, FrameBox* __restrict__ boxes) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= stride) return;
+  const int64_t ch = blockIdx.y;
+  const LiveWinChan w = wchan[ch];
+  FrameBox bx;
+  if (x < w.F) {
+    const double* f = q + 2 * (ch * Fmax + w.first + x);  // (first + x < first + F <= Fmax)
+    bx = frame_box(f[0], f[1], sc);
+  } else {  // a slot past the channel's window: no row hits it
+    bx.L1 = 1, bx.U1 = 0, bx.L2 = 1, bx.U2 = 0;
+    bx.k = 0, bx.flags = 0;
+  }
+  boxes[ch * stride + x] = bx;
+}
+
+__global__ __launch_bounds__(256) void live_pairs_kernel(const unsigned long long* __restrict__ keys,
+                                                         const int32_t* __restrict__ cols,
+                                                         const LiveColRows* __restrict__ rows, int32_t ncols,
+                                                         const LiveWinChan* __restrict__ wchan, int32_t npairs, int32_t K,
+                                                         int64_t stride, const int32_t* __restrict__ bad,
+                                                         AlignPair* __restrict__ pairs, int32_t* __restrict__ flag) {
+  const int32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) *flag = *bad;
+  if (i >= npairs) return;
+  AlignPair p{0, 0, 0, 0};
+  if (keys[i]) {
+    const int32_t col = cols[i], ch = i / K;
+    if (col >= 0 && col < ncols) {
+      const LiveColRows r = rows[col];
+      const int32_t F = wchan[ch].F;
+      if (r.n > 0 && r.n <= INT32_MAX && F > 0) p = AlignPair{r.off, (int64_t)ch * stride, (int32_t)r.n, F};
+    }
+  }
+  pairs[i] = p;
+}
+
 inline unsigned copy_blocks(int64_t max_n) {
   const int64_t g = (max_n + 255) / 256;
   return (unsigned)(g < 1 ? 1 : (g > 64 ? 64 : g));
@@ -417,6 +495,36 @@ hipError_t launch_live_select(const double* d_q, int64_t Fmax, const LiveChan* d
                      live_count_cols(C), d_counts, d_tiekey, d_table, K, d_part, d_bad);
   const hipError_t err = hipGetLastError();
   return err != hipSuccess ? err : launch_rank_merge(d_part, nch, nb * K, K, d_keys, s);
+}
+
+hipError_t launch_live_key_cols(const unsigned long long* d_keys, const LiveChan* d_chan, int32_t nch, int32_t K,
+                                const int32_t* d_tiekey, const int32_t* d_table, const LiveColRows* d_rows, int32_t C,
+                                int32_t* d_cols, hipStream_t s) {
+  if (nch <= 0) return hipSuccess;
+  if (K < 1 || K > kRankMax || C <= 0 || nch > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_key_cols_kernel, dim3(rank_vote_blocks(C), nch), dim3(256), 0, s, d_keys, d_chan, K, d_tiekey,
+                     d_table, d_rows, C, d_cols);
+  return hipGetLastError();
+}
+
+hipError_t launch_live_window_boxes(const double* d_q, int64_t Fmax, const LiveWinChan* d_wchan, int32_t nch, int64_t stride,
+                                    SearchConsts sc, FrameBox* d_boxes, hipStream_t s) {
+  if (nch <= 0 || stride <= 0) return hipSuccess;
+  if (nch > 65535 || stride > Fmax) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(live_window_boxes_kernel, dim3((unsigned)((stride + 255) / 256), nch), dim3(256), 0, s, d_q, Fmax,
+                     d_wchan, stride, sc, d_boxes);
+  return hipGetLastError();
+}
+
+hipError_t launch_live_pairs(const unsigned long long* d_keys, const int32_t* d_cols, const LiveColRows* d_rows, int32_t ncols,
+                             const LiveWinChan* d_wchan, int32_t nch, int32_t K, int64_t stride, const int32_t* d_bad,
+                             AlignPair* d_pairs, int32_t* d_flag, hipStream_t s) {
+  if (nch <= 0) return hipSuccess;
+  if (K < 1 || K > kRankMax || nch > 65535) return hipErrorInvalidValue;
+  const int32_t npairs = nch * K;
+  hipLaunchKernelGGL(live_pairs_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, s, d_keys, d_cols, d_rows, ncols,
+                     d_wchan, npairs, K, stride, d_bad, d_pairs, d_flag);
+  return hipGetLastError();
 }
 
 hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, const int64_t* d_first, int32_t nch,

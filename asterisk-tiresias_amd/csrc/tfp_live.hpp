@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tfp_align.hpp"
 #include "tfp_g711.hpp"
 #include "tfp_kernels.hpp"
 #include "tfp_live_plan.hpp"
@@ -120,5 +121,36 @@ hipError_t launch_live_select(const double* d_q, int64_t Fmax, const LiveChan* d
 // (at most max_n frames per channel).
 hipError_t launch_live_gather(const double* d_q, int64_t Fmax, const int64_t* d_foff, const int64_t* d_first, int32_t nch,
                               int64_t max_n, double* d_out, hipStream_t s);
+
+// ---- the aligned trailing window (tfp_live_window_aligned): where each row's clip lies in the window.
+// Every operand is on the device already: the kept frame values, the selected rows' keys and the
+// clips' staged rows (LiveColRows), so the boxes and the pairs of launch_align (tfp_align.hpp) are
+// built there and one read-back brings the keys and the alignments.
+
+// Per channel and aligned window call: frames [first, first + F) of its call are its window.
+struct LiveWinChan {
+  int32_t first, F;
+};
+
+// d_cols[ch * K + r] = the index column of row r of channel ch (d_keys: launch_live_select's output),
+// found by its tie key (the key's low word) among the columns of the channel's scope that have a
+// clip with rows (d_rows[col].n > 0; tie keys are distinct among those). The caller has set d_cols to
+// -1: a zeroed key's entry, and one whose column is not found, stay -1.
+hipError_t launch_live_key_cols(const unsigned long long* d_keys, const LiveChan* d_chan, int32_t nch, int32_t K,
+                                const int32_t* d_tiekey, const int32_t* d_table, const LiveColRows* d_rows, int32_t C,
+                                int32_t* d_cols, hipStream_t s);
+// boxes[ch * stride + x] = the box (prep_boxes_kernel's, the same device routine) of call frame
+// d_wchan[ch].first + x of channel ch, read from the kept frame values in place; x in [F, stride): an
+// empty box (L > U, no flag). stride >= every channel's F.
+hipError_t launch_live_window_boxes(const double* d_q, int64_t Fmax, const LiveWinChan* d_wchan, int32_t nch, int64_t stride,
+                                    SearchConsts sc, FrameBox* d_boxes, hipStream_t s);
+// pairs[ch * K + r] = row r of channel ch against its window's boxes: the rows of column
+// d_cols[ch * K + r] in staging (d_rows), f0 = ch * stride, F = d_wchan[ch].F; an empty pair for a
+// zeroed key, a column of -1, a clip without rows or a window without frames. d_rows is read only for
+// a non-zero key with a column in [0, ncols). *d_flag = *d_bad (the select's out-of-range flag, copied
+// beside the results so that one read-back brings it).
+hipError_t launch_live_pairs(const unsigned long long* d_keys, const int32_t* d_cols, const LiveColRows* d_rows, int32_t ncols,
+                             const LiveWinChan* d_wchan, int32_t nch, int32_t K, int64_t stride, const int32_t* d_bad,
+                             AlignPair* d_pairs, int32_t* d_flag, hipStream_t s);
 
 }  // namespace tfp

@@ -879,6 +879,29 @@ class _LiveCalls:
                                              None if sc is None else sc.ctypes.data, k, int(window), out, counts, fc, ff))
         return Engine._candidates(out, counts, n, k), list(fc), list(ff)
 
+    def window_aligned(self, p: SearchParams, scopes=None, k: int = 1, window: int = 1):
+        """tfp_live_window_aligned: (rows, aligns, frame_counts, first_frames): window()'s rows, frame counts
+        and first frames, and per channel k alignment dicts (aligned_count, offset, first_frame, last_frame,
+        relative to the window; zeros past the channel's rows). Clip frame 0 of row r of channel c lies at
+        call frame first_frames[c] - aligns[c][r]["offset"]. Ingests nothing."""
+        n, k = self.nchannels, int(k)
+        sc = None if scopes is None else np.ascontiguousarray(scopes, np.int32)
+        if sc is not None and len(sc) != n:
+            raise ValueError("one entry per channel")
+        m = max(1, n * max(k, 1))
+        out, align, counts = (Candidate * m)(), (Alignment * m)(), (C.c_int32 * n)()
+        fc, ff = (C.c_int32 * n)(), (C.c_int32 * n)()
+        self._owner._chk(self._fn("_window_aligned")(self._h, C.byref(p) if p is not None else None,
+                                                     None if sc is None else sc.ctypes.data, k, int(window), out, align,
+                                                     counts, fc, ff))
+        aligns = [[Engine._alignment(align[c * k + r]) for r in range(k)] for c in range(n)]
+        return Engine._candidates(out, counts, n, k), aligns, list(fc), list(ff)
+
+    def _window_aligned_stats(self, *lead):
+        v = [C.c_int64() for _ in range(3)]
+        self._owner._chk(self._fn("_window_aligned_stats")(self._h, *lead, *[C.byref(x) for x in v]))
+        return dict(zip(("inplace_calls", "general_calls", "pairs"), (x.value for x in v)))
+
     def frames(self, channel: int, first: int = 0, cap: int = None) -> np.ndarray:
         """tfp_live_frames: the kept frames [first, F) of the channel's call so far (exact q values).
         cap: the capacity handed to the call (None: what it needs)."""
@@ -925,6 +948,10 @@ class Live(_LiveCalls):
     def window_stats(self) -> dict:
         """tfp_live_window_stats: window calls by form, table restarts, frames added and removed, rows restarted."""
         return self._window_stats()
+
+    def window_aligned_stats(self) -> dict:
+        """tfp_live_window_aligned_stats: aligned window calls by form, and the pairs given to the alignment kernels."""
+        return self._window_aligned_stats()
 
 
 class Plan:
@@ -1213,3 +1240,7 @@ class GroupLive(_LiveCalls):
     def window_stats(self) -> list:
         """tfp_group_live_window_stats: each shard's tfp_live_window_stats, in shard order."""
         return [self._window_stats(shard) for shard in range(len(self._owner.devices))]
+
+    def window_aligned_stats(self) -> list:
+        """tfp_group_live_window_aligned_stats: each shard's tfp_live_window_aligned_stats, in shard order."""
+        return [self._window_aligned_stats(shard) for shard in range(len(self._owner.devices))]

@@ -878,6 +878,54 @@ int tfp_live_frames(tfp_live* lv, int32_t channel, int64_t first, tfp_frame* out
 int tfp_live_window_stats(tfp_live* lv, int64_t* slid_calls, int64_t* general_calls, int64_t* rebuilds,
                           int64_t* frames_added, int64_t* frames_removed, int64_t* rows_restarted);
 
+/* The aligned trailing window: tfp_live_window's rows, each with where its clip lies in the window. The
+ * rows say which clip a call is playing; a record loop (application_handler.c:152-185, record_voice
+ * :248-312) also needs where in the clip the call is: a greeting of N frames that began after an
+ * unknown stretch of ringback ends at call frame clip_start_frame + N, and aligned_count against
+ * match_count tells a prompt heard once in order from the same frames scattered.
+ *
+ * out, counts, frame_counts and first_frames are byte for byte what tfp_live_window writes for the same
+ * arguments; the argument rules, the empty index, a channel with S = 0 and invalid params are
+ * tfp_live_window's too, and align == NULL is TFP_E_ARG with nothing written. For channel c and row
+ * r < counts[c], align[c * k + r] is exactly the tfp_alignment tfp_align_batch returns for one query
+ * holding the kept frame values of frames [first, F) of the call (as tfp_live_frames(c, first) reads
+ * them out, the provisional tail included), the clip out[c * k + r].clip_id and the same params: the
+ * per-frame predicate of fp_handler.c:287-351 applied to the clip's stored rows in frame order,
+ * coefs = 2 testing max2 as tfp_align_batch does, for the rows of :367-374. Entries past counts[c] are
+ * zeroed. All four fields are relative to the window: window frame x is call frame first + x and lies
+ * at clip frame x + offset, so clip frame 0 lies at call frame
+ *   clip_start_frame = first_frames[c] - offset
+ * (negative when the clip began before the call, or was joined midway). offset is the smallest
+ * diagonal attaining aligned_count, exactly as in the batch forms, and their warning holds: on a short
+ * window, or a clip with repeating rows, several diagonals may attain the count, and the smallest need
+ * not be the one the audio was cut from.
+ *
+ * This holds after every call, for any interleaving of int16 and G.711 pushes, resets, tfp_live_window
+ * and tfp_live_window_aligned calls, across index updates (clips of the index delta, removed clips, a
+ * merge between calls) and across changes of params, scope, k or window.
+ *
+ * The call ingests nothing and fingerprints nothing (tfp_fingerprint_stats and tfp_live_stats do not
+ * move). It moves the window count table exactly as tfp_live_window with the same arguments would and
+ * tfp_live_window_stats counts it as that window call, so the two may alternate on one table. Served
+ * from the table (coefs = 1), the selected rows never leave the device before they are aligned: their
+ * columns, the window frames' boxes (from the kept frame values in place) and one (rows, boxes) pair
+ * per row are built there, the alignment kernels of tfp_align_batch follow on the stream, and one
+ * read-back brings rows and alignments. coefs = 2, and a frame key outside the vote range, align after
+ * the general form's rows have come back: exact, not the fast path. (The key route is defensive only:
+ * a frame key is trunc(10 log10|c|) of a DCT coefficient of int16 samples, |key| <= 459 inside the vote
+ * range of +-512, and a live object takes nothing but samples, so no input reaches it and no test
+ * drives it.) The engine's tfp_align_stats is not moved; tfp_live_window_aligned_stats counts instead. */
+int tfp_live_window_aligned(tfp_live* lv, const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                            int32_t window, tfp_candidate* out /*[nchannels * k]*/, tfp_alignment* align /*[nchannels * k]*/,
+                            int32_t* counts, int32_t* frame_counts, int32_t* first_frames);
+/* Aligned window calls whose rows came from the window table and whose pairs were built on the device
+ * (a call over an empty index counts here with 0 pairs, as tfp_live_window_stats counts its own), calls
+ * whose rows came from the general form (coefs = 2, a frame key outside the vote range; the rows of
+ * fp_handler.c:367-374 either way), and the non-empty (channel, row) pairs given to the alignment
+ * kernels (the per-frame predicate of fp_handler.c:287-351 along each pair's diagonals). Any pointer may
+ * be NULL. */
+int tfp_live_window_aligned_stats(tfp_live* lv, int64_t* inplace_calls, int64_t* general_calls, int64_t* pairs);
+
 /* ---- device groups: the node's GPUs behind one index (new in round 3) -------------------
  * The module's enrolled DB sharded over one engine per listed device (the reference
  * has one SQLite DB, fp_handler.c:30): each clip lives on one engine (the one holding the fewest
@@ -1045,6 +1093,17 @@ int tfp_group_live_window(tfp_group_live* lv, const tfp_search_params* params, c
 int tfp_group_live_frames(tfp_group_live* lv, int32_t channel, int64_t first, tfp_frame* out, int64_t cap, int64_t* nframes);
 int tfp_group_live_window_stats(tfp_group_live* lv, int32_t shard, int64_t* slid_calls, int64_t* general_calls,
                                 int64_t* rebuilds, int64_t* frames_added, int64_t* frames_removed, int64_t* rows_restarted);
+/* tfp_live_window_aligned on a group (application_handler.c:152-185, :248-312; the per-frame predicate of
+ * fp_handler.c:287-351 for the rows of :367-374): every shard runs its own tfp_live_window_aligned over
+ * its own clips, the rows merge exactly as tfp_group_live_window's do, and each kept row carries the
+ * alignment its shard computed (every shard keeps the same frame values, so it is the single
+ * engine's). clip_id is the shard. Arguments and failures as tfp_live_window_aligned; a failing shard
+ * fails the call. tfp_group_live_window_aligned_stats is shard `shard`'s tfp_live_window_aligned_stats. */
+int tfp_group_live_window_aligned(tfp_group_live* lv, const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                                  int32_t window, tfp_candidate* out, tfp_alignment* align, int32_t* counts,
+                                  int32_t* frame_counts, int32_t* first_frames);
+int tfp_group_live_window_aligned_stats(tfp_group_live* lv, int32_t shard, int64_t* inplace_calls, int64_t* general_calls,
+                                        int64_t* pairs);
 /* G.711 codes on a group (aubio_source's table[code], fp_handler.c:604, :633; as the engine calls):
  * a fingerprint batch's clips are expanded by the shard that fingerprints them; a search batch is
  * expanded by every shard, or, where an int16 batch would be query-sharded, each shard expands and

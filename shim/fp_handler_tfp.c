@@ -1737,11 +1737,12 @@ struct ast_json* fp_live_verdict(fp_live* lv, const char* const* contexts, const
 /* The calls' trailing windows (tfp_group_live_window): per channel the first k rows of the search of
  * the last window_ms of its call in its context, each with its catalog fields as fp_live_verdict
  * fills the leader's (fp_handler.c:394-401), beside the window's first frame and frame count. */
-struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
-		const int freq_ignore_low, const int freq_ignore_high, const int k)
+static struct ast_json* live_window_json(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k, const bool aligned)
 {
 	tfp_search_params p;
 	tfp_candidate* cand;
+	tfp_alignment* align;
 	int32_t* scopes;
 	int32_t* counts;
 	int32_t* fc;
@@ -1766,15 +1767,22 @@ struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const 
 	}
 	kk = k > TFP_RANK_MAX ? TFP_RANK_MAX : k;
 	cand = ast_calloc((size_t)lv->nch * kk, sizeof(*cand));
+	align = ast_calloc((size_t)lv->nch * kk, sizeof(*align));
 	scopes = ast_calloc(lv->nch, sizeof(*scopes));
 	counts = ast_calloc(lv->nch, sizeof(*counts));
 	fc = ast_calloc(lv->nch, sizeof(*fc));
 	ff = ast_calloc(lv->nch, sizeof(*ff));
-	if(cand != NULL && scopes != NULL && counts != NULL && fc != NULL && ff != NULL) {
+	if(cand != NULL && align != NULL && scopes != NULL && counts != NULL && fc != NULL && ff != NULL) {
 		for(c = 0; c < lv->nch; c++) {
 			scopes[c] = scope_of_context(contexts[c], false); /* as fp_search_fingerprint_in_context maps it */
 		}
-		rc = tfp_group_live_window(lv->lv, &p, scopes, kk, tfp_live_window_frames(window_ms, lv->sr), cand, counts, fc, ff);
+		if(aligned) {
+			rc = tfp_group_live_window_aligned(lv->lv, &p, scopes, kk, tfp_live_window_frames(window_ms, lv->sr), cand, align,
+					counts, fc, ff);
+		}
+		else {
+			rc = tfp_group_live_window(lv->lv, &p, scopes, kk, tfp_live_window_frames(window_ms, lv->sr), cand, counts, fc, ff);
+		}
 		if(rc != TFP_OK) {
 			ast_log(LOG_ERROR, "Could not search the calls' windows: %s\n", tfp_group_last_error(g_tfp));
 		}
@@ -1793,6 +1801,14 @@ struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const 
 				r.frame_count = fc[c];
 				snprintf(r.uuid, sizeof(r.uuid), "%s", cand[(size_t)c * kk + i].uuid);
 				j_tmp = search_result(&r); /* a row whose audio_list entry is missing is skipped */
+				if(j_tmp != NULL && aligned) {
+					const tfp_alignment* a = &align[(size_t)c * kk + i];
+					ast_json_object_set(j_tmp, "aligned_count", ast_json_integer_create(a->aligned_count));
+					ast_json_object_set(j_tmp, "offset", ast_json_integer_create(a->offset));
+					ast_json_object_set(j_tmp, "first_frame", ast_json_integer_create(a->first_frame));
+					ast_json_object_set(j_tmp, "last_frame", ast_json_integer_create(a->last_frame));
+					ast_json_object_set(j_tmp, "clip_start_frame", ast_json_integer_create(ff[c] - a->offset));
+				}
 				if(j_tmp != NULL) {
 					ast_json_array_append(j_rows, j_tmp);
 				}
@@ -1804,11 +1820,26 @@ struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const 
 		}
 	}
 	ast_free(cand);
+	ast_free(align);
 	ast_free(scopes);
 	ast_free(counts);
 	ast_free(fc);
 	ast_free(ff);
 	return j_res;
+}
+
+struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k)
+{
+	return live_window_json(lv, contexts, window_ms, tolerance, freq_ignore_low, freq_ignore_high, k, false);
+}
+
+/* fp_live_window with where each row's clip lies in the window (tfp_group_live_window_aligned): the
+ * per-frame predicate of fp_handler.c:287-351 along the clip's stored rows, for the rows of :367-374. */
+struct ast_json* fp_live_window_aligned(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k)
+{
+	return live_window_json(lv, contexts, window_ms, tolerance, freq_ignore_low, freq_ignore_high, k, true);
 }
 
 void fp_live_reset(fp_live* lv, int channel)

@@ -174,6 +174,13 @@ void fp_channel_close(fp_channel* ch);
  * k results of fp_search_fingerprint_in_context on exactly those frames, each with the fields of
  * fp_search_fingerprint_info (uuid, name, context, hash, match_count, frame_count). It ingests
  * nothing: push, then ask. coefs is 1. NULL: bad arguments (window_ms <= 0 or k < 1 among them).
+ * fp_live_window_aligned: fp_live_window's JSON, each row additionally with where its clip lies in the
+ * window (the per-frame predicate of src/fp_handler.c:287-351 along the clip's stored rows):
+ * "aligned_count", "offset", "first_frame" and "last_frame" (window frames: window frame x is call
+ * frame first_frame(channel) + x and lies at clip frame x + offset) and "clip_start_frame" = the
+ * channel's first_frame - offset, the call frame at which clip frame 0 lies: a greeting of N frames
+ * ends at call frame clip_start_frame + N. The field names are the sliding aligned timeline's. NULL on
+ * bad arguments, as fp_live_window.
  * fp_live_reset: a new call on `channel` (< 0: on every channel). */
 typedef struct fp_live fp_live;
 fp_live* fp_live_open(int nchannels, int sample_rate, int max_ms);
@@ -182,6 +189,8 @@ bool fp_live_push_g711(fp_live* lv, const uint8_t* payload, int tick_samples, in
 struct ast_json* fp_live_verdict(fp_live* lv, const char* const* contexts, const int* duration_ms, const double tolerance,
 		const int freq_ignore_low, const int freq_ignore_high);
 struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k);
+struct ast_json* fp_live_window_aligned(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
 		const int freq_ignore_low, const int freq_ignore_high, const int k);
 void fp_live_reset(fp_live* lv, int channel);
 void fp_live_close(fp_live* lv);
