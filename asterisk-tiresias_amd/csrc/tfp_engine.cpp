@@ -30,6 +30,7 @@
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
 #include "tfp_live.hpp"
+#include "tfp_live_occur.hpp"
 #include "tfp_math.hpp"
 #include "tfp_query_plan.hpp"
 #include "tfp_rank.hpp"
@@ -4148,6 +4149,26 @@ struct tfp_live {
   uint64_t wa_nmax_version = 0;
   int64_t wa_nmax = 0;
   int64_t n_wa_inplace = 0, n_wa_general = 0, n_wa_pairs = 0;
+  // the carried traces (tfp_live_occurrences): per channel its list of tracks, track i's summary in
+  // slot c * kLiveTracksMax + i of tr_segs (allocated by the first occurrence call); a stamp of its
+  // own, counts' fields plus coefs and max_gap
+  struct Track {
+    int32_t clip = -1;
+    std::string uuid;       // the clip's, checked with the id (tfp_index_clear starts the ids again)
+    int32_t s = 0, windows = 0;
+    int64_t done = 0;       // the stored summary covers the final frames [lo, done) of the span
+    bool stored = false;    // the slot holds that summary (else the next step restarts it)
+    bool last_tail = false; // `last` has a tail frame's hit joined in
+    TraceOut last{0, 0, 0, 0, 0, 0};
+  };
+  std::vector<std::vector<Track>> tracks;
+  DevBuf tr_segs, tr_desc, tr_out;
+  HostBuf tr_pin;
+  bool tr_stamp_valid = false;
+  uint64_t tr_stamp_version = 0;
+  SearchConsts tr_stamp_sc{};
+  int32_t tr_stamp_gap = 0;
+  int64_t n_occ_calls = 0, n_tr_added = 0, n_tr_dropped = 0, n_tr_frames = 0, n_tr_retraces = 0;
   ~tfp_live() {
     if (stage_ev) (void)hipEventDestroy(stage_ev);
   }
@@ -4175,6 +4196,7 @@ int tfp_live_create(tfp_engine* e, int32_t nch, int32_t sr, int64_t max_samples,
   lv->added.assign(nch, 0);
   lv->wbeg.assign(nch, 0);
   lv->wend.assign(nch, 0);
+  lv->tracks.assign(nch, {});
   // (neither needs clearing: a push reads only samples and frame values that a push has written)
   if (lv->hist.reserve(sizeof(int16_t) * (size_t)nch * max_samples) != hipSuccess ||
       lv->q.reserve(sizeof(double) * 2 * (size_t)nch * lv->Fmax) != hipSuccess ||
@@ -4212,6 +4234,7 @@ int tfp_live_reset(tfp_live* lv, int32_t ch) {
     lv->samples[c] = lv->added[c] = 0;
     lv->n_wremoved += lv->wend[c] - lv->wbeg[c];
     lv->wbeg[c] = lv->wend[c] = 0;
+    lv->tracks[c].clear();  // a new call starts with an empty log
   }
   return TFP_OK;
 }
@@ -4992,6 +5015,249 @@ int tfp_live_window_stats(tfp_live* lv, int64_t* slid_calls, int64_t* general_ca
   if (frames_removed) *frames_removed = lv->n_wremoved;
   if (rows_restarted) *rows_restarted = lv->n_wrestarted;
   return TFP_OK;
+}
+
+// ---- the carried traces of live calls (tfp_live_occurrences; tfp_live.hpp, tfp_live_trace.hip): the
+// call in four steps, rows, offer, advance and select, each a function of its own: a device group runs
+// the rows and the offer once on its merged rows, every shard advances its own clips' tracks, and the
+// select runs on the union (tfp_group.cpp).
+namespace {
+
+static_assert(TFP_LIVE_TRACKS_MAX == kLiveTracksMax, "tfp_live.hpp and the public header agree");
+
+struct LiveOccCand {
+  int32_t ch, clip, s;
+};
+
+// Step 1: tfp_live_window_aligned's rows as candidates, channel ascending, row ascending: a row with
+// aligned_count >= 1 names (clip, s = first - offset). Moves the window table and both window stats as
+// that call does. Invalid params: no rows.
+int live_occ_rows(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int32_t window,
+                  std::vector<LiveOccCand>& cands) {
+  tfp_engine* e = lv->eng;
+  cands.clear();
+  if (!valid_params(P)) return TFP_OK;
+  std::vector<unsigned long long> keys;
+  LiveAlignReq al;
+  const int rc = live_window_step(lv, P, scopes, K, window, keys, &al);
+  if (rc) return rc;
+  for (int32_t c = 0; c < lv->nch; c++) {
+    const int64_t F = live_frames(lv->samples[c]), first = F > window ? F - window : 0;
+    for (int32_t r = 0; r < K && keys[(size_t)c * K + r]; r++) {  // fill_candidates' walk
+      const int32_t clip = clip_of_col(e, col_of_key(e, (int32_t)(uint32_t)(keys[(size_t)c * K + r] & 0xffffffffu)));
+      if (clip < 0) continue;
+      const AlignOut& a = al.out[(size_t)c * K + r];
+      if (a.aligned_count >= 1) cands.push_back(LiveOccCand{c, clip, (int32_t)(first - a.offset)});
+    }
+  }
+  return TFP_OK;
+}
+
+bool live_track_clip_ok(const tfp_engine* e, const tfp_live::Track& t) {
+  return t.clip >= 0 && (size_t)t.clip < e->clips.size() && e->clips[t.clip].alive && e->clips[t.clip].uuid == t.uuid;
+}
+
+// A new track at the end of channel ch's list (the caller has checked the room and that it is new).
+void live_occ_append(tfp_live* lv, int32_t ch, int32_t clip, int32_t s) {
+  tfp_live::Track t;
+  t.clip = clip;
+  t.uuid = lv->eng->clips[clip].uuid;
+  t.s = s;
+  t.windows = 1;
+  lv->tracks[ch].push_back(std::move(t));
+  lv->n_tr_added++;
+}
+
+// Step 2: the offer rule over the candidates in order. dropped[c] (may be NULL) counts this call's.
+void live_occ_offer(tfp_live* lv, const std::vector<LiveOccCand>& cands, int32_t max_tracks, int32_t* dropped) {
+  for (const LiveOccCand& c : cands) {
+    std::vector<tfp_live::Track>& list = lv->tracks[c.ch];
+    auto it = std::find_if(list.begin(), list.end(), [&](const tfp_live::Track& t) { return t.clip == c.clip && t.s == c.s; });
+    if (it != list.end()) {
+      it->windows++;
+    } else if ((int64_t)list.size() < max_tracks) {
+      live_occ_append(lv, c.ch, c.clip, c.s);
+    } else {
+      lv->n_tr_dropped++;
+      if (dropped) dropped[c.ch]++;
+    }
+  }
+}
+
+bool live_tr_stamp_holds(const tfp_live* lv, const SearchConsts& sc, int32_t max_gap) {
+  const SearchConsts& t = lv->tr_stamp_sc;
+  return lv->tr_stamp_valid && lv->tr_stamp_version == lv->eng->index_version && lv->tr_stamp_gap == max_gap &&
+         t.coefs == sc.coefs && t.tole == sc.tole && t.has_low == sc.has_low && t.has_high == sc.has_high &&
+         (!sc.has_low || t.thr_low == sc.thr_low) && (!sc.has_high || t.thr_high == sc.thr_high);
+}
+
+// Step 3: every track brought up to its channel's frames. Tracks of removed clips are deleted; a
+// changed stamp restarts every summary from its lo. One upload (descriptors), one launch, one
+// read-back; a track with nothing to fold and no tail in its span is answered from its last result.
+// Caller holds e->mu and has run rebuild (step 1 does).
+int live_occ_advance(tfp_live* lv, const tfp_search_params* P, int32_t max_gap) {
+  tfp_engine* e = lv->eng;
+  hipStream_t s = e->stream;
+  const int32_t nch = lv->nch;
+  const SearchConsts sc = search_consts(P);
+  if (!live_tr_stamp_holds(lv, sc, max_gap)) {
+    bool any = false;  // a call retraces when a summary it kept is started again
+    for (int32_t c = 0; c < nch; c++)
+      for (tfp_live::Track& t : lv->tracks[c]) any |= t.stored, t.stored = false;
+    if (any) lv->n_tr_retraces++;
+    lv->tr_stamp_valid = true;
+    lv->tr_stamp_version = e->index_version;
+    lv->tr_stamp_sc = sc;
+    lv->tr_stamp_gap = max_gap;
+  }
+  for (int32_t c = 0; c < nch; c++) {  // (a clip's removal changes the index version: the stamp has restarted all)
+    std::vector<tfp_live::Track>& list = lv->tracks[c];
+    const size_t n0 = list.size();
+    list.erase(std::remove_if(list.begin(), list.end(), [&](const tfp_live::Track& t) { return !live_track_clip_ok(e, t); }),
+               list.end());
+    if (list.size() != n0)  // the slots follow the list's positions: the channel's summaries start again
+      for (tfp_live::Track& t : list) t.stored = false;
+  }
+  std::vector<LiveTrace> desc;
+  std::vector<tfp_live::Track*> who;
+  std::vector<int64_t> folds;
+  for (int32_t c = 0; c < nch; c++) {
+    const int64_t S = lv->samples[c], F = live_frames(S), Ff = S / 256, tail = live_tail_frame(S);
+    for (size_t i = 0; i < lv->tracks[c].size(); i++) {
+      tfp_live::Track& t = lv->tracks[c][i];
+      const Clip& clip = e->clips[t.clip];
+      int64_t lo, hi;
+      trace_span(F, clip.nrows, t.s, &lo, &hi);
+      const int32_t overlap = (int32_t)(hi > lo ? hi - lo : 0);
+      const int64_t end = std::min<int64_t>(Ff, (int64_t)t.s + clip.nrows);
+      if (!t.stored) t.done = lo;
+      const int64_t beg = std::max(t.done, lo), nfold = end > beg ? end - beg : 0;
+      const bool tail_in = tail >= 0 && tail >= lo && tail < (int64_t)t.s + clip.nrows;
+      if (!nfold && !tail_in && (!t.stored || !t.last_tail)) {  // nothing new on this diagonal
+        if (!t.stored) t.last = TraceOut{0, 0, 0, 0, 0, 0};
+        t.last.overlap = overlap;
+        t.last_tail = false;
+        continue;
+      }
+      desc.push_back(LiveTrace{clip.off, (int32_t)clip.nrows, t.s, c, (int32_t)(c * kLiveTracksMax + (int32_t)i), (int32_t)beg,
+                               (int32_t)(beg + nfold), tail_in ? (int32_t)tail : -1, t.stored ? 0 : 1, overlap, 0});
+      who.push_back(&t);
+      folds.push_back(nfold);
+    }
+  }
+  if (desc.empty()) return TFP_OK;
+  const size_t obytes = sizeof(TraceOut) * desc.size();
+  HIPCHK(e, lv->tr_segs.reserve(sizeof(TraceSeg) * (size_t)nch * kLiveTracksMax));
+  HIPCHK(e, lv->tr_out.reserve(obytes));
+  HIPCHK(e, lv->tr_pin.reserve(obytes));
+  int rc = upload(e, lv->tr_desc, desc.data(), sizeof(LiveTrace) * desc.size(), s);
+  if (rc) return rc;
+  lv->tr_stamp_valid = false;  // (until the results are back: a failure below leaves the slots unknown)
+  HIPCHK(e, launch_live_trace(lv->tr_desc.as<LiveTrace>(), (int32_t)desc.size(), max_gap, lv->q.as<double>(), lv->Fmax, sc,
+                              e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(), lv->tr_segs.as<TraceSeg>(),
+                              lv->tr_out.as<TraceOut>(), s));
+  HIPCHK(e, hipMemcpyAsync(lv->tr_pin.p, lv->tr_out.p, obytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (desc is released on return)
+  lv->stage_pending = false;
+  lv->tr_stamp_valid = true;
+  const TraceOut* res = lv->tr_pin.as<TraceOut>();
+  for (size_t i = 0; i < desc.size(); i++) {
+    tfp_live::Track& t = *who[i];
+    t.last = res[i];
+    t.last_tail = desc[i].tail >= 0;
+    t.stored = true;
+    t.done = desc[i].end > desc[i].beg ? desc[i].end : t.done;
+    lv->n_tr_frames += folds[i];
+  }
+  return TFP_OK;
+}
+
+}  // namespace
+
+int tfp_live_occurrences(tfp_live* lv, const tfp_search_params* P, const int32_t* scopes, int32_t K, int32_t window,
+                         int32_t max_gap, int32_t min_hits, int32_t max_tracks, tfp_occurrence* out, int64_t cap,
+                         int64_t* nocc, int32_t* dropped) {
+  if (!lv) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  const int32_t nch = lv->nch;
+  if (const char* bad = live_occ_args(P, scopes, nch, K, window, max_gap, min_hits, max_tracks, out, cap, nocc))
+    return fail(e, TFP_E_ARG, "live occurrences: %s", bad);
+  HIPCHK(e, hipSetDevice(e->device));
+  if (dropped) memset(dropped, 0, sizeof(int32_t) * nch);
+  *nocc = 0;
+  lv->n_occ_calls++;
+  if (!valid_params(P)) return TFP_OK;  // fp_handler.c:247-250: no rows, nothing offered, the lists stay
+  std::vector<LiveOccCand> cands;
+  int rc = live_occ_rows(lv, P, scopes, K, window, cands);
+  if (rc) return rc;
+  live_occ_offer(lv, cands, max_tracks, dropped);
+  if ((rc = live_occ_advance(lv, P, max_gap))) return rc;
+  std::vector<LiveOccTrack> tr;
+  for (int32_t c = 0; c < nch; c++) {
+    const int32_t scope = scopes ? scopes[c] : TFP_SCOPE_ANY;
+    for (const tfp_live::Track& t : lv->tracks[c])  // (step 3 has deleted the tracks of removed clips)
+      if (scope == TFP_SCOPE_ANY || e->clips[t.clip].scope == scope)
+        tr.push_back(LiveOccTrack{c, t.clip, t.clip, t.s, t.windows, t.last, e->clips[t.clip].uuid.c_str()});
+  }
+  std::string err;
+  if ((rc = live_occ_select(tr, min_hits, out, cap, nocc, &err))) return fail(e, rc, "%s", err.c_str());
+  return TFP_OK;
+}
+
+int tfp_live_tracks(tfp_live* lv, int32_t ch, tfp_trace_req* reqs, tfp_trace* traces, int32_t* windows, int64_t cap,
+                    int64_t* ntracks) {
+  if (!lv || !ntracks) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (ch < 0 || ch >= lv->nch) return fail(e, TFP_E_ARG, "live tracks: channel %d outside [0, %d)", ch, lv->nch);
+  const std::vector<tfp_live::Track>& list = lv->tracks[ch];
+  *ntracks = (int64_t)list.size();
+  if (cap < *ntracks)
+    return fail(e, TFP_E_CAPACITY, "live tracks: %lld tracks, room for %lld", (long long)*ntracks, (long long)cap);
+  for (size_t i = 0; i < list.size(); i++) {
+    if (reqs) reqs[i] = tfp_trace_req{ch, list[i].clip, list[i].s, 0};
+    if (traces) memcpy(&traces[i], &list[i].last, sizeof(tfp_trace));
+    if (windows) windows[i] = list[i].windows;
+  }
+  return TFP_OK;
+}
+
+int tfp_live_occurrence_stats(tfp_live* lv, int64_t* calls, int64_t* tracks_added, int64_t* tracks_dropped,
+                              int64_t* frames_traced, int64_t* retraces) {
+  if (!lv) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  if (calls) *calls = lv->n_occ_calls;
+  if (tracks_added) *tracks_added = lv->n_tr_added;
+  if (tracks_dropped) *tracks_dropped = lv->n_tr_dropped;
+  if (frames_traced) *frames_traced = lv->n_tr_frames;
+  if (retraces) *retraces = lv->n_tr_retraces;
+  return TFP_OK;
+}
+
+// (tfp_internal.hpp) a device group's shard: the offer ran on the group's merged rows, so a track is
+// appended as told, and the advance is asked for on its own.
+int tfp_internal_live_occ_add(tfp_live* lv, int32_t ch, int32_t clip_id, int32_t s) {
+  if (!lv || ch < 0 || ch >= lv->nch) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (clip_id < 0 || (size_t)clip_id >= e->clips.size() || !e->clips[clip_id].alive)
+    return fail(e, TFP_E_NOENT, "live occurrences: clip id %d is not in the index", clip_id);
+  if ((int64_t)lv->tracks[ch].size() >= kLiveTracksMax)
+    return fail(e, TFP_E_CAPACITY, "live occurrences: channel %d holds %d tracks", ch, kLiveTracksMax);
+  live_occ_append(lv, ch, clip_id, s);
+  return TFP_OK;
+}
+
+int tfp_internal_live_occ_advance(tfp_live* lv, const tfp_search_params* P, int32_t max_gap) {
+  if (!lv || !valid_params(P) || max_gap < 0) return TFP_E_ARG;
+  tfp_engine* e = lv->eng;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  int rc = rebuild(e);
+  if (rc) return rc;
+  lv->n_occ_calls++;
+  return live_occ_advance(lv, P, max_gap);
 }
 
 int tfp_synth_pcm(const tfp_synth_spec* specs, int32_t nclips, int64_t spc, int16_t* out) {

@@ -41,6 +41,7 @@
 #include "tfp_g711.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
+#include "tfp_live_occur.hpp"
 #include "tfp_live_plan.hpp"
 #include "tfp_occur.hpp"
 #include "tfp_rank_merge.hpp"
@@ -1391,6 +1392,16 @@ struct tfp_group_live {
   int32_t nch = 0;
   int64_t max_samples = 0;
   std::vector<int64_t> samples;  // per channel, as every shard counts them (the capacity check before any shard is told)
+  // tfp_group_live_occurrences: per channel the merged list, each track also on its clip's shard (whose
+  // engine carries its trace); `windows` is counted here, over the merged rows
+  struct Track {
+    int32_t member;
+    std::string uuid;  // the member's, checked with the index (tfp_group_index_clear starts them again)
+    int32_t s, windows;
+    tfp_trace last;    // its trace as of the last occurrence call
+  };
+  std::vector<std::vector<Track>> tracks;
+  int64_t n_occ_calls = 0, n_tr_added = 0, n_tr_dropped = 0;
 };
 
 int tfp_group_live_create(tfp_group* g, int32_t nch, int32_t sr, int64_t max_samples, tfp_group_live** out) {
@@ -1409,6 +1420,7 @@ int tfp_group_live_create(tfp_group* g, int32_t nch, int32_t sr, int64_t max_sam
     return rc;
   }
   gl->samples.assign(nch, 0);
+  gl->tracks.assign(nch, {});
   *out = gl;
   return TFP_OK;
 }
@@ -1424,7 +1436,7 @@ int tfp_group_live_reset(tfp_group_live* gl, int32_t ch) {
   std::lock_guard<std::recursive_mutex> lk(gl->g->mu);
   const int rc = run_all(gl->g, [&](int s) { return tfp_live_reset(gl->lv[s], ch); });
   if (rc) return rc;
-  for (int32_t c = ch < 0 ? 0 : ch; c < (ch < 0 ? gl->nch : ch + 1); c++) gl->samples[c] = 0;
+  for (int32_t c = ch < 0 ? 0 : ch; c < (ch < 0 ? gl->nch : ch + 1); c++) gl->samples[c] = 0, gl->tracks[c].clear();
   return TFP_OK;
 }
 
@@ -1658,6 +1670,130 @@ int tfp_group_live_window_aligned_stats(tfp_group_live* gl, int32_t shard, int64
                                         int64_t* pairs) {
   if (!gl || shard < 0 || (size_t)shard >= gl->lv.size()) return TFP_E_ARG;
   return tfp_live_window_aligned_stats(gl->lv[shard], inplace_calls, general_calls, pairs);
+}
+
+}  // extern "C"
+
+// ---- tfp_live_occurrences on a group: the rows are tfp_group_live_window_aligned's merged rows, the offer
+// rule runs once on them (max_tracks bounds a channel's list over all shards together), every shard
+// advances its own clips' tracks on its own engine, and the selection runs on the union.
+extern "C" {
+
+int tfp_group_live_occurrences(tfp_group_live* gl, const tfp_search_params* P, const int32_t* scopes, int32_t k,
+                               int32_t window, int32_t max_gap, int32_t min_hits, int32_t max_tracks, tfp_occurrence* out,
+                               int64_t cap, int64_t* nocc, int32_t* dropped) {
+  if (!gl) return TFP_E_ARG;
+  tfp_group* g = gl->g;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  const int32_t nch = gl->nch;
+  if (const char* bad = tfp::live_occ_args(P, scopes, nch, k, window, max_gap, min_hits, max_tracks, out, cap, nocc))
+    return gfail(g, TFP_E_ARG, "live occurrences: %s", bad);
+  if (dropped) memset(dropped, 0, sizeof(int32_t) * nch);
+  *nocc = 0;
+  gl->n_occ_calls++;
+  if (!valid_params(P)) return TFP_OK;  // no rows, nothing offered, the lists stay
+  // step 1: the merged rows with their alignments
+  const size_t np = (size_t)nch * k;
+  std::vector<tfp_candidate> rows(np);
+  std::vector<tfp_alignment> al(np);
+  std::vector<int32_t> counts(nch, 0), first(nch, 0);
+  int rc = group_live_window_call(gl, P, scopes, k, window, rows.data(), al.data(), true, counts.data(), nullptr, first.data());
+  if (rc) return rc;
+  // step 2: the offer, a new track also onto its clip's shard
+  for (int32_t c = 0; c < nch; c++)
+    for (int32_t r = 0; r < counts[c]; r++) {
+      const size_t p = (size_t)c * k + r;
+      if (al[p].aligned_count < 1) continue;
+      const auto it = g->where.find(rows[p].uuid);
+      if (it == g->where.end()) continue;
+      const int32_t mi = it->second, s = first[c] - al[p].offset;
+      std::vector<tfp_group_live::Track>& list = gl->tracks[c];
+      auto at = std::find_if(list.begin(), list.end(),
+                             [&](const tfp_group_live::Track& t) { return t.member == mi && t.s == s && t.uuid == rows[p].uuid; });
+      if (at != list.end()) {
+        at->windows++;
+      } else if ((int64_t)list.size() < max_tracks) {
+        const Member& mb = g->members[mi];
+        if ((rc = tfp_internal_live_occ_add(gl->lv[mb.shard], c, mb.id, s))) return shard_fail(g, rc, mb.shard);
+        list.push_back(tfp_group_live::Track{mi, mb.uuid, s, 1, tfp_trace{0, 0, 0, 0, 0, 0}});
+        gl->n_tr_added++;
+      } else {
+        gl->n_tr_dropped++;
+        if (dropped) dropped[c]++;
+      }
+    }
+  // step 3: the tracks of removed clips leave (the shards drop their own), every shard advances its tracks
+  for (int32_t c = 0; c < nch; c++) {
+    std::vector<tfp_group_live::Track>& list = gl->tracks[c];
+    list.erase(std::remove_if(list.begin(), list.end(),
+                              [&](const tfp_group_live::Track& t) {
+                                return t.member < 0 || (size_t)t.member >= g->members.size() || g->members[t.member].uuid != t.uuid ||
+                                       t.uuid.empty();
+                              }),
+               list.end());
+  }
+  if ((rc = run_all(g, [&](int s) { return tfp_internal_live_occ_advance(gl->lv[s], P, max_gap); }))) return rc;
+  const int n = (int)g->eng.size();
+  std::vector<tfp_trace_req> sreq(TFP_LIVE_TRACKS_MAX);
+  std::vector<tfp_trace> strace(TFP_LIVE_TRACKS_MAX);
+  std::vector<tfp::LiveOccTrack> tr;
+  for (int32_t c = 0; c < nch; c++) {
+    std::vector<tfp_group_live::Track>& list = gl->tracks[c];
+    std::vector<bool> found(list.size(), false);
+    for (int s = 0; s < n; s++) {
+      int64_t nt = 0;
+      if ((rc = tfp_live_tracks(gl->lv[s], c, sreq.data(), strace.data(), nullptr, TFP_LIVE_TRACKS_MAX, &nt)))
+        return shard_fail(g, rc, s);
+      for (int64_t i = 0; i < nt; i++)
+        for (size_t j = 0; j < list.size(); j++) {
+          const Member& mb = g->members[list[j].member];
+          if (mb.shard == s && mb.id == sreq[i].clip_id && list[j].s == sreq[i].start) list[j].last = strace[i], found[j] = true;
+        }
+    }
+    const int32_t scope = scopes ? scopes[c] : TFP_SCOPE_ANY;
+    for (size_t j = 0; j < list.size(); j++) {
+      const Member& mb = g->members[list[j].member];
+      if (!found[j]) return gfail(g, TFP_E_HIP, "live occurrences: shard %d has no track of %s", mb.shard, mb.uuid.c_str());
+      int32_t cs = 0;
+      if (scope != TFP_SCOPE_ANY && (rc = tfp_index_scope(g->eng[mb.shard], mb.uuid.c_str(), &cs))) return shard_fail(g, rc, mb.shard);
+      if (scope != TFP_SCOPE_ANY && cs != scope) continue;
+      tfp::TraceOut t;
+      memcpy(&t, &list[j].last, sizeof t);
+      tr.push_back(tfp::LiveOccTrack{c, list[j].member, mb.shard, list[j].s, list[j].windows, t, mb.uuid.c_str()});
+    }
+  }
+  // step 4: on the union
+  std::string err;
+  if ((rc = tfp::live_occ_select(tr, min_hits, out, cap, nocc, &err))) return gfail(g, rc, "%s", err.c_str());
+  return TFP_OK;
+}
+
+int tfp_group_live_tracks(tfp_group_live* gl, int32_t ch, tfp_trace_req* reqs, tfp_trace* traces, int32_t* windows,
+                          int64_t cap, int64_t* ntracks) {
+  if (!gl || !ntracks) return TFP_E_ARG;
+  tfp_group* g = gl->g;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  if (ch < 0 || ch >= gl->nch) return gfail(g, TFP_E_ARG, "live tracks: channel %d outside [0, %d)", ch, gl->nch);
+  const std::vector<tfp_group_live::Track>& list = gl->tracks[ch];
+  *ntracks = (int64_t)list.size();
+  if (cap < *ntracks) return gfail(g, TFP_E_CAPACITY, "live tracks: %lld tracks, room for %lld", (long long)*ntracks, (long long)cap);
+  for (size_t i = 0; i < list.size(); i++) {
+    const bool ok = list[i].member >= 0 && (size_t)list[i].member < g->members.size() && g->members[list[i].member].uuid == list[i].uuid;
+    if (reqs) reqs[i] = tfp_trace_req{ch, ok ? g->members[list[i].member].shard : -1, list[i].s, ok ? g->members[list[i].member].id : -1};
+    if (traces) traces[i] = list[i].last;
+    if (windows) windows[i] = list[i].windows;
+  }
+  return TFP_OK;
+}
+
+int tfp_group_live_occurrence_stats(tfp_group_live* gl, int32_t shard, int64_t* calls, int64_t* tracks_added,
+                                    int64_t* tracks_dropped, int64_t* frames_traced, int64_t* retraces) {
+  if (!gl || shard < 0 || (size_t)shard >= gl->lv.size()) return TFP_E_ARG;
+  const int rc = tfp_live_occurrence_stats(gl->lv[shard], calls, tracks_added, nullptr, frames_traced, retraces);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> lk(gl->g->mu);
+  if (tracks_dropped) *tracks_dropped = gl->n_tr_dropped;  // (the offer runs on the group: dropped by it, not by a shard)
+  return TFP_OK;
 }
 
 }  // extern "C"

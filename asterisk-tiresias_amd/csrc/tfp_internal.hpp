@@ -104,4 +104,11 @@ __attribute__((visibility("hidden"))) int tfp_internal_g711_expand_device(tfp_en
 __attribute__((visibility("hidden"))) int tfp_internal_live_verdict_keys(tfp_live* lv, const int64_t* total_samples,
                                                                          const tfp_search_params* P, const int32_t* scopes,
                                                                          unsigned long long* keys, int32_t* bad);
+// tfp_live_occurrences' steps for a device group's shard. The group offers once on its merged rows:
+// _add appends the track (ch, clip_id, s) to this engine's list unconditionally (the group has applied
+// max_tracks over all shards), and _advance is step 3 alone over this engine's tracks, read out
+// afterwards with tfp_live_tracks.
+__attribute__((visibility("hidden"))) int tfp_internal_live_occ_add(tfp_live* lv, int32_t ch, int32_t clip_id, int32_t s);
+__attribute__((visibility("hidden"))) int tfp_internal_live_occ_advance(tfp_live* lv, const tfp_search_params* P,
+                                                                        int32_t max_gap);
 }

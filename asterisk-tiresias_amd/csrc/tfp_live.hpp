@@ -31,6 +31,7 @@
 #include "tfp_kernels.hpp"
 #include "tfp_live_plan.hpp"
 #include "tfp_live_window.hpp"
+#include "tfp_occur.hpp"
 #include "tfp_rank.hpp"
 #include "tfp_scope.hpp"
 
@@ -152,5 +153,39 @@ hipError_t launch_live_window_boxes(const double* d_q, int64_t Fmax, const LiveW
 hipError_t launch_live_pairs(const unsigned long long* d_keys, const int32_t* d_cols, const LiveColRows* d_rows, int32_t ncols,
                              const LiveWinChan* d_wchan, int32_t nch, int32_t K, int64_t stride, const int32_t* d_bad,
                              AlignPair* d_pairs, int32_t* d_flag, hipStream_t s);
+
+// ---- the carried traces (tfp_live_occurrences, tfp_live_trace.hip): a channel keeps a list of tracks
+// (clip, s), s the call frame at which clip frame 0 lies. A track's diagonal covers the call frames
+// [lo, hi) = trace_span(F, N, s) (tfp_occur.hpp); the TraceSeg of its hits over the final frames
+// [lo, min(Ff, s + N)) folded so far lives in one of nchannels x kLiveTracksMax device slots, allocated by
+// the first occurrence call, and is extended in place by the frames that became final. The lists (clip,
+// s, windows, frames folded so far) are host state, as the window table's ranges are.
+
+constexpr int32_t kLiveTracksMax = 64;  // TFP_LIVE_TRACKS_MAX: tracks a channel's list can hold
+
+// One track's step: fold the final call frames [beg, end) of channel ch (the host has clipped them to the
+// track's span and to the channel's final frames) into the summary at d_segs[slot], then answer with the
+// tail frame joined in.
+struct LiveTrace {
+  int64_t row0;     // the clip's staged rows [row0, row0 + N)
+  int32_t N;
+  int32_t s;        // the call frame at which clip frame 0 lies (any int32)
+  int32_t ch;
+  int32_t slot;     // the track's summary: d_segs[slot]
+  int32_t beg, end; // final frames to fold (end <= beg: none)
+  int32_t tail;     // the provisional tail frame when it lies in the span, else -1
+  int32_t restart;  // 1: the stored summary is trace_none() (the slot is not read)
+  int32_t overlap;  // tfp_trace.overlap, over all F frames
+  int32_t pad;
+};
+
+// Per descriptor i < ndesc: d_segs[slot] = the stored summary (trace_none() on restart) extended by the
+// hits of frames [beg, end), and d_out[i] = trace_result(overlap, that summary with the tail's hit
+// joined in). A frame's box is built from d_q[ch * Fmax + x] (frame_box, prep_boxes_kernel's routine)
+// and tested against staged row x - s with align_box; st_m2 is read only where the box carries the
+// max2 flag (sc.coefs == 2). Descriptors name distinct slots. max_gap >= 0.
+hipError_t launch_live_trace(const LiveTrace* d_desc, int32_t ndesc, int32_t max_gap, const double* d_q, int64_t Fmax,
+                             SearchConsts sc, const int32_t* st_m1, const int32_t* st_m2, TraceSeg* d_segs, TraceOut* d_out,
+                             hipStream_t s);
 
 }  // namespace tfp

@@ -6,7 +6,7 @@
 // frames [lo, hi) are cut into 64 contiguous chunks of ceil((hi - lo) / 64) frames, lane l taking
 // chunk l: it tests its frames in order (align_box, the row at x - s) and folds the hits into a
 // TraceSeg with trace_push. The 64 summaries are then joined in lane order by a shuffle tree
-// (lane l takes lane l + off's summary as its right neighbour, off = 1, 2, .. 32), trace_join
+// (trace_wave_join of tfp_trace_dev.hpp, shared with the live trace), trace_join
 // fusing the left one's trailing segment with the right one's leading segment where the gap between
 // them is at most max_gap, and lane 0 writes the result. No LDS, no atomics, no scratch: a request
 // is one wave's registers, so requests of any length mix in one launch.
@@ -14,26 +14,11 @@
 
 #include "tfp_align_dev.hpp"
 #include "tfp_trace.hpp"
+#include "tfp_trace_dev.hpp"
 
 namespace tfp {
 
 namespace {
-
-__device__ __forceinline__ TraceSeg shfl_down_seg(const TraceSeg& t, int off) {
-  TraceSeg r;
-  r.hits = __shfl_down(t.hits, off, 64);
-  r.first = __shfl_down(t.first, off, 64);
-  r.last = __shfl_down(t.last, off, 64);
-  r.segs = __shfl_down(t.segs, off, 64);
-  r.lead_hits = __shfl_down(t.lead_hits, off, 64);
-  r.lead_last = __shfl_down(t.lead_last, off, 64);
-  r.trail_hits = __shfl_down(t.trail_hits, off, 64);
-  r.trail_first = __shfl_down(t.trail_first, off, 64);
-  r.best_hits = __shfl_down(t.best_hits, off, 64);
-  r.best_first = __shfl_down(t.best_first, off, 64);
-  r.best_last = __shfl_down(t.best_last, off, 64);
-  return r;
-}
 
 template <bool M2>
 __global__ __launch_bounds__(64 * kTraceWaves) void trace_kernel(const TraceReq* __restrict__ reqs, int32_t nreq,
@@ -63,11 +48,7 @@ __global__ __launch_bounds__(64 * kTraceWaves) void trace_kernel(const TraceReq*
     }
     if (hit) trace_push(t, (int32_t)x, max_gap);
   }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const TraceSeg right = shfl_down_seg(t, off);  // lanes [lane + off, lane + 2 * off), where lane is a multiple of 2 * off
-    if (!(lane & (2 * off - 1))) t = trace_join(t, right, max_gap);
-  }
+  t = trace_wave_join(t, lane, max_gap);
   if (lane == 0) out[r] = trace_result((int32_t)n, t);
 }
 

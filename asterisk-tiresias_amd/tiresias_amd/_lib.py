@@ -163,6 +163,14 @@ _SIGS = {
     "tfp_live_window_aligned_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
     "tfp_group_live_window_aligned": (C.c_int, [P, C.POINTER(SearchParams), P, C.c_int32, C.c_int32, P, P, P, P, P]),
     "tfp_group_live_window_aligned_stats": (C.c_int, [P, C.c_int32] + [C.POINTER(C.c_int64)] * 3),
+    "tfp_live_occurrences": (C.c_int, [P, C.POINTER(SearchParams), P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       P, C.c_int64, C.POINTER(C.c_int64), P]),
+    "tfp_live_tracks": (C.c_int, [P, C.c_int32, P, P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_live_occurrence_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 5),
+    "tfp_group_live_occurrences": (C.c_int, [P, C.POINTER(SearchParams), P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, P, C.c_int64, C.POINTER(C.c_int64), P]),
+    "tfp_group_live_tracks": (C.c_int, [P, C.c_int32, P, P, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_group_live_occurrence_stats": (C.c_int, [P, C.c_int32] + [C.POINTER(C.c_int64)] * 5),
     "tfp_group_live_push_g711": (C.c_int, [P, P, C.c_int32, C.c_int32, P, C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
     "tfp_group_live_verdict": (C.c_int, [P, P, C.POINTER(SearchParams), P, P]),
     "tfp_group_live_create": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(P)]),

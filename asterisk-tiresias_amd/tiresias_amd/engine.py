@@ -897,6 +897,45 @@ class _LiveCalls:
         aligns = [[Engine._alignment(align[c * k + r]) for r in range(k)] for c in range(n)]
         return Engine._candidates(out, counts, n, k), aligns, list(fc), list(ff)
 
+    def occurrences(self, p: SearchParams, scopes=None, k: int = 1, window: int = 1, max_gap: int = 0, min_hits: int = 1,
+                    max_tracks: int = 64, cap: int = None):
+        """tfp_live_occurrences: (occurrences, dropped): per channel the occurrence dicts of its call so far
+        (audio_uuid, clip_start_frame, first_frame, last_frame, hits, diagonal_hits, overlap, windows, clip_id,
+        recording = the channel), by first_frame, and per channel the candidates this call's offer dropped.
+        Ingests nothing. cap: the capacity handed to the call (None: grown to what it needs)."""
+        n = self.nchannels
+        sc = None if scopes is None else np.ascontiguousarray(scopes, np.int32)
+        if sc is not None and len(sc) != n:
+            raise ValueError("one entry per channel")
+        dropped, got = (C.c_int32 * n)(), C.c_int64()
+        room = n * 64 if cap is None else int(cap)  # (TFP_LIVE_TRACKS_MAX per channel: every track an occurrence)
+        out = (Occurrence * max(room, 1))()
+        self._owner._chk(self._fn("_occurrences")(self._h, C.byref(p) if p is not None else None,
+                                                  None if sc is None else sc.ctypes.data, int(k), int(window), int(max_gap),
+                                                  int(min_hits), int(max_tracks), out, room, C.byref(got), dropped))
+        per = [[] for _ in range(n)]
+        for o in out[:got.value]:
+            row = {"audio_uuid": o.uuid.decode()}
+            row.update({f: getattr(o, f) for f in _SlidingCalls.OCCURRENCE_KEYS})
+            per[o.recording].append(row)
+        return per, list(dropped)
+
+    def tracks(self, channel: int):
+        """tfp_live_tracks: the channel's list as of the last occurrences() call, in list order: dicts of
+        clip_id, start (s), reserved, windows and the trace's fields (overlap, hits, segments, seg_hits,
+        seg_first, seg_last)."""
+        cap, got = 64, C.c_int64()
+        reqs, tr, win = np.zeros((cap, 4), np.int32), np.zeros((cap, 6), np.int32), np.zeros(cap, np.int32)
+        self._owner._chk(self._fn("_tracks")(self._h, int(channel), reqs.ctypes.data, tr.ctypes.data, win.ctypes.data, cap,
+                                             C.byref(got)))
+        return [dict(clip_id=int(reqs[i, 1]), start=int(reqs[i, 2]), reserved=int(reqs[i, 3]), windows=int(win[i]),
+                     **dict(zip(TRACE_KEYS, map(int, tr[i])))) for i in range(got.value)]
+
+    def _occurrence_stats(self, *lead):
+        v = [C.c_int64() for _ in range(5)]
+        self._owner._chk(self._fn("_occurrence_stats")(self._h, *lead, *[C.byref(x) for x in v]))
+        return dict(zip(("calls", "tracks_added", "tracks_dropped", "frames_traced", "retraces"), (x.value for x in v)))
+
     def _window_aligned_stats(self, *lead):
         v = [C.c_int64() for _ in range(3)]
         self._owner._chk(self._fn("_window_aligned_stats")(self._h, *lead, *[C.byref(x) for x in v]))
@@ -952,6 +991,10 @@ class Live(_LiveCalls):
     def window_aligned_stats(self) -> dict:
         """tfp_live_window_aligned_stats: aligned window calls by form, and the pairs given to the alignment kernels."""
         return self._window_aligned_stats()
+
+    def occurrence_stats(self) -> dict:
+        """tfp_live_occurrence_stats: occurrence calls, tracks added and dropped, (track, frame) pairs folded, retraces."""
+        return self._occurrence_stats()
 
 
 class Plan:
@@ -1244,3 +1287,7 @@ class GroupLive(_LiveCalls):
     def window_aligned_stats(self) -> list:
         """tfp_group_live_window_aligned_stats: each shard's tfp_live_window_aligned_stats, in shard order."""
         return [self._window_aligned_stats(shard) for shard in range(len(self._owner.devices))]
+
+    def occurrence_stats(self) -> list:
+        """tfp_group_live_occurrence_stats: each shard's tfp_live_occurrence_stats, in shard order."""
+        return [self._occurrence_stats(shard) for shard in range(len(self._owner.devices))]

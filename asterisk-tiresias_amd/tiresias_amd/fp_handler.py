@@ -574,3 +574,48 @@ class FpHandler:
                 info[key] = o[key]
             out.append(info)
         return out
+
+    # ---- live calls: the facade's fp_live_open, fp_live_push and fp_live_occurrences (shim/fp_handler_tfp.h)
+    def fp_live_open(self, nchannels: int, sample_rate: int, max_ms: int):
+        """A live object of nchannels calls of at most max_ms each (engine.Live), or None for bad arguments."""
+        if nchannels <= 0 or sample_rate <= 0 or max_ms <= 0:
+            return None
+        from .engine import Live
+        return Live(self.engine, nchannels, (sample_rate * max_ms + 999) // 1000, sample_rate)
+
+    @staticmethod
+    def fp_live_push(lv, slin: np.ndarray, nsamples=None) -> bool:
+        """One tick: slin int16[nchannels, tick_samples], channel c taking its first nsamples[c] samples."""
+        if lv is None or slin is None:
+            return False
+        lv.push(slin, None, nsamples=nsamples)
+        return True
+
+    def fp_live_occurrences(self, lv, contexts, window_ms, max_gap_ms, min_hits, tolerance, freq_ignore_low,
+                            freq_ignore_high, k, sample_rate: int = 8000):
+        """The log of each call so far (Live.occurrences): one list per channel, by first_frame, each entry the
+        clip's audio_list row with clip_start_frame, first_frame, last_frame, hits, diagonal_hits, overlap and
+        windows. window_ms and max_gap_ms convert to frames as tfp_live_window_frames does (0 ms of gap: 0
+        frames); coefs is 1, the contexts map to scopes as fp_search_fingerprint_in_context maps them. None for
+        bad arguments."""
+        if lv is None or contexts is None or window_ms <= 0 or max_gap_ms < 0 or min_hits < 1 or k < 1:
+            return None
+        if len(contexts) != lv.nchannels or any(c is None for c in contexts):
+            return None
+        frames = lambda ms: max(1, -(-(ms * sample_rate) // (1000 * 256)))  # noqa: E731  ceil(ms * rate / 1000 / 256)
+        p = params(1, tolerance, freq_ignore_low, freq_ignore_high)
+        scopes = [self._scope_of(c, False) for c in contexts]
+        occ, _ = lv.occurrences(p, scopes, min(int(k), TFP_RANK_MAX), frames(window_ms),
+                                frames(max_gap_ms) if max_gap_ms > 0 else 0, min_hits, 64)
+        out = []
+        for ch in occ:
+            rows = []
+            for o in ch:
+                info = self._audio_list_info(o["audio_uuid"])
+                if info is None:
+                    continue
+                for key in ("clip_start_frame", "first_frame", "last_frame", "hits", "diagonal_hits", "overlap", "windows"):
+                    info[key] = o[key]
+                rows.append(info)
+            out.append(rows)
+        return out

@@ -926,6 +926,71 @@ int tfp_live_window_aligned(tfp_live* lv, const tfp_search_params* params, const
  * be NULL. */
 int tfp_live_window_aligned_stats(tfp_live* lv, int64_t* inplace_calls, int64_t* general_calls, int64_t* pairs);
 
+/* The log of a live call: which clips have played so far, from which call frame to which. The window
+ * calls above describe the present moment; a monitored call (application_handler.c:152-185, record_voice
+ * :248-312) needs the list tfp_search_occurrences_batch gives for a finished recording (greeting from
+ * frame 40 to 310, ringback, the voicemail prompt from frame 520 and still playing), kept up to date at
+ * O(new frames) per call instead of by reading every channel's frames back and searching the whole
+ * call again at every tick.
+ *
+ * A live object keeps, per channel, a list of tracks (clip, s, windows), s being the call frame at which
+ * clip frame 0 lies, each with a carried summary of its diagonal's hits (the per-frame predicate of
+ * fp_handler.c:287-351, as tfp_trace_batch tests it). tfp_live_reset of a channel empties its list. One
+ * call ingests nothing and fingerprints nothing (tfp_fingerprint_stats and tfp_live_stats do not move)
+ * and does four steps in this order:
+ *  1. rows: exactly what tfp_live_window_aligned(lv, params, scopes, k, window, ...) runs. The window
+ *     count table, tfp_live_window_stats and tfp_live_window_aligned_stats move as that call moves
+ *     them, so all three window calls may alternate on one table; coefs = 2 takes the general form.
+ *  2. offer: for each channel c ascending and its rows r ascending, a row with aligned_count >= 1 names
+ *     the candidate (clip, s = first_frames[c] - offset). A candidate already on the channel's list has
+ *     its `windows` raised by one; otherwise it is appended with windows = 1 while the list holds fewer
+ *     than max_tracks entries; otherwise dropped[c] goes up by one (dropped starts at 0 on every call).
+ *     max_tracks below a list's length drops nothing and only stops additions.
+ *  3. advance: every track of every channel is brought up to the call's current frames. Afterwards the
+ *     tfp_trace of track (c, clip, s) is exactly what tfp_trace_batch returns for one recording holding
+ *     tfp_live_frames(c, 0) (all F frames, the provisional tail included), the request {0, clip, s}, the
+ *     same params and max_gap. The stored summary covers the final frames [0, floor(S / 256)) only (they
+ *     never change); the tail's hit is joined into the answer and not into what is stored.
+ *  4. occurrences: per channel the tracks whose clip is still enrolled, lies in scopes[c]
+ *     (TFP_SCOPE_ANY: every clip) and has seg_hits >= min_hits are thinned per (channel, clip) by
+ *     tfp_search_occurrences_batch's step 4 (seg_hits descending, windows descending, s ascending; one
+ *     is kept unless its [seg_first, seg_last] meets the interval of one already kept) and written as
+ *     tfp_occurrence entries with recording = channel, in that call's output order (channel ascending,
+ *     first_frame ascending, hits descending, audio_uuid descending: the tie order of
+ *     fp_handler.c:367-374). cap, *noccurrences and TFP_E_CAPACITY as tfp_search_occurrences_batch.
+ *
+ * The stored summaries are valid for a stamp: the index version, the resolved tolerance, the ignore
+ * thresholds, coefs and max_gap. A call whose stamp differs from the last call's traces every track
+ * again from the first frame of its span (one `retraces` count per such call that had a summary to
+ * start again); the lists and `windows` are kept, and tracks whose clip has been removed are deleted
+ * (a track names its clip by the engine's clip id, which index updates and merges keep, with the uuid
+ * as a check). A change of scopes, k, window, min_hits or max_tracks needs no retrace.
+ *
+ * TFP_E_ARG with nothing written and no state moved: k outside [1, TFP_RANK_MAX], window < 1,
+ * max_gap < 0, min_hits < 1, max_tracks outside [1, TFP_LIVE_TRACKS_MAX], a scope below TFP_SCOPE_ANY,
+ * NULL params, out (with cap > 0) or noccurrences. scopes and dropped may be NULL. Invalid params (coefs
+ * outside [1, 2]) give no rows as the window calls do (fp_handler.c:247-250): nothing is offered, the
+ * lists stay as they are and no occurrence is written. An empty index and a channel with S = 0 offer
+ * nothing. */
+#define TFP_LIVE_TRACKS_MAX 64
+int tfp_live_occurrences(tfp_live* lv, const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                         int32_t window, int32_t max_gap, int32_t min_hits, int32_t max_tracks, tfp_occurrence* out,
+                         int64_t cap, int64_t* noccurrences, int32_t* dropped /*[nchannels], may be NULL*/);
+/* `channel`'s list as of the last tfp_live_occurrences call, in list order (fp_handler.c:287-351 along
+ * each track's diagonal): reqs[i] = {channel, clip_id, s}, traces[i] its trace, windows[i] its count;
+ * any of the three may be NULL. *ntracks is always set; cap below it is TFP_E_CAPACITY and nothing else
+ * is written. Changes nothing. */
+int tfp_live_tracks(tfp_live* lv, int32_t channel, tfp_trace_req* reqs, tfp_trace* traces, int32_t* windows,
+                    int64_t cap, int64_t* ntracks);
+/* Occurrence calls so far, tracks appended and candidates dropped by the offer, the (track, final
+ * frame) pairs folded into stored summaries (each a test of fp_handler.c:287-351; the tail and frames
+ * outside a track's span are not counted), and calls that started kept summaries again. A track
+ * appended at call frame Ff catches up over [lo, min(Ff, s + N)) once, then costs one pair per newly
+ * final frame inside its span and nothing once s + N <= Ff: the work per call does not grow with the
+ * call's age. Any pointer may be NULL. */
+int tfp_live_occurrence_stats(tfp_live* lv, int64_t* calls, int64_t* tracks_added, int64_t* tracks_dropped,
+                              int64_t* frames_traced, int64_t* retraces);
+
 /* ---- device groups: the node's GPUs behind one index (new in round 3) -------------------
  * The module's enrolled DB sharded over one engine per listed device (the reference
  * has one SQLite DB, fp_handler.c:30): each clip lives on one engine (the one holding the fewest
@@ -1104,6 +1169,26 @@ int tfp_group_live_window_aligned(tfp_group_live* lv, const tfp_search_params* p
                                   int32_t* frame_counts, int32_t* first_frames);
 int tfp_group_live_window_aligned_stats(tfp_group_live* lv, int32_t shard, int64_t* inplace_calls, int64_t* general_calls,
                                         int64_t* pairs);
+/* tfp_live_occurrences on a group (application_handler.c:152-185, :248-312; fp_handler.c:287-351 along
+ * each track's diagonal for the rows of :367-374): step 1 is tfp_group_live_window_aligned's merged rows,
+ * the offer rule runs once on them (max_tracks bounds a channel's list over all shards together), every
+ * shard carries and advances the traces of its own clips' tracks (every shard keeps the same frame
+ * values, so they are the single engine's), and step 4 runs on the union: the entries, dropped and the
+ * lists equal the single engine's. clip_id is the shard. Arguments and failures as
+ * tfp_live_occurrences; a failing shard fails the call, and may leave it partly done: the window tables
+ * moved, candidates offered and `windows` raised, but no track advanced. Nothing is lost: a track that
+ * was appended and not advanced starts from its lo at the next call, which brings every trace up to
+ * date. tfp_group_live_tracks is the merged list, with
+ * reqs[i].clip_id = the shard and reqs[i].reserved = that shard's clip id.
+ * tfp_group_live_occurrence_stats is shard `shard`'s tfp_live_occurrence_stats (its own tracks, frames and
+ * retraces), except tracks_dropped: the group's offer drops, so that count is the group's. */
+int tfp_group_live_occurrences(tfp_group_live* lv, const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                               int32_t window, int32_t max_gap, int32_t min_hits, int32_t max_tracks, tfp_occurrence* out,
+                               int64_t cap, int64_t* noccurrences, int32_t* dropped);
+int tfp_group_live_tracks(tfp_group_live* lv, int32_t channel, tfp_trace_req* reqs, tfp_trace* traces, int32_t* windows,
+                          int64_t cap, int64_t* ntracks);
+int tfp_group_live_occurrence_stats(tfp_group_live* lv, int32_t shard, int64_t* calls, int64_t* tracks_added,
+                                    int64_t* tracks_dropped, int64_t* frames_traced, int64_t* retraces);
 /* G.711 codes on a group (aubio_source's table[code], fp_handler.c:604, :633; as the engine calls):
  * a fingerprint batch's clips are expanded by the shard that fingerprints them; a search batch is
  * expanded by every shard, or, where an int16 batch would be query-sharded, each shard expands and

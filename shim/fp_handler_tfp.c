@@ -1842,6 +1842,77 @@ struct ast_json* fp_live_window_aligned(fp_live* lv, const char* const* contexts
 	return live_window_json(lv, contexts, window_ms, tolerance, freq_ignore_low, freq_ignore_high, k, true);
 }
 
+/* The calls' logs (tfp_group_live_occurrences): per channel the clips of its context that have played so
+ * far, each with its catalog fields (fp_handler.c:394-401) and where it lies in the call: the per-frame
+ * predicate of fp_handler.c:287-351 along each candidate's diagonal, for the rows of :367-374 over the last
+ * window_ms. One JSON array per channel, by first_frame. */
+struct ast_json* fp_live_occurrences(fp_live* lv, const char* const* contexts, const int window_ms, const int max_gap_ms,
+		const int min_hits, const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int k)
+{
+	tfp_search_params p;
+	tfp_occurrence* occ;
+	int32_t* scopes;
+	int64_t n = 0, i, cap;
+	int32_t c, kk;
+	int rc;
+	struct ast_json* j_res = NULL;
+
+	if(lv == NULL || contexts == NULL || window_ms <= 0 || max_gap_ms < 0 || min_hits < 1 || k < 1) {
+		ast_log(LOG_WARNING, "Wrong input parameter.\n");
+		return NULL;
+	}
+	for(c = 0; c < lv->nch; c++) {
+		if(contexts[c] == NULL) {
+			ast_log(LOG_WARNING, "Wrong input parameter.\n");
+			return NULL;
+		}
+	}
+	/* coefs = 1: what the dialplan passes (application_handler.c:180), and the form whose counts slide */
+	if(search_params(&p, contexts[0], 1, tolerance, freq_ignore_low, freq_ignore_high) == false) {
+		return NULL;
+	}
+	kk = k > TFP_RANK_MAX ? TFP_RANK_MAX : k;
+	cap = (int64_t)lv->nch * TFP_LIVE_TRACKS_MAX; /* every track an occurrence: the call never lacks room */
+	occ = ast_calloc((size_t)cap, sizeof(*occ));
+	scopes = ast_calloc(lv->nch, sizeof(*scopes));
+	if(occ != NULL && scopes != NULL) {
+		for(c = 0; c < lv->nch; c++) {
+			scopes[c] = scope_of_context(contexts[c], false); /* as fp_search_fingerprint_in_context maps it */
+		}
+		/* max_gap_ms converts as window_ms does; 0 ms is 0 frames */
+		rc = tfp_group_live_occurrences(lv->lv, &p, scopes, kk, tfp_live_window_frames(window_ms, lv->sr),
+				max_gap_ms > 0 ? tfp_live_window_frames(max_gap_ms, lv->sr) : 0, min_hits, TFP_LIVE_TRACKS_MAX, occ, cap, &n, NULL);
+		if(rc != TFP_OK) {
+			ast_log(LOG_ERROR, "Could not list the calls' occurrences: %s\n", tfp_group_last_error(g_tfp));
+		}
+		else {
+			j_res = ast_json_array_create();
+		}
+		for(c = 0; j_res != NULL && c < lv->nch; c++) {
+			ast_json_array_append(j_res, ast_json_array_create());
+		}
+		for(i = 0; j_res != NULL && i < n; i++) {
+			const tfp_occurrence* o = &occ[i];
+			struct ast_json* j_tmp = fpc_get_audio_list_info(o->uuid); /* an entry whose audio_list row is missing is skipped */
+			if(j_tmp == NULL) {
+				ast_log(LOG_ERROR, "Could not get audio list info. uuid[%s]\n", o->uuid);
+				continue;
+			}
+			ast_json_object_set(j_tmp, "clip_start_frame", ast_json_integer_create(o->clip_start_frame));
+			ast_json_object_set(j_tmp, "first_frame", ast_json_integer_create(o->first_frame));
+			ast_json_object_set(j_tmp, "last_frame", ast_json_integer_create(o->last_frame));
+			ast_json_object_set(j_tmp, "hits", ast_json_integer_create(o->hits));
+			ast_json_object_set(j_tmp, "diagonal_hits", ast_json_integer_create(o->diagonal_hits));
+			ast_json_object_set(j_tmp, "overlap", ast_json_integer_create(o->overlap));
+			ast_json_object_set(j_tmp, "windows", ast_json_integer_create(o->windows));
+			ast_json_array_append(ast_json_array_get(j_res, (size_t)o->recording), j_tmp);
+		}
+	}
+	ast_free(occ);
+	ast_free(scopes);
+	return j_res;
+}
+
 void fp_live_reset(fp_live* lv, int channel)
 {
 	if(lv != NULL && channel < lv->nch) {

@@ -181,6 +181,16 @@ void fp_channel_close(fp_channel* ch);
  * channel's first_frame - offset, the call frame at which clip frame 0 lies: a greeting of N frames
  * ends at call frame clip_start_frame + N. The field names are the sliding aligned timeline's. NULL on
  * bad arguments, as fp_live_window.
+ * fp_live_occurrences: the log of each call so far (tfp_group_live_occurrences; src/fp_handler.c:287-351
+ * along each candidate's diagonal, for the rows of :367-374): a JSON array with one array per channel, by
+ * "first_frame"; each entry has the clip's catalog fields (uuid, name, context, hash) and
+ * "clip_start_frame" (the call frame at which clip frame 0 lies), "first_frame", "last_frame", "hits"
+ * (the best run of hits along the clip's diagonal: its first and last call frame and its hits),
+ * "diagonal_hits", "overlap" and "windows". Each call offers the rows of fp_live_window_aligned for
+ * window_ms to the channel's list of candidates and brings every candidate's trace up to the call's
+ * frames, so ask after each tick or each few ticks. window_ms converts to frames as fp_live_window's;
+ * max_gap_ms (the silence a run may bridge) the same way, 0 ms being 0 frames; min_hits >= 1. NULL: bad
+ * arguments (window_ms <= 0, max_gap_ms < 0, min_hits < 1 or k < 1 among them).
  * fp_live_reset: a new call on `channel` (< 0: on every channel). */
 typedef struct fp_live fp_live;
 fp_live* fp_live_open(int nchannels, int sample_rate, int max_ms);
@@ -192,6 +202,8 @@ struct ast_json* fp_live_window(fp_live* lv, const char* const* contexts, const 
 		const int freq_ignore_low, const int freq_ignore_high, const int k);
 struct ast_json* fp_live_window_aligned(fp_live* lv, const char* const* contexts, const int window_ms, const double tolerance,
 		const int freq_ignore_low, const int freq_ignore_high, const int k);
+struct ast_json* fp_live_occurrences(fp_live* lv, const char* const* contexts, const int window_ms, const int max_gap_ms,
+		const int min_hits, const double tolerance, const int freq_ignore_low, const int freq_ignore_high, const int k);
 void fp_live_reset(fp_live* lv, int channel);
 void fp_live_close(fp_live* lv);
 
