@@ -52,25 +52,27 @@ int bank_cost(const int32_t* filt, const int32_t* start, const int* perm, int le
                                {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
                                {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+  // Read i of a slot (bins 4 i .. 4 i + 3) moves every lane's 16-B slot on by i, which only turns
+  // the banks round: the same lanes collide in every read, so the cost of one read times the
+  // slot's len / 4 reads is the cost of them all.
   int extra = 0;
-  for (int i = 0; i < len / 4; i++)
-    for (int g = 0; g < 4; g++) {
-      int slot_of_bank[16], cnt[16];
-      for (int b = 0; b < 16; b++) { slot_of_bank[b] = -1; cnt[b] = 0; }
-      int worst = 0;
-      for (int k = 0; k < 16; k++) {
-        const int l = G[g][k], fr = l >> 4, L = l & 15;
-        if (filt[perm[L]] < 0) continue;
-        const int sl = 136 * fr + 4 * (fr & 1) + start[perm[L]] / 4 + i;
-        const int b = sl & 15;
-        // distinct slots on one bank group cost a cycle each (same slot broadcasts); lanes of one
-        // frame never share a slot, lanes of two frames do only by coincidence: count distinct
-        if (slot_of_bank[b] != sl) { cnt[b]++; slot_of_bank[b] = sl; }
-        if (cnt[b] > worst) worst = cnt[b];
-      }
-      extra += worst > 0 ? worst - 1 : 0;
+  for (int g = 0; g < 4; g++) {
+    int slot_of_bank[16], cnt[16];
+    for (int b = 0; b < 16; b++) { slot_of_bank[b] = -1; cnt[b] = 0; }
+    int worst = 0;
+    for (int k = 0; k < 16; k++) {
+      const int l = G[g][k], fr = l >> 4, L = l & 15;
+      if (filt[perm[L]] < 0) continue;
+      const int sl = 136 * fr + 4 * (fr & 1) + start[perm[L]] / 4;
+      const int b = sl & 15;
+      // distinct slots on one bank group cost a cycle each (same slot broadcasts); lanes of one
+      // frame never share a slot, lanes of two frames do only by coincidence: count distinct
+      if (slot_of_bank[b] != sl) { cnt[b]++; slot_of_bank[b] = sl; }
+      if (cnt[b] > worst) worst = cnt[b];
     }
-  return extra;
+    extra += worst > 0 ? worst - 1 : 0;
+  }
+  return extra * (len / 4);
 }
 
 void lane_order_for_banks(int32_t* filt, int32_t* start, int len) {

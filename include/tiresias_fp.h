@@ -157,6 +157,15 @@ int tfp_wav_read_g711(const char* path, uint8_t* codes, int64_t cap, int64_t* ns
                       int32_t* law);
 
 /* ---- fingerprinting: create_audio_fingerprints (fp_handler.c:577-671) -------------- */
+/* sample_rate, here and in every call below that takes one (the search-from-PCM forms, plans,
+ * streams, live calls, groups): any rate >= 1 is taken, as aubio 0.4.5 takes it
+ * (aubio_filterbank_set_triangle_bands only warns when bands pass Nyquist; their filters are then
+ * empty and their log rows the constant log of the clamped 0). A rate <= 0 is refused with
+ * TFP_E_ARG and "bad sample rate <rate>" in tfp_engine_last_error; nothing else about a rate is
+ * refused (the filterbank schedule's own size limit is met by no rate). Tables are built per rate on
+ * first use and kept for the engine's lifetime. Rates whose filterbank schedule has the 8 kHz shape
+ * (7954..7959 and 7997..8020 Hz) run the 8 kHz kernels on their own tables, every other rate the
+ * generic kernel; the frames are bit-exact either way. */
 /* One clip of mono int16 PCM at its native rate (DEF_AUBIO_SAMPLERATE 0, :37). */
 int tfp_fingerprint_pcm(tfp_engine* eng, const int16_t* pcm, int64_t nsamples, int32_t sample_rate,
                         tfp_frame* out, int64_t cap, int64_t* nframes);
