@@ -37,6 +37,7 @@
 #include "tfp_census.hpp"
 #include "tfp_scope.hpp"
 #include "tfp_slide.hpp"
+#include "tfp_neighbour.hpp"
 #include "tfp_slide_align.hpp"
 #include "tfp_trace.hpp"
 #include "tfp_synth.hpp"
@@ -297,6 +298,17 @@ struct tfp_engine {
   uint64_t scope_version = 0;
   bool scope_dirty = true;
   int64_t n_scope_vote = 0, n_scope_general = 0, n_scope_builds = 0;
+  // catalog neighbours (tfp_neighbour.hpp): the launch's named clips, the columns' staged rows and the
+  // clips' columns (host) as of index version nbr_version with the longest live clip's rows, the
+  // selected rows' columns, the frame boxes / gathered frame values, the pairs, the bands' partial keys,
+  // [keys][bad flag][alignments] and their pinned copy; the calls each form served, the pairs aligned
+  // and the stored rows used as query frames
+  DevBuf nbr_clips, nbr_colrows, nbr_cols, nbr_boxes, nbr_q, nbr_pairs, nbr_part, nbr_res;
+  HostBuf nbr_pin;
+  std::vector<int32_t> nbr_col_of_clip;
+  uint64_t nbr_version = 0;
+  int64_t nbr_nmax = 0;
+  int64_t n_nbr_vote = 0, n_nbr_general = 0, n_nbr_pairs = 0, n_nbr_frames = 0;
   // match census (tfp_census.hpp): the batch's bins [nq][nbins] with the vote form's bad flag after
   // them, their pinned copy, and the batches each form served
   DevBuf census_hist;
@@ -2056,8 +2068,9 @@ int rank_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, cons
 // Shaped like search_core. The vote form reads the key bitsets, which hold a live index delta's
 // columns at the tolerances delta_tol_ok() names; every other ranked search merges the delta first.
 // scopes (or nullptr: ranked search): scopes[q] restricts query q to that scope's clips (tfp_scope.hpp).
+// count: the batch is a ranked / scoped search's own (catalog neighbours run the core for theirs and count there).
 int rank_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_q, const tfp_search_params* P, int32_t K,
-              const int32_t* scopes, std::vector<unsigned long long>& keys, hipStream_t s) {
+              const int32_t* scopes, std::vector<unsigned long long>& keys, hipStream_t s, bool count = true) {
   int rc = rebuild(e);  // synchronous on e->stream
   if (rc) return rc;
   const SearchConsts sc = search_consts(P);
@@ -2069,12 +2082,12 @@ int rank_core(tfp_engine* e, const int64_t* h_qoff, int32_t nq, const double* d_
     bool bad = false;
     if ((rc = rank_vote(e, qo, nq, d_q, sc, K, scopes, keys, &bad, s))) return rc;
     if (!bad) {
-      (scopes ? e->n_scope_vote : e->n_rank_vote)++;
+      if (count) (scopes ? e->n_scope_vote : e->n_rank_vote)++;
       return TFP_OK;
     }
   }
   if ((rc = consolidate(e)) || (rc = rank_general(e, qo, nq, d_q, sc, K, scopes, keys, s))) return rc;
-  (scopes ? e->n_scope_general : e->n_rank_general)++;
+  if (count) (scopes ? e->n_scope_general : e->n_rank_general)++;
   return TFP_OK;
 }
 
@@ -2352,8 +2365,9 @@ int slide_args(tfp_engine* e, const tfp_search_params* P, int32_t window, int32_
 // delta aligns like any other. qo: the queries' relative frame offsets into d_q.
 static_assert(sizeof(tfp_alignment) == sizeof(AlignOut), "tfp_align.hpp and the public header agree");
 
+// count: the batch moves tfp_align_stats (catalog neighbours count their own pairs).
 int align_core(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const double* d_q, const tfp_search_params* P,
-               int32_t K, const int32_t* ids, tfp_alignment* out, hipStream_t s) {
+               int32_t K, const int32_t* ids, tfp_alignment* out, hipStream_t s, bool count = true) {
   const int64_t npairs = (int64_t)nq * K;
   memset(out, 0, sizeof(tfp_alignment) * (size_t)npairs);
   std::vector<AlignPair> pairs((size_t)npairs, AlignPair{0, 0, 0, 0});
@@ -2396,8 +2410,10 @@ int align_core(tfp_engine* e, const std::vector<int64_t>& qo, int32_t nq, const 
   HIPCHK(e, hipMemcpyAsync(pin + pbytes, e->align_out.p, obytes, hipMemcpyDeviceToHost, s));
   HIPCHK(e, hipStreamSynchronize(s));
   memcpy(out, pin + pbytes, obytes);
-  e->n_align_batches++;
-  e->n_align_pairs += named;
+  if (count) {
+    e->n_align_batches++;
+    e->n_align_pairs += named;
+  }
   return TFP_OK;
 }
 
@@ -3366,6 +3382,377 @@ int tfp_scope_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batch
   if (vote_batches) *vote_batches = e->n_scope_vote;
   if (general_batches) *general_batches = e->n_scope_general;
   if (table_builds) *table_builds = e->n_scope_builds;
+  return TFP_OK;
+}
+
+// ---- catalog neighbours (tfp_neighbour.hpp): fp_handler.c:367-374 for a clip's own stored rows ----
+namespace {
+
+// The columns' staged rows on the device and the clips' columns on the host, for the current index
+// (caller has run rebuild): rebuilt when the index version changed, else they stand.
+int ensure_neighbour_cols(tfp_engine* e, hipStream_t s) {
+  if (e->nbr_version == e->index_version) return TFP_OK;
+  const int32_t Cp = scope_table_cols(e->ncols);
+  std::vector<NeighbourCol> rows((size_t)std::max(Cp, 1), NeighbourCol{0, 0});
+  e->nbr_col_of_clip.assign(e->clips.size(), -1);
+  e->nbr_nmax = 0;
+  auto put = [&](size_t col, int32_t clip) {
+    if (clip < 0 || !e->clips[clip].alive) return;
+    rows[col] = NeighbourCol{e->clips[clip].off, e->clips[clip].nrows};
+    e->nbr_col_of_clip[clip] = (int32_t)col;
+    e->nbr_nmax = std::max(e->nbr_nmax, e->clips[clip].nrows);
+  };
+  for (size_t c = 0; c < e->col_clip.size(); c++) put(c, e->col_clip[c]);
+  for (size_t j = 0; j < e->delta.clip.size(); j++) put((size_t)e->delta.col0 + j, e->delta.clip[j]);
+  HIPCHK(e, e->nbr_colrows.reserve_grow(sizeof(NeighbourCol) * rows.size()));
+  HIPCHK(e, hipMemcpyAsync(e->nbr_colrows.p, rows.data(), sizeof(NeighbourCol) * rows.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (rows is released on return)
+  e->nbr_version = e->index_version;
+  return TFP_OK;
+}
+
+// The launch descriptors of named clips ids[0, n): boxes laid end to end from 0. with_cols: the own
+// columns from ensure_neighbour_cols (the vote form), else -1. *total = the clips' rows, *longest = the
+// longest clip's.
+void neighbour_clips(const tfp_engine* e, const int32_t* ids, const int32_t* scopes, int32_t n, bool with_cols,
+                     std::vector<NeighbourClip>& nc, int64_t* total, int64_t* longest) {
+  nc.resize((size_t)n);
+  int64_t box0 = 0, mx = 0;
+  for (int32_t i = 0; i < n; i++) {
+    const Clip& c = e->clips[ids[i]];
+    nc[i] = NeighbourClip{c.off, box0, (int32_t)c.nrows, scopes ? scopes[i] : kScopeAny,
+                          with_cols ? e->nbr_col_of_clip[ids[i]] : -1, 0};
+    box0 += c.nrows;
+    mx = std::max(mx, c.nrows);
+  }
+  *total = box0;
+  *longest = mx;
+}
+
+// The vote form for named clips ids[0, n) (a batch the partial keys' scratch holds): keys[n * K] and, with
+// al, the rows' alignments, one upload, one read-back, one wait. *bad: a row's key lay outside the vote
+// range (nothing written). Caller has run the ensure_* of the vote and ensure_neighbour_cols.
+int neighbour_vote(tfp_engine* e, const int32_t* ids, const int32_t* scopes, int32_t n, const SearchConsts& sc, int32_t K,
+                   unsigned long long* keys, AlignOut* al, bool* bad, hipStream_t s) {
+  const int32_t C = e->ncols, nb = rank_vote_blocks(C);
+  const size_t nkeys = (size_t)n * K;
+  int64_t total, longest;
+  std::vector<NeighbourClip> nc;
+  neighbour_clips(e, ids, scopes, n, true, nc, &total, &longest);
+  if (longest + e->nbr_nmax > (int64_t(1) << 31))  // align_core's limit
+    return fail(e, TFP_E_CAPACITY, "neighbours: %lld rows against %lld rows", (long long)longest, (long long)e->nbr_nmax);
+  const int64_t max_bands = std::max<int64_t>(align_bands(longest, e->nbr_nmax), 1);
+  // pairs in chunks of <= 256 MB of partial keys (and of the launch grid's second dimension), as align_core
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({(int64_t(1) << 25) / max_bands, kAlignMaxPairs, (int64_t)nkeys}));
+  const size_t rbytes = (sizeof(unsigned long long) + sizeof(AlignOut)) * nkeys + 8;
+  int rc;
+  if ((rc = upload(e, e->nbr_clips, nc.data(), sizeof(NeighbourClip) * nc.size(), s))) return rc;
+  HIPCHK(e, e->rank_part.reserve(sizeof(unsigned long long) * (size_t)n * nb * K));
+  HIPCHK(e, e->nbr_res.reserve(rbytes));
+  HIPCHK(e, e->nbr_pin.reserve(rbytes));
+  unsigned long long* d_keys = e->nbr_res.as<unsigned long long>();  // [keys][bad flag][AlignOut]
+  int32_t* d_flag = reinterpret_cast<int32_t*>(d_keys + nkeys);
+  AlignOut* d_out = reinterpret_cast<AlignOut*>(d_keys + nkeys + 1);
+  HIPCHK(e, hipMemsetAsync(d_flag, 0, sizeof(unsigned long long), s));
+  const NeighbourClip* d_nc = e->nbr_clips.as<NeighbourClip>();
+  HIPCHK(e, launch_neighbour_vote(e->st_m1.as<int32_t>(), d_nc, n, sc, e->tc.ranges.active().key_bits.as<uint32_t>(), C,
+                                  e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(), K,
+                                  e->rank_part.as<unsigned long long>(), d_keys, d_flag, s));
+  size_t back = sizeof(unsigned long long) * (nkeys + 1);
+  if (al) {
+    HIPCHK(e, e->nbr_cols.reserve(sizeof(int32_t) * nkeys));
+    HIPCHK(e, e->nbr_boxes.reserve(sizeof(FrameBox) * (size_t)(total + 1)));
+    HIPCHK(e, e->nbr_pairs.reserve(sizeof(AlignPair) * nkeys));
+    HIPCHK(e, e->nbr_part.reserve(sizeof(unsigned long long) * (size_t)(chunk * max_bands)));
+    HIPCHK(e, hipMemsetAsync(e->nbr_cols.p, 0xff, sizeof(int32_t) * nkeys, s));  // -1: no column
+    HIPCHK(e, launch_neighbour_boxes(e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(), d_nc, n, longest, sc,
+                                     e->nbr_boxes.as<FrameBox>(), s));
+    HIPCHK(e, launch_neighbour_key_cols(d_keys, d_nc, n, K, e->tiekey.as<int32_t>(), e->scope_table.as<int32_t>(),
+                                        e->nbr_colrows.as<NeighbourCol>(), C, e->nbr_cols.as<int32_t>(), s));
+    HIPCHK(e, launch_neighbour_pairs(d_keys, e->nbr_cols.as<int32_t>(), e->nbr_colrows.as<NeighbourCol>(), C, d_nc, n, K,
+                                     e->nbr_pairs.as<AlignPair>(), s));
+    for (int64_t p0 = 0; p0 < (int64_t)nkeys; p0 += chunk) {
+      const int32_t m = (int32_t)std::min<int64_t>(chunk, (int64_t)nkeys - p0);
+      HIPCHK(e, launch_align(e->nbr_pairs.as<AlignPair>() + p0, m, max_bands, e->nbr_boxes.as<FrameBox>(),
+                             e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(), false, e->nbr_part.as<unsigned long long>(),
+                             d_out + p0, s));
+    }
+    back = rbytes;
+  }
+  HIPCHK(e, hipMemcpyAsync(e->nbr_pin.p, d_keys, back, hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));  // (nc is released on return)
+  const unsigned long long* hk = e->nbr_pin.as<unsigned long long>();
+  *bad = (uint32_t)hk[nkeys] != 0;
+  if (*bad) return TFP_OK;
+  std::copy(hk, hk + nkeys, keys);
+  if (al) {
+    const AlignOut* ho = reinterpret_cast<const AlignOut*>(hk + nkeys + 1);
+    for (size_t p = 0; p < nkeys; p++) {
+      al[p] = AlignOut{0, 0, 0, 0};
+      if (!keys[p]) continue;
+      // a row has a frame that hits one of its clip's rows, so its best diagonal holds a hit
+      if (ho[p].aligned_count <= 0)
+        return fail(e, TFP_E_HIP, "neighbours: no staged rows found for tie-break key %u", (unsigned)(keys[p] & 0xffffffffu));
+      al[p] = ho[p];
+    }
+  }
+  return TFP_OK;
+}
+
+// The clip behind a row's key (-1: none).
+int32_t clip_of_key(const tfp_engine* e, unsigned long long key) {
+  return clip_of_col(e, col_of_key(e, (int32_t)(uint32_t)(key & 0xffffffffu)));
+}
+
+// The general form over frame values on the device (query i at qo[i] .. qo[i + 1] of d_q): the scoped
+// search's core at k + 1 rows (the one caller of the ranked launchers' internal bound), self_ids[i] (-1:
+// none on this engine) deleted on the host, k rows kept; with al their alignments as aligned search's.
+// The cores run uncounted: these are not the scoped and aligned searches' batches.
+int neighbour_general(tfp_engine* e, const std::vector<int64_t>& qo, int32_t n, const double* d_q, const tfp_search_params* P,
+                      const int32_t* scopes, const int32_t* self_ids, int32_t K, unsigned long long* keys, AlignOut* al,
+                      hipStream_t s) {
+  std::vector<unsigned long long> wide;
+  int rc = rank_core(e, qo.data(), n, d_q, P, K + 1, scopes, wide, s, false);
+  if (rc) return rc;
+  std::vector<int32_t> ids((size_t)n * K, -1), row((size_t)K + 1), keep((size_t)K);
+  for (int32_t i = 0; i < n; i++) {
+    int32_t nr = 0;
+    while (nr <= K && wide[(size_t)i * (K + 1) + nr]) {
+      row[nr] = clip_of_key(e, wide[(size_t)i * (K + 1) + nr]);
+      nr++;
+    }
+    const int32_t m = neighbour_drop_self(row.data(), nr, self_ids ? self_ids[i] : -1, K, keep.data());
+    for (int32_t r = 0; r < K; r++) {
+      keys[(size_t)i * K + r] = r < m ? wide[(size_t)i * (K + 1) + keep[r]] : 0ull;
+      if (r < m) ids[(size_t)i * K + r] = row[keep[r]];
+    }
+  }
+  if (!al) return TFP_OK;
+  static_assert(sizeof(tfp_alignment) == sizeof(AlignOut), "one layout");
+  return align_core(e, qo, n, d_q, P, K, ids.data(), reinterpret_cast<tfp_alignment*>(al), s, false);
+}
+
+// Keys to rows for named clips, as fill_candidates; the alignments of the rows kept move with them.
+void fill_neighbours(tfp_engine* e, const std::vector<unsigned long long>& keys, const std::vector<AlignOut>& al, int32_t n,
+                     int32_t K, tfp_candidate* out, tfp_alignment* align, int32_t* counts) {
+  std::vector<int32_t> cnt((size_t)std::max(n, 1));
+  fill_candidates(e, keys, n, K, out, cnt.data());
+  if (align) {
+    memset(align, 0, sizeof(tfp_alignment) * (size_t)n * K);
+    for (int32_t i = 0; i < n; i++) {
+      int32_t w = 0;
+      for (int32_t r = 0; r < K && keys[(size_t)i * K + r]; r++) {
+        if (clip_of_key(e, keys[(size_t)i * K + r]) < 0) continue;  // (fill_candidates skipped it too)
+        const AlignOut& a = al[(size_t)i * K + r];
+        align[(size_t)i * K + w++] = tfp_alignment{a.aligned_count, a.offset, a.first_frame, a.last_frame};
+      }
+    }
+  }
+  std::copy(cnt.begin(), cnt.begin() + n, counts);
+}
+
+// The body of tfp_index_neighbours over resolved clip ids. Shaped like slide_core: the vote form at the
+// tolerances whose key bitsets hold a live index delta's columns, else (and for a key outside the vote
+// range) the general form over the merged index.
+int neighbours_core(tfp_engine* e, const std::vector<int32_t>& ids, const tfp_search_params* P, const int32_t* scopes,
+                    int32_t K, std::vector<unsigned long long>& keys, std::vector<AlignOut>* al, hipStream_t s) {
+  const int32_t n = (int32_t)ids.size();
+  int rc = rebuild(e);  // synchronous on e->stream
+  if (rc) return rc;
+  const SearchConsts sc = search_consts(P);
+  keys.assign((size_t)n * K, 0ull);
+  if (al) al->assign((size_t)n * K, AlignOut{0, 0, 0, 0});
+  int64_t frames = 0;
+  for (const int32_t id : ids) frames += e->clips[id].nrows;
+  if (sc.coefs == 1 && delta_tol_ok(sc.tole)) {
+    if (e->ncols <= 0 || e->nrows + e->delta.rows <= 0) {  // no row that can match: no neighbour, nothing launched
+      e->n_nbr_vote++;
+      e->n_nbr_frames += frames;
+      return TFP_OK;
+    }
+    if ((rc = ensure_ranges(e, sc.tole, s)) || (rc = ensure_key_bits(e, s)) || (rc = ensure_scope_table(e, s)) ||
+        (rc = ensure_neighbour_cols(e, s)))
+      return rc;
+    // named clips in batches of <= 256 MB of partial keys (and of the launch grid's second dimension), as rank_vote
+    const int32_t nb = rank_vote_blocks(e->ncols);
+    int64_t chunk = (int64_t)(256ll << 20) / ((int64_t)sizeof(unsigned long long) * nb * K);
+    chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(chunk, 65535 / K), n));
+    bool bad = false;
+    for (int64_t i0 = 0; i0 < n && !bad; i0 += chunk) {
+      const int32_t m = (int32_t)std::min<int64_t>(chunk, n - i0);
+      if ((rc = neighbour_vote(e, ids.data() + i0, scopes ? scopes + i0 : nullptr, m, sc, K, keys.data() + i0 * K,
+                               al ? al->data() + i0 * K : nullptr, &bad, s)))
+        return rc;
+    }
+    if (!bad) {
+      e->n_nbr_vote++;
+      e->n_nbr_frames += frames;
+      for (const unsigned long long k : keys) e->n_nbr_pairs += al && k != 0;
+      return TFP_OK;
+    }
+    keys.assign((size_t)n * K, 0ull);
+    if (al) al->assign((size_t)n * K, AlignOut{0, 0, 0, 0});
+  }
+  if ((rc = consolidate(e))) return rc;  // (the clips' staged rows may move: descriptors are built after it)
+  std::vector<int32_t> any;
+  if (!scopes) any.assign((size_t)n, kScopeAny);
+  const int32_t* sv = scopes ? scopes : any.data();
+  // named clips in batches of <= 256 MB of gathered frame values (and of the launch grid's second dimension)
+  const int64_t cap_frames = (int64_t)(256ll << 20) / (2 * sizeof(double));
+  for (int32_t i0 = 0; i0 < n;) {
+    int32_t i1 = i0;
+    int64_t nf = 0;
+    while (i1 < n && i1 - i0 < 65535 && (i1 == i0 || nf + e->clips[ids[i1]].nrows <= cap_frames)) nf += e->clips[ids[i1++]].nrows;
+    const int32_t m = i1 - i0;
+    int64_t total, longest;
+    std::vector<NeighbourClip> nc;
+    neighbour_clips(e, ids.data() + i0, sv + i0, m, false, nc, &total, &longest);
+    std::vector<int64_t> qo((size_t)m + 1, 0);
+    for (int32_t i = 0; i < m; i++) qo[i + 1] = qo[i] + nc[i].nrows;
+    if ((rc = upload(e, e->nbr_clips, nc.data(), sizeof(NeighbourClip) * nc.size(), s))) return rc;
+    HIPCHK(e, e->nbr_q.reserve(2 * sizeof(double) * (size_t)(total + 1)));
+    HIPCHK(e, launch_neighbour_gather(e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(), e->nbr_clips.as<NeighbourClip>(), m,
+                                      longest, e->nbr_q.as<double>(), s));
+    if ((rc = neighbour_general(e, qo, m, e->nbr_q.as<double>(), P, sv + i0, ids.data() + i0, K, keys.data() + (size_t)i0 * K,
+                                al ? al->data() + (size_t)i0 * K : nullptr, s)))
+      return rc;
+    HIPCHK(e, hipStreamSynchronize(s));  // (an empty index returns before any wait: nc is released here)
+    i0 = i1;
+  }
+  e->n_nbr_general++;
+  e->n_nbr_frames += frames;
+  for (const unsigned long long k : keys) e->n_nbr_pairs += al && k != 0;
+  return TFP_OK;
+}
+
+int neighbour_args(tfp_engine* e, int32_t n, const void* ptrs, const tfp_search_params* P, const int32_t* scopes, int32_t k,
+                   const void* out, const void* counts) {
+  if (n < 0 || (n && (!ptrs || !out || !counts))) return fail(e, TFP_E_ARG, "neighbours: bad clip count or NULL array");
+  int rc = check_k(e, "neighbours", k);
+  if (rc || (rc = check_params(e, "neighbours", P))) return rc;
+  return check_scopes(e, "neighbours", scopes, n, "clip");
+}
+
+}  // namespace
+
+int tfp_index_neighbours(tfp_engine* e, int32_t nclips, const char* const* uuids, const tfp_search_params* P,
+                         const int32_t* scopes, int32_t k, tfp_candidate* out, tfp_alignment* align, int32_t* counts,
+                         int32_t* frame_counts) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = neighbour_args(e, nclips, uuids, P, scopes, k, out, counts);
+  if (rc) return rc;
+  std::vector<int32_t> ids((size_t)nclips);
+  for (int32_t i = 0; i < nclips; i++) {  // all or nothing: every name resolved before anything is written
+    if (!uuids[i]) return fail(e, TFP_E_ARG, "neighbours: uuid %d is NULL", i);
+    const auto it = e->by_uuid.find(uuids[i]);
+    if (it == e->by_uuid.end()) return fail(e, TFP_E_NOENT, "uuid %s not indexed", uuids[i]);
+    ids[i] = it->second;
+  }
+  if (!nclips) return TFP_OK;
+  HIPCHK(e, hipSetDevice(e->device));
+  std::vector<unsigned long long> keys;
+  std::vector<AlignOut> al;
+  if ((rc = neighbours_core(e, ids, P, scopes, k, keys, align ? &al : nullptr, e->stream))) return rc;
+  fill_neighbours(e, keys, al, nclips, k, out, align, counts);
+  for (int32_t i = 0; frame_counts && i < nclips; i++) frame_counts[i] = (int32_t)e->clips[ids[i]].nrows;
+  return TFP_OK;
+}
+
+int tfp_neighbour_stats(tfp_engine* e, int64_t* vote_batches, int64_t* general_batches, int64_t* pairs_aligned,
+                        int64_t* frames_read) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (vote_batches) *vote_batches = e->n_nbr_vote;
+  if (general_batches) *general_batches = e->n_nbr_general;
+  if (pairs_aligned) *pairs_aligned = e->n_nbr_pairs;
+  if (frames_read) *frames_read = e->n_nbr_frames;
+  return TFP_OK;
+}
+
+// A device group's steps (tfp_group_index_neighbours). _frames: the frame values of this engine's named
+// clips (the gather kernel), clip i at out[foff[i]]. _of_frames: the rows of host frames over this
+// engine's clips with self_ids[i] (-1: the clip lies on another shard) deleted, general form's body.
+int tfp_internal_neighbour_rows(tfp_engine* e, int32_t nclips, const char* const* uuids, int64_t* nrows) {
+  if (!e || nclips < 0 || (nclips && (!uuids || !nrows))) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  for (int32_t i = 0; i < nclips; i++) {
+    const auto it = e->by_uuid.find(uuids[i]);
+    if (it == e->by_uuid.end()) return fail(e, TFP_E_NOENT, "uuid %s not indexed", uuids[i]);
+    nrows[i] = e->clips[it->second].nrows;
+  }
+  return TFP_OK;
+}
+
+int tfp_internal_neighbour_frames(tfp_engine* e, int32_t nclips, const char* const* uuids, const int64_t* foff,
+                                  tfp_frame* out) {
+  if (!e || nclips < 0 || (nclips && (!uuids || !foff || !out))) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  std::vector<int32_t> ids((size_t)nclips);
+  for (int32_t i = 0; i < nclips; i++) {
+    const auto it = e->by_uuid.find(uuids[i]);
+    if (it == e->by_uuid.end()) return fail(e, TFP_E_NOENT, "uuid %s not indexed", uuids[i]);
+    ids[i] = it->second;
+  }
+  if (!nclips) return TFP_OK;
+  HIPCHK(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  int64_t total, longest;
+  std::vector<NeighbourClip> nc;
+  neighbour_clips(e, ids.data(), nullptr, nclips, false, nc, &total, &longest);
+  if (!total) return TFP_OK;
+  int rc = upload(e, e->nbr_clips, nc.data(), sizeof(NeighbourClip) * nc.size(), s);
+  if (rc) return rc;
+  HIPCHK(e, e->nbr_q.reserve(2 * sizeof(double) * (size_t)(total + 1)));
+  for (int32_t i0 = 0; i0 < nclips; i0 += 65535)
+    HIPCHK(e, launch_neighbour_gather(e->st_m1.as<int32_t>(), e->st_m2.as<int32_t>(), e->nbr_clips.as<NeighbourClip>() + i0,
+                                      std::min(65535, nclips - i0), longest, e->nbr_q.as<double>(), s));
+  std::vector<double> q(2 * (size_t)total);
+  HIPCHK(e, hipMemcpyAsync(q.data(), e->nbr_q.p, sizeof(double) * q.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(e, hipStreamSynchronize(s));
+  for (int32_t i = 0; i < nclips; i++)
+    for (int64_t j = 0; j < nc[i].nrows; j++) {
+      tfp_frame& f = out[foff[i] + j];
+      memset(&f, 0, sizeof f);
+      f.frame_idx = (int32_t)j;
+      f.q1 = q[2 * (size_t)(nc[i].box0 + j)];
+      f.q2 = q[2 * (size_t)(nc[i].box0 + j) + 1];
+    }
+  return TFP_OK;
+}
+
+int tfp_internal_neighbours_of_frames(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                                      const tfp_search_params* P, const int32_t* scopes, const int32_t* self_ids, int32_t k,
+                                      tfp_candidate* out, int32_t* counts) {
+  if (!e || !qoff || nq < 0 || !out || !counts || !scopes) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = check_k(e, "neighbours", k);
+  if (rc || (rc = check_params(e, "neighbours", P))) return rc;
+  if (!nq) return TFP_OK;
+  const std::vector<int64_t> qo = relative_offsets(qoff, nq);
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = upload_frames(e, frames, qoff, nq))) return rc;
+  std::vector<unsigned long long> keys((size_t)nq * k, 0ull);
+  if ((rc = neighbour_general(e, qo, nq, e->q.as<double>(), P, scopes, self_ids, k, keys.data(), nullptr, e->stream))) return rc;
+  fill_candidates(e, keys, nq, k, out, counts);
+  e->n_nbr_general++;
+  for (int32_t i = 0; self_ids && i < nq; i++)  // a clip's stored rows are read on its own shard: counted there, once
+    if (self_ids[i] >= 0) e->n_nbr_frames += qo[i + 1] - qo[i];
+  return TFP_OK;
+}
+
+int tfp_internal_neighbour_align(tfp_engine* e, const tfp_frame* frames, const int64_t* qoff, int32_t nq,
+                                 const tfp_search_params* P, const int32_t* clip_ids, int32_t k, tfp_alignment* out) {
+  if (!e || !qoff || nq < 0 || !out || (nq && !clip_ids)) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  int rc = check_k(e, "neighbours", k);
+  if (rc || (rc = check_params(e, "neighbours", P)) || !nq) return rc;
+  const std::vector<int64_t> qo = relative_offsets(qoff, nq);
+  HIPCHK(e, hipSetDevice(e->device));
+  if ((rc = upload_frames(e, frames, qoff, nq)) ||
+      (rc = align_core(e, qo, nq, e->q.as<double>(), P, k, clip_ids, out, e->stream, false)))
+    return rc;
+  for (size_t p = 0; p < (size_t)nq * k; p++) e->n_nbr_pairs += clip_ids[p] >= 0;
   return TFP_OK;
 }
 

@@ -840,6 +840,93 @@ int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const in
   });
 }
 
+// Catalog neighbours on a group (tfp_neighbour.hpp). The shard that holds a named clip produces its
+// frame values (the gather kernel over its staged rows); they travel to every shard as a frames batch
+// does, from the host. Every shard returns its first k rows over its own clips, the owner with the
+// clip's own row deleted from k + 1 (no other shard has a row to delete), so the merged first k are
+// one engine's over all the clips. The rows are aligned on the shard that holds their clip.
+int tfp_group_index_neighbours(tfp_group* g, int32_t nclips, const char* const* uuids, const tfp_search_params* P,
+                               const int32_t* scopes, int32_t k, tfp_candidate* out, tfp_alignment* align, int32_t* counts,
+                               int32_t* frame_counts) {
+  if (!g) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  if (nclips < 0 || (nclips && (!uuids || !out || !counts))) return gfail(g, TFP_E_ARG, "neighbours: bad clip count or NULL array");
+  if (k < 1 || k > TFP_RANK_MAX) return gfail(g, TFP_E_ARG, "neighbours: k = %d outside [1, %d]", k, TFP_RANK_MAX);
+  if (!valid_params(P)) return gfail(g, TFP_E_ARG, "neighbours: coefs outside [1, 2]");
+  for (int32_t i = 0; scopes && i < nclips; i++)
+    if (scopes[i] < TFP_SCOPE_ANY) return gfail(g, TFP_E_ARG, "neighbours: scope %d of clip %d", scopes[i], i);
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<const char*>> names(n);
+  std::vector<std::vector<int32_t>> which(n), self(n, std::vector<int32_t>((size_t)std::max(nclips, 1), -1));
+  for (int32_t i = 0; i < nclips; i++) {  // all or nothing: every name resolved before anything is written
+    if (!uuids[i]) return gfail(g, TFP_E_ARG, "neighbours: uuid %d is NULL", i);
+    const auto it = g->where.find(uuids[i]);
+    if (it == g->where.end()) return gfail(g, TFP_E_NOENT, "uuid %s not indexed", uuids[i]);
+    const Member& mb = g->members[it->second];
+    names[mb.shard].push_back(uuids[i]);
+    which[mb.shard].push_back(i);
+    self[mb.shard][i] = mb.id;
+  }
+  if (!nclips) return TFP_OK;
+  std::vector<int64_t> qoff((size_t)nclips + 1, 0);
+  for (int s = 0; s < n; s++) {
+    if (names[s].empty()) continue;
+    std::vector<int64_t> nr(names[s].size());
+    const int rc = tfp_internal_neighbour_rows(g->eng[s], (int32_t)names[s].size(), names[s].data(), nr.data());
+    if (rc) return shard_fail(g, rc, s);
+    for (size_t j = 0; j < nr.size(); j++) qoff[which[s][j] + 1] = nr[j];
+  }
+  for (int32_t i = 0; i < nclips; i++) qoff[i + 1] += qoff[i];
+  std::vector<tfp_frame> frames((size_t)std::max<int64_t>(qoff[nclips], 1));
+  int rc = run_all(g, [&](int s) {
+    if (names[s].empty()) return (int)TFP_OK;
+    std::vector<int64_t> foff(names[s].size());
+    for (size_t j = 0; j < foff.size(); j++) foff[j] = qoff[which[s][j]];
+    return tfp_internal_neighbour_frames(g->eng[s], (int32_t)names[s].size(), names[s].data(), foff.data(), frames.data());
+  });
+  if (rc) return rc;
+  std::vector<int32_t> sv((size_t)nclips, TFP_SCOPE_ANY);
+  if (scopes) sv.assign(scopes, scopes + nclips);
+  std::vector<int32_t> kept;
+  std::vector<tfp_candidate> rows((size_t)nclips * k);
+  std::vector<int32_t> cnt((size_t)nclips);
+  rc = group_rank(
+      g, nclips, P, k, rows.data(), cnt.data(),
+      [&](int s, tfp_candidate* o, int32_t* c) {
+        return tfp_internal_neighbours_of_frames(g->eng[s], frames.data(), qoff.data(), nclips, P, sv.data(), self[s].data(), k,
+                                                 o, c);
+      },
+      &kept);
+  if (rc) return rc;
+  const size_t np = (size_t)nclips * k;
+  std::vector<tfp_alignment> al(np);
+  if (align) {
+    std::vector<std::vector<int32_t>> ids(n, std::vector<int32_t>(np, -1));
+    std::vector<char> used(n, 0);
+    for (size_t p = 0; p < np; p++)
+      if (kept[p] >= 0) {
+        const Member& mb = g->members[kept[p]];
+        ids[mb.shard][p] = mb.id;
+        used[mb.shard] = 1;
+      }
+    std::vector<std::vector<tfp_alignment>> res(n, std::vector<tfp_alignment>(np));
+    rc = run_all(g, [&](int s) {
+      return used[s] ? tfp_internal_neighbour_align(g->eng[s], frames.data(), qoff.data(), nclips, P, ids[s].data(), k,
+                                                    res[s].data())
+                     : (int)TFP_OK;
+    });
+    if (rc) return rc;
+    memset(al.data(), 0, sizeof(tfp_alignment) * np);
+    for (size_t p = 0; p < np; p++)
+      if (kept[p] >= 0) al[p] = res[g->members[kept[p]].shard][p];
+    std::copy(al.begin(), al.end(), align);
+  }
+  std::copy(rows.begin(), rows.end(), out);
+  std::copy(cnt.begin(), cnt.end(), counts);
+  for (int32_t i = 0; frame_counts && i < nclips; i++) frame_counts[i] = (int32_t)(qoff[i + 1] - qoff[i]);
+  return TFP_OK;
+}
+
 // Match census on a group (tfp_census.hpp): each shard's census of its own clips runs on its worker
 // and the rows are summed on the host, bin 0 (the shard's live clips of the scope with count 0)
 // included. A clip lies on one shard, so the sum is exact.

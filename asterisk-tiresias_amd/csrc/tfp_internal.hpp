@@ -108,6 +108,26 @@ __attribute__((visibility("hidden"))) int tfp_internal_live_verdict_keys(tfp_liv
 // _add appends the track (ch, clip_id, s) to this engine's list unconditionally (the group has applied
 // max_tracks over all shards), and _advance is step 3 alone over this engine's tracks, read out
 // afterwards with tfp_live_tracks.
+// tfp_group_index_neighbours' steps on a shard. _frames: the frame values of this engine's named clips
+// (the gather kernel over their staged rows), clip i at out[foff[i]]; _rows: their stored row counts. _of_frames: the first k rows of
+// host frames over this engine's clips of scopes[i], the clip self_ids[i] (-1: it lies on another
+// shard) deleted from k + 1 rows; the group merges the shards' rows as scoped search's.
+__attribute__((visibility("hidden"))) int tfp_internal_neighbour_rows(tfp_engine* e, int32_t nclips,
+                                                                      const char* const* uuids, int64_t* nrows);
+__attribute__((visibility("hidden"))) int tfp_internal_neighbour_frames(tfp_engine* e, int32_t nclips,
+                                                                        const char* const* uuids, const int64_t* foff,
+                                                                        tfp_frame* out);
+__attribute__((visibility("hidden"))) int tfp_internal_neighbours_of_frames(tfp_engine* e, const tfp_frame* frames,
+                                                                            const int64_t* qoff, int32_t nq,
+                                                                            const tfp_search_params* P, const int32_t* scopes,
+                                                                            const int32_t* self_ids, int32_t k,
+                                                                            tfp_candidate* out, int32_t* counts);
+// ... and tfp_align_batch for the merged rows of this shard's clips, counted as neighbour pairs
+// (tfp_neighbour_stats), not as an aligned search's.
+__attribute__((visibility("hidden"))) int tfp_internal_neighbour_align(tfp_engine* e, const tfp_frame* frames,
+                                                                       const int64_t* qoff, int32_t nq,
+                                                                       const tfp_search_params* P, const int32_t* clip_ids,
+                                                                       int32_t k, tfp_alignment* out);
 __attribute__((visibility("hidden"))) int tfp_internal_live_occ_add(tfp_live* lv, int32_t ch, int32_t clip_id, int32_t s);
 __attribute__((visibility("hidden"))) int tfp_internal_live_occ_advance(tfp_live* lv, const tfp_search_params* P,
                                                                         int32_t max_gap);

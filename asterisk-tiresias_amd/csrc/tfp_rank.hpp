@@ -15,6 +15,8 @@
 namespace tfp {
 
 constexpr int32_t kRankMax = 32;         // TFP_RANK_MAX
+// the launchers' own bound: catalog neighbours (tfp_neighbour.hpp) select k + 1 rows and delete one
+constexpr int32_t kRankMaxInternal = kRankMax + 1;
 constexpr int32_t kRankVoteCols = 1024;  // columns per rank_vote block (4 per thread)
 inline int32_t rank_vote_blocks(int32_t C) { return (C + kRankVoteCols - 1) / kRankVoteCols; }
 

@@ -209,7 +209,7 @@ hipError_t launch_scope_vote(const double* d_q, const int64_t* d_qoff, const int
                              const uint32_t* d_bits, int32_t C, const int32_t* d_tiekey, const int32_t* d_table, int32_t K,
                              unsigned long long* d_part, unsigned long long* d_keys, int32_t* d_bad, hipStream_t s) {
   if (nq <= 0) return hipSuccess;
-  if (K < 1 || K > kRankMax || C <= 0 || nq > 65535) return hipErrorInvalidValue;
+  if (K < 1 || K > kRankMaxInternal || C <= 0 || nq > 65535) return hipErrorInvalidValue;
   const int32_t nb = rank_vote_blocks(C);
   hipLaunchKernelGGL(scope_vote_kernel, dim3(nb, nq), dim3(256), 0, s, d_q, d_qoff, d_qscope, sc, d_bits, C, d_tiekey,
                      d_table, K, d_part, d_bad);
@@ -222,7 +222,7 @@ hipError_t launch_scope_final(int32_t q_begin, int32_t nq, const int32_t* d_qsco
                               const int32_t* d_touched, int32_t* d_tcnt, int32_t K, unsigned long long* d_keys,
                               hipStream_t s) {
   if (nq <= 0) return hipSuccess;
-  if (K < 1 || K > kRankMax) return hipErrorInvalidValue;
+  if (K < 1 || K > kRankMaxInternal) return hipErrorInvalidValue;
   hipLaunchKernelGGL(scope_final_kernel, dim3(nq), dim3(256), 0, s, q_begin, d_qscope, d_tiekey, d_table, C, d_stamp,
                      d_score, d_touched, d_tcnt, K, d_keys);
   return hipGetLastError();

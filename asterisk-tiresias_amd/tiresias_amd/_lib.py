@@ -234,6 +234,11 @@ _SIGS = {
     "tfp_group_search_scoped_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P, P]),
     "tfp_group_search_scoped_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32,
                                                     P, P]),
+    "tfp_index_neighbours": (C.c_int, [P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(SearchParams), P, C.c_int32, P, P, P,
+                                       P]),
+    "tfp_neighbour_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 4),
+    "tfp_group_index_neighbours": (C.c_int, [P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(SearchParams), P, C.c_int32, P,
+                                             P, P, P]),
     "tfp_census_batch": (C.c_int, [P, P, P, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P, C.POINTER(C.c_int32)]),
     "tfp_census_pcm_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32, P,
                                        C.POINTER(C.c_int32)]),

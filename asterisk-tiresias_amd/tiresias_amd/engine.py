@@ -251,6 +251,25 @@ class _ScopedCalls:
                                                        C.byref(p), scopes.ctypes.data, k, out, counts))
         return Engine._candidates(out, counts, nq, k)
 
+    def index_neighbours(self, uuids, p: SearchParams, k: int, scopes=None, aligned: bool = True):
+        """tfp_index_neighbours: per named clip {"frame_count", "neighbours"}: the first k rows of the result
+        query for the clip's own stored rows over the clips of scopes[i] (None: every clip), its own row
+        deleted; with aligned each row carries its alignment's four fields."""
+        n, k = len(uuids), int(k)
+        arr = (C.c_char_p * max(1, n))(*[u.encode() for u in uuids])
+        sp = None
+        if scopes is not None:
+            scopes = np.ascontiguousarray(scopes, np.int32)
+            if len(scopes) != n:
+                raise ValueError("one scope per uuid")
+            sp = scopes.ctypes.data
+        m = max(1, n * max(k, 1))
+        out, counts, fc = (Candidate * m)(), (C.c_int32 * max(1, n))(), (C.c_int32 * max(1, n))()
+        align = (Alignment * m)() if aligned else None
+        self._chk(self._fn("_index_neighbours")(self._h, n, arr, C.byref(p), sp, k, out, align, counts, fc))
+        rows = Engine._aligned(out, align, counts, n, k) if aligned else Engine._candidates(out, counts, n, k)
+        return [{"frame_count": fc[i], "neighbours": rows[i]} for i in range(n)]
+
 
 def census_at_least(hist_row, count: int) -> int:
     """tfp_census_at_least: the clips of one census row with count >= `count` (bin 0 only for count <= 0)."""
@@ -687,6 +706,12 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
         v, g, t = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(lib().tfp_scope_stats(self._h, C.byref(v), C.byref(g), C.byref(t)))
         return {"vote_batches": v.value, "general_batches": g.value, "table_builds": t.value}
+
+    def neighbour_stats(self) -> dict:
+        """tfp_neighbour_stats: neighbour calls by form, the rows aligned, the stored rows used as query frames."""
+        x = [C.c_int64() for _ in range(4)]
+        self._chk(lib().tfp_neighbour_stats(self._h, *[C.byref(v) for v in x]))
+        return dict(zip(("vote_batches", "general_batches", "pairs_aligned", "frames_read"), (v.value for v in x)))
 
     def census_stats(self) -> dict:
         """tfp_census_stats: census batches served by the vote form and by the general form."""
@@ -1211,6 +1236,16 @@ class Group(_ScopedCalls, _SlidingCalls, _CensusCalls):
             check(lib().tfp_scope_stats(lib().tfp_group_engine(self._h, s), C.byref(v), C.byref(g), C.byref(t)))
             for key, x in zip(tot, (v, g, t)):
                 tot[key] += x.value
+        return tot
+
+    def neighbour_stats(self) -> dict:
+        """Engine.neighbour_stats summed over the shards' engines."""
+        tot = {"vote_batches": 0, "general_batches": 0, "pairs_aligned": 0, "frames_read": 0}
+        for s in range(self.size()):
+            x = [C.c_int64() for _ in tot]
+            check(lib().tfp_neighbour_stats(lib().tfp_group_engine(self._h, s), *[C.byref(v) for v in x]))
+            for key, v in zip(tot, x):
+                tot[key] += v.value
         return tot
 
 

@@ -229,6 +229,55 @@ class FpHandler:
             return False
         return True
 
+    # ---- catalog neighbours: which enrolled audios sound like each other (tfp_index_neighbours)
+    NEIGHBOUR_FLUSH = 512  # audios per tfp_index_neighbours call
+
+    def _neighbours(self, infos, scope, p, k):
+        """infos (catalog rows) with frame_count and neighbours added; an audio the engine does not hold is
+        left out. One engine call per NEIGHBOUR_FLUSH audios."""
+        infos = [i for i in infos if self._indexed(i["uuid"])]
+        out = []
+        for a in range(0, len(infos), self.NEIGHBOUR_FLUSH):
+            part = infos[a:a + self.NEIGHBOUR_FLUSH]
+            res = self.engine.index_neighbours([i["uuid"] for i in part], p, k, [scope] * len(part))
+            self.neighbour_calls += 1
+            for info, r in zip(part, res):
+                info["frame_count"] = r["frame_count"]
+                info["neighbours"] = []
+                for row in r["neighbours"]:
+                    n = self._audio_list_info(row["audio_uuid"])
+                    if n is None:
+                        continue
+                    for key in ("match_count", "aligned_count", "offset", "first_frame", "last_frame"):
+                        n[key] = row[key]
+                    info["neighbours"].append(n)
+                out.append(info)
+        return out
+
+    neighbour_calls = 0  # engine calls made by the two entries below (tests)
+
+    def fp_get_audio_list_neighbours(self, context, coefs, tolerance, freq_ignore_low, freq_ignore_high, k):
+        """For every audio of the context (fp_get_audio_lists_by_contextname's rows) its catalog fields,
+        frame_count (its stored rows) and neighbours: the first k rows of the search of fp_handler.c:287-374
+        for its own stored rows over the same context's audios, its own row deleted, each with its catalog
+        fields, match_count, aligned_count, offset, first_frame and last_frame."""
+        if context is None or coefs < 1 or coefs > DEF_AUBIO_COEFS or k < 1:
+            return None
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        return self._neighbours(self.fp_get_audio_lists_by_contextname(context), self._scope_of(context, False), p,
+                                min(int(k), TFP_RANK_MAX))
+
+    def fp_get_audio_neighbours(self, uuid, coefs, tolerance, freq_ignore_low, freq_ignore_high, k):
+        """The same for one audio, over the audios of every context; None for an unknown uuid."""
+        if uuid is None or coefs < 1 or coefs > DEF_AUBIO_COEFS or k < 1:
+            return None
+        info = self._audio_list_info(uuid)
+        if info is None:
+            return None
+        p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
+        got = self._neighbours([info], -1, p, min(int(k), TFP_RANK_MAX))
+        return got[0] if got else None
+
     def _fingerprint(self, samples: np.ndarray, offsets, sr: int, law=None):
         if law is not None:
             return self.engine.fingerprint_g711_batch(samples, offsets, law, sr)

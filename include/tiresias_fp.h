@@ -1000,6 +1000,39 @@ int tfp_live_tracks(tfp_live* lv, int32_t channel, tfp_trace_req* reqs, tfp_trac
 int tfp_live_occurrence_stats(tfp_live* lv, int64_t* calls, int64_t* tracks_added, int64_t* tracks_dropped,
                               int64_t* frames_traced, int64_t* retraces);
 
+/* ---- catalog neighbours: which enrolled clips sound like a given clip (new) -------------- */
+/* The reference deduplicates enrolments by MD5 alone (fp_handler.c:713-753), so the same prompt from
+ * another encoder, or two prompts that share most of their keys, is found only when a search
+ * (fp_handler.c:287-374) returns the wrong one. These calls ask the catalog itself.
+ *
+ * A stored row (m1, m2) used as a query frame has the frame values (double)m / 1e6 by IEEE division,
+ * -inf where m is TFP_NULL_MICRO: the double SQLite reads back from the "%f" text of
+ * fp_handler.c:559-571. The neighbours of clip a under (params, scope, k) are the first k rows of the
+ * result query (fp_handler.c:367-374) for the recording whose fingerprints are a's stored rows, NULL
+ * rows included as frames, restricted to scope as tfp_search_scoped_batch restricts it
+ * (fp_handler.c:308-314 with the context predicate), with the row of a itself deleted. A clip need not
+ * match itself (its own row lies in a frame's box only when the value's fraction is within the
+ * tolerance), so this is "k + 1 rows minus self": self is dropped if it is among the first k + 1 rows,
+ * else row k + 1 is. Each row carries the tfp_alignment tfp_align_batch gives those frames against
+ * the row's clip. */
+/* fp_handler.c:287-374 for each named clip's stored rows (fp_handler.c:713-753: the catalog's clips)
+ * over the clips of scopes[i] (TFP_SCOPE_ANY or >= 0; scopes NULL: ANY everywhere; a scope the named
+ * clip is not in is legal). out[i * k + r] is row r of clip i, align[i * k + r] its alignment (align
+ * NULL: none computed), counts[i] the rows, frame_counts[i] (or NULL) the clip's stored rows; entries
+ * past counts[i] are zeroed. k < 1, k > TFP_RANK_MAX, coefs outside [1,2] or a scope below -1 is
+ * TFP_E_ARG; an unknown or removed uuid TFP_E_NOENT, nothing written then. A uuid may be named
+ * twice; nclips = 0 is TFP_OK. No frame value is written and no row leaves the device on the vote
+ * form (coefs = 1, keys inside the vote range). */
+int tfp_index_neighbours(tfp_engine* eng, int32_t nclips, const char* const* uuids, const tfp_search_params* params,
+                         const int32_t* scopes /* [nclips] or NULL */, int32_t k, tfp_candidate* out /* [nclips*k] */,
+                         tfp_alignment* align /* [nclips*k] or NULL */, int32_t* counts /* [nclips] */,
+                         int32_t* frame_counts /* [nclips] or NULL */);
+/* Neighbour calls served so far by the vote form and by the general form (the rows of
+ * fp_handler.c:287-374 over stored rows of fp_handler.c:713-753's clips), the rows aligned, and the
+ * stored rows used as query frames. Any pointer may be NULL. */
+int tfp_neighbour_stats(tfp_engine* eng, int64_t* vote_batches, int64_t* general_batches, int64_t* pairs_aligned,
+                        int64_t* frames_read);
+
 /* ---- device groups: the node's GPUs behind one index (new in round 3) -------------------
  * The module's enrolled DB sharded over one engine per listed device (the reference
  * has one SQLite DB, fp_handler.c:30): each clip lives on one engine (the one holding the fewest
@@ -1069,6 +1102,18 @@ int tfp_group_search_scoped_batch(tfp_group* g, const tfp_frame* frames, const i
 int tfp_group_search_scoped_pcm_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
                                       int32_t sample_rate, const tfp_search_params* params, const int32_t* scopes,
                                       int32_t k, tfp_candidate* out, int32_t* counts);
+/* Catalog neighbours on a group (fp_handler.c:287-374 for the stored rows of fp_handler.c:713-753's
+ * clips, as tfp_index_neighbours): the shard that holds a named clip produces its frame values, every
+ * shard returns its first k rows for them (only the owner has a row to delete), the rows merge as
+ * tfp_group_search_scoped_batch's do and each is aligned on the shard that holds its clip. The result
+ * equals one engine over all the clips; clip_id is the shard. Arguments and rules as the engine call's.
+ * tfp_neighbour_stats of a shard's engine (tfp_group_engine): every shard serves each group call once and
+ * counts it as a general batch, whatever the parameters (the shards rank the owner's frame values, which
+ * reach them as frames); frames_read is counted on the owner shard and pairs_aligned on the shard that
+ * aligned the row, so their sums over the shards equal one engine's. */
+int tfp_group_index_neighbours(tfp_group* g, int32_t nclips, const char* const* uuids, const tfp_search_params* params,
+                               const int32_t* scopes, int32_t k, tfp_candidate* out, tfp_alignment* align, int32_t* counts,
+                               int32_t* frame_counts);
 /* Census on a group (fp_handler.c:287-374 counted by count(*), as tfp_census_batch): every shard
  * takes the census of its own clips and the rows are summed bin by bin, bin 0 included. A clip lies
  * on one shard, so the sum is exact. The arguments and rules as the engine calls'. */

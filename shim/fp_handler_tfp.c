@@ -197,6 +197,19 @@ static bool load_scopes(const fpc_rows* rows)
 	return ret;
 }
 
+/* Every shard serves each tfp_group_index_neighbours call once, so shard 0's batches are the calls. */
+bool fp_get_neighbour_stats(int64_t* calls)
+{
+	int64_t vote = 0, general = 0;
+
+	if(g_tfp == NULL || calls == NULL ||
+			tfp_neighbour_stats(tfp_group_engine(g_tfp, 0), &vote, &general, NULL, NULL) != TFP_OK) {
+		return false;
+	}
+	*calls = vote + general;
+	return true;
+}
+
 bool fp_get_search_stats(int64_t* calls, int64_t* batches)
 {
 	return g_tfp != NULL && tfp_group_search_coalesce_stats(g_tfp, calls, batches) == TFP_OK;
@@ -1911,6 +1924,154 @@ struct ast_json* fp_live_occurrences(fp_live* lv, const char* const* contexts, c
 	ast_free(occ);
 	ast_free(scopes);
 	return j_res;
+}
+
+#define FP_NEIGHBOUR_FLUSH 512 /* audios per tfp_group_index_neighbours call */
+
+/* The audios j_list[first, first + n) (catalog objects) that have fingerprint rows, each as a fresh catalog
+ * object with frame_count and neighbours, appended to j_res: one tfp_group_index_neighbours call. */
+static bool neighbours_flush(struct ast_json* j_list, size_t first, size_t n, int32_t scope, const tfp_search_params* p,
+		int k, struct ast_json* j_res)
+{
+	const char** uu = ast_calloc(n, sizeof(*uu));
+	int32_t* scopes = ast_calloc(n, sizeof(*scopes));
+	int32_t* counts = ast_calloc(n, sizeof(*counts));
+	int32_t* frames = ast_calloc(n, sizeof(*frames));
+	tfp_candidate* cand = ast_calloc(n * k, sizeof(*cand));
+	tfp_alignment* align = ast_calloc(n * k, sizeof(*align));
+	int32_t m = 0, s, i, r;
+	size_t a;
+	bool ret = (uu != NULL) && (scopes != NULL) && (counts != NULL) && (frames != NULL) && (cand != NULL) && (align != NULL);
+
+	for(a = first; ret && a < first + n; a++) {
+		const char* uuid = ast_json_string_get(ast_json_object_get(ast_json_array_get(j_list, a), "uuid"));
+		if(uuid != NULL && tfp_group_index_scope(g_tfp, uuid, &s) == TFP_OK) { /* else: a catalog row without fingerprint rows */
+			uu[m] = uuid;
+			scopes[m++] = scope;
+		}
+	}
+	if(ret && m > 0 && tfp_group_index_neighbours(g_tfp, m, uu, p, scopes, k, cand, align, counts, frames) != TFP_OK) {
+		ast_log(LOG_ERROR, "Could not get neighbours: %s\n", tfp_group_last_error(g_tfp));
+		ret = false;
+	}
+	for(i = 0; ret && i < m; i++) {
+		struct ast_json* j_audio = fpc_get_audio_list_info(uu[i]);
+		struct ast_json* j_rows;
+		if(j_audio == NULL) {
+			continue;
+		}
+		j_rows = ast_json_array_create();
+		for(r = 0; r < counts[i]; r++) {
+			const tfp_candidate* c = &cand[(size_t)i * k + r];
+			const tfp_alignment* al = &align[(size_t)i * k + r];
+			struct ast_json* j_tmp = fpc_get_audio_list_info(c->uuid); /* a row whose audio_list entry is missing is skipped */
+			if(j_tmp == NULL) {
+				ast_log(LOG_ERROR, "Could not get audio list info. uuid[%s]\n", c->uuid);
+				continue;
+			}
+			ast_json_object_set(j_tmp, "match_count", ast_json_integer_create(c->match_count));
+			ast_json_object_set(j_tmp, "aligned_count", ast_json_integer_create(al->aligned_count));
+			ast_json_object_set(j_tmp, "offset", ast_json_integer_create(al->offset));
+			ast_json_object_set(j_tmp, "first_frame", ast_json_integer_create(al->first_frame));
+			ast_json_object_set(j_tmp, "last_frame", ast_json_integer_create(al->last_frame));
+			ast_json_array_append(j_rows, j_tmp);
+		}
+		ast_json_object_set(j_audio, "frame_count", ast_json_integer_create(frames[i]));
+		ast_json_object_set(j_audio, "neighbours", j_rows);
+		ast_json_array_append(j_res, j_audio);
+	}
+	ast_free(uu);
+	ast_free(scopes);
+	ast_free(counts);
+	ast_free(frames);
+	ast_free(cand);
+	ast_free(align);
+	return ret;
+}
+
+/* j_list (consumed): an array of catalog objects; the array of their neighbour objects, or NULL */
+static struct ast_json* audio_neighbours(struct ast_json* j_list, int32_t scope, const tfp_search_params* p, const int k)
+{
+	const int kk = k > TFP_RANK_MAX ? TFP_RANK_MAX : k;
+	struct ast_json* j_res;
+	size_t n, a;
+
+	if(j_list == NULL) {
+		return NULL;
+	}
+	n = ast_json_array_size(j_list);
+	j_res = ast_json_array_create();
+	for(a = 0; j_res != NULL && a < n; a += FP_NEIGHBOUR_FLUSH) {
+		if(neighbours_flush(j_list, a, n - a < FP_NEIGHBOUR_FLUSH ? n - a : FP_NEIGHBOUR_FLUSH, scope, p, kk, j_res) == false) {
+			ast_json_unref(j_res);
+			j_res = NULL;
+		}
+	}
+	ast_json_unref(j_list);
+	return j_res;
+}
+
+struct ast_json* fp_get_audio_list_neighbours(const char* context, const int coefs, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k)
+{
+	tfp_search_params p;
+
+	if((k < 1) || (search_params(&p, context, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false)) {
+		return NULL;
+	}
+	return audio_neighbours(fp_get_audio_lists_by_contextname(context), scope_of_context(context, false), &p, k);
+}
+
+struct ast_json* fp_get_audio_neighbours(const char* uuid, const int coefs, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k)
+{
+	tfp_search_params p;
+	struct ast_json* j_list;
+	struct ast_json* j_info;
+	struct ast_json* j_res;
+	struct ast_json* j_one = NULL;
+
+	if((k < 1) || (search_params(&p, uuid, coefs, tolerance, freq_ignore_low, freq_ignore_high) == false)) {
+		return NULL;
+	}
+	j_info = fpc_get_audio_list_info(uuid);
+	if(j_info == NULL) {
+		return NULL;
+	}
+	j_list = ast_json_array_create();
+	ast_json_array_append(j_list, j_info);
+	j_res = audio_neighbours(j_list, TFP_SCOPE_ANY, &p, k);
+	if(j_res != NULL && ast_json_array_size(j_res) == 1) {
+		/* the one object rebuilt on its own: j_res is freed with its elements below */
+		struct ast_json* j_src = ast_json_array_get(j_res, 0);
+		struct ast_json* j_rows = ast_json_object_get(j_src, "neighbours");
+		struct ast_json* j_new = ast_json_array_create();
+		size_t r;
+		static const char* const keys[] = {"match_count", "aligned_count", "offset", "first_frame", "last_frame"};
+		j_one = fpc_get_audio_list_info(uuid);
+		for(r = 0; j_one != NULL && r < ast_json_array_size(j_rows); r++) {
+			struct ast_json* j_row = ast_json_array_get(j_rows, r);
+			struct ast_json* j_tmp = fpc_get_audio_list_info(ast_json_string_get(ast_json_object_get(j_row, "uuid")));
+			size_t f;
+			if(j_tmp == NULL) {
+				continue;
+			}
+			for(f = 0; f < sizeof(keys) / sizeof(keys[0]); f++) {
+				ast_json_object_set(j_tmp, keys[f], ast_json_integer_create(ast_json_integer_get(ast_json_object_get(j_row, keys[f]))));
+			}
+			ast_json_array_append(j_new, j_tmp);
+		}
+		if(j_one != NULL) {
+			ast_json_object_set(j_one, "frame_count",
+					ast_json_integer_create(ast_json_integer_get(ast_json_object_get(j_src, "frame_count"))));
+			ast_json_object_set(j_one, "neighbours", j_new);
+		}
+		else {
+			ast_json_unref(j_new);
+		}
+	}
+	ast_json_unref(j_res);
+	return j_one;
 }
 
 void fp_live_reset(fp_live* lv, int channel)

@@ -193,6 +193,23 @@ void fp_channel_close(fp_channel* ch);
  * arguments (window_ms <= 0, max_gap_ms < 0, min_hits < 1 or k < 1 among them).
  * fp_live_reset: a new call on `channel` (< 0: on every channel). */
 typedef struct fp_live fp_live;
+/* New: catalog neighbours, which enrolled audios sound like each other at a set of search parameters. The
+ * MD5 dedup of fp_craete_audio_list_info (src/fp_handler.c:479-530) catches a byte-identical file and
+ * nothing else. fp_get_audio_list_neighbours returns a JSON array with one object per audio of the context
+ * (fp_get_audio_lists_by_contextname's rows, in their order; an audio without fingerprint rows is left out):
+ * its catalog fields, frame_count (its stored rows) and neighbours, the first k rows (at most 32) of the
+ * search of src/fp_handler.c:287-374 for the audio's own stored rows over the same context's audios, its
+ * own row deleted. Each row is the audio's catalog object with match_count, aligned_count, offset,
+ * first_frame and last_frame. One tfp_group_index_neighbours call per 512 audios.
+ * fp_get_audio_neighbours is that object for one audio, over the audios of every context. NULL: bad
+ * arguments (a NULL context or uuid, coefs outside [1,2], k < 1), an unknown uuid, or a failed search. */
+struct ast_json* fp_get_audio_list_neighbours(const char* context, const int coefs, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k);
+struct ast_json* fp_get_audio_neighbours(const char* uuid, const int coefs, const double tolerance,
+		const int freq_ignore_low, const int freq_ignore_high, const int k);
+/* The tfp_group_index_neighbours calls the two entries above have made so far. false before fp_init. */
+bool fp_get_neighbour_stats(int64_t* calls);
+
 fp_live* fp_live_open(int nchannels, int sample_rate, int max_ms);
 bool fp_live_push(fp_live* lv, const int16_t* slin, int tick_samples, const int32_t* nsamples);
 bool fp_live_push_g711(fp_live* lv, const uint8_t* payload, int tick_samples, int law, const int32_t* nsamples);
