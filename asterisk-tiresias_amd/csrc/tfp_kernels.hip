@@ -729,18 +729,26 @@ __device__ __forceinline__ void load_w(const float* __restrict__ w, float4 (&wv)
 #define TFP_ACC(i, a, b)
 #endif
 
+// The undecided lanes of a fused tail (micro_of_coef_fast; about 5 in 10^7 values): the full log. A
+// call, so the tail's straight path carries none of its code or registers.
+__device__ __noinline__ int32_t finish_slow(float c) { return micro_of_db(db_of_coef(c)); }
+
 // kPasses = passes of 4 frames per tile: 4 (16-frame tiles, throughput) or 1 (4-frame tiles, for
 // small batches: 4x the waves on a short query, a quarter of the per-wave latency).
-template <int kPasses>
+// kFused (throughput launches that want no doubles, db == nullptr): the tile tail finishes its
+// micro-units itself with micro_of_coef_fast, and the step is this one launch.
+template <int kPasses, bool kFused = false>
 __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void fingerprint8k_kernel(
     const DspTables* __restrict__ T, const int16_t* __restrict__ pcm, const int64_t* __restrict__ sbeg,
     const int64_t* __restrict__ send, const int64_t* __restrict__ foff, const int32_t* __restrict__ toff,
     const int32_t* __restrict__ tclip, int32_t ntiles, int32_t* __restrict__ micro, double* __restrict__ db,
-    float rare_thr, LogFix fx, int64_t single_ns) {
+    float rare_thr, LogFix fx, int64_t single_ns, double fin_thr) {
+  static_assert(!kFused || kPasses >= 2, "the fused finish belongs to the throughput tile");
   constexpr int LA = 36, LB = 16, LC = 8;  // DspTables::fixed8k()
-  // dB + "%f" in finish_db_kernel for throughput launches (full waves); in the tile tail for small
-  // ones (4-frame tiles, batch-1 latency), which saves a launch
-  constexpr bool kSplitTail = kPasses >= 2;
+  // Throughput launches that hand back doubles (db != nullptr) store float bits and leave dB + "%f"
+  // to finish_db_kernel (the full log on full waves); fused ones finish in the tile tail with the
+  // fast exact finish; small ones (4-frame tiles, batch-1 latency) run the full log in the tail.
+  constexpr bool kSplitTail = kPasses >= 2 && !kFused;
 #ifdef TFP_STAMPS
   const uint64_t t_entry = __builtin_amdgcn_s_memtime();
 #endif
@@ -751,6 +759,7 @@ __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void
   using WaveT = WaveLds8;
   __shared__ __attribute__((aligned(16))) LdsTables S;
   __shared__ __attribute__((aligned(16))) WaveT WL[kBW];
+  __shared__ __attribute__((aligned(16))) FinEntry FT[kFused ? 128 : 1];  // micro_of_coef_fast's table
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, grp = lane >> 4, L = lane & 15;
@@ -886,6 +895,8 @@ __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void
   const int i3 = ts < 3 ? ts : 2;
   const int msl = T->ms_len[i3], mso = T->ms_woff[i3];
   const LogfEntry lge = logf_table()[ts & 15];
+  FinEntry fte;
+  if constexpr (kFused) fte = fin_table()[ts & 127];
   float mw[(kMsW + kStage - 1) / kStage];
 #pragma unroll
   for (int r = 0; r < (kMsW + kStage - 1) / kStage; r++) {
@@ -917,6 +928,9 @@ __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void
   if (tid < 3) { S.ms_len[tid] = msl; S.ms_woff[tid] = mso; }
   if (tid < 16) S.logf[tid] = lge;
   if (kPairFb && tid < kLogf2Entries) S.logf2[tid] = logf2_entry(tid, logf_table());
+  if constexpr (kFused) {
+    if (tid < 128) FT[tid] = fte;
+  }
   if (tid == 0) { S.c_defer = T->ms_c_defer; S.c_real[0] = T->ms_c_real[0]; S.c_real[1] = T->ms_c_real[1]; }
 #pragma unroll
     for (int r = 0; r < (kMsW + kStage - 1) / kStage; r++) {
@@ -975,6 +989,12 @@ __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void
       fbc[k] = fblog + T->fb_filter[L][k];
       fbk[k] = T->fb_new[L][k] ? 0.f : 1.f;
     }
+  }
+  // (fused) the tail's DCT terms of the empty filters kFbNf .. kFilters - 1, the same in every tile
+  float lemp[kFilters - kFbNf];
+  if constexpr (kFused) {
+#pragma unroll
+    for (int i = kFbNf; i < kFilters; i++) lemp[i - kFbNf] = lempty * S.dct[lane & 1][i];
   }
 
 #ifdef TFP_STAMPS
@@ -1300,15 +1320,25 @@ __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void
 #pragma unroll
           for (int i = 0; i < kFbNf; i++) acc = acc + prow[2 * i];
 #pragma unroll
-          for (int i = kFbNf; i < kFilters; i++) acc = acc + lempty * S.dct[cfi][i];
+          for (int i = kFbNf; i < kFilters; i++) {
+            if constexpr (kFused) acc = acc + lemp[i - kFbNf];
+            else acc = acc + lempty * S.dct[cfi][i];
+          }
         } else {
           const float* lrow = M.logs + row * kLogStride;
 #pragma unroll 8
           for (int i = 0; i < kFilters; i++) acc = acc + lrow[i] * S.dct[cfi][i];
         }
         const int64_t g = (single_ns >= 0 ? 0 : foff[cur.c]) + f;
-        if constexpr (kSplitTail) {
-          micro[2 * g + cfi] = __builtin_bit_cast(int32_t, acc);  // finish_db_kernel: dB + "%f" on full waves
+        if constexpr (kFused) {
+          bool und;
+          int32_t mv = micro_of_coef_fast(acc, &und, FT, fin_thr);
+          if (__builtin_expect(__any(und), 0)) {  // wave-uniform; about 3 tiles in 10^5
+            if (und) mv = finish_slow(acc);
+          }
+          micro[2 * g + cfi] = mv;
+        } else if constexpr (kSplitTail) {
+          micro[2 * g + cfi] = __builtin_bit_cast(int32_t, acc);  // float bits: finish_db_kernel takes the log
         } else {
           const double q = db ? db_of_coef(acc, fx) : db_of_coef(acc);  // frame values glibc-exact
           micro[2 * g + cfi] = micro_of_db(q);
@@ -1331,8 +1361,9 @@ __global__ __launch_bounds__(64 * fp8_block_waves<kPasses>(), TFP_FP_WAVES) void
 }
 
 // 10*log10|c| (fp_handler.c:651) and "%f" micro-units / NULL (db_ctx_handler.c:479-481) of every
-// coefficient fingerprint8k_kernel stored (as float bits) in micro[], in place, on full waves: the
-// kernel's tile tail would run this double-precision work on 32 of 64 lanes.
+// coefficient the unfused fingerprint8k_kernel stored (as float bits) in micro[], in place, on full
+// waves, for launches that hand back the glibc-exact doubles (db != nullptr): the kernel's tile tail
+// would run the full log on 32 of 64 lanes. (Launches without db finish in the tile tail.)
 __global__ void finish_db_kernel(int32_t* __restrict__ micro, double* __restrict__ db, int64_t nvals, LogFix fx) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvals; i += (int64_t)gridDim.x * blockDim.x) {
     const float c = __builtin_bit_cast(float, micro[i]);
@@ -1375,7 +1406,8 @@ hipError_t fp_launch_config(int device, FpLaunchCfg* cfg) {
   hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   if (e != hipSuccess) return e;
   auto cap = [&](const void* k, int waves = kBlockWaves) { return cus * resident_blocks(k, waves); };
-  cfg->grid_cap_8k = cap(reinterpret_cast<const void*>(fingerprint8k_kernel<kTile8k / 4>), kBW8);
+  cfg->grid_cap_8k = cap(reinterpret_cast<const void*>(fingerprint8k_kernel<kTile8k / 4, true>), kBW8);
+  cfg->grid_cap_8k_db = cap(reinterpret_cast<const void*>(fingerprint8k_kernel<kTile8k / 4>), kBW8);
   cfg->grid_cap_8k_small = cap(reinterpret_cast<const void*>(fingerprint8k_kernel<1>));
   cfg->grid_cap_generic = cap(reinterpret_cast<const void*>(fingerprint_kernel<int16_t>));
   cfg->grid_cap_f32 = cap(reinterpret_cast<const void*>(fingerprint_kernel<float>));
@@ -1399,6 +1431,7 @@ hipError_t fp_launch_config(int device, FpLaunchCfg* cfg) {
   if (const char* b = knob("TFP_FP_BLOCKS_PER_CU")) {
     const int n = atoi(b);
     if (n > 0 && cus * n < cfg->grid_cap_8k) cfg->grid_cap_8k = cus * n;
+    if (n > 0 && cus * n < cfg->grid_cap_8k_db) cfg->grid_cap_8k_db = cus * n;
   }
   const char* g = knob("TFP_GENERIC");
   cfg->force_generic = g && atoi(g);
@@ -1406,6 +1439,10 @@ hipError_t fp_launch_config(int device, FpLaunchCfg* cfg) {
   int rl = rt ? atoi(rt) : -98;
   rl = rl < -98 ? -98 : (rl > 100 ? 100 : rl);  // any threshold >= 2^-98 gives the same, exact, result
   cfg->rare_thr = ldexpf(1.f, rl);
+  const char* fm = knob("TFP_FINISH_MARGIN_LOG2");
+  int ml = fm ? atoi(fm) : -22;
+  ml = ml < -22 ? -22 : (ml > 0 ? 0 : ml);  // any margin >= kFinMargin gives the same, exact, result
+  cfg->fin_thr = 0.5 - ldexp(1.0, ml);     // (0: every finite non-zero value takes the tail's slow branch)
   return hipSuccess;
 }
 
@@ -1417,7 +1454,9 @@ hipError_t launch_fingerprint(const FpLaunchCfg& cfg, const DspTables* d_tables,
   const bool v8 = fixed8k && (tile_frames == 4 || !cfg.force_generic);
   if (v8 ? !(tile_frames == 4 || tile_frames == kTile8k) : tile_frames != kFramesPerBlock) return hipErrorInvalidValue;
   if (ntiles <= 0) return hipSuccess;
-  const int cap = v8 ? (tile_frames == 4 ? cfg.grid_cap_8k_small : cfg.grid_cap_8k) : cfg.grid_cap_generic;
+  const bool fused = d_db == nullptr;  // (throughput launch) no doubles wanted: finished in the tile tail
+  const int cap = v8 ? (tile_frames == 4 ? cfg.grid_cap_8k_small : fused ? cfg.grid_cap_8k : cfg.grid_cap_8k_db)
+                     : cfg.grid_cap_generic;
   if (cap <= 0) return hipErrorInvalidValue;
   const int bw = (v8 && tile_frames != 4) ? kBW8 : kBlockWaves;
   const int want = (ntiles + bw - 1) / bw;  // one tile per wave per step
@@ -1425,11 +1464,16 @@ hipError_t launch_fingerprint(const FpLaunchCfg& cfg, const DspTables* d_tables,
   if (v8) {
     if (tile_frames == 4) {  // fingerprint8k_kernel<1> finishes its own tail
       hipLaunchKernelGGL(fingerprint8k_kernel<1>, dim3(grid), dim3(kBlockThreads), 0, s, d_tables, d_pcm, d_sbeg, d_send,
-                         d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, cfg.rare_thr, fx, single_ns);
+                         d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, cfg.rare_thr, fx, single_ns, cfg.fin_thr);
       if (stats) stats->small8k++;
+    } else if (fused) {  // one launch: dB + "%f" in the tile tail
+      hipLaunchKernelGGL((fingerprint8k_kernel<kTile8k / 4, true>), dim3(grid), dim3(64 * kBW8), 0, s, d_tables, d_pcm,
+                         d_sbeg, d_send, d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, cfg.rare_thr, fx, single_ns,
+                         cfg.fin_thr);
+      if (stats) stats->throughput8k++;
     } else {
       hipLaunchKernelGGL(fingerprint8k_kernel<kTile8k / 4>, dim3(grid), dim3(64 * kBW8), 0, s, d_tables, d_pcm, d_sbeg,
-                         d_send, d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, cfg.rare_thr, fx, single_ns);
+                         d_send, d_foff, d_toff, d_tclip, ntiles, d_micro, d_db, cfg.rare_thr, fx, single_ns, cfg.fin_thr);
       if (stats) stats->throughput8k++;
       // (each HIP call overwrites the last error: a failed launch must be caught before the next one)
       if (const hipError_t le = hipGetLastError(); le != hipSuccess) return le;

@@ -115,18 +115,20 @@ struct SynthSpecDev {
 // Per-engine launch configuration: read once when the engine is created (fp_launch_config),
 // grid caps from the engine's own device.
 struct FpLaunchCfg {
-  int32_t grid_cap_8k = 0;       // resident blocks of fingerprint8k_kernel (kTile8k-frame tiles) on the device
+  int32_t grid_cap_8k = 0;       // resident blocks of fingerprint8k_kernel (kTile8k-frame tiles, fused finish) on the device
+  int32_t grid_cap_8k_db = 0;    // ... of its form that leaves the finish to finish_db_kernel (launches with d_db)
   int32_t grid_cap_8k_small = 0; // ... of its 4-frame-tile form (small batches)
   int32_t grid_cap_generic = 0;  // resident blocks of fingerprint_kernel<int16_t>
   int32_t grid_cap_f32 = 0;      // resident blocks of fingerprint_kernel<float>
   bool force_generic = false;    // TFP_GENERIC=1: the generic kernel at 8 kHz too (tests)
   float rare_thr = 0x1p-98f;     // TFP_RARE_THR_LOG2=n: bins with 0 < |S|^2 < 2^n take the spec-order path (tests)
+  double fin_thr = kFinThr;      // TFP_FINISH_MARGIN_LOG2=n: the fused tail's margin 2^n micro-units, thr = 1/2 - 2^n (tests)
 };
 // Launches issued so far per fingerprint kernel (tfp_fingerprint_stats): counted by launch_fingerprint /
 // launch_fingerprint_f32 in the branch that issues the kernel, so the count is what ran.
 struct FpLaunchStats {
   int64_t small8k = 0;       // fingerprint8k_kernel<1> (4-frame tiles)
-  int64_t throughput8k = 0;  // fingerprint8k_kernel<kTile8k / 4> + finish_db_kernel
+  int64_t throughput8k = 0;  // fingerprint8k_kernel<kTile8k / 4>: fused finish, or (with d_db) + finish_db_kernel
   int64_t generic_i16 = 0;   // fingerprint_kernel<int16_t>
   int64_t generic_f32 = 0;   // fingerprint_kernel<float>
 };

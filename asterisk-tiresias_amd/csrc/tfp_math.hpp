@@ -292,4 +292,144 @@ TFP_HD int32_t micro_of_db(double q) {
   return (int32_t)fmt6(q);
 }
 
+// ---------------------------------------------------------------------------------------
+// Fast exact finish: micro_of_db(10 * log10|c|) of a float coefficient without the full log.
+// The stored value is an integer of micro-units, so 10 log10|c| is needed to full precision only
+// when it lies next to a rounding boundary of the 10^-6 grid. micro_of_coef_fast() computes
+//   q~ = e K + l10c[i] + P(r),   |c| = 2^e m, m in [1, 2), i = the top 7 mantissa bits,
+//   r = m invc[i] - 1,  l10c[i] = -10 log10(invc[i]),  P(r) ~ 10 log10(1 + r),
+// then p = q~ 10^6, n = rint(p), and decides n when |p - n| < 1/2 - kFinMargin; otherwise it
+// reports the value undecided and the caller runs micro_of_db(db_of_coef(c)).
+//
+// Error of q~ against the true 10 log10|c| (normal floats: |e| <= 127, |q| < 2^9):
+//   r      exact: invc has 24 significant bits, so m invc (48 bits) and m invc - 1 are doubles;
+//          |r| <= 2^-8 + 2^-23 (the bucket's half width over its centre, plus invc's rounding).
+//   l10c   the correctly rounded double of -10 log10 of the rounded invc, < 3.02: <= 2^-53.
+//   P      degree-6 Taylor of (10 / ln 10) log(1 + r): truncation <= 4.35 |r|^7 / (7 (1 - |r|))
+//          < 2^-56.5; Horner's roundings (each <= 2^-53 of a partial sum < 4.4, then times
+//          |r| <= 2^-8) and the last product's < 2^-57; coefficient rounding < 2^-58: < 2^-55.
+//   e K    K = K_HI + K_LO with K_HI of 45 bits: e K_HI is exact; K_HI + K_LO is 10 log10(2) to
+//          2^-97, times 127; t1 = fma(e, K_LO, l10c) and t2 = t1 + P round at < 4: 2 * 2^-52.
+//   q~     = fma(e, K_HI, t2) rounds at < 2^9: <= 2^-45 (the dominant term).
+//   total  < 2^-45 + 2^-51 + 2^-53 + 2^-55 < 1.02 * 2^-45 = 2.9e-14, i.e. 2.9e-8 micro-units.
+// p = q~ 10^6 rounds at < 2^29: <= 2^-25 = 3.0e-8 micro-units. p - n is exact.
+// glibc's own value q_g = 10.0 * log10(x) against the true one (e_log10.c: z = y log10_2lo +
+// ivln10 log(m'); v = z + y log10_2hi, m' in [0.5, 2)): log(m') within 1 ulp <= 2^-53; ivln10
+// log(m') (ivln10 to 2^-55, the product rounded at < 0.31) < 2^-53.3; z rounds at < 0.31:
+// 2^-55; y log10_2hi is exact (40 x 8 bits); v rounds at < 2^6: 2^-48; so |v - log10 x| <
+// 2^-47.95, and q_g = 10 v rounds at < 2^9: 2^-45; |q_g - q| < 10 * 2^-47.95 + 2^-45 < 6.6e-14,
+// i.e. 6.6e-8 micro-units.
+// So |p - 10^6 q_g| < 2.9e-8 + 3.0e-8 + 6.6e-8 = 1.25e-7 < kFinMargin = 2^-22 = 2.38e-7. When
+// |p - n| < 1/2 - kFinMargin, the exact 10^6 q_g lies strictly inside (n - 1/2, n + 1/2), and
+// fmt6(q_g) = n: no tie, no dependence on glibc's last bits. Checked against glibc over all 2^32
+// bit patterns (tests/native/check_micro_fast.cpp; log under profiles/). A value is undecided
+// with probability 2 kFinMargin = 4.8e-7.
+// Zeros, infinities and NaNs give kNullMicro (log10 is -inf, +inf, NaN: micro_of_db's NULL) from
+// the bit pattern alone; subnormals are reported undecided.
+struct FinEntry { double invc, l10c; };
+constexpr double kFinMargin = 0x1p-22;             // micro-units
+constexpr double kFinThr = 0.5 - kFinMargin;       // decided iff |p - rint(p)| < thr (exact)
+#if defined(__HIPCC__) || defined(__HIP__)
+__host__ __device__
+#endif
+inline const FinEntry* fin_table() {
+  // scripts/gen_fin_table.py
+  static constexpr FinEntry T[128] = {
+      {0x1.fe01fe0000000p-1, 0x1.156832e30da53p-6}, {0x1.fa11ca0000000p-1, 0x1.9e7fd7c55e623p-5},
+      {0x1.f6310a0000000p-1, 0x1.58162d40b97dep-4}, {0x1.f25f640000000p-1, 0x1.dfe0ed39f1e47p-4},
+      {0x1.ee9c800000000p-1, 0x1.335224efb067cp-3}, {0x1.eae8080000000p-1, 0x1.7632307771537p-3},
+      {0x1.e741aa0000000p-1, 0x1.b892826586226p-3}, {0x1.e3a9180000000p-1, 0x1.fa74dbdcccda9p-3},
+      {0x1.e01e020000000p-1, 0x1.1deda15a5edcbp-2}, {0x1.dca01e0000000p-1, 0x1.3e63b6ed6b043p-2},
+      {0x1.d92f220000000p-1, 0x1.5e9d992a97c67p-2}, {0x1.d5cac80000000p-1, 0x1.7e9c1be8e9f4bp-2},
+      {0x1.d272ca0000000p-1, 0x1.9e60213ea9aedp-2}, {0x1.cf26e60000000p-1, 0x1.bdea733b7a662p-2},
+      {0x1.cbe6da0000000p-1, 0x1.dd3be95c238fcp-2}, {0x1.c8b2660000000p-1, 0x1.fc555531014b4p-2},
+      {0x1.c5894e0000000p-1, 0x1.0d9bb71970a54p-1}, {0x1.c26b540000000p-1, 0x1.1cf185e18bf34p-1},
+      {0x1.bf583e0000000p-1, 0x1.2c2c75282d466p-1}, {0x1.bc4fd60000000p-1, 0x1.3b4cd50ba1060p-1},
+      {0x1.b951e20000000p-1, 0x1.4a530f3fc3f47p-1}, {0x1.b65e2e0000000p-1, 0x1.593f750f5f56fp-1},
+      {0x1.b374840000000p-1, 0x1.6812673e01d0ep-1}, {0x1.b094b40000000p-1, 0x1.76cc2d4bc0c3fp-1},
+      {0x1.adbe880000000p-1, 0x1.856d32939d748p-1}, {0x1.aaf1d20000000p-1, 0x1.93f5be7187247p-1},
+      {0x1.a82e660000000p-1, 0x1.a2661265c70aep-1}, {0x1.a574100000000p-1, 0x1.b0be9e8b61fdep-1},
+      {0x1.a2c2a80000000p-1, 0x1.beff98cb092f1p-1}, {0x1.a01a020000000p-1, 0x1.cd29505c669b8p-1},
+      {0x1.9d79f20000000p-1, 0x1.db3c18faabaf5p-1}, {0x1.9ae24e0000000p-1, 0x1.e938401b283bcp-1},
+      {0x1.9852f00000000p-1, 0x1.f71e01bb5b478p-1}, {0x1.95cbb00000000p-1, 0x1.0276d44e55ee6p+0},
+      {0x1.934c680000000p-1, 0x1.0953bc4afda64p+0}, {0x1.90d4f20000000p-1, 0x1.1025dcaeacebfp+0},
+      {0x1.8e65280000000p-1, 0x1.16ed5b4806afbp+0}, {0x1.8bfce80000000p-1, 0x1.1daa54a22568ep+0},
+      {0x1.899c100000000p-1, 0x1.245ce6fdec20bp+0}, {0x1.87427c0000000p-1, 0x1.2b05380492b06p+0},
+      {0x1.84f00c0000000p-1, 0x1.31a363cfe97f2p+0}, {0x1.82a4a00000000p-1, 0x1.38378817745afp+0},
+      {0x1.8060180000000p-1, 0x1.3ec1c433c3033p+0}, {0x1.7e22560000000p-1, 0x1.454233500f5a0p+0},
+      {0x1.7beb3a0000000p-1, 0x1.4bb8f7f69887bp+0}, {0x1.79baa60000000p-1, 0x1.522630791ff9fp+0},
+      {0x1.7790820000000p-1, 0x1.5889eaf114c56p+0}, {0x1.756cac0000000p-1, 0x1.5ee454632ab89p+0},
+      {0x1.734f0c0000000p-1, 0x1.65357db8b662fp+0}, {0x1.7137860000000p-1, 0x1.6b7d851179863p+0},
+      {0x1.6f26020000000p-1, 0x1.71bc7de36c150p+0}, {0x1.6d1a620000000p-1, 0x1.77f28f1a0a259p+0},
+      {0x1.6b14900000000p-1, 0x1.7e1fc8bc801a2p+0}, {0x1.6914740000000p-1, 0x1.8444420cd482dp+0},
+      {0x1.6719f40000000p-1, 0x1.8a6019b5b4b00p+0}, {0x1.6524f80000000p-1, 0x1.9073698477f5ap+0},
+      {0x1.63356c0000000p-1, 0x1.967e3ffd63d1dp+0}, {0x1.614b360000000p-1, 0x1.9c80bf7f282a9p+0},
+      {0x1.5f66440000000p-1, 0x1.a27af27bdaceep+0}, {0x1.5d867c0000000p-1, 0x1.a86cfdb226461p+0},
+      {0x1.5babcc0000000p-1, 0x1.ae56edb2b2247p+0}, {0x1.59d6200000000p-1, 0x1.b438d65a41ed1p+0},
+      {0x1.5805600000000p-1, 0x1.ba12d975b48a8p+0}, {0x1.56397c0000000p-1, 0x1.bfe5001ea5306p+0},
+      {0x1.54725e0000000p-1, 0x1.c5af67c7bef85p+0}, {0x1.52aff60000000p-1, 0x1.cb721b5c78451p+0},
+      {0x1.50f22e0000000p-1, 0x1.d12d3a58ef232p+0}, {0x1.4f38f60000000p-1, 0x1.d6e0d18152b87p+0},
+      {0x1.4d843c0000000p-1, 0x1.dc8cf50c5686ap+0}, {0x1.4bd3ee0000000p-1, 0x1.e231ba1cc050bp+0},
+      {0x1.4a27fa0000000p-1, 0x1.e7cf36c2f45f2p+0}, {0x1.4880520000000p-1, 0x1.ed657474cc47bp+0},
+      {0x1.46dce40000000p-1, 0x1.f2f48aee491c9p+0}, {0x1.453d9e0000000p-1, 0x1.f87c92dd74abdp+0},
+      {0x1.43a2740000000p-1, 0x1.fdfd91471a2dfp+0}, {0x1.420b520000000p-1, 0x1.01bbd3ad73423p+1},
+      {0x1.40782e0000000p-1, 0x1.04756a5809cc9p+1}, {0x1.3ee8f40000000p-1, 0x1.072b9e1387f5cp+1},
+      {0x1.3d5d9a0000000p-1, 0x1.09de6f59c6068p+1}, {0x1.3bd60e0000000p-1, 0x1.0c8decf0bbc8dp+1},
+      {0x1.3a52440000000p-1, 0x1.0f3a1b7f6fc4ep+1}, {0x1.38d22e0000000p-1, 0x1.11e30384cc624p+1},
+      {0x1.3755be0000000p-1, 0x1.1488addbb9786p+1}, {0x1.35dce60000000p-1, 0x1.172b23bbac056p+1},
+      {0x1.34679a0000000p-1, 0x1.19ca6b1e5250ep+1}, {0x1.32f5ce0000000p-1, 0x1.1c668a499df32p+1},
+      {0x1.3187760000000p-1, 0x1.1eff87d049ae6p+1}, {0x1.301c820000000p-1, 0x1.219571e22b4dfp+1},
+      {0x1.2eb4ea0000000p-1, 0x1.2428486ea5062p+1}, {0x1.2d50a00000000p-1, 0x1.26b816a268838p+1},
+      {0x1.2bef980000000p-1, 0x1.2944e45559daep+1}, {0x1.2a91ca0000000p-1, 0x1.2bceb23c08e97p+1},
+      {0x1.2937260000000p-1, 0x1.2e55902e6f18ap+1}, {0x1.27dfa40000000p-1, 0x1.30d97f6f8a42dp+1},
+      {0x1.268b380000000p-1, 0x1.335a88fcc4d58p+1}, {0x1.2539d80000000p-1, 0x1.35d8b259deaf6p+1},
+      {0x1.23eb7a0000000p-1, 0x1.3854014a9e27ep+1}, {0x1.22a0120000000p-1, 0x1.3acc7fa68d7e9p+1},
+      {0x1.2157980000000p-1, 0x1.3d422fe80f84cp+1}, {0x1.2012020000000p-1, 0x1.3fb51895645e8p+1},
+      {0x1.1ecf440000000p-1, 0x1.42254456c1ac6p+1}, {0x1.1d8f560000000p-1, 0x1.4492b65e4a89dp+1},
+      {0x1.1c52300000000p-1, 0x1.46fd720f17927p+1}, {0x1.1b17c60000000p-1, 0x1.496582d85a773p+1},
+      {0x1.19e0120000000p-1, 0x1.4bcae8a87894cp+1}, {0x1.18ab080000000p-1, 0x1.4e2daf70b4657p+1},
+      {0x1.1778a20000000p-1, 0x1.508dd78821b1ep+1}, {0x1.1648d60000000p-1, 0x1.52eb6964a5658p+1},
+      {0x1.151b9a0000000p-1, 0x1.55466dc07eab5p+1}, {0x1.13f0e80000000p-1, 0x1.579ee58bb0d35p+1},
+      {0x1.12c8b80000000p-1, 0x1.59f4d5e44424dp+1}, {0x1.11a3020000000p-1, 0x1.5c48441c26e13p+1},
+      {0x1.107fbc0000000p-1, 0x1.5e9939cdf2b90p+1}, {0x1.0f5ee00000000p-1, 0x1.60e7b8a87698ep+1},
+      {0x1.0e40660000000p-1, 0x1.6333c69b0ebccp+1}, {0x1.0d24460000000p-1, 0x1.657d69ca2055dp+1},
+      {0x1.0c0a780000000p-1, 0x1.67c4a88f5e97cp+1}, {0x1.0af2f80000000p-1, 0x1.6a098125ab909p+1},
+      {0x1.09ddba0000000p-1, 0x1.6c4c0295239bap+1}, {0x1.08cabc0000000p-1, 0x1.6e8c2740515a0p+1},
+      {0x1.07b9f20000000p-1, 0x1.70c9fea01234ep+1}, {0x1.06ab5a0000000p-1, 0x1.7305835cc1db7p+1},
+      {0x1.059eea0000000p-1, 0x1.753ec1210fc73p+1}, {0x1.04949c0000000p-1, 0x1.7775bb5796076p+1},
+      {0x1.038c6c0000000p-1, 0x1.79aa71483df15p+1}, {0x1.0286500000000p-1, 0x1.7bdcef3681af8p+1},
+      {0x1.0182440000000p-1, 0x1.7e0d34bb1c4c5p+1}, {0x1.0080400000000p-1, 0x1.803b4a2f38bd8p+1},
+  };
+  return T;
+}
+
+// T: the 128-entry table (device code passes a copy staged in LDS). thr: kFinThr, or less (tests:
+// thr <= 0 leaves every finite non-zero value undecided). *undecided is always written.
+TFP_HD int32_t micro_of_coef_fast(float c, bool* undecided, const FinEntry* T = fin_table(), double thr = kFinThr) {
+  const double K_HI = 0x1.8151824c75800p+1, K_LO = 0x1.fabf59b5d80b8p-45;  // 10 log10(2)
+  const double A1 = 0x1.15f2ced384f29p+2, A2 = -0x1.15f2ced384f29p+1, A3 = 0x1.729913c4b1436p+0;
+  const double A4 = -0x1.15f2ced384f29p+0, A5 = 0x1.bcb7b1526e50ep-1, A6 = -0x1.729913c4b1436p-1;
+  const uint32_t ix = f2u(c) & 0x7fffffffu;
+  const uint32_t be = ix >> 23;
+  const bool null = ix == 0 || be == 255;  // +-0, +-inf, NaN
+  const uint32_t mant = ix & 0x7fffffu;
+  const FinEntry t = T[mant >> 16];
+  const double m = u2d(0x3ff0000000000000ull | ((uint64_t)mant << 29));
+  const double e = (double)((int32_t)be - 127);
+  const double r = __builtin_fma(m, t.invc, -1.0);
+  double P = __builtin_fma(A6, r, A5);
+  P = __builtin_fma(P, r, A4);
+  P = __builtin_fma(P, r, A3);
+  P = __builtin_fma(P, r, A2);
+  P = __builtin_fma(P, r, A1);
+  P = P * r;
+  const double t1 = __builtin_fma(e, K_LO, t.l10c);
+  const double q = __builtin_fma(e, K_HI, t1 + P);
+  const double p = q * 1e6;
+  const double n = __builtin_rint(p);
+  const double d = p - n;
+  *undecided = !null && !(be != 0 && (d < 0.0 ? -d : d) < thr);
+  return null ? kNullMicro : (int32_t)n;
+}
+
 }  // namespace tfp
