@@ -193,11 +193,24 @@ int tfp_g711_stats(tfp_engine* eng, int64_t* expand_launches, int64_t* stream_la
 
 /* Device-resident batches (inputs already in HBM; used by the benchmark and by callers that
  * keep PCM on the GPU). A plan uploads the clip layout once. d_micro receives 2 int32 per
- * frame (m1, m2), d_db 2 doubles per frame (q1, q2) or may be NULL. stream: hipStream_t or
- * NULL for the engine's stream; a NULL-stream call (here and in every device form below) is
- * ordered after the work queued on the HIP null stream before it and before the null stream's
- * later work (the null stream is torch's default stream; the engine's stream is non-blocking).
- * Asynchronous: returns after the launch. */
+ * frame (m1, m2), d_db 2 doubles per frame (q1, q2) or may be NULL.
+ *
+ * The stream contract of the five device forms (tfp_fingerprint_device, tfp_index_add_device,
+ * tfp_search_device, tfp_search_q_device, tfp_synth_pcm_device; tests/test_gpu_stream_order.py):
+ * - stream == NULL: the work runs on the engine's own, non-blocking stream, ordered after the work
+ *   queued on the HIP null stream before the call and before the work queued on it after the call
+ *   returns (the null stream is torch's default stream). Only the null stream is ordered: no other
+ *   stream of the caller's is waited for.
+ * - stream != NULL (a hipStream_t): every kernel and copy that reads the caller's device inputs
+ *   or writes the caller's device outputs is queued on that stream, behind its earlier work. (The
+ *   engine's own small uploads, the clip layout or the synth specs, go through its own stream and
+ *   are waited for on the host before the launch that reads them.)
+ * - tfp_fingerprint_device returns after its launch, without waiting: its outputs are ready to
+ *   later work on the same stream (stream == NULL: on the null stream), or after tfp_synchronize.
+ * - The other four wait on the host for the work they queued before they return (a
+ *   tfp_index_add_device of no frames queues none): their outputs are complete on return.
+ * Work on two streams that share one of HIP's hardware queues runs in submission order, whatever
+ * the contract leaves unordered. */
 int tfp_plan_create(tfp_engine* eng, const int64_t* offsets, int32_t nclips, int32_t sample_rate,
                     tfp_plan** out);
 void tfp_plan_destroy(tfp_plan* plan);

@@ -1,5 +1,6 @@
 """Device-resident paths (inputs already in HBM): plan + tfp_fingerprint_device,
 tfp_index_add_device, tfp_search_device, tfp_synth_pcm_device — equal to the host paths."""
+# (current_stream().cuda_stream is 0 here: these calls take the stream == NULL branch; test_gpu_stream_order.py pins its ordering)
 import numpy as np
 import pytest
 
