@@ -26,6 +26,7 @@
 #include "tfp_align.hpp"
 #include "tfp_coalesce.hpp"
 #include "tfp_g711.hpp"
+#include "tfp_resample.hpp"
 #include "tfp_index.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
@@ -335,6 +336,15 @@ struct tfp_engine {
   int64_t n_trace_batches = 0, n_traces = 0;
   DevBuf g711_codes;  // a large G.711 batch's codes, expanded into pcm
   int64_t n_g711_expand = 0, n_g711_stream = 0, n_g711_codes = 0;  // tfp_g711_stats
+  // rate-normalised ingest (tfp_resample.hpp): the tables by (M, L) with their device copies, kept for
+  // the engine's lifetime as the rate tables are; a large batch's input samples, converted into pcm
+  struct RsTable {
+    std::shared_ptr<const ResampleTable> host;
+    DevBuf dev;
+  };
+  std::map<std::pair<int32_t, int32_t>, RsTable> rs_tables;
+  DevBuf rs_in;
+  int64_t n_rs_launch = 0, n_rs_in = 0, n_rs_out = 0;  // tfp_resample_stats
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   FpLaunchStats fpstats;  // fingerprint launches so far per kernel (tfp_fingerprint_stats)
@@ -512,6 +522,16 @@ struct G711Src {
   int32_t law;
 };
 
+// A batch of int16 clips at another rate laid end to end (clip c = the samples [in_off[c], in_off[c + 1])
+// of pcm, in_off[0] = 0), and the table that brings them to the call's rate. The call's lens are the
+// output lengths (resample_count of the input lengths).
+struct RateSrc {
+  const int16_t* pcm;
+  std::vector<int64_t> in_off;
+  const ResampleTable* tab;
+  const int16_t* d_taps;
+};
+
 // Fingerprint host samples (int16 PCM, or with f32 the fp32 values aubio_source produced):
 // clip c is the lens[c] samples at ptrs[c] (the clips may lie anywhere: a coalesced batch gathers
 // the queries of several callers); leaves micro/db on the device in e->micro / e->db.
@@ -520,11 +540,15 @@ struct G711Src {
 // g711: the clips are G.711 codes laid end to end at g711->codes (ptrs is not read). The codes go to
 // the device at one byte per sample and g711_expand_kernel writes their int16 into e->pcm; from
 // there on (layout, tile choice, launch) the call is the int16 call of the same lengths.
+// rate: the clips are int16 at another rate laid end to end at rate->pcm (ptrs is not read) and lens
+// are their lengths at sr. The samples go to the device as they are and resample_kernel writes their
+// conversion into e->pcm; the layout, tile choice and launch are the int16 call's of lens.
 int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens, bool f32, int32_t nclips, int32_t sr,
                      int64_t* nframes_out, std::vector<int64_t>* foff_out, bool exact_q = true,
-                     const G711Src* g711 = nullptr) {
+                     const G711Src* g711 = nullptr, const RateSrc* rate = nullptr) {
   const size_t ss = f32 ? sizeof(float) : sizeof(int16_t);
   const size_t hs = g711 ? sizeof(uint8_t) : ss;  // bytes per sample as the host hands them over
+  const bool flat = g711 || rate;                 // one flat source array in front of e->pcm
   const DspTables* T;
   bool fx = false;
   int rc = ensure_tables(e, sr, &T, &fx);
@@ -561,11 +585,12 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
   int64_t ns = 0;
   for (int32_t c = 0; c < nclips; c++) {
     ns += lens[c];
-    if (!g711 && c + 1 < nclips && static_cast<const char*>(ptrs[c]) + ss * lens[c] != ptrs[c + 1]) contiguous = false;
+    if (!flat && c + 1 < nclips && static_cast<const char*>(ptrs[c]) + ss * lens[c] != ptrs[c + 1]) contiguous = false;
   }
+  const int64_t n_src = rate ? rate->in_off[nclips] : ns;  // samples the host hands over
   std::vector<int64_t> sbeg(nclips + 1, 0), send(nclips + 1, 0);
   const char* base_dev = nullptr;
-  bool in_place = !g711 && ns > 0 && (small || !contiguous);
+  bool in_place = !flat && ns > 0 && (small || !contiguous);
   if (in_place) {
     std::vector<const char*> dv(nclips, nullptr);
     for (int32_t c = 0; c < nclips && in_place; c++) {
@@ -588,20 +613,32 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     }
   }
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_pcm = in_place ? 0 : al(hs * ns), b_sb = al(sizeof(int64_t) * nclips),
+  // the resample launch's own layout, after the fingerprint launch's: the input offsets, the output
+  // offsets (sbeg, all nclips + 1 of them) and the tiles of kRsTile outputs
+  std::vector<int32_t> rs_toff, rs_tclip;
+  if (rate) resample_tiles(sbeg.data(), nclips, &rs_toff, &rs_tclip);
+  const size_t b_pcm = in_place ? 0 : al(hs * n_src), b_sb = al(sizeof(int64_t) * nclips),
                b_fo = al(sizeof(int64_t) * foff.size()), b_to = al(sizeof(int32_t) * toff.size()),
                b_tc = al(sizeof(int32_t) * tclip.size());
-  const size_t lay = 2 * b_sb + b_fo + b_to + b_tc, total = b_pcm + lay;
+  const size_t b_ro = rate ? al(sizeof(int64_t) * (nclips + 1)) : 0, b_rt = rate ? al(sizeof(int32_t) * rs_toff.size()) : 0,
+               b_rc = rate ? al(sizeof(int32_t) * rs_tclip.size()) : 0;
+  const size_t lay_fp = 2 * b_sb + b_fo + b_to + b_tc, lay = lay_fp + 2 * b_ro + b_rt + b_rc, total = b_pcm + lay;
   auto pack_layout = [&](char* h) {
     memcpy(h, sbeg.data(), sizeof(int64_t) * nclips);
     memcpy(h + b_sb, send.data(), sizeof(int64_t) * nclips);
     memcpy(h + 2 * b_sb, foff.data(), sizeof(int64_t) * foff.size());
     memcpy(h + 2 * b_sb + b_fo, toff.data(), sizeof(int32_t) * toff.size());
     memcpy(h + 2 * b_sb + b_fo + b_to, tclip.data(), sizeof(int32_t) * tclip.size());
+    if (!rate) return;
+    memcpy(h + lay_fp, rate->in_off.data(), sizeof(int64_t) * (nclips + 1));
+    memcpy(h + lay_fp + b_ro, sbeg.data(), sizeof(int64_t) * (nclips + 1));
+    memcpy(h + lay_fp + 2 * b_ro, rs_toff.data(), sizeof(int32_t) * rs_toff.size());
+    if (!rs_tclip.empty()) memcpy(h + lay_fp + 2 * b_ro + b_rt, rs_tclip.data(), sizeof(int32_t) * rs_tclip.size());
   };
   auto pack_samples = [&](char* h) {
     if (contiguous) {
-      if (ns) memcpy(h, g711 ? static_cast<const void*>(g711->codes) : ptrs[0], hs * ns);
+      const void* src = g711 ? static_cast<const void*>(g711->codes) : rate ? static_cast<const void*>(rate->pcm) : ptrs[0];
+      if (n_src) memcpy(h, src, hs * n_src);
       return;
     }
     for (int32_t c = 0; c < nclips; c++)
@@ -658,6 +695,9 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     } else if (g711) {
       if ((rc = upload(e, e->g711_codes, g711->codes, hs * ns))) return rc;
       d_pcm = e->g711_codes.p;
+    } else if (rate) {
+      if ((rc = upload(e, e->rs_in, rate->pcm, hs * n_src))) return rc;
+      d_pcm = e->rs_in.p;
     } else {
       HIPCHK(e, e->pcm.reserve(ss * ns));
       if (contiguous) {
@@ -679,6 +719,20 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     HIPCHK(e, launch_g711_expand(static_cast<const uint8_t*>(d_pcm), ns, g711->law, e->pcm.as<int16_t>(), e->stream));
     e->n_g711_expand++;
     e->n_g711_codes += ns;
+    d_pcm = e->pcm.p;
+  }
+  if (rate && ns) {
+    // d_pcm holds the input samples so far (staging, or rs_in): their conversion into the device PCM buffer
+    HIPCHK(e, e->pcm.reserve(ss * ns));
+    const char* r = lay_d + lay_fp;
+    HIPCHK(e, launch_resample(rate->tab->plan, rate->d_taps, static_cast<const int16_t*>(d_pcm),
+                              reinterpret_cast<const int64_t*>(r), reinterpret_cast<const int64_t*>(r + b_ro),
+                              reinterpret_cast<const int32_t*>(r + 2 * b_ro),
+                              reinterpret_cast<const int32_t*>(r + 2 * b_ro + b_rt), rs_toff[nclips], e->pcm.as<int16_t>(),
+                              e->stream));
+    e->n_rs_launch++;
+    e->n_rs_in += n_src;
+    e->n_rs_out += ns;
     d_pcm = e->pcm.p;
   }
   const int64_t* d_sbeg = reinterpret_cast<const int64_t*>(lay_d);
@@ -1912,6 +1966,44 @@ int check_monotone(tfp_engine* e, const int64_t* off, int32_t n, bool samples) {
   if (offsets_monotone(off, n)) return TFP_OK;
   if (samples) return fail(e, TFP_E_ARG, "offsets not monotone");
   return fail(e, TFP_E_ARG, "qoffsets not monotone");
+}
+
+// ---- rate-normalised ingest (tfp_resample.hpp) ---------------------------------------------
+// The rate source of a batch at rate_in != rate_out: checks the pair and the offsets, takes the pair's
+// table onto the device (once per pair, kept), and gives the clips' offsets at rate_out (out_off[0] = 0).
+int rate_source(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t n, int32_t rate_in, int32_t rate_out,
+                RateSrc* rs, std::vector<int64_t>* out_off) {
+  if (rate_in < 1 || rate_out < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : rate_out);
+  if (int rc = check_monotone(e, offsets, n, true)) return rc;
+  ResamplePlan P;
+  bool bad = false;
+  if (!resample_plan(rate_in, rate_out, &P, &bad))
+    return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, rate_out);
+  HIPCHK(e, hipSetDevice(e->device));
+  auto it = e->rs_tables.find({P.M, P.L});
+  if (it == e->rs_tables.end()) {
+    std::shared_ptr<const ResampleTable> host = resample_table(rate_in, rate_out, &bad);
+    if (!host) return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, rate_out);
+    DevBuf dev;
+    if (int rc = upload(e, dev, host->taps.data(), sizeof(int16_t) * host->taps.size())) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    tfp_engine::RsTable& t = e->rs_tables[{P.M, P.L}];
+    t.host = host;
+    t.dev.swap_with(dev);
+    it = e->rs_tables.find({P.M, P.L});
+  }
+  rs->pcm = pcm && n ? pcm + offsets[0] : pcm;
+  rs->tab = it->second.host.get();
+  rs->d_taps = it->second.dev.as<int16_t>();
+  rs->in_off.assign((size_t)std::max(n, 0) + 1, 0);
+  out_off->assign((size_t)std::max(n, 0) + 1, 0);
+  for (int32_t c = 0; c < n; c++) {
+    const int64_t len = offsets[c + 1] - offsets[c], no = resample_count(P, len);
+    if (no < 0) return fail(e, TFP_E_ARG, "clip %d: %lld samples past the index range", c, (long long)len);
+    rs->in_off[c + 1] = rs->in_off[c] + len;
+    (*out_off)[c + 1] = (*out_off)[c] + no;
+  }
+  return TFP_OK;
 }
 
 // ---- ranked search (tfp_rank.hpp): keys[q * K + r] = row r of query q's result set, 0 past the last
@@ -3182,6 +3274,8 @@ struct QuerySrc {
   int32_t sr;
   bool samples;
   bool fingerprinted = false;  // materialise() queued a fingerprint that settle() waits for
+  // samples at another rate (rate_source): off are the offsets at sr and data is rate->pcm
+  const RateSrc* rate = nullptr;
 
   int check_offsets(tfp_engine* e, int32_t n) const { return check_monotone(e, off, n, samples); }
   int check_data(tfp_engine* e, int64_t nframes) const {  // frames to search need their data
@@ -3202,7 +3296,8 @@ struct QuerySrc {
       std::vector<int64_t> lens;
       split_offsets(data, sizeof(int16_t), off, n, &ptrs, &lens);
       int64_t nf;
-      rc = fingerprint_host(e, ptrs.data(), lens.data(), false, n, sr, &nf, nullptr, P->coefs == 2);
+      rc = fingerprint_host(e, rate ? nullptr : ptrs.data(), lens.data(), false, n, sr, &nf, nullptr, P->coefs == 2, nullptr,
+                            rate);
       fingerprinted = rc == TFP_OK;
     }
     *d_q = samples ? e->db.as<double>() : e->q.as<double>();
@@ -4017,7 +4112,8 @@ int tfp_trace_stats(tfp_engine* e, int64_t* batches, int64_t* traces) {
 namespace {
 // One search over host samples, the queries given as (pointer, samples); no coalescing.
 int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* lens, int32_t nq, bool f32, int32_t sr,
-                       const tfp_search_params* P, tfp_result* out, const G711Src* g711 = nullptr) {
+                       const tfp_search_params* P, tfp_result* out, const G711Src* g711 = nullptr,
+                       const RateSrc* rate = nullptr) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   std::vector<int64_t> foff(nq + 1, 0);
@@ -4029,7 +4125,7 @@ int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* le
   std::vector<unsigned long long> keys(nq, 0ull);
   if (valid_params(P) && nq && foff[nq] > 0) {
     int64_t nf;
-    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2, g711);
+    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2, g711, rate);
     if (rc) return rc;
     if ((rc = search_core(e, foff.data(), nq, e->db.as<double>(), P, keys, nullptr, e->stream))) return rc;
     e->stage_pending = false;  // search_core waited for e->stream (keys on the host)
@@ -4119,6 +4215,87 @@ int tfp_internal_g711_expand_device(tfp_engine* e, const uint8_t* d_codes, int64
 int tfp_search_g711_batch(tfp_engine* e, const uint8_t* codes, const int64_t* offsets, int32_t nq, int32_t law, int32_t sr,
                           const tfp_search_params* P, tfp_result* out) {
   return tfp_internal_search_g711(e, codes, offsets, nq, law, sr, P, out);
+}
+
+// ---- rate-normalised ingest: the forms over int16 at another rate (tfp_resample.hpp) -------
+// Equal rates are the plain forms (no table, no launch), entered as their own callers enter them: before
+// the engine's lock is taken, since tfp_search_pcm_batch may wait in the coalescer for a leader that
+// needs that lock. The converting forms are not coalesced, as the G.711 forms.
+int tfp_fingerprint_rate_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nclips, int32_t rate_in,
+                               int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!e) return TFP_E_ARG;
+  if (rate_in < 1 || rate_out < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : rate_out);
+  if (rate_in == rate_out) return tfp_fingerprint_batch(e, pcm, offsets, nclips, rate_out, out, cap, nframes);
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!offsets || nclips < 0 || !nframes || (!pcm && nclips && offsets[nclips] > offsets[0]))
+    return fail(e, TFP_E_ARG, "bad arguments");
+  RateSrc rs;
+  std::vector<int64_t> out_off;
+  if (int rc = rate_source(e, pcm, offsets, nclips, rate_in, rate_out, &rs, &out_off)) return rc;
+  const int64_t need = sample_frame_offsets(out_off.data(), nclips)[nclips];
+  *nframes = need;
+  if (need > 0 && (!out || cap < need)) return fail(e, TFP_E_CAPACITY, "need %lld frames", (long long)need);
+  if (need == 0) return TFP_OK;
+  std::vector<int64_t> lens(nclips), foff;
+  for (int32_t c = 0; c < nclips; c++) lens[c] = out_off[c + 1] - out_off[c];
+  int64_t nf;
+  if (int rc = fingerprint_host(e, nullptr, lens.data(), false, nclips, rate_out, &nf, &foff, true, nullptr, &rs)) return rc;
+  return copy_frames_out(e, nf, foff, out);
+}
+
+int tfp_search_rate_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t rate_in,
+                          int32_t rate_out, const tfp_search_params* P, tfp_result* out) {
+  if (!e) return TFP_E_ARG;
+  if (rate_in < 1 || rate_out < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : rate_out);
+  if (rate_in == rate_out) return tfp_search_pcm_batch(e, pcm, offsets, nq, rate_out, P, out);  // (no lock held: coalesced)
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!offsets || nq < 0 || !out) return TFP_E_ARG;
+  RateSrc rs;
+  std::vector<int64_t> out_off;
+  if (int rc = rate_source(e, pcm, offsets, nq, rate_in, rate_out, &rs, &out_off)) return rc;
+  if (!pcm && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
+  std::vector<int64_t> lens(nq);
+  for (int32_t i = 0; i < nq; i++) lens[i] = out_off[i + 1] - out_off[i];
+  return search_gather_impl(e, nullptr, lens.data(), nq, false, rate_out, P, out, nullptr, &rs);
+}
+
+int tfp_search_scoped_rate_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t rate_in,
+                                 int32_t rate_out, const tfp_search_params* P, const int32_t* scopes, int32_t k,
+                                 tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (rate_in < 1 || rate_out < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : rate_out);
+  // the cheap arguments first, in search_ranked's order: an argument error does no device work
+  if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
+  if (int rc0 = check_k(e, "ranked search", k)) return rc0;
+  if (int rc0 = check_params(e, "ranked search", P)) return rc0;
+  if (nq && !scopes) return fail(e, TFP_E_ARG, "scoped search: scopes is NULL");
+  if (int rc0 = check_scopes(e, "scoped search", scopes, nq, "query")) return rc0;
+  RateSrc rs;
+  std::vector<int64_t> out_off;
+  int rc;
+  if (rate_in == rate_out) {
+    if ((rc = check_monotone(e, offsets, nq, true))) return rc;
+    out_off = relative_offsets(offsets, nq);
+    rc = search_ranked(e, QuerySrc{pcm, offsets, rate_out, true}, nq, P, k, out, counts, nullptr, true, scopes);
+  } else {
+    if ((rc = rate_source(e, pcm, offsets, nq, rate_in, rate_out, &rs, &out_off))) return rc;
+    QuerySrc src{rs.pcm, out_off.data(), rate_out, true};
+    src.rate = &rs;
+    rc = search_ranked(e, src, nq, P, k, out, counts, nullptr, true, scopes);
+  }
+  if (rc) return rc;
+  for (int32_t i = 0; frame_counts && i < nq; i++) frame_counts[i] = (int32_t)tfp_frame_count(out_off[i + 1] - out_off[i]);
+  return TFP_OK;
+}
+
+int tfp_resample_stats(tfp_engine* e, int64_t* launches, int64_t* samples_in, int64_t* samples_out) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (launches) *launches = e->n_rs_launch;
+  if (samples_in) *samples_in = e->n_rs_in;
+  if (samples_out) *samples_out = e->n_rs_out;
+  return TFP_OK;
 }
 
 int tfp_search_pcm_gather(tfp_engine* e, const int16_t* const* pcms, const int64_t* nsamples, int32_t nq, int32_t sr,

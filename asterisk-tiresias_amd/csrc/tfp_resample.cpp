@@ -1,0 +1,93 @@
+// tfp_resample.cpp — the host side of rate conversion (tfp_resample.hpp): the process's tables and the
+// host-only entry points tfp_resample_count / _taps / _pcm. tfp_resample_pcm is the map the kernel of
+// tfp_resample.hip computes (one routine, resample_sample), for the search forms without a rate twin.
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+
+#include "tfp_resample.hpp"
+#include "tiresias_fp.h"
+
+// engine-less calls report through tfp_engine_last_error(NULL) (tfp_wav.cpp)
+extern "C" __attribute__((visibility("hidden"))) void tfp_ingest_set_error(const char* msg);
+
+namespace tfp {
+
+std::shared_ptr<const ResampleTable> resample_table(int32_t rate_in, int32_t rate_out, bool* bad_rate) {
+  static std::mutex mu;
+  static std::map<std::pair<int32_t, int32_t>, std::shared_ptr<const ResampleTable>> tables;
+  ResamplePlan P;
+  if (!resample_plan(rate_in, rate_out, &P, bad_rate)) return nullptr;
+  const int64_t g = rs_gcd(rate_in, rate_out);  // the table depends on the ratio alone
+  const std::pair<int32_t, int32_t> key((int32_t)(rate_in / g), (int32_t)(rate_out / g));
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = tables.find(key);
+  if (it != tables.end()) return it->second;
+  auto t = std::make_shared<ResampleTable>();
+  t->plan = P;
+  if (!resample_build(P, &t->taps)) return nullptr;
+  if (tables.size() >= 64) tables.clear();  // (holders keep theirs)
+  tables[key] = t;
+  return t;
+}
+
+}  // namespace tfp
+
+namespace {
+
+int fail(int code, const std::string& msg) {
+  tfp_ingest_set_error(msg.c_str());
+  return code;
+}
+
+// The pair's table, or the error the engine forms give for it.
+int table_of(int32_t rate_in, int32_t rate_out, std::shared_ptr<const tfp::ResampleTable>* t) {
+  bool bad = false;
+  *t = tfp::resample_table(rate_in, rate_out, &bad);
+  if (*t) return TFP_OK;
+  if (bad) return fail(TFP_E_ARG, "bad sample rate " + std::to_string(rate_in < 1 ? rate_in : rate_out));
+  return fail(TFP_E_ARG, "unsupported rate ratio " + std::to_string(rate_in) + " -> " + std::to_string(rate_out));
+}
+
+}  // namespace
+
+extern "C" int64_t tfp_resample_count(int64_t nsamples, int32_t rate_in, int32_t rate_out) {
+  tfp::ResamplePlan P;
+  bool bad = false;
+  if (!tfp::resample_plan(rate_in, rate_out, &P, &bad)) return -1;
+  return tfp::resample_count(P, nsamples);
+}
+
+extern "C" int tfp_resample_taps(int32_t rate_in, int32_t rate_out, int32_t* L, int32_t* M, int32_t* k_lo, int32_t* ntaps,
+                                 int16_t* taps, int64_t cap) {
+  std::shared_ptr<const tfp::ResampleTable> t;
+  if (int rc = table_of(rate_in, rate_out, &t)) return rc;
+  if (L) *L = t->plan.L;
+  if (M) *M = t->plan.M;
+  if (k_lo) *k_lo = t->plan.k_lo;
+  if (ntaps) *ntaps = t->plan.ntaps;
+  const int64_t n = (int64_t)t->taps.size();
+  if (!taps && cap == 0) return TFP_OK;  // size query
+  if (!taps || cap < n) return fail(TFP_E_CAPACITY, "tap buffer holds " + std::to_string(cap) + " of " + std::to_string(n) + " entries");
+  std::memcpy(taps, t->taps.data(), sizeof(int16_t) * (size_t)n);
+  return TFP_OK;
+}
+
+extern "C" int tfp_resample_pcm(const int16_t* pcm, int64_t n, int32_t rate_in, int32_t rate_out, int16_t* out, int64_t cap,
+                                int64_t* nout) {
+  if (n < 0 || !nout || (n > 0 && !pcm)) return fail(TFP_E_ARG, "bad argument");
+  std::shared_ptr<const tfp::ResampleTable> t;
+  if (int rc = table_of(rate_in, rate_out, &t)) return rc;
+  const int64_t no = rate_in == rate_out ? n : tfp::resample_count(t->plan, n);
+  if (no < 0) return fail(TFP_E_ARG, "sample count " + std::to_string(n) + " past the index range");
+  *nout = no;
+  if (!out && cap == 0) return TFP_OK;  // size query
+  if (!out || cap < no) return fail(TFP_E_CAPACITY, "pcm buffer holds " + std::to_string(cap) + " of " + std::to_string(no) + " samples");
+  if (rate_in == rate_out) {
+    if (n) std::memmove(out, pcm, sizeof(int16_t) * (size_t)n);  // equal rates: the filter is not run
+    return TFP_OK;
+  }
+  tfp::resample_clip(*t, pcm, n, out);
+  return TFP_OK;
+}

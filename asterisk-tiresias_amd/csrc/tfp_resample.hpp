@@ -1,0 +1,185 @@
+// tfp_resample.hpp — rate conversion in front of the int16 fingerprint path: the per-sample
+// definition (one routine, host and device), the table builder (host) and the launch of
+// tfp_resample.hip.
+//
+// A fingerprint is comparable only with fingerprints taken at the same sample rate (the window is 512
+// samples, the filterbank is built per rate), and the reference takes every file at its native rate
+// (/root/reference/src/fp_handler.c:37 DEF_AUBIO_SAMPLERATE 0). The converter is defined in integers
+// alone, so host and device agree bit for bit and there is nothing to tolerate: int16 samples, int16
+// Q15 taps, an exact 64-bit sum, one rounding, one clamp.
+//
+//   g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g, D = max(L, M)
+//   n_out = ceil(n_in L / M)                             (the output instants n M / L before n_in)
+//   y[n]  = clamp((sum_k h[p][k] x[i0 + k] + 16384) >> 15), i0 = n M div L, p = n M mod L,
+//           k = k_lo .. k_hi, x = 0 outside the clip's own [0, n_in)
+//   k_lo = -(Z D div L), k_hi = ceil(Z D / L); tap k of phase p at u = (k L - p) / D:
+//   h(u) = rho sinc(rho u) I0(beta sqrt(1 - (u / Z)^2)) / I0(beta) for |u| < Z, else 0
+//   (a Kaiser-windowed sinc over Z zero crossings of the lower rate, cut off at rho of its Nyquist),
+//   each phase scaled to sum 32768 exactly (the remainder goes to the phase's largest tap).
+#pragma once
+
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define TFP_RS_HD __host__ __device__ __forceinline__
+#else
+#define TFP_RS_HD static inline
+#endif
+
+#include <cmath>
+#include <memory>
+#include <vector>
+
+namespace tfp {
+
+constexpr int32_t kRsZ = 24;            // zero crossings each side, in periods of the lower rate
+constexpr double kRsBeta = 8.0;         // Kaiser window
+constexpr double kRsRho = 0.90;         // cutoff, as a fraction of the lower rate's Nyquist
+constexpr int64_t kRsMaxEntries = (int64_t)1 << 20;  // L * ntaps
+constexpr int32_t kRsTile = 1024;       // outputs per workgroup (tests/resample_util.py reads it here)
+
+struct ResamplePlan {
+  int32_t L, M, k_lo, ntaps;  // k_hi = k_lo + ntaps - 1
+};
+
+inline int64_t rs_gcd(int64_t a, int64_t b) {
+  while (b) {
+    const int64_t t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+// The plan of a rate pair; false for a rate < 1 (*bad_rate set) or a table past kRsMaxEntries.
+inline bool resample_plan(int32_t rate_in, int32_t rate_out, ResamplePlan* P, bool* bad_rate) {
+  *bad_rate = rate_in < 1 || rate_out < 1;
+  if (*bad_rate) return false;
+  const int64_t g = rs_gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g, D = L > M ? L : M;
+  const int64_t k_lo = -((kRsZ * D) / L), k_hi = (kRsZ * D + L - 1) / L, ntaps = k_hi - k_lo + 1;
+  if (L * ntaps > kRsMaxEntries) return false;  // (ntaps > 2 Z D / L >= 48: L stays below 2^15)
+  P->L = (int32_t)L;
+  P->M = (int32_t)M;
+  P->k_lo = (int32_t)k_lo;
+  P->ntaps = (int32_t)ntaps;
+  return true;
+}
+
+// ceil(n_in L / M), 0 for n_in <= 0; -1 when n_in L + M passes int64 (the index arithmetic's range).
+inline int64_t resample_count(const ResamplePlan& P, int64_t n_in) {
+  if (n_in <= 0) return 0;
+  if (n_in > (INT64_MAX - P.M) / P.L) return -1;
+  return (n_in * P.L + P.M - 1) / P.M;
+}
+
+TFP_RS_HD int16_t resample_round(int64_t acc) {
+  const int64_t y = (acc + 16384) >> 15;  // arithmetic shift: floor
+  return (int16_t)(y < -32768 ? -32768 : y > 32767 ? 32767 : y);
+}
+
+// Output sample n of one clip. taps: the table, phase p at taps + p * ntaps. x holds the clip's samples
+// [x_lo, x_hi) (sample i at x[i - x_lo]); every sample outside counts as 0. The host passes the whole
+// clip (x_lo = 0, x_hi = n_in), the kernel its staged span (zeros staged past the clip's ends) or
+// the whole clip in global memory. n M stays below 2^63 for every n < n_out (n M < n_in L + M, resample_count).
+TFP_RS_HD int16_t resample_sample(const ResamplePlan& P, const int16_t* __restrict__ taps, const int16_t* __restrict__ x,
+                                  int64_t x_lo, int64_t x_hi, int64_t n) {
+  const int64_t t = n * P.M, i0 = t / P.L, p = t - i0 * P.L;
+  int64_t ka = P.k_lo, kb = (int64_t)P.k_lo + P.ntaps - 1;
+  if (ka < x_lo - i0) ka = x_lo - i0;
+  if (kb > x_hi - 1 - i0) kb = x_hi - 1 - i0;
+  if (kb < ka) return 0;  // no sample under the filter
+  const int16_t* __restrict__ h = taps + p * P.ntaps + (ka - P.k_lo);
+  const int16_t* __restrict__ s = x + (i0 + ka - x_lo);
+  const int32_t cnt = (int32_t)(kb - ka + 1);  // <= ntaps
+  int64_t acc = 0;
+  for (int32_t j = 0; j < cnt; j++) acc += (int64_t)((int32_t)h[j] * (int32_t)s[j]);  // |product| <= 2^30
+  return resample_round(acc);
+}
+
+struct ResampleTable {
+  ResamplePlan plan;
+  std::vector<int16_t> taps;  // [L][ntaps]
+};
+
+// I0 by its power series (every term positive; x <= beta here, 1e-17 relative after ~30 terms).
+inline double rs_i0(double x) {
+  const double q = x * x / 4.0;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 200; k++) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < sum * 1e-17) break;
+  }
+  return sum;
+}
+
+inline double rs_h(double u) {
+  const double a = u / kRsZ;
+  if (!(a > -1.0 && a < 1.0)) return 0.0;
+  const double v = kRsRho * u, pi = 3.14159265358979323846;
+  const double sinc = v == 0.0 ? 1.0 : std::sin(pi * v) / (pi * v);
+  return kRsRho * sinc * rs_i0(kRsBeta * std::sqrt(1.0 - a * a)) / rs_i0(kRsBeta);
+}
+
+// The table of a plan, in double, each phase scaled to sum exactly 32768. false when a tap leaves
+// int16 (no supported pair does: the largest tap is about rho * 32768).
+inline bool resample_build(const ResamplePlan& P, std::vector<int16_t>* taps) {
+  const int64_t D = P.L > P.M ? P.L : P.M;
+  taps->assign((size_t)P.L * P.ntaps, 0);
+  std::vector<double> h(P.ntaps);
+  for (int32_t p = 0; p < P.L; p++) {
+    double sum = 0.0;
+    for (int32_t j = 0; j < P.ntaps; j++) {
+      h[j] = rs_h((double)((int64_t)(P.k_lo + j) * P.L - p) / (double)D);
+      sum += h[j];
+    }
+    int64_t isum = 0;
+    int32_t big = 0;
+    std::vector<int64_t> q(P.ntaps);
+    for (int32_t j = 0; j < P.ntaps; j++) {
+      q[j] = (int64_t)std::nearbyint(h[j] / sum * 32768.0);
+      isum += q[j];
+      if (q[j] > q[big]) big = j;
+    }
+    q[big] += 32768 - isum;
+    for (int32_t j = 0; j < P.ntaps; j++) {
+      if (q[j] < -32768 || q[j] > 32767) return false;
+      (*taps)[(size_t)p * P.ntaps + j] = (int16_t)q[j];
+    }
+  }
+  return true;
+}
+
+// One clip on the host: out[resample_count(n_in)].
+inline void resample_clip(const ResampleTable& T, const int16_t* x, int64_t n_in, int16_t* out) {
+  const int64_t n_out = resample_count(T.plan, n_in);
+  for (int64_t n = 0; n < n_out; n++) out[n] = resample_sample(T.plan, T.taps.data(), x, 0, n_in, n);
+}
+
+// The process's tables (tfp_resample.cpp): built once per rate pair, shared by the host routine and
+// every engine. nullptr for a bad or unsupported pair, *bad_rate telling which.
+std::shared_ptr<const ResampleTable> resample_table(int32_t rate_in, int32_t rate_out, bool* bad_rate);
+
+// Tile t of the launch covers outputs [(t - toff[c]) * kRsTile, ...) of clip c = tclip[t].
+inline void resample_tiles(const int64_t* out_off, int32_t nclips, std::vector<int32_t>* toff, std::vector<int32_t>* tclip) {
+  toff->assign((size_t)nclips + 1, 0);
+  tclip->clear();
+  for (int32_t c = 0; c < nclips; c++) {
+    const int64_t nt = (out_off[c + 1] - out_off[c] + kRsTile - 1) / kRsTile;
+    (*toff)[c + 1] = (*toff)[c] + (int32_t)nt;
+    tclip->insert(tclip->end(), (size_t)nt, c);
+  }
+}
+
+#if defined(__HIPCC__) || defined(__HIP__)
+// A packed ragged batch: clip c is the input samples [in_off[c], in_off[c + 1]) of d_in and the output
+// samples [out_off[c], out_off[c + 1]) of d_out, out_off[c + 1] - out_off[c] = resample_count of its
+// input length; d_toff / d_tclip are resample_tiles of out_off, ntiles = toff[nclips]. All arrays on
+// the device. One launch; ntiles = 0 launches nothing.
+hipError_t launch_resample(const ResamplePlan& P, const int16_t* d_taps, const int16_t* d_in, const int64_t* d_in_off,
+                           const int64_t* d_out_off, const int32_t* d_toff, const int32_t* d_tclip, int32_t ntiles,
+                           int16_t* d_out, hipStream_t stream);
+#endif
+
+}  // namespace tfp

@@ -118,6 +118,8 @@ int find_data(const uint8_t* b, uint64_t n, WavData* out) {
 
 // tfp_engine_last_error(NULL) (tfp_engine.cpp) reads this; not part of the C-ABI.
 extern "C" __attribute__((visibility("hidden"))) const char* tfp_ingest_last_error() { return g_err.c_str(); }
+// ... and the other engine-less ingest calls (tfp_resample.cpp) write it.
+extern "C" __attribute__((visibility("hidden"))) void tfp_ingest_set_error(const char* msg) { g_err = msg; }
 
 extern "C" int tfp_wav_decode(const void* bytes, int64_t nbytes, int16_t* pcm, int64_t cap, int64_t* nsamples,
                               int32_t* sample_rate) {

@@ -110,6 +110,20 @@ _SIGS = {
                                                    C.POINTER(C.c_int64)]),
     "tfp_group_search_g711_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_group_stream_push_g711": (C.c_int, [P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_resample_count": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "tfp_resample_taps": (C.c_int, [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4 + [P, C.c_int64]),
+    "tfp_resample_pcm": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_fingerprint_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                             C.POINTER(C.c_int64)]),
+    "tfp_search_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_search_scoped_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P,
+                                               C.c_int32, P, P, P]),
+    "tfp_resample_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
+    "tfp_group_fingerprint_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                   C.POINTER(C.c_int64)]),
+    "tfp_group_search_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_group_search_scoped_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams),
+                                                     P, C.c_int32, P, P, P]),
     "tfp_fingerprint_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
     "tfp_search_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_fingerprint_pcm": (C.c_int, [P, P, C.c_int64, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),

@@ -72,6 +72,34 @@ def decode_g711(codes, law: int) -> np.ndarray:
     return pcm
 
 
+def resample_count(nsamples: int, rate_in: int, rate_out: int) -> int:
+    """tfp_resample_count: the samples nsamples at rate_in become at rate_out (ceil(n L / M)); -1 for a bad
+    or unsupported pair."""
+    return int(lib().tfp_resample_count(int(nsamples), int(rate_in), int(rate_out)))
+
+
+def resample_taps(rate_in: int, rate_out: int) -> dict:
+    """tfp_resample_taps: {"L", "M", "k_lo", "ntaps", "taps": int16[L, ntaps]}, the pair's Q15 table."""
+    v = [C.c_int32() for _ in range(4)]
+    refs = [C.byref(x) for x in v]
+    check(lib().tfp_resample_taps(int(rate_in), int(rate_out), *refs, None, 0))
+    L, ntaps = v[0].value, v[3].value
+    taps = np.empty(L * ntaps, np.int16)
+    check(lib().tfp_resample_taps(int(rate_in), int(rate_out), *refs, taps.ctypes.data, len(taps)))
+    return {"L": L, "M": v[1].value, "k_lo": v[2].value, "ntaps": ntaps, "taps": taps.reshape(L, ntaps)}
+
+
+def resample_pcm(pcm, rate_in: int, rate_out: int) -> np.ndarray:
+    """tfp_resample_pcm: one int16 clip of rate_in at rate_out, the map the GPU rate forms compute (exact)."""
+    pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+    n = C.c_int64()
+    check(lib().tfp_resample_pcm(pcm.ctypes.data, len(pcm), int(rate_in), int(rate_out), None, 0, C.byref(n)))
+    out = np.empty(n.value, np.int16)
+    check(lib().tfp_resample_pcm(pcm.ctypes.data, len(pcm), int(rate_in), int(rate_out), out.ctypes.data, len(out),
+                                 C.byref(n)))
+    return out
+
+
 def _wav_g711(call) -> tuple[np.ndarray, int, int]:
     n, sr, law = C.c_int64(), C.c_int32(), C.c_int32()
     check(call(None, 0, C.byref(n), C.byref(sr), C.byref(law)))
@@ -277,6 +305,52 @@ def census_at_least(hist_row, count: int) -> int:
     return int(lib().tfp_census_at_least(row.ctypes.data, len(row), int(count)))
 
 
+class _RateCalls:
+    """Rate-normalised ingest, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*), as _ScopedCalls:
+    int16 clips of rate_in converted to rate_out on the GPU in front of the unchanged fingerprint kernels."""
+
+    resample_count = staticmethod(resample_count)
+    resample_taps = staticmethod(resample_taps)
+    resample_pcm = staticmethod(resample_pcm)
+
+    def fingerprint_rate_batch(self, pcm, offsets, rate_in: int, rate_out: int) -> np.ndarray:
+        """The frames of fingerprint_batch(resample_pcm(clip), rate_out) per clip, bit for bit."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nclips = len(offsets) - 1
+        n = sum(frame_count(max(resample_count(int(offsets[i + 1] - offsets[i]), rate_in, rate_out), 0))
+                for i in range(nclips))
+        out = np.zeros(max(n, 1), FRAME_DTYPE)
+        got = C.c_int64()
+        self._chk(self._fn("_fingerprint_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nclips, int(rate_in),
+                                                      int(rate_out), out.ctypes.data, n, C.byref(got)))
+        return out[:got.value]
+
+    def search_rate_batch(self, pcm, offsets, rate_in: int, rate_out: int, p: SearchParams):
+        """search_pcm_batch at rate_out on the resampled queries."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq = len(offsets) - 1
+        res = (Result * max(1, nq))()
+        self._chk(self._fn("_search_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(rate_in),
+                                                 int(rate_out), C.byref(p), res))
+        return Engine._results(res, nq)
+
+    def search_scoped_rate_batch(self, pcm, offsets, rate_in: int, rate_out: int, p: SearchParams, scopes, k: int):
+        """search_scoped_pcm_batch at rate_out on the resampled queries: (rows per query, frame counts)."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq, k = len(offsets) - 1, int(k)
+        scopes = np.ascontiguousarray(scopes, np.int32)
+        if len(scopes) != nq:
+            raise ValueError("one scope per query")
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        fc = (C.c_int32 * max(1, nq))()
+        self._chk(self._fn("_search_scoped_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(rate_in),
+                                                        int(rate_out), C.byref(p), scopes.ctypes.data, k, out, counts, fc))
+        return Engine._candidates(out, counts, nq, k), list(fc[:nq])
+
+
 class _CensusCalls:
     """The match census, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*), as _ScopedCalls."""
 
@@ -311,7 +385,7 @@ class _CensusCalls:
                             (int(sample_rate),), p, scopes, nbins)
 
 
-class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
+class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls):
     """One engine per GPU (tfp_engine)."""
     _PFX = "tfp"
 
@@ -404,6 +478,12 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls):
         v = [C.c_int64() for _ in range(3)]
         self._chk(lib().tfp_g711_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("expand_launches", "stream_launches", "codes"), (x.value for x in v)))
+
+    def resample_stats(self) -> dict:
+        """tfp_resample_stats: rate conversion launches, the samples they read and the samples they wrote."""
+        v = [C.c_int64() for _ in range(3)]
+        self._chk(lib().tfp_resample_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("launches", "samples_in", "samples_out"), (x.value for x in v)))
 
     def fingerprint_stats(self) -> dict:
         """tfp_fingerprint_stats: fingerprint kernel launches so far, by kernel."""
@@ -1041,7 +1121,7 @@ class Plan:
             self._h = C.c_void_p()
 
 
-class Group(_ScopedCalls, _SlidingCalls, _CensusCalls):
+class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls):
     """tfp_group: one engine per listed device (a device may repeat), the enrolled clips sharded
     over them, searches combined on the host (tiresias_fp.h, device groups)."""
     _PFX = "tfp_group"
@@ -1113,6 +1193,16 @@ class Group(_ScopedCalls, _SlidingCalls, _CensusCalls):
         self._chk(lib().tfp_group_fingerprint_batch(self._h, pcm.ctypes.data, offsets.ctypes.data, nclips, sample_rate,
                                                     out.ctypes.data, n, C.byref(got)))
         return out[:n]
+
+    def resample_stats(self) -> dict:
+        """tfp_resample_stats summed over the shards' engines."""
+        tot = {"launches": 0, "samples_in": 0, "samples_out": 0}
+        for sh in range(self.size()):
+            v = [C.c_int64() for _ in range(3)]
+            check(lib().tfp_resample_stats(lib().tfp_group_engine(self._h, sh), *[C.byref(x) for x in v]))
+            for key, x in zip(tot, v):
+                tot[key] += x.value
+        return tot
 
     def fingerprint_g711_batch(self, codes, offsets, law: int, sample_rate: int = 8000) -> np.ndarray:
         codes = np.ascontiguousarray(codes, np.uint8)

@@ -28,7 +28,7 @@ import numpy as np
 from . import dbio
 from ._lib import TFP_RANK_MAX, TfpError
 from .engine import (ALAW, ULAW, Engine, decode_g711, frame_count as frame_count_of, params, read_wav, read_wav_f32,
-                     read_wav_g711)
+                     read_wav_g711, resample_count, resample_pcm)
 
 TFP_E_FORMAT = -8
 
@@ -93,11 +93,17 @@ def write_wav_mono16(filename: str, pcm: np.ndarray, sample_rate: int = 8000):
 class FpHandler:
     """One loaded module instance (g_db_ctx + the GPU engine)."""
 
-    def __init__(self, device: int = 0, backup_path: str | None = None):
+    def __init__(self, device: int = 0, backup_path: str | None = None, index_rate: int = 0):
         """backup_path: the snapshot file (the reference hard-codes dbio.DEF_BACKUP_DATABASE);
-        None keeps the state in memory only."""
+        None keeps the state in memory only. index_rate: 0 takes every file at its native rate, as the
+        reference does (DEF_AUBIO_SAMPLERATE 0); a rate > 0 is the index's rate (new behaviour): int16 and
+        G.711 files of another rate are brought to it (tfp_resample_pcm's map: on the GPU in the
+        directory enrolment, create_new_audio_info; on the host for a single file, fp_craete_audio_list_info
+        and the searches), fp32 files and files at an unsupported rate ratio are refused."""
         self.device = device
         self.backup_path = backup_path
+        self.index_rate = int(index_rate)
+        self.last_error = ""  # why the last file was refused for its rate
         self.db = None
         self.engine = None
         # context name -> scope id of its clips in the engine (tfp_index_set_scope), from 1 in order of
@@ -220,7 +226,7 @@ class FpHandler:
         self.db.execute("insert into audio_list(uuid, name, context, hash) values (?, ?, ?, ?);",
                         (uuid, os.path.basename(filename), context, h))
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
             fr = self._fingerprint(pcm, [0, len(pcm)], sr)
             self.engine.index_add(uuid, fr["m1"], fr["m2"])
             self.engine.index_set_scope([uuid], [self._scope_of(context, True)])
@@ -278,7 +284,27 @@ class FpHandler:
         got = self._neighbours([info], -1, p, min(int(k), TFP_RANK_MAX))
         return got[0] if got else None
 
+    def _other_rate(self, sr: int) -> bool:
+        return self.index_rate > 0 and sr != self.index_rate
+
+    def _refuse_f32(self, filename: str, sr: int) -> str:
+        self.last_error = ("%s: fp32 audio at %d Hz cannot be normalised to the index rate %d Hz "
+                           "(rate conversion takes int16 and G.711 only)" % (filename, sr, self.index_rate))
+        return self.last_error
+
+    def _read_query(self, filename: str):
+        """read_audio for a search: with an index rate set, a file of another rate is normalised on the host
+        (G.711 expanded first); an fp32 file of another rate raises TfpError(TFP_E_FORMAT)."""
+        pcm, sr = read_audio(filename)
+        if not self._other_rate(sr):
+            return pcm, sr
+        if pcm.dtype == np.float32:
+            raise TfpError(TFP_E_FORMAT, self._refuse_f32(filename, sr))
+        return resample_pcm(pcm, sr, self.index_rate), self.index_rate
+
     def _fingerprint(self, samples: np.ndarray, offsets, sr: int, law=None):
+        if self._other_rate(sr):  # (int16: the enrolment expanded G.711 and refused fp32)
+            return self.engine.fingerprint_rate_batch(samples, offsets, sr, self.index_rate)
         if law is not None:
             return self.engine.fingerprint_g711_batch(samples, offsets, law, sr)
         if samples.dtype == np.float32:
@@ -316,6 +342,15 @@ class FpHandler:
                 pcm, sr, law = read_audio_codes(path)
             except TfpError:
                 continue
+            if self._other_rate(sr):
+                if law is not None:
+                    pcm, law = decode_g711(pcm, law), None  # (the converter takes int16)
+                elif pcm.dtype == np.float32:
+                    self._refuse_f32(path, sr)  # refused, as _read_query refuses it for a search
+                    continue
+                if resample_count(len(pcm), sr, self.index_rate) < 0:  # before any catalog row is written
+                    self.last_error = "%s: unsupported rate ratio %d -> %d" % (path, sr, self.index_rate)
+                    continue
             uuid = self.fp_generate_uuid()
             self.db.execute("insert into audio_list(uuid, name, context, hash) values (?, ?, ?, ?);",
                             (uuid, os.path.basename(path), context, h))
@@ -327,6 +362,8 @@ class FpHandler:
             lens = [len(n[1]) for n in group]
             off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
             fr = self._fingerprint(np.concatenate([n[1] for n in group]), off, sr, law)
+            if self._other_rate(sr):
+                lens = [resample_count(n, sr, self.index_rate) for n in lens]
             foff = np.concatenate([[0], np.cumsum([(n + 255) // 256 for n in lens])]).astype(np.int64)
             self.engine.index_add_batch([n[0] for n in group], foff, fr["m1"], fr["m2"])
             self.engine.index_set_scope([n[0] for n in group], [self._scope_of(context, True)] * len(group))
@@ -352,7 +389,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS:
             return None
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return None
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
@@ -380,7 +417,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1:
             return []
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return []
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
@@ -412,7 +449,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1:
             return []
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return []
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
@@ -447,7 +484,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS:
             return None
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return None
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
@@ -483,7 +520,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1:
             return []
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return []
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
@@ -519,7 +556,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1 or window_frames < 1 or hop_frames < 1:
             return []
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return []
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
@@ -557,7 +594,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS or max_results < 1 or window_frames < 1 or hop_frames < 1:
             return []
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return []
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)
@@ -600,7 +637,7 @@ class FpHandler:
         if coefs < 1 or coefs > DEF_AUBIO_COEFS or k < 1 or window_frames < 1 or hop_frames < 1 or max_gap < 0 or min_hits < 1:
             return []
         try:
-            pcm, sr = read_audio(filename)
+            pcm, sr = self._read_query(filename)
         except TfpError:
             return []
         p = params(coefs, tolerance, freq_ignore_low, freq_ignore_high)

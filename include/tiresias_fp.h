@@ -1268,6 +1268,69 @@ int tfp_group_search_g711_batch(tfp_group* g, const uint8_t* codes, const int64_
 int tfp_group_stream_push_g711(tfp_group_stream* st, const uint8_t* codes, int32_t tick_samples, int32_t law,
                                const tfp_search_params* params, tfp_result* out);
 
+/* ---- rate-normalised ingest: int16 PCM of one rate at the index's rate (new) ------------- */
+/* A fingerprint is comparable only with fingerprints taken at the same sample rate: the window is 512
+ * samples and the filterbank is built per rate, and the reference takes every file at its native rate
+ * (fp_handler.c:37 DEF_AUBIO_SAMPLERATE 0). These forms bring int16 audio of rate_in to rate_out with
+ * one converter, defined in integers alone, so that the GPU and the host agree bit for bit:
+ *   g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g, D = max(L, M), Z = 24
+ *   n_out = ceil(n_in L / M)
+ *   y[n] = clamp((sum_k h[p][k] x[i0 + k] + 16384) >> 15, -32768, 32767), i0 = n M div L, p = n M mod L,
+ *          k = k_lo .. k_lo + ntaps - 1, x = 0 outside the clip's own samples, the sum exact (64-bit)
+ *   k_lo = -(Z D div L), ntaps = ceil(Z D / L) - k_lo + 1; h[p][k] is int16 Q15, from
+ *   h(u) = 0.9 sinc(0.9 u) I0(8 sqrt(1 - (u / Z)^2)) / I0(8) at u = (k L - p) / D (|u| < Z, else 0), each
+ *   phase divided by its sum, times 32768, rounded, and 32768 - sum added to its largest tap: every
+ *   phase sums to exactly 32768, so a constant stays that constant away from a clip's ends.
+ * A rate <= 0 is TFP_E_ARG with "bad sample rate"; a pair with L * ntaps above 2^20 is TFP_E_ARG with
+ * "unsupported rate ratio". rate_in == rate_out runs no filter: the rate forms are then the plain forms.
+ * Not covered: tfp_stream_push / tfp_live_push (a carried input tail per channel), fp32 input. No claim
+ * of equality with any other resampler is made. */
+/* n_out for nsamples at rate_in; 0 for nsamples <= 0, -1 for a bad or unsupported pair. Host-only. */
+int64_t tfp_resample_count(int64_t nsamples, int32_t rate_in, int32_t rate_out);
+/* The pair's table taps[L][ntaps] and its shape (any of L, M, k_lo, ntaps may be NULL). taps == NULL
+ * (cap 0) only sets the shape; cap < L * ntaps -> TFP_E_CAPACITY with the shape set, as tfp_wav_decode.
+ * Host-only; errors via tfp_engine_last_error(NULL). */
+int tfp_resample_taps(int32_t rate_in, int32_t rate_out, int32_t* L, int32_t* M, int32_t* k_lo, int32_t* ntaps,
+                      int16_t* taps, int64_t cap);
+/* One clip on the host: the map the GPU forms compute, sample for sample. out == NULL (cap 0) only sets
+ * *nout = tfp_resample_count; cap < *nout -> TFP_E_CAPACITY with *nout set. Equal rates copy. Host-only.
+ * The search forms without a rate twin (ranked, census, sliding, aligned, occurrences) take the output
+ * of this call through their pcm form at rate_out. */
+int tfp_resample_pcm(const int16_t* pcm, int64_t nsamples, int32_t rate_in, int32_t rate_out, int16_t* out, int64_t cap,
+                     int64_t* nout);
+/* tfp_fingerprint_batch over clips of rate_in: offsets[nclips+1] index into pcm, the frames equal
+ * tfp_fingerprint_batch at rate_out over each clip's tfp_resample_pcm, bit for bit. The samples are
+ * copied to the GPU as they are, converted there by one launch (each clip on its own: a clip's edge
+ * never sees its neighbour), and fingerprinted by the launch an int16 batch of the output lengths at
+ * rate_out takes (tfp_fingerprint_stats counts it alike). */
+int tfp_fingerprint_rate_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
+                               int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes);
+/* The results equal tfp_search_pcm_batch at rate_out on each query's tfp_resample_pcm. Not coalesced. */
+int tfp_search_rate_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                          int32_t rate_in, int32_t rate_out, const tfp_search_params* params, tfp_result* out);
+/* The rows equal tfp_search_scoped_pcm_batch at rate_out on each query's tfp_resample_pcm (the
+ * dialplan's context search of a call heard at another rate). frame_counts[nqueries] (may be NULL)
+ * receives each query's frame count at rate_out, which the caller's sample counts do not tell. */
+int tfp_search_scoped_rate_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                 int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                                 const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                 int32_t* frame_counts);
+/* Rate conversion on the GPU so far: launches, the samples they read and the samples they wrote.
+ * Counted where the kernel is issued (a batch without an output sample launches nothing). Any pointer
+ * may be NULL. */
+int tfp_resample_stats(tfp_engine* eng, int64_t* launches, int64_t* samples_in, int64_t* samples_out);
+/* The same on a group, equal to the engine forms: a fingerprint batch's clips are converted by the
+ * shard that fingerprints them (cut by their frames at rate_out); a search batch is converted and
+ * fingerprinted by every shard, and the shards' results are combined as the pcm forms' are. */
+int tfp_group_fingerprint_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
+                                     int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes);
+int tfp_group_search_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                int32_t rate_in, int32_t rate_out, const tfp_search_params* params, tfp_result* out);
+int tfp_group_search_scoped_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                       int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                                       const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                       int32_t* frame_counts);
+
 /* ---- deterministic synthetic PCM (benchmark / test data; identical host and device) -- */
 /* One spec per clip: samples s of clip = synth(seed, clip, offset + s). */
 typedef struct tfp_synth_spec {
