@@ -32,6 +32,7 @@
 #include "tfp_kernels.hpp"
 #include "tfp_live.hpp"
 #include "tfp_live_occur.hpp"
+#include "tfp_live_rate.hpp"
 #include "tfp_math.hpp"
 #include "tfp_query_plan.hpp"
 #include "tfp_rank.hpp"
@@ -1969,19 +1970,13 @@ int check_monotone(tfp_engine* e, const int64_t* off, int32_t n, bool samples) {
 }
 
 // ---- rate-normalised ingest (tfp_resample.hpp) ---------------------------------------------
-// The rate source of a batch at rate_in != rate_out: checks the pair and the offsets, takes the pair's
-// table onto the device (once per pair, kept), and gives the clips' offsets at rate_out (out_off[0] = 0).
-int rate_source(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t n, int32_t rate_in, int32_t rate_out,
-                RateSrc* rs, std::vector<int64_t>* out_off) {
-  if (rate_in < 1 || rate_out < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : rate_out);
-  if (int rc = check_monotone(e, offsets, n, true)) return rc;
-  ResamplePlan P;
-  bool bad = false;
-  if (!resample_plan(rate_in, rate_out, &P, &bad))
-    return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, rate_out);
+// The table of a supported pair (P its plan) on the device: uploaded once per pair and kept for the
+// engine's lifetime (the entry and its device copy never move).
+int ensure_rs_table(tfp_engine* e, const ResamplePlan& P, int32_t rate_in, int32_t rate_out, const tfp_engine::RsTable** tab) {
   HIPCHK(e, hipSetDevice(e->device));
   auto it = e->rs_tables.find({P.M, P.L});
   if (it == e->rs_tables.end()) {
+    bool bad = false;
     std::shared_ptr<const ResampleTable> host = resample_table(rate_in, rate_out, &bad);
     if (!host) return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, rate_out);
     DevBuf dev;
@@ -1992,9 +1987,25 @@ int rate_source(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32
     t.dev.swap_with(dev);
     it = e->rs_tables.find({P.M, P.L});
   }
+  *tab = &it->second;
+  return TFP_OK;
+}
+
+// The rate source of a batch at rate_in != rate_out: checks the pair and the offsets, takes the pair's
+// table onto the device (once per pair, kept), and gives the clips' offsets at rate_out (out_off[0] = 0).
+int rate_source(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t n, int32_t rate_in, int32_t rate_out,
+                RateSrc* rs, std::vector<int64_t>* out_off) {
+  if (rate_in < 1 || rate_out < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : rate_out);
+  if (int rc = check_monotone(e, offsets, n, true)) return rc;
+  ResamplePlan P;
+  bool bad = false;
+  if (!resample_plan(rate_in, rate_out, &P, &bad))
+    return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, rate_out);
+  const tfp_engine::RsTable* tab;
+  if (int rc = ensure_rs_table(e, P, rate_in, rate_out, &tab)) return rc;
   rs->pcm = pcm && n ? pcm + offsets[0] : pcm;
-  rs->tab = it->second.host.get();
-  rs->d_taps = it->second.dev.as<int16_t>();
+  rs->tab = tab->host.get();
+  rs->d_taps = tab->dev.as<int16_t>();
   rs->in_off.assign((size_t)std::max(n, 0) + 1, 0);
   out_off->assign((size_t)std::max(n, 0) + 1, 0);
   for (int32_t c = 0; c < n; c++) {
@@ -4733,15 +4744,38 @@ struct tfp_live {
   SearchConsts tr_stamp_sc{};
   int32_t tr_stamp_gap = 0;
   int64_t n_occ_calls = 0, n_tr_added = 0, n_tr_dropped = 0, n_tr_frames = 0, n_tr_retraces = 0;
+  // a rate object (tfp_live_create_rate, tfp_live_rate.hpp): the ticks arrive at rate_in and are converted
+  // into hist; `samples` is then the settled count. Per channel the input samples since its last reset and
+  // the carry side its next push reads; carry: int16 [2][nch][ntaps - 1] (never cleared: a sample below
+  // index 0 is never read from it)
+  bool rated = false;
+  int32_t rate_in = 0, rs_tile = 0;
+  ResamplePlan rs_plan{};
+  const int16_t* rs_taps = nullptr;  // the engine's device table of the pair (kept for its lifetime)
+  std::vector<int64_t> in_samples;
+  std::vector<int32_t> parity;
+  DevBuf carry;
+  int64_t n_rt_launch = 0, n_rt_in = 0, n_rt_out = 0;  // tfp_live_rate_stats
   ~tfp_live() {
     if (stage_ev) (void)hipEventDestroy(stage_ev);
   }
 };
 
 int tfp_live_create(tfp_engine* e, int32_t nch, int32_t sr, int64_t max_samples, tfp_live** out) {
+  return tfp_live_create_rate(e, nch, sr, sr, max_samples, out);
+}
+
+int tfp_live_create_rate(tfp_engine* e, int32_t nch, int32_t rate_in, int32_t sr, int64_t max_samples, tfp_live** out) {
   if (!e || !out) return TFP_E_ARG;
   *out = nullptr;
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  ResamplePlan rs_plan{};
+  if (rate_in != sr) {
+    if (rate_in < 1 || sr < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : sr);
+    bool bad = false;
+    if (!resample_plan(rate_in, sr, &rs_plan, &bad) || !live_rate_supported(rs_plan))
+      return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, sr);
+  }
   if (nch <= 0 || nch > 65535) return fail(e, TFP_E_ARG, "live calls: %d channels outside [1, 65535]", nch);
   if (!live_capacity_ok(max_samples))
     return fail(e, TFP_E_ARG, "live calls: max_samples %lld outside [1, %lld]", (long long)max_samples,
@@ -4761,6 +4795,19 @@ int tfp_live_create(tfp_engine* e, int32_t nch, int32_t sr, int64_t max_samples,
   lv->wbeg.assign(nch, 0);
   lv->wend.assign(nch, 0);
   lv->tracks.assign(nch, {});
+  if (rate_in != sr) {
+    const tfp_engine::RsTable* tab;
+    if ((rc = ensure_rs_table(e, rs_plan, rate_in, sr, &tab))) return rc;
+    lv->rated = true;
+    lv->rate_in = rate_in;
+    lv->rs_plan = rs_plan;
+    lv->rs_tile = live_rate_tile(rs_plan);
+    lv->rs_taps = tab->dev.as<int16_t>();
+    lv->in_samples.assign(nch, 0);
+    lv->parity.assign(nch, 0);
+    if (lv->carry.reserve(sizeof(int16_t) * 2 * (size_t)nch * (rs_plan.ntaps - 1)) != hipSuccess)
+      return fail(e, TFP_E_NOMEM, "live calls: the carried input of %d channels", nch);
+  }
   // (neither needs clearing: a push reads only samples and frame values that a push has written)
   if (lv->hist.reserve(sizeof(int16_t) * (size_t)nch * max_samples) != hipSuccess ||
       lv->q.reserve(sizeof(double) * 2 * (size_t)nch * lv->Fmax) != hipSuccess ||
@@ -4796,6 +4843,7 @@ int tfp_live_reset(tfp_live* lv, int32_t ch) {
                              sizeof(uint16_t) * (size_t)(c1 - c0) * lv->wcount_cols, e->stream));
   for (int32_t c = c0; c < c1; c++) {
     lv->samples[c] = lv->added[c] = 0;
+    if (lv->rated) lv->in_samples[c] = 0;  // (the carry stays: a sample below index 0 is never read from it)
     lv->n_wremoved += lv->wend[c] - lv->wbeg[c];
     lv->wbeg[c] = lv->wend[c] = 0;
     lv->tracks[c].clear();  // a new call starts with an empty log
@@ -4807,6 +4855,30 @@ int tfp_live_samples(tfp_live* lv, int32_t ch, int64_t* nsamples) {
   if (!lv || ch < 0 || ch >= lv->nch || !nsamples) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
   *nsamples = lv->samples[ch];
+  return TFP_OK;
+}
+
+int tfp_live_input_samples(tfp_live* lv, int32_t ch, int64_t* nsamples) {
+  if (!lv || ch < 0 || ch >= lv->nch || !nsamples) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  *nsamples = lv->rated ? lv->in_samples[ch] : lv->samples[ch];
+  return TFP_OK;
+}
+
+int tfp_live_rate_info(tfp_live* lv, int32_t* rate_in, int64_t* lag_in) {
+  if (!lv) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  if (rate_in) *rate_in = lv->rated ? lv->rate_in : lv->sr;
+  if (lag_in) *lag_in = lv->rated ? live_rate_lag(lv->rs_plan) : 0;
+  return TFP_OK;
+}
+
+int tfp_live_rate_stats(tfp_live* lv, int64_t* launches, int64_t* samples_in, int64_t* samples_out) {
+  if (!lv) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(lv->eng->mu);
+  if (launches) *launches = lv->n_rt_launch;
+  if (samples_in) *samples_in = lv->n_rt_in;
+  if (samples_out) *samples_out = lv->n_rt_out;
   return TFP_OK;
 }
 
@@ -4914,9 +4986,31 @@ int live_step(tfp_live* lv, const void* pcm, int32_t law, int32_t T, const int32
   for (int32_t c = 0; nsamples && c < nch; c++)
     if (nsamples[c] < 0 || nsamples[c] > T)
       return fail(e, TFP_E_ARG, "live push: nsamples[%d] = %d outside [0, %d]", c, nsamples[c], T);
-  for (int32_t c = 0; c < nch; c++)  // all or nothing: no channel has taken a sample yet
-    if (lv->samples[c] + (nsamples ? nsamples[c] : T) > lv->max_samples)
+  // A rate object's push (tfp_live_rate.hpp): the tick is at rate_in, and what enters the history is each
+  // channel's newly settled samples; from the descriptors on it is the plain push of those.
+  const bool rate = lv->rated && !vd;
+  std::vector<LiveRateChan> rchan(rate ? nch : 0);
+  for (int32_t c = 0; c < nch; c++) {  // all or nothing: no channel has taken a sample yet
+    const int32_t n_in = nsamples ? nsamples[c] : T;
+    int64_t s_new = lv->samples[c] + n_in;
+    if (rate) {
+      LiveRateStep st;
+      if (!live_rate_step(lv->rs_plan, lv->in_samples[c], n_in, &st))
+        return fail(e, TFP_E_ARG, "live push: channel %d past the index range", c);
+      s_new = st.n_old + st.n_new;  // (st.n_old = lv->samples[c])
+      if (s_new <= lv->max_samples)
+        rchan[c] = LiveRateChan{lv->in_samples[c], st.n_old, n_in, (int32_t)st.n_new, lv->parity[c], 0};
+    }
+    if (s_new > lv->max_samples)
       return fail(e, TFP_E_CAPACITY, "live push: channel %d past %lld samples", c, (long long)lv->max_samples);
+  }
+  std::vector<int32_t> rs_toff(1, 0), rs_tclip;
+  int32_t rs_ntiles = 0, rs_max_new = 0;
+  if (rate) {
+    rs_ntiles = live_rate_tiles(rchan.data(), nch, lv->rs_tile, &rs_toff, &rs_tclip);
+    for (const LiveRateChan& r : rchan) rs_max_new = std::max(rs_max_new, r.n_new);
+  }
+  if (rs_tclip.empty()) rs_tclip.push_back(0);  // (staged like the other tables: never an empty copy)
   HIPCHK(e, hipSetDevice(e->device));
   hipStream_t s = e->stream;
   int rc;
@@ -4951,7 +5045,7 @@ int live_step(tfp_live* lv, const void* pcm, int32_t law, int32_t T, const int32
     vchan[c].complete = lv->samples[c] == vd->total[c] ? 1 : 0;
   }
   for (int32_t c = 0; c < nch; c++) {
-    const int32_t n = nsamples ? nsamples[c] : T;
+    const int32_t n = rate ? rchan[c].n_new : nsamples ? nsamples[c] : T;
     chan[c].s_old = lv->samples[c];
     chan[c].n_new = n;
     chan[c].scope = scopes ? scopes[c] : TFP_SCOPE_ANY;
@@ -5004,9 +5098,11 @@ int live_step(tfp_live* lv, const void* pcm, int32_t law, int32_t T, const int32
                b_sb = al(sizeof(int64_t) * sbeg.size()), b_fo = al(sizeof(int64_t) * foff.size()),
                b_to = al(sizeof(int32_t) * toff.size()), b_tc = al(sizeof(int32_t) * tclip.size()),
                b_cp = al(sizeof(LiveCopy) * copies.size()), b_add = al(sizeof(LiveAdd) * std::max<size_t>(adds.size(), 1)),
-               b_vch = al(sizeof(LiveVerdictChan) * vchan.size());
+               b_vch = al(sizeof(LiveVerdictChan) * vchan.size()), b_rch = al(sizeof(LiveRateChan) * rchan.size()),
+               b_rto = al(sizeof(int32_t) * rs_toff.size());
   const size_t o_chan = b_pcm, o_sb = o_chan + b_chan, o_se = o_sb + b_sb, o_fo = o_se + b_sb, o_to = o_fo + b_fo,
-               o_tc = o_to + b_to, o_cp = o_tc + b_tc, o_add = o_cp + b_cp, o_vch = o_add + b_add, total = o_vch + b_vch;
+               o_tc = o_to + b_to, o_cp = o_tc + b_tc, o_add = o_cp + b_cp, o_vch = o_add + b_add, o_rch = o_vch + b_vch,
+               o_rto = o_rch + b_rch, o_rtc = o_rto + b_rto, total = o_rtc + al(sizeof(int32_t) * rs_tclip.size());
   if (lv->stage_pending) HIPCHK(e, hipEventSynchronize(lv->stage_ev));  // the last push's upload has read stage_h
   lv->stage_pending = false;
   HIPCHK(e, lv->stage_h.reserve(total));
@@ -5022,6 +5118,11 @@ int live_step(tfp_live* lv, const void* pcm, int32_t law, int32_t T, const int32
   memcpy(h + o_tc, tclip.data(), sizeof(int32_t) * tclip.size());
   memcpy(h + o_cp, copies.data(), sizeof(LiveCopy) * copies.size());
   if (!adds.empty()) memcpy(h + o_add, adds.data(), sizeof(LiveAdd) * adds.size());
+  if (rate) {
+    memcpy(h + o_rch, rchan.data(), sizeof(LiveRateChan) * rchan.size());
+    memcpy(h + o_rto, rs_toff.data(), sizeof(int32_t) * rs_toff.size());
+    memcpy(h + o_rtc, rs_tclip.data(), sizeof(int32_t) * rs_tclip.size());
+  }
   const int64_t nf = foff[na];
   HIPCHK(e, e->micro.reserve(sizeof(int32_t) * 2 * (nf + 1)));
   HIPCHK(e, e->db.reserve(sizeof(double) * 2 * (nf + 1)));
@@ -5040,7 +5141,27 @@ int live_step(tfp_live* lv, const void* pcm, int32_t law, int32_t T, const int32
   const char* d = lv->dstage.as<char>();
   const LiveChan* d_chan = reinterpret_cast<const LiveChan*>(d + o_chan);
   // 1: scatter (codes are expanded on their way into the int16 history: everything after is one path)
-  if (law < 0) {
+  if (rate) {
+    // ... a rate object: the one launch that converts the tick into the history and moves the carry on
+    int32_t nmove = 0;
+    int64_t n_in_all = 0, n_out_all = 0;
+    for (const LiveRateChan& r : rchan) nmove += r.n_in > 0, n_in_all += r.n_in, n_out_all += r.n_new;
+    HIPCHK(e, launch_live_rate(lv->rs_plan, lv->rs_taps, d, law, T, reinterpret_cast<const LiveRateChan*>(d + o_rch), nch,
+                               reinterpret_cast<const int32_t*>(d + o_rto), reinterpret_cast<const int32_t*>(d + o_rtc),
+                               rs_ntiles, nmove, rs_max_new, lv->carry.as<int16_t>(), lv->max_samples,
+                               lv->hist.as<int16_t>(), s));
+    for (int32_t c = 0; c < nch; c++) {
+      lv->in_samples[c] += rchan[c].n_in;
+      if (rchan[c].n_in > 0) lv->parity[c] ^= 1;
+    }
+    if (rs_ntiles + nmove > 0) lv->n_rt_launch++;
+    lv->n_rt_in += n_in_all;
+    lv->n_rt_out += n_out_all;
+    if (law >= 0) {
+      e->n_g711_stream++;
+      e->n_g711_codes += n_in_all;
+    }
+  } else if (law < 0) {
     HIPCHK(e, launch_live_scatter(reinterpret_cast<const int16_t*>(d), T, d_chan, nch, lv->max_samples, lv->hist.as<int16_t>(), s));
   } else {
     HIPCHK(e, launch_live_scatter_g711(reinterpret_cast<const uint8_t*>(d), T, d_chan, nch, law, lv->max_samples,

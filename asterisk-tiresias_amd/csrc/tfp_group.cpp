@@ -44,6 +44,7 @@
 #include "tfp_kernels.hpp"
 #include "tfp_live_occur.hpp"
 #include "tfp_live_plan.hpp"
+#include "tfp_live_rate.hpp"
 #include "tfp_occur.hpp"
 #include "tfp_rank_merge.hpp"
 #include "tfp_shardpool.hpp"
@@ -1567,6 +1568,11 @@ struct tfp_group_live {
   int32_t nch = 0;
   int64_t max_samples = 0;
   std::vector<int64_t> samples;  // per channel, as every shard counts them (the capacity check before any shard is told)
+  // a rate object (tfp_live_rate.hpp): the shards take the tick at rate_in; samples is then the settled
+  // count and in_samples the input samples, both as every shard counts them
+  bool rated = false;
+  tfp::ResamplePlan rs_plan{};
+  std::vector<int64_t> in_samples;
   // tfp_group_live_occurrences: per channel the merged list, each track also on its clip's shard (whose
   // engine carries its trace); `windows` is counted here, over the merged rows
   struct Track {
@@ -1580,6 +1586,11 @@ struct tfp_group_live {
 };
 
 int tfp_group_live_create(tfp_group* g, int32_t nch, int32_t sr, int64_t max_samples, tfp_group_live** out) {
+  return tfp_group_live_create_rate(g, nch, sr, sr, max_samples, out);
+}
+
+int tfp_group_live_create_rate(tfp_group* g, int32_t nch, int32_t rate_in, int32_t sr, int64_t max_samples,
+                               tfp_group_live** out) {
   if (!g || !out) return TFP_E_ARG;
   *out = nullptr;
   std::lock_guard<std::recursive_mutex> lk(g->mu);
@@ -1588,7 +1599,10 @@ int tfp_group_live_create(tfp_group* g, int32_t nch, int32_t sr, int64_t max_sam
   gl->nch = nch;
   gl->max_samples = max_samples;
   gl->lv.assign(g->eng.size(), nullptr);
-  const int rc = run_all(g, [&](int s) { return tfp_live_create(g->eng[s], nch, sr, max_samples, &gl->lv[s]); });
+  bool bad = false;  // (a pair the plan refuses is refused by every shard, with the message)
+  gl->rated = rate_in != sr && tfp::resample_plan(rate_in, sr, &gl->rs_plan, &bad);
+  gl->in_samples.assign(gl->rated && nch > 0 ? nch : 0, 0);
+  const int rc = run_all(g, [&](int s) { return tfp_live_create_rate(g->eng[s], nch, rate_in, sr, max_samples, &gl->lv[s]); });
   if (rc) {
     for (auto* p : gl->lv) tfp_live_destroy(p);
     delete gl;
@@ -1611,8 +1625,28 @@ int tfp_group_live_reset(tfp_group_live* gl, int32_t ch) {
   std::lock_guard<std::recursive_mutex> lk(gl->g->mu);
   const int rc = run_all(gl->g, [&](int s) { return tfp_live_reset(gl->lv[s], ch); });
   if (rc) return rc;
-  for (int32_t c = ch < 0 ? 0 : ch; c < (ch < 0 ? gl->nch : ch + 1); c++) gl->samples[c] = 0, gl->tracks[c].clear();
+  for (int32_t c = ch < 0 ? 0 : ch; c < (ch < 0 ? gl->nch : ch + 1); c++) {
+    gl->samples[c] = 0, gl->tracks[c].clear();
+    if (gl->rated) gl->in_samples[c] = 0;
+  }
   return TFP_OK;
+}
+
+int tfp_group_live_input_samples(tfp_group_live* gl, int32_t ch, int64_t* nsamples) {
+  if (!gl || ch < 0 || ch >= gl->nch || !nsamples) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(gl->g->mu);
+  *nsamples = gl->rated ? gl->in_samples[ch] : gl->samples[ch];
+  return TFP_OK;
+}
+
+int tfp_group_live_rate_info(tfp_group_live* gl, int32_t* rate_in, int64_t* lag_in) {
+  if (!gl) return TFP_E_ARG;
+  return tfp_live_rate_info(gl->lv[0], rate_in, lag_in);  // (every shard was created alike)
+}
+
+int tfp_group_live_rate_stats(tfp_group_live* gl, int32_t shard, int64_t* launches, int64_t* samples_in, int64_t* samples_out) {
+  if (!gl || shard < 0 || (size_t)shard >= gl->lv.size()) return TFP_E_ARG;
+  return tfp_live_rate_stats(gl->lv[shard], launches, samples_in, samples_out);
 }
 
 int tfp_group_live_samples(tfp_group_live* gl, int32_t ch, int64_t* nsamples) {
@@ -1655,9 +1689,18 @@ int group_live_push(tfp_group_live* gl, const void* pcm, int32_t law, int32_t T,
     if (scopes)
       if (int rc = group_scope_args(g, scopes, nch)) return rc;
   }
-  for (int32_t c = 0; c < nch; c++)  // before any shard is told: a capacity failure leaves every shard unchanged
-    if (gl->samples[c] + (nsamples ? nsamples[c] : T) > gl->max_samples)
+  std::vector<int64_t> settled(nch);  // what each channel's history gains (a rate object: its newly settled samples)
+  for (int32_t c = 0; c < nch; c++) {  // before any shard is told: a capacity failure leaves every shard unchanged
+    settled[c] = nsamples ? nsamples[c] : T;
+    if (gl->rated) {
+      tfp::LiveRateStep st;
+      if (!tfp::live_rate_step(gl->rs_plan, gl->in_samples[c], settled[c], &st))
+        return gfail(g, TFP_E_ARG, "live push: channel %d past the index range", c);
+      settled[c] = st.n_new;  // (st.n_old = gl->samples[c])
+    }
+    if (gl->samples[c] + settled[c] > gl->max_samples)
       return gfail(g, TFP_E_CAPACITY, "live push: channel %d past %lld samples", c, (long long)gl->max_samples);
+  }
   int rc;
   if (P && valid_params(P)) {
     // each shard's first k rows of every channel, merged as scoped search's (shard 0 reports the frame counts)
@@ -1677,7 +1720,10 @@ int group_live_push(tfp_group_live* gl, const void* pcm, int32_t law, int32_t T,
     }
   }
   if (rc) return rc;
-  for (int32_t c = 0; c < nch; c++) gl->samples[c] += nsamples ? nsamples[c] : T;
+  for (int32_t c = 0; c < nch; c++) {
+    gl->samples[c] += settled[c];
+    if (gl->rated) gl->in_samples[c] += nsamples ? nsamples[c] : T;
+  }
   return TFP_OK;
 }
 }  // namespace

@@ -193,6 +193,14 @@ _SIGS = {
     "tfp_group_live_push": (C.c_int, [P, P, C.c_int32, P, C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
     "tfp_group_live_samples": (C.c_int, [P, C.c_int32, C.POINTER(C.c_int64)]),
     "tfp_group_live_stats": (C.c_int, [P, C.c_int32] + [C.POINTER(C.c_int64)] * 5),
+    "tfp_live_create_rate": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(P)]),
+    "tfp_live_input_samples": (C.c_int, [P, C.c_int32, C.POINTER(C.c_int64)]),
+    "tfp_live_rate_info": (C.c_int, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "tfp_live_rate_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 3),
+    "tfp_group_live_create_rate": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(P)]),
+    "tfp_group_live_input_samples": (C.c_int, [P, C.c_int32, C.POINTER(C.c_int64)]),
+    "tfp_group_live_rate_info": (C.c_int, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "tfp_group_live_rate_stats": (C.c_int, [P, C.c_int32] + [C.POINTER(C.c_int64)] * 3),
     "tfp_synth_pcm": (C.c_int, [P, C.c_int32, C.c_int64, P]),
     "tfp_synth_pcm_device": (C.c_int, [P, P, C.c_int32, C.c_int64, P, P]),
     "tfp_synchronize": (C.c_int, [P, P]),

@@ -903,10 +903,15 @@ class Stream:
 class _LiveCalls:
     """Live calls (tfp_live / tfp_group_live): the same calls on an Engine's and on a Group's object."""
 
-    def _open(self, owner, nchannels: int, max_samples: int, sample_rate: int):
+    def _open(self, owner, nchannels: int, max_samples: int, sample_rate: int, rate_in=None):
         self._owner = owner
         self._h = C.c_void_p()
-        owner._chk(self._fn("_create")(owner.handle, int(nchannels), int(sample_rate), int(max_samples), C.byref(self._h)))
+        if rate_in is None:
+            rc = self._fn("_create")(owner.handle, int(nchannels), int(sample_rate), int(max_samples), C.byref(self._h))
+        else:
+            rc = self._fn("_create_rate")(owner.handle, int(nchannels), int(rate_in), int(sample_rate), int(max_samples),
+                                          C.byref(self._h))
+        owner._chk(rc)
         self.nchannels = int(nchannels)
         self.max_samples = int(max_samples)
         owner._streams.add(self)
@@ -922,6 +927,33 @@ class _LiveCalls:
         n = C.c_int64()
         self._owner._chk(self._fn("_samples")(self._h, int(channel), C.byref(n)))
         return n.value
+
+    def input_samples(self, channel: int) -> int:
+        """tfp_live_input_samples: the input samples the channel has taken since its last reset (at rate_in)."""
+        n = C.c_int64()
+        self._owner._chk(self._fn("_input_samples")(self._h, int(channel), C.byref(n)))
+        return n.value
+
+    def rate_info(self) -> dict:
+        """tfp_live_rate_info: rate_in and lag_in (k_hi input samples; 0 on a plain object)."""
+        r, lag = C.c_int32(), C.c_int64()
+        self._owner._chk(self._fn("_rate_info")(self._h, C.byref(r), C.byref(lag)))
+        return {"rate_in": r.value, "lag_in": lag.value}
+
+    def _rate_stats(self, *lead):
+        v = [C.c_int64() for _ in range(3)]
+        self._owner._chk(self._fn("_rate_stats")(self._h, *lead, *[C.byref(x) for x in v]))
+        return dict(zip(("launches", "samples_in", "samples_out"), (x.value for x in v)))
+
+    def finish(self, channels=None):
+        """The end of a call on a rate object: lag_in int16 zeros to the named channels (None: every channel),
+        ingest only, after which every output of their calls is settled. Nothing on a plain object."""
+        lag = self.rate_info()["lag_in"]
+        if lag <= 0:
+            return
+        ns = np.zeros(self.nchannels, np.int32)
+        ns[list(range(self.nchannels)) if channels is None else list(channels)] = lag
+        self.push(np.zeros((self.nchannels, lag), np.int16), nsamples=ns)
 
     def push(self, pcm: np.ndarray, p: SearchParams = None, scopes=None, k: int = 1, nsamples=None):
         """pcm int16[nchannels, tick]; channel c takes its first nsamples[c] samples (None: the whole tick).
@@ -1079,8 +1111,14 @@ class Live(_LiveCalls):
     """tfp_live: every channel's call so far on one engine, the per-clip counts carried from push to push."""
     _PFX = "tfp_live"
 
-    def __init__(self, eng: Engine, nchannels: int, max_samples: int, sample_rate: int = 8000):
-        self._open(eng, nchannels, max_samples, sample_rate)
+    def __init__(self, eng: Engine, nchannels: int, max_samples: int, sample_rate: int = 8000, rate_in: int = None):
+        """rate_in: the rate the ticks arrive at (tfp_live_create_rate); None: sample_rate, a plain object.
+        max_samples and everything returned are at sample_rate."""
+        self._open(eng, nchannels, max_samples, sample_rate, rate_in)
+
+    def rate_stats(self) -> dict:
+        """tfp_live_rate_stats: conversion launches of this object's pushes, input samples taken, samples settled."""
+        return self._rate_stats()
 
     def stats(self) -> dict:
         """tfp_live_stats: searching pushes by form, count-table rebuilds, frames fingerprinted and added."""
@@ -1392,8 +1430,13 @@ class GroupLive(_LiveCalls):
     """tfp_group_live: live calls matched against every shard of a Group (every shard keeps every channel)."""
     _PFX = "tfp_group_live"
 
-    def __init__(self, g: Group, nchannels: int, max_samples: int, sample_rate: int = 8000):
-        self._open(g, nchannels, max_samples, sample_rate)
+    def __init__(self, g: Group, nchannels: int, max_samples: int, sample_rate: int = 8000, rate_in: int = None):
+        """rate_in: the rate the ticks arrive at (tfp_group_live_create_rate); None: a plain object."""
+        self._open(g, nchannels, max_samples, sample_rate, rate_in)
+
+    def rate_stats(self) -> list:
+        """tfp_group_live_rate_stats: each shard's tfp_live_rate_stats, in shard order."""
+        return [self._rate_stats(shard) for shard in range(len(self._owner.devices))]
 
     def stats(self) -> list:
         """tfp_group_live_stats: each shard's tfp_live_stats, in shard order."""

@@ -1283,8 +1283,9 @@ int tfp_group_stream_push_g711(tfp_group_stream* st, const uint8_t* codes, int32
  *   phase sums to exactly 32768, so a constant stays that constant away from a clip's ends.
  * A rate <= 0 is TFP_E_ARG with "bad sample rate"; a pair with L * ntaps above 2^20 is TFP_E_ARG with
  * "unsupported rate ratio". rate_in == rate_out runs no filter: the rate forms are then the plain forms.
- * Not covered: tfp_stream_push / tfp_live_push (a carried input tail per channel), fp32 input. No claim
- * of equality with any other resampler is made. */
+ * Not covered: tfp_stream_push (the ring), fp32 input. A live object takes its ticks at another rate
+ * through tfp_live_create_rate (the last section of this header). No claim of equality with any other
+ * resampler is made. */
 /* n_out for nsamples at rate_in; 0 for nsamples <= 0, -1 for a bad or unsupported pair. Host-only. */
 int64_t tfp_resample_count(int64_t nsamples, int32_t rate_in, int32_t rate_out);
 /* The pair's table taps[L][ntaps] and its shape (any of L, M, k_lo, ntaps may be NULL). taps == NULL
@@ -1344,6 +1345,61 @@ int tfp_synth_pcm_device(tfp_engine* eng, const tfp_synth_spec* specs, int32_t n
 
 /* ---- misc --------------------------------------------------------------------------- */
 int tfp_synchronize(tfp_engine* eng, void* stream);
+
+/* ---- live calls at another rate: each push converted to the index's rate on the GPU (new) -------- */
+/* An Asterisk channel is often not at the index's rate (slin16 from G.722, slin48 from Opus, an 8 kHz
+ * G.711 leg against a catalog enrolled at 16 kHz), and record_voice hands over its frames as they arrive
+ * (application_handler.c:248-312; the reference takes every file at its native rate, fp_handler.c:37).
+ * A rate object is a live object whose ticks arrive at rate_in: every push is converted by the converter
+ * of "rate-normalised ingest" (L, M, k_lo, ntaps, k_hi = k_lo + ntaps - 1; output n reads the input
+ * samples i0 + k_lo .. i0 + k_hi, i0 = n M div L) on its way into the int16 history, and everything
+ * behind the history is unchanged. With S_in input samples taken by a channel since its last reset:
+ *   settled  output n is settled once i0 + k_hi <= S_in - 1. N(S_in) = tfp_resample_count(S_in - k_hi)
+ *            outputs are settled, 0 while S_in <= k_hi, and the channel's history is exactly the first
+ *            N(S_in) samples of tfp_resample_pcm of its S_in input samples, hence of every continuation
+ *            of the call: a settled sample never changes.
+ *   lag      k_hi input samples: 48 at 16000 -> 8000, 144 at 48000 -> 8000, 24 at 8000 -> 16000,
+ *            133 at 44100 -> 8000; 3 ms in every case.
+ *   carry    the last ntaps - 1 input samples per channel are kept on the GPU between pushes; samples
+ *            before the call's start are zeros, as the batch definition has them.
+ *   flush    after k_hi zero samples N = tfp_resample_count(S_in) over the call's own samples and the
+ *            history equals tfp_resample_pcm of the call, its last outputs included (zero flush).
+ * By contract a rate object is a plain live object that has been pushed each tick's newly settled
+ * samples: rows, frame counts, tfp_live_samples (the settled count), a verdict's total_samples, window
+ * frames and occurrence frames are all in index-rate terms. One input rate per object: a caller with
+ * legs at several rates keeps one object per rate. */
+/* tfp_live_create with an input rate (record_voice's channel format, application_handler.c:248-312;
+ * fp_handler.c:37). max_samples is in samples at sample_rate, range as tfp_live_create. rate_in < 1 is
+ * TFP_E_ARG "bad sample rate"; a pair whose table passes 2^20 entries, or whose filter alone
+ * (ntaps + ceil(M / L) + 1 samples) passes the 30,720 samples a workgroup stages, is TFP_E_ARG
+ * "unsupported rate ratio". rate_in == sample_rate gives a plain object (no filter, no carry, lag 0).
+ * On a rate object tfp_live_push and tfp_live_push_g711 take the tick at rate_in (int16, mu-law and
+ * A-law pushes of one call may alternate: the carry is int16); a push that would take any channel's
+ * settled count past max_samples is TFP_E_CAPACITY and ingests nothing (no carry or input count moves);
+ * tfp_live_reset restarts the channel's input count. */
+int tfp_live_create_rate(tfp_engine* eng, int32_t nchannels, int32_t rate_in, int32_t sample_rate, int64_t max_samples,
+                         tfp_live** out);
+/* Input samples `channel` has taken since its last reset (record_voice's running length at the
+ * channel's own rate, application_handler.c:248-312); on a plain object tfp_live_samples. */
+int tfp_live_input_samples(tfp_live* lv, int32_t channel, int64_t* nsamples);
+/* The object's input rate and its lag k_hi in input samples (fp_handler.c:37: the rate the audio came
+ * at); a plain object: its sample rate and 0. Pushing lag_in zeros to a channel at the end of its call
+ * settles every output. Either pointer may be NULL. */
+int tfp_live_rate_info(tfp_live* lv, int32_t* rate_in, int64_t* lag_in);
+/* Conversion launches of this object's pushes, the input samples they took and the samples they settled
+ * (the per-tick conversion of record_voice's frames, application_handler.c:248-312). Apart from
+ * tfp_resample_stats, whose meaning stays. Any pointer may be NULL. */
+int tfp_live_rate_stats(tfp_live* lv, int64_t* launches, int64_t* samples_in, int64_t* samples_out);
+/* The same on a group (application_handler.c:248-312; fp_handler.c:37): every shard keeps every channel,
+ * so the shards are created with the rate and pushed the same tick; the capacity check, made before any
+ * shard is told, uses the same arithmetic over the group's own input counts. tfp_group_live_rate_stats is
+ * shard `shard`'s tfp_live_rate_stats. */
+int tfp_group_live_create_rate(tfp_group* g, int32_t nchannels, int32_t rate_in, int32_t sample_rate, int64_t max_samples,
+                               tfp_group_live** out);
+int tfp_group_live_input_samples(tfp_group_live* lv, int32_t channel, int64_t* nsamples);
+int tfp_group_live_rate_info(tfp_group_live* lv, int32_t* rate_in, int64_t* lag_in);
+int tfp_group_live_rate_stats(tfp_group_live* lv, int32_t shard, int64_t* launches, int64_t* samples_in,
+                              int64_t* samples_out);
 
 #ifdef __cplusplus
 }
