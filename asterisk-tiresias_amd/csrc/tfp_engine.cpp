@@ -346,6 +346,7 @@ struct tfp_engine {
   std::map<std::pair<int32_t, int32_t>, RsTable> rs_tables;
   DevBuf rs_in;
   int64_t n_rs_launch = 0, n_rs_in = 0, n_rs_out = 0;  // tfp_resample_stats
+  int64_t n_mix_launch = 0, n_mix_in = 0, n_mix_out = 0, n_mix_staged = 0;  // tfp_resample_mix_stats
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   FpLaunchStats fpstats;  // fingerprint launches so far per kernel (tfp_fingerprint_stats)
@@ -533,6 +534,18 @@ struct RateSrc {
   const int16_t* d_taps;
 };
 
+// A batch of interleaved int16 clips of `channels` channels laid end to end (clip c = the frames
+// [in_off[c], in_off[c + 1]) of pcm, channels samples each, in_off[0] = 0) and the table that brings
+// their channel sums to the call's rate; tab == nullptr at equal rates (the downmix alone, in_off = the
+// call's own offsets). The call's lens are the output lengths.
+struct MixSrc {
+  const int16_t* pcm;
+  std::vector<int64_t> in_off;
+  int32_t channels;
+  const ResampleTable* tab;
+  const int16_t* d_taps;
+};
+
 // Fingerprint host samples (int16 PCM, or with f32 the fp32 values aubio_source produced):
 // clip c is the lens[c] samples at ptrs[c] (the clips may lie anywhere: a coalesced batch gathers
 // the queries of several callers); leaves micro/db on the device in e->micro / e->db.
@@ -544,12 +557,14 @@ struct RateSrc {
 // rate: the clips are int16 at another rate laid end to end at rate->pcm (ptrs is not read) and lens
 // are their lengths at sr. The samples go to the device as they are and resample_kernel writes their
 // conversion into e->pcm; the layout, tile choice and launch are the int16 call's of lens.
+// mix: the same for interleaved multichannel int16 at mix->pcm, by resample_mix_kernel (offsets in frames).
 int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens, bool f32, int32_t nclips, int32_t sr,
                      int64_t* nframes_out, std::vector<int64_t>* foff_out, bool exact_q = true,
-                     const G711Src* g711 = nullptr, const RateSrc* rate = nullptr) {
+                     const G711Src* g711 = nullptr, const RateSrc* rate = nullptr, const MixSrc* mix = nullptr) {
   const size_t ss = f32 ? sizeof(float) : sizeof(int16_t);
   const size_t hs = g711 ? sizeof(uint8_t) : ss;  // bytes per sample as the host hands them over
-  const bool flat = g711 || rate;                 // one flat source array in front of e->pcm
+  const bool flat = g711 || rate || mix;          // one flat source array in front of e->pcm
+  const std::vector<int64_t>* rs_in_off = rate ? &rate->in_off : mix ? &mix->in_off : nullptr;  // a converting launch's input offsets
   const DspTables* T;
   bool fx = false;
   int rc = ensure_tables(e, sr, &T, &fx);
@@ -588,7 +603,7 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     ns += lens[c];
     if (!flat && c + 1 < nclips && static_cast<const char*>(ptrs[c]) + ss * lens[c] != ptrs[c + 1]) contiguous = false;
   }
-  const int64_t n_src = rate ? rate->in_off[nclips] : ns;  // samples the host hands over
+  const int64_t n_src = rate ? rate->in_off[nclips] : mix ? mix->in_off[nclips] * mix->channels : ns;  // samples the host hands over
   std::vector<int64_t> sbeg(nclips + 1, 0), send(nclips + 1, 0);
   const char* base_dev = nullptr;
   bool in_place = !flat && ns > 0 && (small || !contiguous);
@@ -617,12 +632,12 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
   // the resample launch's own layout, after the fingerprint launch's: the input offsets, the output
   // offsets (sbeg, all nclips + 1 of them) and the tiles of kRsTile outputs
   std::vector<int32_t> rs_toff, rs_tclip;
-  if (rate) resample_tiles(sbeg.data(), nclips, &rs_toff, &rs_tclip);
+  if (rs_in_off) resample_tiles(sbeg.data(), nclips, &rs_toff, &rs_tclip);
   const size_t b_pcm = in_place ? 0 : al(hs * n_src), b_sb = al(sizeof(int64_t) * nclips),
                b_fo = al(sizeof(int64_t) * foff.size()), b_to = al(sizeof(int32_t) * toff.size()),
                b_tc = al(sizeof(int32_t) * tclip.size());
-  const size_t b_ro = rate ? al(sizeof(int64_t) * (nclips + 1)) : 0, b_rt = rate ? al(sizeof(int32_t) * rs_toff.size()) : 0,
-               b_rc = rate ? al(sizeof(int32_t) * rs_tclip.size()) : 0;
+  const size_t b_ro = rs_in_off ? al(sizeof(int64_t) * (nclips + 1)) : 0, b_rt = rs_in_off ? al(sizeof(int32_t) * rs_toff.size()) : 0,
+               b_rc = rs_in_off ? al(sizeof(int32_t) * rs_tclip.size()) : 0;
   const size_t lay_fp = 2 * b_sb + b_fo + b_to + b_tc, lay = lay_fp + 2 * b_ro + b_rt + b_rc, total = b_pcm + lay;
   auto pack_layout = [&](char* h) {
     memcpy(h, sbeg.data(), sizeof(int64_t) * nclips);
@@ -630,15 +645,18 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     memcpy(h + 2 * b_sb, foff.data(), sizeof(int64_t) * foff.size());
     memcpy(h + 2 * b_sb + b_fo, toff.data(), sizeof(int32_t) * toff.size());
     memcpy(h + 2 * b_sb + b_fo + b_to, tclip.data(), sizeof(int32_t) * tclip.size());
-    if (!rate) return;
-    memcpy(h + lay_fp, rate->in_off.data(), sizeof(int64_t) * (nclips + 1));
+    if (!rs_in_off) return;
+    memcpy(h + lay_fp, rs_in_off->data(), sizeof(int64_t) * (nclips + 1));
     memcpy(h + lay_fp + b_ro, sbeg.data(), sizeof(int64_t) * (nclips + 1));
     memcpy(h + lay_fp + 2 * b_ro, rs_toff.data(), sizeof(int32_t) * rs_toff.size());
     if (!rs_tclip.empty()) memcpy(h + lay_fp + 2 * b_ro + b_rt, rs_tclip.data(), sizeof(int32_t) * rs_tclip.size());
   };
   auto pack_samples = [&](char* h) {
     if (contiguous) {
-      const void* src = g711 ? static_cast<const void*>(g711->codes) : rate ? static_cast<const void*>(rate->pcm) : ptrs[0];
+      const void* src = g711   ? static_cast<const void*>(g711->codes)
+                        : rate ? static_cast<const void*>(rate->pcm)
+                        : mix  ? static_cast<const void*>(mix->pcm)
+                               : ptrs[0];
       if (n_src) memcpy(h, src, hs * n_src);
       return;
     }
@@ -696,8 +714,8 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     } else if (g711) {
       if ((rc = upload(e, e->g711_codes, g711->codes, hs * ns))) return rc;
       d_pcm = e->g711_codes.p;
-    } else if (rate) {
-      if ((rc = upload(e, e->rs_in, rate->pcm, hs * n_src))) return rc;
+    } else if (rs_in_off) {
+      if ((rc = upload(e, e->rs_in, rate ? rate->pcm : mix->pcm, hs * n_src))) return rc;
       d_pcm = e->rs_in.p;
     } else {
       HIPCHK(e, e->pcm.reserve(ss * ns));
@@ -734,6 +752,23 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     e->n_rs_launch++;
     e->n_rs_in += n_src;
     e->n_rs_out += ns;
+    d_pcm = e->pcm.p;
+  }
+  if (mix && ns) {
+    // d_pcm holds the interleaved frames so far (staging, or rs_in): their downmix and conversion into the
+    // device PCM buffer (the staging and rs_in are 256-byte aligned, as the launch's word reads need)
+    HIPCHK(e, e->pcm.reserve(ss * ns));
+    const char* r = lay_d + lay_fp;
+    bool staged = false;
+    HIPCHK(e, launch_resample_mix(mix->tab ? mix->tab->plan : ResamplePlan{1, 1, 0, 1}, mix->d_taps, !mix->tab, mix->channels,
+                                  static_cast<const int16_t*>(d_pcm), reinterpret_cast<const int64_t*>(r),
+                                  reinterpret_cast<const int64_t*>(r + b_ro), reinterpret_cast<const int32_t*>(r + 2 * b_ro),
+                                  reinterpret_cast<const int32_t*>(r + 2 * b_ro + b_rt), rs_toff[nclips],
+                                  e->pcm.as<int16_t>(), e->stream, &staged));
+    e->n_mix_launch++;
+    e->n_mix_in += mix->in_off[nclips];
+    e->n_mix_out += ns;
+    e->n_mix_staged += staged ? 1 : 0;
     d_pcm = e->pcm.p;
   }
   const int64_t* d_sbeg = reinterpret_cast<const int64_t*>(lay_d);
@@ -3287,6 +3322,8 @@ struct QuerySrc {
   bool fingerprinted = false;  // materialise() queued a fingerprint that settle() waits for
   // samples at another rate (rate_source): off are the offsets at sr and data is rate->pcm
   const RateSrc* rate = nullptr;
+  // interleaved multichannel samples (mix_source): off are the offsets at sr and data is mix->pcm
+  const MixSrc* mix = nullptr;
 
   int check_offsets(tfp_engine* e, int32_t n) const { return check_monotone(e, off, n, samples); }
   int check_data(tfp_engine* e, int64_t nframes) const {  // frames to search need their data
@@ -3307,8 +3344,8 @@ struct QuerySrc {
       std::vector<int64_t> lens;
       split_offsets(data, sizeof(int16_t), off, n, &ptrs, &lens);
       int64_t nf;
-      rc = fingerprint_host(e, rate ? nullptr : ptrs.data(), lens.data(), false, n, sr, &nf, nullptr, P->coefs == 2, nullptr,
-                            rate);
+      rc = fingerprint_host(e, rate || mix ? nullptr : ptrs.data(), lens.data(), false, n, sr, &nf, nullptr, P->coefs == 2,
+                            nullptr, rate, mix);
       fingerprinted = rc == TFP_OK;
     }
     *d_q = samples ? e->db.as<double>() : e->q.as<double>();
@@ -4124,7 +4161,7 @@ namespace {
 // One search over host samples, the queries given as (pointer, samples); no coalescing.
 int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* lens, int32_t nq, bool f32, int32_t sr,
                        const tfp_search_params* P, tfp_result* out, const G711Src* g711 = nullptr,
-                       const RateSrc* rate = nullptr) {
+                       const RateSrc* rate = nullptr, const MixSrc* mix = nullptr) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   std::vector<int64_t> foff(nq + 1, 0);
@@ -4136,7 +4173,7 @@ int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* le
   std::vector<unsigned long long> keys(nq, 0ull);
   if (valid_params(P) && nq && foff[nq] > 0) {
     int64_t nf;
-    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2, g711, rate);
+    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2, g711, rate, mix);
     if (rc) return rc;
     if ((rc = search_core(e, foff.data(), nq, e->db.as<double>(), P, keys, nullptr, e->stream))) return rc;
     e->stage_pending = false;  // search_core waited for e->stream (keys on the host)
@@ -4306,6 +4343,125 @@ int tfp_resample_stats(tfp_engine* e, int64_t* launches, int64_t* samples_in, in
   if (launches) *launches = e->n_rs_launch;
   if (samples_in) *samples_in = e->n_rs_in;
   if (samples_out) *samples_out = e->n_rs_out;
+  return TFP_OK;
+}
+
+// ---- rate-normalised ingest of multichannel int16 (tfp_resample.hpp, "the multichannel form") ----
+namespace {
+// The mix source of a batch of `channels` > 1 interleaved channels: checks the pair and the offsets (in
+// frames), takes the pair's table onto the device (none at equal rates: the downmix alone), and gives
+// the clips' offsets at rate_out (out_off[0] = 0).
+int mix_source(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t n, int32_t channels, int32_t rate_in,
+               int32_t rate_out, MixSrc* ms, std::vector<int64_t>* out_off) {
+  if (int rc = check_monotone(e, offsets, n, true)) return rc;
+  ResamplePlan P;
+  bool bad = false;
+  if (!resample_plan(rate_in, rate_out, &P, &bad))
+    return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, rate_out);
+  ms->tab = nullptr;
+  ms->d_taps = nullptr;
+  if (rate_in != rate_out) {
+    const tfp_engine::RsTable* tab;
+    if (int rc = ensure_rs_table(e, P, rate_in, rate_out, &tab)) return rc;
+    ms->tab = tab->host.get();
+    ms->d_taps = tab->dev.as<int16_t>();
+  }
+  ms->channels = channels;
+  ms->pcm = pcm && n > 0 ? pcm + offsets[0] * channels : pcm;
+  ms->in_off.assign((size_t)std::max(n, 0) + 1, 0);
+  out_off->assign((size_t)std::max(n, 0) + 1, 0);
+  for (int32_t c = 0; c < n; c++) {
+    const int64_t len = offsets[c + 1] - offsets[c], no = rate_in == rate_out ? len : resample_count(P, len);
+    if (no < 0 || len > INT64_MAX / (2 * channels) - ms->in_off[c])
+      return fail(e, TFP_E_ARG, "clip %d: %lld frames past the index range", c, (long long)len);
+    ms->in_off[c + 1] = ms->in_off[c] + len;
+    (*out_off)[c + 1] = (*out_off)[c] + no;
+  }
+  return TFP_OK;
+}
+
+// The checks every mix form makes first: the channel count, then the rates, as the rate forms word them.
+int check_mix(tfp_engine* e, int32_t channels, int32_t rate_in, int32_t rate_out) {
+  if (channels < 1 || channels > TFP_MIX_CHANNELS_MAX) return fail(e, TFP_E_ARG, "unsupported channel count %d", channels);
+  if (rate_in < 1 || rate_out < 1) return fail(e, TFP_E_ARG, "bad sample rate %d", rate_in < 1 ? rate_in : rate_out);
+  return TFP_OK;
+}
+}  // namespace
+
+// One channel is the rate form itself (hence, at equal rates, the plain form), entered before the
+// engine's lock is taken, as the rate forms enter the plain ones. Not coalesced.
+int tfp_fingerprint_mix_rate_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
+                                   int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                   int64_t* nframes) {
+  if (!e) return TFP_E_ARG;
+  if (channels == 1) return tfp_fingerprint_rate_batch(e, pcm, offsets, nclips, rate_in, rate_out, out, cap, nframes);
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (int rc = check_mix(e, channels, rate_in, rate_out)) return rc;
+  if (!offsets || nclips < 0 || !nframes || (!pcm && nclips && offsets[nclips] > offsets[0]))
+    return fail(e, TFP_E_ARG, "bad arguments");
+  MixSrc ms;
+  std::vector<int64_t> out_off;
+  if (int rc = mix_source(e, pcm, offsets, nclips, channels, rate_in, rate_out, &ms, &out_off)) return rc;
+  const int64_t need = sample_frame_offsets(out_off.data(), nclips)[nclips];
+  *nframes = need;
+  if (need > 0 && (!out || cap < need)) return fail(e, TFP_E_CAPACITY, "need %lld frames", (long long)need);
+  if (need == 0) return TFP_OK;
+  std::vector<int64_t> lens(nclips), foff;
+  for (int32_t c = 0; c < nclips; c++) lens[c] = out_off[c + 1] - out_off[c];
+  int64_t nf;
+  if (int rc = fingerprint_host(e, nullptr, lens.data(), false, nclips, rate_out, &nf, &foff, true, nullptr, nullptr, &ms))
+    return rc;
+  return copy_frames_out(e, nf, foff, out);
+}
+
+int tfp_search_mix_rate_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t channels,
+                              int32_t rate_in, int32_t rate_out, const tfp_search_params* P, tfp_result* out) {
+  if (!e) return TFP_E_ARG;
+  if (channels == 1) return tfp_search_rate_batch(e, pcm, offsets, nq, rate_in, rate_out, P, out);
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (int rc = check_mix(e, channels, rate_in, rate_out)) return rc;
+  if (!offsets || nq < 0 || !out) return TFP_E_ARG;
+  MixSrc ms;
+  std::vector<int64_t> out_off;
+  if (int rc = mix_source(e, pcm, offsets, nq, channels, rate_in, rate_out, &ms, &out_off)) return rc;
+  if (!pcm && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
+  std::vector<int64_t> lens(nq);
+  for (int32_t i = 0; i < nq; i++) lens[i] = out_off[i + 1] - out_off[i];
+  return search_gather_impl(e, nullptr, lens.data(), nq, false, rate_out, P, out, nullptr, nullptr, &ms);
+}
+
+int tfp_search_scoped_mix_rate_batch(tfp_engine* e, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t channels,
+                                     int32_t rate_in, int32_t rate_out, const tfp_search_params* P, const int32_t* scopes,
+                                     int32_t k, tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
+  if (!e || !offsets) return TFP_E_ARG;
+  if (channels == 1)
+    return tfp_search_scoped_rate_batch(e, pcm, offsets, nq, rate_in, rate_out, P, scopes, k, out, counts, frame_counts);
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (int rc0 = check_mix(e, channels, rate_in, rate_out)) return rc0;
+  // the cheap arguments first, in search_ranked's order: an argument error does no device work
+  if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
+  if (int rc0 = check_k(e, "ranked search", k)) return rc0;
+  if (int rc0 = check_params(e, "ranked search", P)) return rc0;
+  if (nq && !scopes) return fail(e, TFP_E_ARG, "scoped search: scopes is NULL");
+  if (int rc0 = check_scopes(e, "scoped search", scopes, nq, "query")) return rc0;
+  MixSrc ms;
+  std::vector<int64_t> out_off;
+  if (int rc = mix_source(e, pcm, offsets, nq, channels, rate_in, rate_out, &ms, &out_off)) return rc;
+  QuerySrc src{ms.pcm, out_off.data(), rate_out, true};
+  src.mix = &ms;
+  if (int rc = search_ranked(e, src, nq, P, k, out, counts, nullptr, true, scopes)) return rc;
+  for (int32_t i = 0; frame_counts && i < nq; i++) frame_counts[i] = (int32_t)tfp_frame_count(out_off[i + 1] - out_off[i]);
+  return TFP_OK;
+}
+
+int tfp_resample_mix_stats(tfp_engine* e, int64_t* launches, int64_t* frames_in, int64_t* samples_out,
+                           int64_t* staged_launches) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (launches) *launches = e->n_mix_launch;
+  if (frames_in) *frames_in = e->n_mix_in;
+  if (samples_out) *samples_out = e->n_mix_out;
+  if (staged_launches) *staged_launches = e->n_mix_staged;
   return TFP_OK;
 }
 

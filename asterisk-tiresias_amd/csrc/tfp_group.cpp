@@ -580,6 +580,51 @@ int tfp_group_fingerprint_rate_batch(tfp_group* g, const int16_t* pcm, const int
   });
 }
 
+namespace {
+// A mix form's channel count and pair on a group: the engine forms' own refusals, in their order.
+int group_mix_plan(tfp_group* g, int32_t channels, int32_t rate_in, int32_t rate_out, tfp::ResamplePlan* P) {
+  if (channels < 1 || channels > TFP_MIX_CHANNELS_MAX) return gfail(g, TFP_E_ARG, "unsupported channel count %d", channels);
+  return group_rate_plan(g, rate_in, rate_out, P);
+}
+}  // namespace
+
+// Interleaved multichannel int16 on a group (tfp_resample.hpp, "the multichannel form"): offsets count
+// frames; the clips are cut by their frames at rate_out exactly as tfp_group_fingerprint_rate_batch cuts
+// its own, and each shard downmixes and converts the clips it fingerprints. One channel is the rate form.
+int tfp_group_fingerprint_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
+                                         int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                         int64_t* nframes) {
+  if (!g) return TFP_E_ARG;
+  if (channels == 1) return tfp_group_fingerprint_rate_batch(g, pcm, offsets, nclips, rate_in, rate_out, out, cap, nframes);
+  tfp::ResamplePlan P;
+  if (int rc = group_mix_plan(g, channels, rate_in, rate_out, &P)) return rc;
+  if (!offsets || nclips < 0 || !nframes) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  const int n = (int)g->eng.size();
+  std::vector<int64_t> foff(nclips + 1, 0);
+  for (int32_t c = 0; c < nclips; c++) {
+    if (offsets[c + 1] < offsets[c]) return gfail(g, TFP_E_ARG, "offsets not monotone");
+    const int64_t len = offsets[c + 1] - offsets[c], no = rate_in == rate_out ? len : tfp::resample_count(P, len);
+    if (no < 0) return gfail(g, TFP_E_ARG, "clip %d: frames past the index range", c);
+    foff[c + 1] = foff[c] + tfp_frame_count(no);
+  }
+  *nframes = foff[nclips];
+  if (foff[nclips] > 0 && (!out || cap < foff[nclips])) return gfail(g, TFP_E_CAPACITY, "need %lld frames", (long long)foff[nclips]);
+  if (!foff[nclips]) return TFP_OK;
+  std::vector<int32_t> cut(n + 1, nclips);
+  cut[0] = 0;
+  for (int s = 1; s < n; s++)
+    cut[s] = (int32_t)(std::lower_bound(foff.begin(), foff.end(), foff[nclips] * s / n) - foff.begin());
+  for (int s = 1; s <= n; s++) cut[s] = std::max(cut[s], cut[s - 1]);
+  return run_all(g, [&](int s) -> int {
+    const int32_t a = cut[s], b = cut[s + 1];
+    if (a >= b) return TFP_OK;
+    int64_t got = 0;
+    return tfp_fingerprint_mix_rate_batch(g->eng[s], pcm, offsets + a, b - a, channels, rate_in, rate_out, out + foff[a],
+                                          foff[b] - foff[a], &got);
+  });
+}
+
 int tfp_group_index_add(tfp_group* g, const char* uuid, const int32_t* m1, const int32_t* m2, int32_t nframes) {
   if (!g) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(g->mu);
@@ -897,6 +942,29 @@ int tfp_group_search_scoped_rate_batch(tfp_group* g, const int16_t* pcm, const i
   if (int rc = group_scope_args(g, scopes, nq)) return rc;
   const int rc = group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
     return tfp_search_scoped_rate_batch(g->eng[s], pcm, offsets, nq, rate_in, rate_out, P, scopes, k, o, c, nullptr);
+  });
+  if (rc) return rc;
+  for (int32_t i = 0; frame_counts && i < nq; i++) {
+    const int64_t len = offsets[i + 1] - offsets[i];
+    frame_counts[i] = (int32_t)tfp_frame_count(rate_in == rate_out ? len : tfp::resample_count(rp, len));
+  }
+  return TFP_OK;
+}
+
+// Every shard downmixes, converts and fingerprints the batch, as the rate twin's shards do.
+int tfp_group_search_scoped_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nq,
+                                           int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* P,
+                                           const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                           int32_t* frame_counts) {
+  if (!g || !offsets) return TFP_E_ARG;
+  if (channels == 1)
+    return tfp_group_search_scoped_rate_batch(g, pcm, offsets, nq, rate_in, rate_out, P, scopes, k, out, counts, frame_counts);
+  tfp::ResamplePlan rp;
+  if (int rc = group_mix_plan(g, channels, rate_in, rate_out, &rp)) return rc;
+  if (int rc = group_scope_args(g, scopes, nq)) return rc;
+  const int rc = group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    return tfp_search_scoped_mix_rate_batch(g->eng[s], pcm, offsets, nq, channels, rate_in, rate_out, P, scopes, k, o, c,
+                                            nullptr);
   });
   if (rc) return rc;
   for (int32_t i = 0; frame_counts && i < nq; i++) {
@@ -1380,6 +1448,31 @@ int tfp_group_search_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t*
   const int n = (int)g->eng.size();
   std::vector<std::vector<tfp_result>> res(n, std::vector<tfp_result>(std::max(nq, 1)));
   rc = run_all(g, [&](int s) { return tfp_search_rate_batch(g->eng[s], pcm, offsets, nq, rate_in, rate_out, P, res[s].data()); });
+  if (rc) return rc;
+  combine(g, res, nq, out);
+  return TFP_OK;
+}
+
+// Interleaved multichannel int16: every shard downmixes, converts and fingerprints the batch, combined
+// as the rate twin's results are. One channel is the rate form. Not coalesced.
+int tfp_group_search_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nq, int32_t channels,
+                                    int32_t rate_in, int32_t rate_out, const tfp_search_params* P, tfp_result* out) {
+  if (!g) return TFP_E_ARG;
+  if (channels == 1) return tfp_group_search_rate_batch(g, pcm, offsets, nq, rate_in, rate_out, P, out);
+  tfp::ResamplePlan rp;
+  if (int rc = group_mix_plan(g, channels, rate_in, rate_out, &rp)) return rc;
+  if (!offsets || nq < 0 || !out) return TFP_E_ARG;
+  for (int32_t i = 0; i < nq; i++)
+    if (offsets[i + 1] < offsets[i]) return gfail(g, TFP_E_ARG, "offsets not monotone");
+  if (!pcm && nq && offsets[nq] > offsets[0]) return gfail(g, TFP_E_ARG, "samples are NULL");
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  int rc = refresh_ranks(g);
+  if (rc) return rc;
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<tfp_result>> res(n, std::vector<tfp_result>(std::max(nq, 1)));
+  rc = run_all(g, [&](int s) {
+    return tfp_search_mix_rate_batch(g->eng[s], pcm, offsets, nq, channels, rate_in, rate_out, P, res[s].data());
+  });
   if (rc) return rc;
   combine(g, res, nq, out);
   return TFP_OK;

@@ -91,3 +91,33 @@ extern "C" int tfp_resample_pcm(const int16_t* pcm, int64_t n, int32_t rate_in, 
   tfp::resample_clip(*t, pcm, n, out);
   return TFP_OK;
 }
+
+static_assert(tfp::kRsMixChannelsMax == TFP_MIX_CHANNELS_MAX, "tfp_resample.hpp and the public header agree");
+
+// The multichannel form on the host: the map the kernel of tfp_resample_mix.hip computes (one routine,
+// resample_mix_sample). One channel is tfp_resample_pcm.
+extern "C" int tfp_resample_mix_pcm(const int16_t* pcm, int64_t nframes, int32_t channels, int32_t rate_in, int32_t rate_out,
+                                    int16_t* out, int64_t cap, int64_t* nout) {
+  if (channels < 1 || channels > TFP_MIX_CHANNELS_MAX)
+    return fail(TFP_E_ARG, "unsupported channel count " + std::to_string(channels));
+  if (channels == 1) return tfp_resample_pcm(pcm, nframes, rate_in, rate_out, out, cap, nout);
+  if (nframes < 0 || !nout || (nframes > 0 && !pcm)) return fail(TFP_E_ARG, "bad argument");
+  std::shared_ptr<const tfp::ResampleTable> t;
+  if (int rc = table_of(rate_in, rate_out, &t)) return rc;
+  const int64_t no = rate_in == rate_out ? nframes : tfp::resample_count(t->plan, nframes);
+  if (no < 0 || nframes > INT64_MAX / channels)
+    return fail(TFP_E_ARG, "frame count " + std::to_string(nframes) + " past the index range");
+  *nout = no;
+  if (!out && cap == 0) return TFP_OK;  // size query
+  if (!out || cap < no) return fail(TFP_E_CAPACITY, "pcm buffer holds " + std::to_string(cap) + " of " + std::to_string(no) + " samples");
+  if (rate_in == rate_out) {  // equal rates: the integer mean, the filter is not run
+    for (int64_t i = 0; i < nframes; i++) {
+      int32_t S = 0;
+      for (int32_t c = 0; c < channels; c++) S += pcm[i * channels + c];
+      out[i] = tfp::resample_mix_mean(S, channels);
+    }
+    return TFP_OK;
+  }
+  tfp::resample_mix_clip(*t, pcm, nframes, channels, out);
+  return TFP_OK;
+}

@@ -97,6 +97,83 @@ TFP_RS_HD int16_t resample_sample(const ResamplePlan& P, const int16_t* __restri
   return resample_round(acc);
 }
 
+// ---- the multichannel form: interleaved int16 frames of C channels, downmixed and converted -------
+// (include/tiresias_fp.h, "rate-normalised ingest of multichannel int16"). The converter is linear and
+// exact, so the exact sum over channels commutes with the exact sum over taps:
+//   S[i] = sum_c x[i][c]                       (exact; 0 outside the clip's own frames)
+//   acc  = sum_k h[p][k] S[i0 + k]             (exact, 64-bit: |h S| reaches 2^35 at C = 32, |acc| < 2^37)
+//   y[n] = clamp(floor((acc + 16384 C) / (32768 C)), -32768, 32767)
+// with L, M, k_lo, ntaps, h and n_out those of the pair's own table. C = 1 is resample_sample bit for
+// bit. Equal rates run no filter (an identity tap of 32768 is no int16): y[i] = floor((2 S[i] + C) / (2 C)).
+constexpr int32_t kRsMixChannelsMax = 32;  // TFP_MIX_CHANNELS_MAX
+// Channel sums (int32) a workgroup of tfp_resample_mix.hip stages per tile; a pair whose span passes it
+// takes the kernel's global-memory form (tests read it here, as they read kRsTile).
+constexpr int32_t kRsMixSpanMax = 15360;
+
+// floor((acc + 16384 C) / (32768 C)), clamped. floor(floor(a / 32768) / C) = floor(a / (32768 C)) for
+// C >= 1, so the 64-bit part is one arithmetic shift and the division is a 32-bit one (|q| < 2^23).
+TFP_RS_HD int16_t resample_mix_round(int64_t acc, int32_t C) {
+  const int32_t q = (int32_t)((acc + (int64_t)16384 * C) >> 15);
+  int32_t y = q / C;
+  if (q - y * C < 0) y--;  // C++ truncates: floor
+  return (int16_t)(y < -32768 ? -32768 : y > 32767 ? 32767 : y);
+}
+
+// Equal rates: the integer mean of a frame's channel sum, rounded half up.
+TFP_RS_HD int16_t resample_mix_mean(int32_t S, int32_t C) {
+  const int32_t q = 2 * S + C, d = 2 * C;  // |q| <= 2^21 + 32
+  int32_t y = q / d;
+  if (q - y * d < 0) y--;
+  return (int16_t)y;  // (a mean of int16 values rounded half up stays in int16)
+}
+
+// Output sample n of one clip over its channel sums: resample_sample with S in x's place. S holds the
+// sums of the frames [x_lo, x_hi) (frame i at S[i - x_lo]); every frame outside counts as 0.
+TFP_RS_HD int16_t resample_mix_sample(const ResamplePlan& P, const int16_t* __restrict__ taps, const int32_t* __restrict__ S,
+                                      int64_t x_lo, int64_t x_hi, int64_t n, int32_t C) {
+  const int64_t t = n * P.M, i0 = t / P.L, p = t - i0 * P.L;
+  int64_t ka = P.k_lo, kb = (int64_t)P.k_lo + P.ntaps - 1;
+  if (ka < x_lo - i0) ka = x_lo - i0;
+  if (kb > x_hi - 1 - i0) kb = x_hi - 1 - i0;
+  if (kb < ka) return 0;  // no frame under the filter
+  const int16_t* __restrict__ h = taps + p * P.ntaps + (ka - P.k_lo);
+  const int32_t* __restrict__ s = S + (i0 + ka - x_lo);
+  const int32_t cnt = (int32_t)(kb - ka + 1);  // <= ntaps
+  int64_t acc = 0;
+  for (int32_t j = 0; j < cnt; j++) acc += (int64_t)h[j] * (int64_t)s[j];  // |product| <= 2^35
+  return resample_mix_round(acc, C);
+}
+
+// The same over the clip's interleaved frames themselves (frame i, channel c at x[i * C + c], frames
+// [0, n_in)): the channels are summed per tap. The kernel's form for a span past kRsMixSpanMax.
+TFP_RS_HD int16_t resample_mix_sample_frames(const ResamplePlan& P, const int16_t* __restrict__ taps,
+                                             const int16_t* __restrict__ x, int64_t n_in, int64_t n, int32_t C) {
+  const int64_t t = n * P.M, i0 = t / P.L, p = t - i0 * P.L;
+  int64_t ka = P.k_lo, kb = (int64_t)P.k_lo + P.ntaps - 1;
+  if (ka < -i0) ka = -i0;
+  if (kb > n_in - 1 - i0) kb = n_in - 1 - i0;
+  if (kb < ka) return 0;
+  const int16_t* __restrict__ h = taps + p * P.ntaps + (ka - P.k_lo);
+  const int16_t* __restrict__ s = x + (i0 + ka) * C;
+  const int32_t cnt = (int32_t)(kb - ka + 1);
+  int64_t acc = 0;
+  for (int32_t j = 0; j < cnt; j++) {
+    int32_t sum = 0;
+    for (int32_t c = 0; c < C; c++) sum += (int32_t)s[(int64_t)j * C + c];
+    acc += (int64_t)h[j] * (int64_t)sum;
+  }
+  return resample_mix_round(acc, C);
+}
+
+// The channel sums of nframes interleaved frames.
+inline void resample_mix_sums(const int16_t* x, int64_t nframes, int32_t C, int32_t* S) {
+  for (int64_t i = 0; i < nframes; i++) {
+    int32_t sum = 0;
+    for (int32_t c = 0; c < C; c++) sum += (int32_t)x[i * C + c];
+    S[i] = sum;
+  }
+}
+
 struct ResampleTable {
   ResamplePlan plan;
   std::vector<int16_t> taps;  // [L][ntaps]
@@ -157,6 +234,14 @@ inline void resample_clip(const ResampleTable& T, const int16_t* x, int64_t n_in
   for (int64_t n = 0; n < n_out; n++) out[n] = resample_sample(T.plan, T.taps.data(), x, 0, n_in, n);
 }
 
+// One multichannel clip on the host: out[resample_count(nframes)].
+inline void resample_mix_clip(const ResampleTable& T, const int16_t* x, int64_t nframes, int32_t C, int16_t* out) {
+  std::vector<int32_t> S((size_t)nframes);
+  resample_mix_sums(x, nframes, C, S.data());
+  const int64_t n_out = resample_count(T.plan, nframes);
+  for (int64_t n = 0; n < n_out; n++) out[n] = resample_mix_sample(T.plan, T.taps.data(), S.data(), 0, nframes, n, C);
+}
+
 // The process's tables (tfp_resample.cpp): built once per rate pair, shared by the host routine and
 // every engine. nullptr for a bad or unsupported pair, *bad_rate telling which.
 std::shared_ptr<const ResampleTable> resample_table(int32_t rate_in, int32_t rate_out, bool* bad_rate);
@@ -180,6 +265,15 @@ inline void resample_tiles(const int64_t* out_off, int32_t nclips, std::vector<i
 hipError_t launch_resample(const ResamplePlan& P, const int16_t* d_taps, const int16_t* d_in, const int64_t* d_in_off,
                            const int64_t* d_out_off, const int32_t* d_toff, const int32_t* d_tclip, int32_t ntiles,
                            int16_t* d_out, hipStream_t stream);
+
+// The multichannel launch (tfp_resample_mix.hip): clip c is the frames [in_off[c], in_off[c + 1]) of d_in,
+// C interleaved int16 each (its first sample at d_in[in_off[c] * C]; d_in itself 4-byte aligned), the
+// outputs and tiles as launch_resample's. downmix: equal rates, out_off = in_off, no table is read (P
+// and d_taps are ignored). *staged receives whether the LDS form ran (a plan's span within
+// kRsMixSpanMax; the downmix always). One launch; ntiles = 0 launches nothing.
+hipError_t launch_resample_mix(const ResamplePlan& P, const int16_t* d_taps, bool downmix, int32_t C, const int16_t* d_in,
+                               const int64_t* d_in_off, const int64_t* d_out_off, const int32_t* d_toff,
+                               const int32_t* d_tclip, int32_t ntiles, int16_t* d_out, hipStream_t stream, bool* staged);
 #endif
 
 }  // namespace tfp

@@ -150,6 +150,47 @@ extern "C" int tfp_wav_decode(const void* bytes, int64_t nbytes, int16_t* pcm, i
   return TFP_OK;
 }
 
+// Interleaved form: 8/16-bit integer PCM of 1 to 32 channels, the samples as stored (frame i, channel c
+// at pcm[i * channels + c]), for the multichannel rate forms (tfp_resample_mix_pcm,
+// tfp_fingerprint_mix_rate_batch), which downmix and convert in integers. No downmix happens here.
+extern "C" int tfp_wav_decode_interleaved(const void* bytes, int64_t nbytes, int16_t* pcm, int64_t cap, int64_t* nframes,
+                                          int32_t* channels, int32_t* sample_rate) {
+  if (!bytes || nbytes < 0 || !nframes || cap < 0 || (cap > 0 && !pcm)) return fail(TFP_E_ARG, "bad argument");
+  WavData w;
+  if (const int rc = find_data(static_cast<const uint8_t*>(bytes), (uint64_t)nbytes, &w)) return rc;
+  const WavFormat& f = w.f;
+  if (f.tag != kFormatPcm)
+    return fail(TFP_E_FORMAT, "format tag " + std::to_string(f.tag) + " is not integer PCM (float and G.711 are not taken)");
+  if (f.bits != 16 && f.bits != 8)
+    return fail(TFP_E_FORMAT, std::to_string(f.bits) + "-bit samples: only 8- and 16-bit PCM map exactly to int16");
+  if (f.channels < 1 || f.channels > TFP_MIX_CHANNELS_MAX)
+    return fail(TFP_E_FORMAT, std::to_string(f.channels) + " channels: 1 to " + std::to_string(TFP_MIX_CHANNELS_MAX) + " are taken");
+  if (f.rate == 0 || f.rate > (uint32_t)INT32_MAX) return fail(TFP_E_FORMAT, "bad sample rate");
+  const uint32_t width = f.bits / 8;
+  if (f.block_align != width * f.channels) return fail(TFP_E_FORMAT, "block align does not match the format");
+  const int64_t nf = (int64_t)(w.size / f.block_align), ns = nf * f.channels;  // a trailing partial frame is dropped
+  *nframes = nf;
+  if (channels) *channels = (int32_t)f.channels;
+  if (sample_rate) *sample_rate = (int32_t)f.rate;
+  if (!pcm) return TFP_OK;  // size query
+  if (cap < ns) return fail(TFP_E_CAPACITY, "pcm buffer holds " + std::to_string(cap) + " of " + std::to_string(ns) + " samples");
+  const uint8_t* d = w.data;
+  if (width == 2) {
+    for (int64_t i = 0; i < ns; ++i) pcm[i] = (int16_t)le16(d + 2 * i);
+  } else {
+    for (int64_t i = 0; i < ns; ++i) pcm[i] = (int16_t)(((int)d[i] - 128) * 256);
+  }
+  return TFP_OK;
+}
+
+extern "C" int tfp_wav_read_interleaved(const char* path, int16_t* pcm, int64_t cap, int64_t* nframes, int32_t* channels,
+                                        int32_t* sample_rate) {
+  std::vector<uint8_t> buf;
+  const int rc = read_file(path, buf);
+  if (rc) return rc;
+  return tfp_wav_decode_interleaved(buf.data(), (int64_t)buf.size(), pcm, cap, nframes, channels, sample_rate);
+}
+
 // fp32 form: every PCM width and float data, any channel count, as aubio 0.4.5's sndfile and
 // wavread sources compute the mono hop (aubio_source_do with its default downmix): each sample
 // to fp32 (unsigned 8-bit (u - 128) / 128, w-bit signed x / 2^(w-1) with 32-bit x first rounded

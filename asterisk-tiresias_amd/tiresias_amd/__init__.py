@@ -4,7 +4,7 @@ The compute lives in lib/libtiresias_fp.so (HIP, gfx950) behind include/tiresias
 this package is its ctypes binding plus a mirror of the reference's fp_handler interface.
 """
 from ._lib import LIB_PATH, NULL_MICRO, TfpError, header_symbols, lib  # noqa: F401
-from .engine import (ALAW, FRAME_DTYPE, ULAW, Engine, Group, GroupLive, GroupStream, Live, Plan, Stream, census_at_least,  # noqa: F401
-                     decode_g711, decode_wav_g711, device_count, frame_count, params, read_wav_g711, resample_count, resample_pcm,
+from .engine import (ALAW, FRAME_DTYPE, MIX_CHANNELS_MAX, ULAW, Engine, Group, GroupLive, GroupStream, Live, Plan, Stream, census_at_least,  # noqa: F401
+                     decode_g711, decode_wav_g711, decode_wav_interleaved, device_count, frame_count, params, read_wav_g711, read_wav_interleaved, resample_count, resample_mix_pcm, resample_pcm,
                      resample_taps, sliding_windows, synth_pcm)
 from .fp_handler import FpHandler  # noqa: F401

@@ -124,6 +124,23 @@ _SIGS = {
     "tfp_group_search_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_group_search_scoped_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams),
                                                      P, C.c_int32, P, P, P]),
+    "tfp_wav_decode_interleaved": (C.c_int, [P, C.c_int64, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]),
+    "tfp_wav_read_interleaved": (C.c_int, [C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32)]),
+    "tfp_resample_mix_pcm": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_fingerprint_mix_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                 C.POINTER(C.c_int64)]),
+    "tfp_search_mix_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_search_scoped_mix_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_resample_mix_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 4),
+    "tfp_group_fingerprint_mix_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                       C.POINTER(C.c_int64)]),
+    "tfp_group_search_mix_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.POINTER(SearchParams), P]),
+    "tfp_group_search_scoped_mix_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                         C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
     "tfp_fingerprint_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
     "tfp_search_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_fingerprint_pcm": (C.c_int, [P, P, C.c_int64, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),

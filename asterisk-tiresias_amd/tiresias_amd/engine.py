@@ -100,6 +100,44 @@ def resample_pcm(pcm, rate_in: int, rate_out: int) -> np.ndarray:
     return out
 
 
+MIX_CHANNELS_MAX = 32  # TFP_MIX_CHANNELS_MAX
+
+
+def resample_mix_pcm(pcm, channels: int, rate_in: int, rate_out: int) -> np.ndarray:
+    """tfp_resample_mix_pcm: one clip of interleaved int16 frames ([nframes, channels], or flat) downmixed and
+    brought to rate_out, the map the GPU mix forms compute (exact)."""
+    pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+    channels = int(channels)
+    nfr = len(pcm) // channels if channels > 0 else 0
+    n = C.c_int64()
+    check(lib().tfp_resample_mix_pcm(pcm.ctypes.data, nfr, channels, int(rate_in), int(rate_out), None, 0, C.byref(n)))
+    out = np.empty(n.value, np.int16)
+    check(lib().tfp_resample_mix_pcm(pcm.ctypes.data, nfr, channels, int(rate_in), int(rate_out), out.ctypes.data, len(out),
+                                     C.byref(n)))
+    return out
+
+
+def _wav_interleaved(call) -> tuple[np.ndarray, int]:
+    n, ch, sr = C.c_int64(), C.c_int32(), C.c_int32()
+    check(call(None, 0, C.byref(n), C.byref(ch), C.byref(sr)))
+    pcm = np.empty(n.value * ch.value, np.int16)
+    check(call(pcm.ctypes.data, len(pcm), C.byref(n), C.byref(ch), C.byref(sr)))
+    return pcm.reshape(n.value, ch.value), sr.value
+
+
+def decode_wav_interleaved(data: bytes) -> tuple[np.ndarray, int]:
+    """tfp_wav_decode_interleaved: RIFF/WAVE bytes of 8/16-bit integer PCM with 1 to 32 channels ->
+    (int16[nframes, channels] as stored, native rate). TfpError(TFP_E_FORMAT) for every other file."""
+    buf = C.create_string_buffer(bytes(data), len(data))
+    return _wav_interleaved(lambda x, cap, n, ch, sr: lib().tfp_wav_decode_interleaved(buf, len(data), x, cap, n, ch, sr))
+
+
+def read_wav_interleaved(path: str) -> tuple[np.ndarray, int]:
+    """tfp_wav_read_interleaved: decode_wav_interleaved of a file."""
+    p = path.encode()
+    return _wav_interleaved(lambda x, cap, n, ch, sr: lib().tfp_wav_read_interleaved(p, x, cap, n, ch, sr))
+
+
 def _wav_g711(call) -> tuple[np.ndarray, int, int]:
     n, sr, law = C.c_int64(), C.c_int32(), C.c_int32()
     check(call(None, 0, C.byref(n), C.byref(sr), C.byref(law)))
@@ -351,6 +389,55 @@ class _RateCalls:
         return Engine._candidates(out, counts, nq, k), list(fc[:nq])
 
 
+class _MixCalls:
+    """Rate-normalised ingest of multichannel int16, the same calls on an Engine and on a Group, as _RateCalls:
+    pcm holds interleaved frames of `channels` int16 each and offsets count frames."""
+
+    resample_mix_pcm = staticmethod(resample_mix_pcm)
+
+    @staticmethod
+    def _mix_count(nframes: int, rate_in: int, rate_out: int) -> int:
+        return int(nframes) if rate_in == rate_out else max(resample_count(nframes, rate_in, rate_out), 0)
+
+    def fingerprint_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int) -> np.ndarray:
+        """The frames of fingerprint_batch(resample_mix_pcm(clip), rate_out) per clip, bit for bit."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nclips = len(offsets) - 1
+        n = sum(frame_count(self._mix_count(int(offsets[i + 1] - offsets[i]), rate_in, rate_out)) for i in range(nclips))
+        out = np.zeros(max(n, 1), FRAME_DTYPE)
+        got = C.c_int64()
+        self._chk(self._fn("_fingerprint_mix_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nclips, int(channels),
+                                                          int(rate_in), int(rate_out), out.ctypes.data, n, C.byref(got)))
+        return out[:got.value]
+
+    def search_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams):
+        """search_pcm_batch at rate_out on the downmixed, resampled queries."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq = len(offsets) - 1
+        res = (Result * max(1, nq))()
+        self._chk(self._fn("_search_mix_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(channels),
+                                                     int(rate_in), int(rate_out), C.byref(p), res))
+        return Engine._results(res, nq)
+
+    def search_scoped_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams, scopes,
+                                     k: int):
+        """search_scoped_pcm_batch at rate_out on the downmixed, resampled queries: (rows per query, frame counts)."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        nq, k = len(offsets) - 1, int(k)
+        scopes = np.ascontiguousarray(scopes, np.int32)
+        if len(scopes) != nq:
+            raise ValueError("one scope per query")
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        fc = (C.c_int32 * max(1, nq))()
+        self._chk(self._fn("_search_scoped_mix_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(channels),
+                                                            int(rate_in), int(rate_out), C.byref(p), scopes.ctypes.data, k, out,
+                                                            counts, fc))
+        return Engine._candidates(out, counts, nq, k), list(fc[:nq])
+
+
 class _CensusCalls:
     """The match census, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*), as _ScopedCalls."""
 
@@ -385,7 +472,7 @@ class _CensusCalls:
                             (int(sample_rate),), p, scopes, nbins)
 
 
-class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls):
+class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls):
     """One engine per GPU (tfp_engine)."""
     _PFX = "tfp"
 
@@ -484,6 +571,13 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls):
         v = [C.c_int64() for _ in range(3)]
         self._chk(lib().tfp_resample_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("launches", "samples_in", "samples_out"), (x.value for x in v)))
+
+    def resample_mix_stats(self) -> dict:
+        """tfp_resample_mix_stats: the multichannel kernel's launches, the frames they read, the samples they
+        wrote, and how many of the launches staged their channel sums in LDS."""
+        v = [C.c_int64() for _ in range(4)]
+        self._chk(lib().tfp_resample_mix_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("launches", "frames_in", "samples_out", "staged_launches"), (x.value for x in v)))
 
     def fingerprint_stats(self) -> dict:
         """tfp_fingerprint_stats: fingerprint kernel launches so far, by kernel."""
@@ -1159,7 +1253,7 @@ class Plan:
             self._h = C.c_void_p()
 
 
-class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls):
+class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls):
     """tfp_group: one engine per listed device (a device may repeat), the enrolled clips sharded
     over them, searches combined on the host (tiresias_fp.h, device groups)."""
     _PFX = "tfp_group"
@@ -1241,6 +1335,15 @@ class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls):
             for key, x in zip(tot, v):
                 tot[key] += x.value
         return tot
+
+    def resample_mix_stats(self) -> list:
+        """tfp_resample_mix_stats of every shard's engine, in shard order."""
+        keys, out = ("launches", "frames_in", "samples_out", "staged_launches"), []
+        for sh in range(self.size()):
+            v = [C.c_int64() for _ in range(4)]
+            check(lib().tfp_resample_mix_stats(lib().tfp_group_engine(self._h, sh), *[C.byref(x) for x in v]))
+            out.append(dict(zip(keys, (x.value for x in v))))
+        return out
 
     def fingerprint_g711_batch(self, codes, offsets, law: int, sample_rate: int = 8000) -> np.ndarray:
         codes = np.ascontiguousarray(codes, np.uint8)

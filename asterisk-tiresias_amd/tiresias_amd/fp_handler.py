@@ -28,7 +28,7 @@ import numpy as np
 from . import dbio
 from ._lib import TFP_RANK_MAX, TfpError
 from .engine import (ALAW, ULAW, Engine, decode_g711, frame_count as frame_count_of, params, read_wav, read_wav_f32,
-                     read_wav_g711, resample_count, resample_pcm)
+                     read_wav_g711, read_wav_interleaved, resample_count, resample_mix_pcm, resample_pcm)
 
 TFP_E_FORMAT = -8
 
@@ -93,16 +93,22 @@ def write_wav_mono16(filename: str, pcm: np.ndarray, sample_rate: int = 8000):
 class FpHandler:
     """One loaded module instance (g_db_ctx + the GPU engine)."""
 
-    def __init__(self, device: int = 0, backup_path: str | None = None, index_rate: int = 0):
+    def __init__(self, device: int = 0, backup_path: str | None = None, index_rate: int = 0, mix_channels: bool = False):
         """backup_path: the snapshot file (the reference hard-codes dbio.DEF_BACKUP_DATABASE);
         None keeps the state in memory only. index_rate: 0 takes every file at its native rate, as the
         reference does (DEF_AUBIO_SAMPLERATE 0); a rate > 0 is the index's rate (new behaviour): int16 and
         G.711 files of another rate are brought to it (tfp_resample_pcm's map: on the GPU in the
         directory enrolment, create_new_audio_info; on the host for a single file, fp_craete_audio_list_info
-        and the searches), fp32 files and files at an unsupported rate ratio are refused."""
+        and the searches), fp32 files and files at an unsupported rate ratio are refused. mix_channels
+        (with an index rate): 8/16-bit integer files of more than one channel at another rate are normalised
+        too instead of refused (tfp_resample_mix_pcm's map: the integer downmix, defined for the rate change;
+        at the index's own rate such a file keeps the fp32 path, the reference's value). It is off by
+        default, so that a handler behaves as it did before the option existed; 24/32-bit and float files
+        of another rate are refused either way."""
         self.device = device
         self.backup_path = backup_path
         self.index_rate = int(index_rate)
+        self.mix_channels = bool(mix_channels)
         self.last_error = ""  # why the last file was refused for its rate
         self.db = None
         self.engine = None
@@ -289,21 +295,41 @@ class FpHandler:
 
     def _refuse_f32(self, filename: str, sr: int) -> str:
         self.last_error = ("%s: fp32 audio at %d Hz cannot be normalised to the index rate %d Hz "
-                           "(rate conversion takes int16 and G.711 only)" % (filename, sr, self.index_rate))
+                           "(rate conversion takes 8/16-bit integer PCM and G.711 only%s)"
+                           % (filename, sr, self.index_rate, "" if self.mix_channels else ", of several channels with mix_channels"))
         return self.last_error
+
+    def _read_interleaved(self, filename: str):
+        """With mix_channels, an fp32 file of another rate as int16[nframes, channels], if it is 8/16-bit
+        integer PCM of 1 to 32 channels (tfp_wav_read_interleaved); None for the files that stay refused
+        (24/32-bit, float; every fp32 file without mix_channels)."""
+        if not self.mix_channels:
+            return None
+        try:
+            return read_wav_interleaved(filename)[0]
+        except TfpError as e:
+            if e.code != TFP_E_FORMAT:
+                raise
+        return None
 
     def _read_query(self, filename: str):
         """read_audio for a search: with an index rate set, a file of another rate is normalised on the host
-        (G.711 expanded first); an fp32 file of another rate raises TfpError(TFP_E_FORMAT)."""
+        (G.711 expanded first; an 8/16-bit integer file of several channels by tfp_resample_mix_pcm); a
+        24/32-bit or float file of another rate raises TfpError(TFP_E_FORMAT)."""
         pcm, sr = read_audio(filename)
         if not self._other_rate(sr):
             return pcm, sr
         if pcm.dtype == np.float32:
-            raise TfpError(TFP_E_FORMAT, self._refuse_f32(filename, sr))
+            frames = self._read_interleaved(filename)
+            if frames is None:
+                raise TfpError(TFP_E_FORMAT, self._refuse_f32(filename, sr))
+            return resample_mix_pcm(frames, frames.shape[1], sr, self.index_rate), self.index_rate
         return resample_pcm(pcm, sr, self.index_rate), self.index_rate
 
-    def _fingerprint(self, samples: np.ndarray, offsets, sr: int, law=None):
+    def _fingerprint(self, samples: np.ndarray, offsets, sr: int, law=None, channels: int = 1):
         if self._other_rate(sr):  # (int16: the enrolment expanded G.711 and refused fp32)
+            if channels > 1:  # interleaved frames, offsets in frames
+                return self.engine.fingerprint_mix_rate_batch(samples, offsets, channels, sr, self.index_rate)
             return self.engine.fingerprint_rate_batch(samples, offsets, sr, self.index_rate)
         if law is not None:
             return self.engine.fingerprint_g711_batch(samples, offsets, law, sr)
@@ -318,8 +344,9 @@ class FpHandler:
         fp_craete_audio_list_info per file, skipping files that fail. Here the same catalog rows
         are written in the same order and with the same per-context MD5 dedup (also among the
         files of this scan). The fingerprints of all new files are computed by one fingerprint
-        call per sample rate and kind (int16, fp32, or G.711 codes of one law, which go to the GPU
-        as codes) and enrolled by one tfp_index_add_batch."""
+        call per sample rate and kind (int16, fp32, G.711 codes of one law, which go to the GPU
+        as codes, or with an index rate set interleaved int16 of one channel count) and enrolled by one
+        tfp_index_add_batch."""
         ctx = self.fp_get_context_list_info(context) if context is not None else None
         if ctx is None or ctx["directory"] is None:
             return False
@@ -342,12 +369,19 @@ class FpHandler:
                 pcm, sr, law = read_audio_codes(path)
             except TfpError:
                 continue
+            channels = 1
             if self._other_rate(sr):
                 if law is not None:
                     pcm, law = decode_g711(pcm, law), None  # (the converter takes int16)
                 elif pcm.dtype == np.float32:
-                    self._refuse_f32(path, sr)  # refused, as _read_query refuses it for a search
-                    continue
+                    try:
+                        pcm = self._read_interleaved(path)
+                    except TfpError:
+                        continue
+                    if pcm is None:
+                        self._refuse_f32(path, sr)  # refused, as _read_query refuses it for a search
+                        continue
+                    channels = pcm.shape[1]  # (its frames are counted below: len(pcm))
                 if resample_count(len(pcm), sr, self.index_rate) < 0:  # before any catalog row is written
                     self.last_error = "%s: unsupported rate ratio %d -> %d" % (path, sr, self.index_rate)
                     continue
@@ -355,13 +389,13 @@ class FpHandler:
             self.db.execute("insert into audio_list(uuid, name, context, hash) values (?, ?, ?, ?);",
                             (uuid, os.path.basename(path), context, h))
             seen.add(h)
-            new.append((uuid, pcm, sr, law))
-        for sr, dt, law in sorted({(n[2], n[1].dtype.str, -1 if n[3] is None else n[3]) for n in new}):
+            new.append((uuid, pcm, sr, law, channels))
+        for sr, dt, law, channels in sorted({(n[2], n[1].dtype.str, -1 if n[3] is None else n[3], n[4]) for n in new}):
             law = None if law < 0 else law
-            group = [n for n in new if n[2] == sr and n[1].dtype.str == dt and n[3] == law]
-            lens = [len(n[1]) for n in group]
+            group = [n for n in new if n[2] == sr and n[1].dtype.str == dt and n[3] == law and n[4] == channels]
+            lens = [len(n[1]) for n in group]  # (frames, for interleaved audio)
             off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-            fr = self._fingerprint(np.concatenate([n[1] for n in group]), off, sr, law)
+            fr = self._fingerprint(np.concatenate([n[1].reshape(-1) for n in group]), off, sr, law, channels)
             if self._other_rate(sr):
                 lens = [resample_count(n, sr, self.index_rate) for n in lens]
             foff = np.concatenate([[0], np.cumsum([(n + 255) // 256 for n in lens])]).astype(np.int64)

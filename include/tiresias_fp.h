@@ -1284,8 +1284,9 @@ int tfp_group_stream_push_g711(tfp_group_stream* st, const uint8_t* codes, int32
  * A rate <= 0 is TFP_E_ARG with "bad sample rate"; a pair with L * ntaps above 2^20 is TFP_E_ARG with
  * "unsupported rate ratio". rate_in == rate_out runs no filter: the rate forms are then the plain forms.
  * Not covered: tfp_stream_push (the ring), fp32 input. A live object takes its ticks at another rate
- * through tfp_live_create_rate (the last section of this header). No claim of equality with any other
- * resampler is made. */
+ * through tfp_live_create_rate (the last section of this header). Interleaved multichannel int16 has
+ * forms of its own (tfp_fingerprint_mix_rate_batch, the section after tfp_synchronize). No claim of
+ * equality with any other resampler is made. */
 /* n_out for nsamples at rate_in; 0 for nsamples <= 0, -1 for a bad or unsupported pair. Host-only. */
 int64_t tfp_resample_count(int64_t nsamples, int32_t rate_in, int32_t rate_out);
 /* The pair's table taps[L][ntaps] and its shape (any of L, M, k_lo, ntaps may be NULL). taps == NULL
@@ -1345,6 +1346,81 @@ int tfp_synth_pcm_device(tfp_engine* eng, const tfp_synth_spec* specs, int32_t n
 
 /* ---- misc --------------------------------------------------------------------------- */
 int tfp_synchronize(tfp_engine* eng, void* stream);
+
+/* ---- rate-normalised ingest of multichannel int16: downmix and convert on the GPU (new) -------- */
+/* The files the rate forms were built for are seldom mono: a prompt master is 44.1 or 48 kHz stereo, a
+ * MixMonitor recording is two-channel. These forms take interleaved int16 frames of C channels
+ * (1 <= C <= TFP_MIX_CHANNELS_MAX; frame i, channel c at pcm[i * C + c]) at rate_in to mono int16 at
+ * rate_out. Clip lengths and offsets[] count FRAMES, not samples. L, M, k_lo, ntaps, h[p][k] and n_out
+ * are exactly those of the pair's table above (tfp_resample_taps, tfp_resample_count of the frame
+ * count); no new table is built. The converter is linear and exact, so the exact sum over channels
+ * commutes with the exact sum over taps:
+ *   S[i] = sum_c x[i][c]                        (exact; 0 outside the clip's own frames)
+ *   acc  = sum_k h[p][k] S[i0 + k]              (exact, 64-bit; i0 = n M div L, p = n M mod L)
+ *   y[n] = clamp(floor((acc + 16384 C) / (32768 C)), -32768, 32767)
+ * The division is a floor, not a truncation. One exact sum, one rounding, one clamp: host and GPU agree
+ * bit for bit, and C = 1 is tfp_resample_pcm bit for bit. A product h S needs more than 32 bits from
+ * C = 3 on; |acc| stays below 2^37 for C <= 32. rate_in == rate_out runs no filter: n_out = n_in and
+ * y[i] = floor((2 S[i] + C) / (2 C)), the integer mean rounded half up (an identity tap of 32768 does
+ * not fit the int16 table, so this is a case of its own).
+ * This is a new definition and NOT aubio's fp32 channel mean (fp_handler.c:604, :633), which lies
+ * between int16 steps. It exists for the rate change: a file at the index's own rate should keep using
+ * tfp_wav_decode_f32 and the f32 forms, which reproduce the reference.
+ * channels < 1 or > TFP_MIX_CHANNELS_MAX is TFP_E_ARG with "unsupported channel count"; a bad rate and
+ * an unsupported pair are refused as the rate forms refuse them. An argument error writes nothing to
+ * the outputs.
+ * Not covered: 24/32-bit and float input, live pushes and tfp_stream_push with more than one channel,
+ * the compiled shim, per-clip channel counts inside one call. */
+#define TFP_MIX_CHANNELS_MAX 32
+/* RIFF/WAVE -> the interleaved int16 samples as stored: integer PCM (format 1, or EXTENSIBLE with the
+ * PCM subformat), 8-bit ((u - 128) << 8) or 16-bit, 1 to TFP_MIX_CHANNELS_MAX channels. 24/32-bit,
+ * float, G.711 and more channels are TFP_E_FORMAT with a reason. *nframes receives the whole frames
+ * present (a trailing partial frame is dropped); cap counts samples, nframes * channels of them are
+ * written. Chunk skipping, unpatched and truncated data sizes, the size query (pcm == NULL, cap 0) and
+ * TFP_E_CAPACITY (with *nframes / *channels set) as tfp_wav_decode. Host-only. */
+int tfp_wav_decode_interleaved(const void* bytes, int64_t nbytes, int16_t* pcm, int64_t cap, int64_t* nframes,
+                               int32_t* channels, int32_t* sample_rate);
+int tfp_wav_read_interleaved(const char* path, int16_t* pcm, int64_t cap, int64_t* nframes, int32_t* channels,
+                             int32_t* sample_rate);
+/* One clip on the host: the map the GPU forms compute, sample for sample. The size query and
+ * TFP_E_CAPACITY as tfp_resample_pcm (*nout = tfp_resample_count(nframes), or nframes at equal rates). */
+int tfp_resample_mix_pcm(const int16_t* pcm, int64_t nframes, int32_t channels, int32_t rate_in, int32_t rate_out,
+                         int16_t* out, int64_t cap, int64_t* nout);
+/* The twins of tfp_fingerprint_rate_batch, tfp_search_rate_batch and tfp_search_scoped_rate_batch with
+ * `channels` added and offsets in frames: the frames / results / rows equal the pcm forms at rate_out
+ * over each clip's tfp_resample_mix_pcm, bit for bit. The interleaved samples are copied to the GPU as
+ * they are and downmixed and converted there by one launch (each clip on its own); the fingerprint
+ * launch is the one an int16 batch of the output lengths takes (tfp_fingerprint_stats counts it alike).
+ * channels == 1 IS the rate form (counted by tfp_resample_stats); at equal rates it is the plain form.
+ * Equal rates with channels > 1 run the downmix alone. Not coalesced. */
+int tfp_fingerprint_mix_rate_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
+                                   int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                   int64_t* nframes);
+int tfp_search_mix_rate_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                              int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                              tfp_result* out);
+int tfp_search_scoped_mix_rate_batch(tfp_engine* eng, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                     int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                                     const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                     int32_t* frame_counts);
+/* The multichannel kernel's launches so far, the frames they read, the samples they wrote, and how many
+ * of the launches ran the form that stages channel sums in LDS (the others read global memory per tap:
+ * a pair whose tile spans more than 15,360 frames). Counted where the kernel is issued; tfp_resample_stats
+ * keeps its meaning and does not count these. Any pointer may be NULL. */
+int tfp_resample_mix_stats(tfp_engine* eng, int64_t* launches, int64_t* frames_in, int64_t* samples_out,
+                           int64_t* staged_launches);
+/* The same on a group, split and combined exactly as the rate twins: fingerprint clips are cut by their
+ * frames at rate_out, a search batch is converted on every shard. */
+int tfp_group_fingerprint_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
+                                         int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                         int64_t* nframes);
+int tfp_group_search_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                    int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                                    tfp_result* out);
+int tfp_group_search_scoped_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nqueries,
+                                           int32_t channels, int32_t rate_in, int32_t rate_out,
+                                           const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                                           tfp_candidate* out, int32_t* counts, int32_t* frame_counts);
 
 /* ---- live calls at another rate: each push converted to the index's rate on the GPU (new) -------- */
 /* An Asterisk channel is often not at the index's rate (slin16 from G.722, slin48 from Opus, an 8 kHz
