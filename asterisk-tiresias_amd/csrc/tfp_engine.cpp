@@ -347,6 +347,7 @@ struct tfp_engine {
   DevBuf rs_in;
   int64_t n_rs_launch = 0, n_rs_in = 0, n_rs_out = 0;  // tfp_resample_stats
   int64_t n_mix_launch = 0, n_mix_in = 0, n_mix_out = 0, n_mix_staged = 0;  // tfp_resample_mix_stats
+  int64_t n_wide_launch = 0, n_wide_in = 0, n_wide_out = 0, n_wide_staged = 0;  // tfp_resample_wide_stats
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   FpLaunchStats fpstats;  // fingerprint launches so far per kernel (tfp_fingerprint_stats)
@@ -537,9 +538,11 @@ struct RateSrc {
 // A batch of interleaved int16 clips of `channels` channels laid end to end (clip c = the frames
 // [in_off[c], in_off[c + 1]) of pcm, channels samples each, in_off[0] = 0) and the table that brings
 // their channel sums to the call's rate; tab == nullptr at equal rates (the downmix alone, in_off = the
-// call's own offsets). The call's lens are the output lengths.
+// call's own offsets). The call's lens are the output lengths. The wide forms (wide_source) hand over int32
+// Q31 frames instead: q31 is set, pcm is not read, and the launch is tfp_resample_wide.hip's.
 struct MixSrc {
   const int16_t* pcm;
+  const int32_t* q31 = nullptr;
   std::vector<int64_t> in_off;
   int32_t channels;
   const ResampleTable* tab;
@@ -557,12 +560,14 @@ struct MixSrc {
 // rate: the clips are int16 at another rate laid end to end at rate->pcm (ptrs is not read) and lens
 // are their lengths at sr. The samples go to the device as they are and resample_kernel writes their
 // conversion into e->pcm; the layout, tile choice and launch are the int16 call's of lens.
-// mix: the same for interleaved multichannel int16 at mix->pcm, by resample_mix_kernel (offsets in frames).
+// mix: the same for interleaved multichannel int16 at mix->pcm, by resample_mix_kernel (offsets in frames),
+// or for interleaved int32 Q31 at mix->q31, by resample_wide_kernel.
 int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens, bool f32, int32_t nclips, int32_t sr,
                      int64_t* nframes_out, std::vector<int64_t>* foff_out, bool exact_q = true,
                      const G711Src* g711 = nullptr, const RateSrc* rate = nullptr, const MixSrc* mix = nullptr) {
   const size_t ss = f32 ? sizeof(float) : sizeof(int16_t);
-  const size_t hs = g711 ? sizeof(uint8_t) : ss;  // bytes per sample as the host hands them over
+  const bool wide = mix && mix->q31;
+  const size_t hs = g711 ? sizeof(uint8_t) : wide ? sizeof(int32_t) : ss;  // bytes per sample as the host hands them over
   const bool flat = g711 || rate || mix;          // one flat source array in front of e->pcm
   const std::vector<int64_t>* rs_in_off = rate ? &rate->in_off : mix ? &mix->in_off : nullptr;  // a converting launch's input offsets
   const DspTables* T;
@@ -655,6 +660,7 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     if (contiguous) {
       const void* src = g711   ? static_cast<const void*>(g711->codes)
                         : rate ? static_cast<const void*>(rate->pcm)
+                        : wide ? static_cast<const void*>(mix->q31)
                         : mix  ? static_cast<const void*>(mix->pcm)
                                : ptrs[0];
       if (n_src) memcpy(h, src, hs * n_src);
@@ -715,7 +721,8 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
       if ((rc = upload(e, e->g711_codes, g711->codes, hs * ns))) return rc;
       d_pcm = e->g711_codes.p;
     } else if (rs_in_off) {
-      if ((rc = upload(e, e->rs_in, rate ? rate->pcm : mix->pcm, hs * n_src))) return rc;
+      if ((rc = upload(e, e->rs_in, rate ? static_cast<const void*>(rate->pcm) : wide ? static_cast<const void*>(mix->q31) : mix->pcm,
+                       hs * n_src))) return rc;
       d_pcm = e->rs_in.p;
     } else {
       HIPCHK(e, e->pcm.reserve(ss * ns));
@@ -754,7 +761,23 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     e->n_rs_out += ns;
     d_pcm = e->pcm.p;
   }
-  if (mix && ns) {
+  if (wide && ns) {
+    // d_pcm holds the interleaved Q31 frames so far (staging, or rs_in): their conversion into the device PCM buffer
+    HIPCHK(e, e->pcm.reserve(ss * ns));
+    const char* r = lay_d + lay_fp;
+    ResampleWideForm form = kRsWideNone;
+    HIPCHK(e, launch_resample_wide(mix->tab ? mix->tab->plan : ResamplePlan{1, 1, 0, 1}, mix->d_taps, !mix->tab, mix->channels,
+                                   static_cast<const int32_t*>(d_pcm), reinterpret_cast<const int64_t*>(r),
+                                   reinterpret_cast<const int64_t*>(r + b_ro), reinterpret_cast<const int32_t*>(r + 2 * b_ro),
+                                   reinterpret_cast<const int32_t*>(r + 2 * b_ro + b_rt), rs_toff[nclips],
+                                   e->pcm.as<int16_t>(), e->stream, &form));
+    e->n_wide_launch++;
+    e->n_wide_in += mix->in_off[nclips];
+    e->n_wide_out += ns;
+    e->n_wide_staged += form != kRsWideGlobal ? 1 : 0;
+    d_pcm = e->pcm.p;
+  }
+  if (mix && !wide && ns) {
     // d_pcm holds the interleaved frames so far (staging, or rs_in): their downmix and conversion into the
     // device PCM buffer (the staging and rs_in are 256-byte aligned, as the launch's word reads need)
     HIPCHK(e, e->pcm.reserve(ss * ns));
@@ -4462,6 +4485,98 @@ int tfp_resample_mix_stats(tfp_engine* e, int64_t* launches, int64_t* frames_in,
   if (frames_in) *frames_in = e->n_mix_in;
   if (samples_out) *samples_out = e->n_mix_out;
   if (staged_launches) *staged_launches = e->n_mix_staged;
+  return TFP_OK;
+}
+
+// ---- rate-normalised ingest of 24/32-bit and float audio (tfp_resample.hpp, "the wide form") ----
+namespace {
+// The source of a batch of interleaved int32 Q31 frames: mix_source's checks, table and offsets, the range
+// the wide accumulator needs of the pair (A C < 2^30), and the frames in place of the int16 samples.
+int wide_source(tfp_engine* e, const int32_t* q31, const int64_t* offsets, int32_t n, int32_t channels, int32_t rate_in,
+                int32_t rate_out, MixSrc* ms, std::vector<int64_t>* out_off) {
+  if (int rc = mix_source(e, nullptr, offsets, n, channels, rate_in, rate_out, ms, out_off)) return rc;
+  if (ms->tab && !resample_wide_in_range(*ms->tab, channels))
+    return fail(e, TFP_E_ARG, "unsupported rate ratio %d -> %d for %d wide channels", rate_in, rate_out, channels);
+  if (ms->in_off[std::max(n, 0)] > INT64_MAX / (4 * (int64_t)channels))
+    return fail(e, TFP_E_ARG, "%lld frames past the index range", (long long)ms->in_off[std::max(n, 0)]);
+  ms->q31 = q31 && n > 0 ? q31 + offsets[0] * channels : q31;
+  return TFP_OK;
+}
+}  // namespace
+
+// The twins of the mix forms over int32 Q31 frames. One channel is a form of its own here (the samples are
+// not the rate forms' int16), and so are equal rates (a rounding and a clamp). Not coalesced.
+int tfp_fingerprint_wide_rate_batch(tfp_engine* e, const int32_t* q31, const int64_t* offsets, int32_t nclips,
+                                    int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                    int64_t* nframes) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (int rc = check_mix(e, channels, rate_in, rate_out)) return rc;
+  if (!offsets || nclips < 0 || !nframes || (!q31 && nclips && offsets[nclips] > offsets[0]))
+    return fail(e, TFP_E_ARG, "bad arguments");
+  HIPCHK(e, hipSetDevice(e->device));
+  MixSrc ms;
+  std::vector<int64_t> out_off;
+  if (int rc = wide_source(e, q31, offsets, nclips, channels, rate_in, rate_out, &ms, &out_off)) return rc;
+  const int64_t need = sample_frame_offsets(out_off.data(), nclips)[nclips];
+  *nframes = need;
+  if (need > 0 && (!out || cap < need)) return fail(e, TFP_E_CAPACITY, "need %lld frames", (long long)need);
+  if (need == 0) return TFP_OK;
+  std::vector<int64_t> lens(nclips), foff;
+  for (int32_t c = 0; c < nclips; c++) lens[c] = out_off[c + 1] - out_off[c];
+  int64_t nf;
+  if (int rc = fingerprint_host(e, nullptr, lens.data(), false, nclips, rate_out, &nf, &foff, true, nullptr, nullptr, &ms))
+    return rc;
+  return copy_frames_out(e, nf, foff, out);
+}
+
+int tfp_search_wide_rate_batch(tfp_engine* e, const int32_t* q31, const int64_t* offsets, int32_t nq, int32_t channels,
+                               int32_t rate_in, int32_t rate_out, const tfp_search_params* P, tfp_result* out) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (int rc = check_mix(e, channels, rate_in, rate_out)) return rc;
+  if (!offsets || nq < 0 || !out) return TFP_E_ARG;
+  HIPCHK(e, hipSetDevice(e->device));
+  MixSrc ms;
+  std::vector<int64_t> out_off;
+  if (int rc = wide_source(e, q31, offsets, nq, channels, rate_in, rate_out, &ms, &out_off)) return rc;
+  if (!q31 && nq && offsets[nq] > offsets[0]) return fail(e, TFP_E_ARG, "samples are NULL");
+  std::vector<int64_t> lens(nq);
+  for (int32_t i = 0; i < nq; i++) lens[i] = out_off[i + 1] - out_off[i];
+  return search_gather_impl(e, nullptr, lens.data(), nq, false, rate_out, P, out, nullptr, nullptr, &ms);
+}
+
+int tfp_search_scoped_wide_rate_batch(tfp_engine* e, const int32_t* q31, const int64_t* offsets, int32_t nq, int32_t channels,
+                                      int32_t rate_in, int32_t rate_out, const tfp_search_params* P, const int32_t* scopes,
+                                      int32_t k, tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
+  if (!e || !offsets) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (int rc0 = check_mix(e, channels, rate_in, rate_out)) return rc0;
+  // the cheap arguments first, in search_ranked's order: an argument error does no device work
+  if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
+  if (int rc0 = check_k(e, "ranked search", k)) return rc0;
+  if (int rc0 = check_params(e, "ranked search", P)) return rc0;
+  if (nq && !scopes) return fail(e, TFP_E_ARG, "scoped search: scopes is NULL");
+  if (int rc0 = check_scopes(e, "scoped search", scopes, nq, "query")) return rc0;
+  HIPCHK(e, hipSetDevice(e->device));
+  MixSrc ms;
+  std::vector<int64_t> out_off;
+  if (int rc = wide_source(e, q31, offsets, nq, channels, rate_in, rate_out, &ms, &out_off)) return rc;
+  QuerySrc src{ms.q31, out_off.data(), rate_out, true};
+  src.mix = &ms;
+  if (int rc = search_ranked(e, src, nq, P, k, out, counts, nullptr, true, scopes)) return rc;
+  for (int32_t i = 0; frame_counts && i < nq; i++) frame_counts[i] = (int32_t)tfp_frame_count(out_off[i + 1] - out_off[i]);
+  return TFP_OK;
+}
+
+int tfp_resample_wide_stats(tfp_engine* e, int64_t* launches, int64_t* frames_in, int64_t* samples_out,
+                            int64_t* staged_launches) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (launches) *launches = e->n_wide_launch;
+  if (frames_in) *frames_in = e->n_wide_in;
+  if (samples_out) *samples_out = e->n_wide_out;
+  if (staged_launches) *staged_launches = e->n_wide_staged;
   return TFP_OK;
 }
 

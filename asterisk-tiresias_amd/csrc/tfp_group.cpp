@@ -586,19 +586,25 @@ int group_mix_plan(tfp_group* g, int32_t channels, int32_t rate_in, int32_t rate
   if (channels < 1 || channels > TFP_MIX_CHANNELS_MAX) return gfail(g, TFP_E_ARG, "unsupported channel count %d", channels);
   return group_rate_plan(g, rate_in, rate_out, P);
 }
-}  // namespace
 
-// Interleaved multichannel int16 on a group (tfp_resample.hpp, "the multichannel form"): offsets count
-// frames; the clips are cut by their frames at rate_out exactly as tfp_group_fingerprint_rate_batch cuts
-// its own, and each shard downmixes and converts the clips it fingerprints. One channel is the rate form.
-int tfp_group_fingerprint_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
-                                         int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
-                                         int64_t* nframes) {
-  if (!g) return TFP_E_ARG;
-  if (channels == 1) return tfp_group_fingerprint_rate_batch(g, pcm, offsets, nclips, rate_in, rate_out, out, cap, nframes);
-  tfp::ResamplePlan P;
-  if (int rc = group_mix_plan(g, channels, rate_in, rate_out, &P)) return rc;
-  if (!offsets || nclips < 0 || !nframes) return TFP_E_ARG;
+// A wide form's pair on a group: the mix refusals, then the range the wide accumulator needs (A C < 2^30).
+int group_wide_plan(tfp_group* g, int32_t channels, int32_t rate_in, int32_t rate_out, tfp::ResamplePlan* P) {
+  if (int rc = group_mix_plan(g, channels, rate_in, rate_out, P)) return rc;
+  if (rate_in == rate_out) return TFP_OK;
+  bool bad = false;
+  const std::shared_ptr<const tfp::ResampleTable> t = tfp::resample_table(rate_in, rate_out, &bad);
+  if (!t) return gfail(g, TFP_E_ARG, "unsupported rate ratio %d -> %d", rate_in, rate_out);
+  if (!tfp::resample_wide_in_range(*t, channels))
+    return gfail(g, TFP_E_ARG, "unsupported rate ratio %d -> %d for %d wide channels", rate_in, rate_out, channels);
+  return TFP_OK;
+}
+
+// The fingerprint split of the interleaved forms: the clips (offsets in frames) are cut by their frames at
+// rate_out exactly as tfp_group_fingerprint_rate_batch cuts its own, and shard s runs
+// call(s, first clip, clips, out, cap) on the clips it fingerprints.
+extern "C++" template <typename Call>
+int group_fingerprint_frames(tfp_group* g, const tfp::ResamplePlan& P, const int64_t* offsets, int32_t nclips, int32_t rate_in,
+                             int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes, Call call) {
   std::lock_guard<std::recursive_mutex> lk(g->mu);
   const int n = (int)g->eng.size();
   std::vector<int64_t> foff(nclips + 1, 0);
@@ -619,10 +625,43 @@ int tfp_group_fingerprint_mix_rate_batch(tfp_group* g, const int16_t* pcm, const
   return run_all(g, [&](int s) -> int {
     const int32_t a = cut[s], b = cut[s + 1];
     if (a >= b) return TFP_OK;
-    int64_t got = 0;
-    return tfp_fingerprint_mix_rate_batch(g->eng[s], pcm, offsets + a, b - a, channels, rate_in, rate_out, out + foff[a],
-                                          foff[b] - foff[a], &got);
+    return call(s, a, b - a, out + foff[a], foff[b] - foff[a]);
   });
+}
+}  // namespace
+
+// Interleaved multichannel int16 on a group (tfp_resample.hpp, "the multichannel form"): offsets count
+// frames; each shard downmixes and converts the clips it fingerprints. One channel is the rate form.
+int tfp_group_fingerprint_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int64_t* offsets, int32_t nclips,
+                                         int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                         int64_t* nframes) {
+  if (!g) return TFP_E_ARG;
+  if (channels == 1) return tfp_group_fingerprint_rate_batch(g, pcm, offsets, nclips, rate_in, rate_out, out, cap, nframes);
+  tfp::ResamplePlan P;
+  if (int rc = group_mix_plan(g, channels, rate_in, rate_out, &P)) return rc;
+  if (!offsets || nclips < 0 || !nframes) return TFP_E_ARG;
+  return group_fingerprint_frames(g, P, offsets, nclips, rate_in, rate_out, out, cap, nframes,
+                                  [&](int s, int32_t a, int32_t n, tfp_frame* o, int64_t ocap) {
+                                    int64_t got = 0;
+                                    return tfp_fingerprint_mix_rate_batch(g->eng[s], pcm, offsets + a, n, channels, rate_in,
+                                                                          rate_out, o, ocap, &got);
+                                  });
+}
+
+// Interleaved int32 Q31 on a group (tfp_resample.hpp, "the wide form"), split as the mix twin's clips are.
+int tfp_group_fingerprint_wide_rate_batch(tfp_group* g, const int32_t* q31, const int64_t* offsets, int32_t nclips,
+                                          int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                          int64_t* nframes) {
+  if (!g) return TFP_E_ARG;
+  tfp::ResamplePlan P;
+  if (int rc = group_wide_plan(g, channels, rate_in, rate_out, &P)) return rc;
+  if (!offsets || nclips < 0 || !nframes) return TFP_E_ARG;
+  return group_fingerprint_frames(g, P, offsets, nclips, rate_in, rate_out, out, cap, nframes,
+                                  [&](int s, int32_t a, int32_t n, tfp_frame* o, int64_t ocap) {
+                                    int64_t got = 0;
+                                    return tfp_fingerprint_wide_rate_batch(g->eng[s], q31, offsets + a, n, channels, rate_in,
+                                                                           rate_out, o, ocap, &got);
+                                  });
 }
 
 int tfp_group_index_add(tfp_group* g, const char* uuid, const int32_t* m1, const int32_t* m2, int32_t nframes) {
@@ -965,6 +1004,27 @@ int tfp_group_search_scoped_mix_rate_batch(tfp_group* g, const int16_t* pcm, con
   const int rc = group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
     return tfp_search_scoped_mix_rate_batch(g->eng[s], pcm, offsets, nq, channels, rate_in, rate_out, P, scopes, k, o, c,
                                             nullptr);
+  });
+  if (rc) return rc;
+  for (int32_t i = 0; frame_counts && i < nq; i++) {
+    const int64_t len = offsets[i + 1] - offsets[i];
+    frame_counts[i] = (int32_t)tfp_frame_count(rate_in == rate_out ? len : tfp::resample_count(rp, len));
+  }
+  return TFP_OK;
+}
+
+// The wide twin: every shard converts and fingerprints the Q31 batch.
+int tfp_group_search_scoped_wide_rate_batch(tfp_group* g, const int32_t* q31, const int64_t* offsets, int32_t nq,
+                                            int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* P,
+                                            const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                            int32_t* frame_counts) {
+  if (!g || !offsets) return TFP_E_ARG;
+  tfp::ResamplePlan rp;
+  if (int rc = group_wide_plan(g, channels, rate_in, rate_out, &rp)) return rc;
+  if (int rc = group_scope_args(g, scopes, nq)) return rc;
+  const int rc = group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    return tfp_search_scoped_wide_rate_batch(g->eng[s], q31, offsets, nq, channels, rate_in, rate_out, P, scopes, k, o, c,
+                                             nullptr);
   });
   if (rc) return rc;
   for (int32_t i = 0; frame_counts && i < nq; i++) {
@@ -1472,6 +1532,29 @@ int tfp_group_search_mix_rate_batch(tfp_group* g, const int16_t* pcm, const int6
   std::vector<std::vector<tfp_result>> res(n, std::vector<tfp_result>(std::max(nq, 1)));
   rc = run_all(g, [&](int s) {
     return tfp_search_mix_rate_batch(g->eng[s], pcm, offsets, nq, channels, rate_in, rate_out, P, res[s].data());
+  });
+  if (rc) return rc;
+  combine(g, res, nq, out);
+  return TFP_OK;
+}
+
+// The wide twin: every shard converts and fingerprints the Q31 batch. Not coalesced.
+int tfp_group_search_wide_rate_batch(tfp_group* g, const int32_t* q31, const int64_t* offsets, int32_t nq, int32_t channels,
+                                     int32_t rate_in, int32_t rate_out, const tfp_search_params* P, tfp_result* out) {
+  if (!g) return TFP_E_ARG;
+  tfp::ResamplePlan rp;
+  if (int rc = group_wide_plan(g, channels, rate_in, rate_out, &rp)) return rc;
+  if (!offsets || nq < 0 || !out) return TFP_E_ARG;
+  for (int32_t i = 0; i < nq; i++)
+    if (offsets[i + 1] < offsets[i]) return gfail(g, TFP_E_ARG, "offsets not monotone");
+  if (!q31 && nq && offsets[nq] > offsets[0]) return gfail(g, TFP_E_ARG, "samples are NULL");
+  std::lock_guard<std::recursive_mutex> lk(g->mu);
+  int rc = refresh_ranks(g);
+  if (rc) return rc;
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<tfp_result>> res(n, std::vector<tfp_result>(std::max(nq, 1)));
+  rc = run_all(g, [&](int s) {
+    return tfp_search_wide_rate_batch(g->eng[s], q31, offsets, nq, channels, rate_in, rate_out, P, res[s].data());
   });
   if (rc) return rc;
   combine(g, res, nq, out);

@@ -1,5 +1,6 @@
 // tfp_resample.cpp — the host side of rate conversion (tfp_resample.hpp): the process's tables and the
-// host-only entry points tfp_resample_count / _taps / _pcm. tfp_resample_pcm is the map the kernel of
+// host-only entry points tfp_resample_count / _taps / _pcm / _mix_pcm / _wide_pcm and tfp_q31_from_*.
+// tfp_resample_pcm is the map the kernel of
 // tfp_resample.hip computes (one routine, resample_sample), for the search forms without a rate twin.
 #include <cstring>
 #include <map>
@@ -27,6 +28,7 @@ std::shared_ptr<const ResampleTable> resample_table(int32_t rate_in, int32_t rat
   auto t = std::make_shared<ResampleTable>();
   t->plan = P;
   if (!resample_build(P, &t->taps)) return nullptr;
+  t->abs_sum = resample_abs_sum(P, t->taps);
   if (tables.size() >= 64) tables.clear();  // (holders keep theirs)
   tables[key] = t;
   return t;
@@ -119,5 +121,50 @@ extern "C" int tfp_resample_mix_pcm(const int16_t* pcm, int64_t nframes, int32_t
     return TFP_OK;
   }
   tfp::resample_mix_clip(*t, pcm, nframes, channels, out);
+  return TFP_OK;
+}
+
+// The wide form on the host: the map the kernel of tfp_resample_wide.hip computes (one routine,
+// resample_wide_sample). The frames are int32 Q31; one channel runs the same routine over the samples
+// themselves, and equal rates round and clamp (resample_wide_mean) without a filter.
+extern "C" int tfp_resample_wide_pcm(const int32_t* q31, int64_t nframes, int32_t channels, int32_t rate_in, int32_t rate_out,
+                                     int16_t* out, int64_t cap, int64_t* nout) {
+  if (channels < 1 || channels > TFP_MIX_CHANNELS_MAX)
+    return fail(TFP_E_ARG, "unsupported channel count " + std::to_string(channels));
+  if (nframes < 0 || !nout || (nframes > 0 && !q31)) return fail(TFP_E_ARG, "bad argument");
+  std::shared_ptr<const tfp::ResampleTable> t;
+  if (int rc = table_of(rate_in, rate_out, &t)) return rc;
+  if (rate_in != rate_out && !tfp::resample_wide_in_range(*t, channels))
+    return fail(TFP_E_ARG, "unsupported rate ratio " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) +
+                               " for " + std::to_string(channels) + " wide channels");
+  const int64_t no = rate_in == rate_out ? nframes : tfp::resample_count(t->plan, nframes);
+  if (no < 0 || nframes > INT64_MAX / channels)
+    return fail(TFP_E_ARG, "frame count " + std::to_string(nframes) + " past the index range");
+  *nout = no;
+  if (!out && cap == 0) return TFP_OK;  // size query
+  if (!out || cap < no) return fail(TFP_E_CAPACITY, "pcm buffer holds " + std::to_string(cap) + " of " + std::to_string(no) + " samples");
+  if (rate_in == rate_out) {  // equal rates: the filter is not run
+    for (int64_t i = 0; i < nframes; i++) {
+      int64_t S = 0;
+      for (int32_t c = 0; c < channels; c++) S += (int64_t)q31[i * channels + c];
+      out[i] = tfp::resample_wide_mean(S, channels);
+    }
+    return TFP_OK;
+  }
+  tfp::resample_wide_clip(*t, q31, nframes, channels, out);
+  return TFP_OK;
+}
+
+// Sample to Q31 (tfp_resample.hpp, q31_from_f32 / q31_from_f64): the map tfp_wav_decode_interleaved_q31
+// applies to float data. dst may not overlap src.
+extern "C" int tfp_q31_from_f32(const float* src, int64_t n, int32_t* dst) {
+  if (n < 0 || (n > 0 && (!src || !dst))) return fail(TFP_E_ARG, "bad argument");
+  for (int64_t i = 0; i < n; i++) dst[i] = tfp::q31_from_f32(src[i]);
+  return TFP_OK;
+}
+
+extern "C" int tfp_q31_from_f64(const double* src, int64_t n, int32_t* dst) {
+  if (n < 0 || (n > 0 && (!src || !dst))) return fail(TFP_E_ARG, "bad argument");
+  for (int64_t i = 0; i < n; i++) dst[i] = tfp::q31_from_f64(src[i]);
   return TFP_OK;
 }

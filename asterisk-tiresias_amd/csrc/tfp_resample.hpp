@@ -174,10 +174,113 @@ inline void resample_mix_sums(const int16_t* x, int64_t nframes, int32_t C, int3
   }
 }
 
+// ---- the wide form: interleaved int32 Q31 frames of C channels, downmixed and converted ------------
+// (include/tiresias_fp.h, "rate-normalised ingest of 24/32-bit and float audio"). Value v in [-1, 1) is
+// stored as v 2^31. The converter is linear, so widening the samples changes no table and no rate
+// arithmetic, only the accumulator's range, the final rounding and the staged width:
+//   S[i] = sum_c q[i][c]                       (exact, |S| <= 2^36; 0 outside the clip's own frames)
+//   acc  = sum_k h[p][k] S[i0 + k]             (exact, 64-bit: |acc| <= 2^31 C A, A = max_p sum_k |h[p][k]|)
+//   y[n] = clamp(floor((acc + 2^30 C) / (2^31 C)), -32768, 32767)
+// A wide call needs A C < 2^30 (ResampleTable::abs_sum, resample_wide_in_range): then |acc| < 2^61 and
+// the quotient by 2^31 fits int32. On int16 frames x widened to x << 16, acc is 2^16 times the mix form's,
+// so the output is resample_mix_sample's bit for bit. Equal rates run no filter:
+// y[i] = clamp(floor((S[i] + 2^15 C) / (2^16 C))) (Q31 full scale rounds to 32768: the clamp is needed).
+// Sums (int64) a workgroup of tfp_resample_wide.hip stages per tile for C >= 2: the bytes of
+// kRsMixSpanMax int32. One channel stages its int32 samples themselves, up to kRsMixSpanMax of them.
+constexpr int32_t kRsWideSpanMax = 7680;
+
+// floor((acc + 2^30 C) / (2^31 C)), clamped: one arithmetic shift, then a 32-bit floor division, as
+// resample_mix_round (|q| <= A C + C < 2^30 + 32).
+TFP_RS_HD int16_t resample_wide_round(int64_t acc, int32_t C) {
+  const int32_t q = (int32_t)((acc + ((int64_t)1 << 30) * C) >> 31);
+  int32_t y = q / C;
+  if (q - y * C < 0) y--;  // C++ truncates: floor
+  return (int16_t)(y < -32768 ? -32768 : y > 32767 ? 32767 : y);
+}
+
+// Equal rates: a frame's channel sum to int16, rounded half up and clamped (|q| <= 2^15 C + C).
+TFP_RS_HD int16_t resample_wide_mean(int64_t S, int32_t C) {
+  const int32_t q = (int32_t)((S + ((int64_t)1 << 15) * C) >> 16);
+  int32_t y = q / C;
+  if (q - y * C < 0) y--;
+  return (int16_t)(y < -32768 ? -32768 : y > 32767 ? 32767 : y);
+}
+
+// Output sample n of one clip over its staged elements: resample_mix_sample with T = int32_t samples
+// (C = 1) or int64_t channel sums (C >= 2) in S's place. S holds the frames [x_lo, x_hi) (frame i at
+// S[i - x_lo]); every frame outside counts as 0.
+template <typename T>
+TFP_RS_HD int16_t resample_wide_sample(const ResamplePlan& P, const int16_t* __restrict__ taps, const T* __restrict__ S,
+                                       int64_t x_lo, int64_t x_hi, int64_t n, int32_t C) {
+  const int64_t t = n * P.M, i0 = t / P.L, p = t - i0 * P.L;
+  int64_t ka = P.k_lo, kb = (int64_t)P.k_lo + P.ntaps - 1;
+  if (ka < x_lo - i0) ka = x_lo - i0;
+  if (kb > x_hi - 1 - i0) kb = x_hi - 1 - i0;
+  if (kb < ka) return 0;  // no frame under the filter
+  const int16_t* __restrict__ h = taps + p * P.ntaps + (ka - P.k_lo);
+  const T* __restrict__ s = S + (i0 + ka - x_lo);
+  const int32_t cnt = (int32_t)(kb - ka + 1);  // <= ntaps
+  int64_t acc = 0;
+  for (int32_t j = 0; j < cnt; j++) acc += (int64_t)h[j] * (int64_t)s[j];  // |product| <= 2^51
+  return resample_wide_round(acc, C);
+}
+
+// The same over the clip's interleaved frames themselves (frame i, channel c at x[i * C + c], frames
+// [0, n_in)): the channels are summed per tap. The kernel's form for a span past its staging limit.
+TFP_RS_HD int16_t resample_wide_sample_frames(const ResamplePlan& P, const int16_t* __restrict__ taps,
+                                              const int32_t* __restrict__ x, int64_t n_in, int64_t n, int32_t C) {
+  const int64_t t = n * P.M, i0 = t / P.L, p = t - i0 * P.L;
+  int64_t ka = P.k_lo, kb = (int64_t)P.k_lo + P.ntaps - 1;
+  if (ka < -i0) ka = -i0;
+  if (kb > n_in - 1 - i0) kb = n_in - 1 - i0;
+  if (kb < ka) return 0;
+  const int16_t* __restrict__ h = taps + p * P.ntaps + (ka - P.k_lo);
+  const int32_t* __restrict__ s = x + (i0 + ka) * C;
+  const int32_t cnt = (int32_t)(kb - ka + 1);
+  int64_t acc = 0;
+  for (int32_t j = 0; j < cnt; j++) {
+    int64_t sum = 0;
+    for (int32_t c = 0; c < C; c++) sum += (int64_t)s[(int64_t)j * C + c];
+    acc += (int64_t)h[j] * sum;
+  }
+  return resample_wide_round(acc, C);
+}
+
+// Sample to Q31, on the host only: clamp(nearbyint(x 2^31)) in the sample's own precision, ties to even
+// (the product is exact: a power-of-two scale), +1.0 to 2^31 - 1, NaN to 0, +-inf clamped.
+inline int32_t q31_from_f32(float x) {
+  const float v = std::nearbyint(x * 2147483648.0f);
+  if (!(v == v)) return 0;
+  return v >= 2147483648.0f ? INT32_MAX : v <= -2147483648.0f ? INT32_MIN : (int32_t)v;
+}
+inline int32_t q31_from_f64(double x) {
+  const double v = std::nearbyint(x * 2147483648.0);
+  if (!(v == v)) return 0;
+  return v >= 2147483648.0 ? INT32_MAX : v <= -2147483648.0 ? INT32_MIN : (int32_t)v;
+}
+
 struct ResampleTable {
   ResamplePlan plan;
   std::vector<int16_t> taps;  // [L][ntaps]
+  int64_t abs_sum = 0;        // A = max_p sum_k |h[p][k]| (resample_abs_sum), set where the table is built
 };
+
+// A of a table: the largest absolute tap sum of a phase, the bound |acc| <= max|S| A of every form.
+inline int64_t resample_abs_sum(const ResamplePlan& P, const std::vector<int16_t>& taps) {
+  int64_t A = 0;
+  for (int32_t p = 0; p < P.L; p++) {
+    int64_t a = 0;
+    for (int32_t j = 0; j < P.ntaps; j++) {
+      const int32_t h = taps[(size_t)p * P.ntaps + j];
+      a += h < 0 ? -h : h;
+    }
+    if (a > A) A = a;
+  }
+  return A;
+}
+
+// The wide form's range: A C < 2^30 keeps the accumulator below 2^61 and its quotient in int32.
+inline bool resample_wide_in_range(const ResampleTable& T, int32_t C) { return T.abs_sum * C < ((int64_t)1 << 30); }
 
 // I0 by its power series (every term positive; x <= beta here, 1e-17 relative after ~30 terms).
 inline double rs_i0(double x) {
@@ -242,6 +345,22 @@ inline void resample_mix_clip(const ResampleTable& T, const int16_t* x, int64_t 
   for (int64_t n = 0; n < n_out; n++) out[n] = resample_mix_sample(T.plan, T.taps.data(), S.data(), 0, nframes, n, C);
 }
 
+// One wide clip on the host: out[resample_count(nframes)]. One channel filters its samples as they are.
+inline void resample_wide_clip(const ResampleTable& T, const int32_t* x, int64_t nframes, int32_t C, int16_t* out) {
+  const int64_t n_out = resample_count(T.plan, nframes);
+  if (C == 1) {
+    for (int64_t n = 0; n < n_out; n++) out[n] = resample_wide_sample(T.plan, T.taps.data(), x, 0, nframes, n, 1);
+    return;
+  }
+  std::vector<int64_t> S((size_t)nframes);
+  for (int64_t i = 0; i < nframes; i++) {
+    int64_t sum = 0;
+    for (int32_t c = 0; c < C; c++) sum += (int64_t)x[i * C + c];
+    S[i] = sum;
+  }
+  for (int64_t n = 0; n < n_out; n++) out[n] = resample_wide_sample(T.plan, T.taps.data(), S.data(), 0, nframes, n, C);
+}
+
 // The process's tables (tfp_resample.cpp): built once per rate pair, shared by the host routine and
 // every engine. nullptr for a bad or unsupported pair, *bad_rate telling which.
 std::shared_ptr<const ResampleTable> resample_table(int32_t rate_in, int32_t rate_out, bool* bad_rate);
@@ -274,6 +393,16 @@ hipError_t launch_resample(const ResamplePlan& P, const int16_t* d_taps, const i
 hipError_t launch_resample_mix(const ResamplePlan& P, const int16_t* d_taps, bool downmix, int32_t C, const int16_t* d_in,
                                const int64_t* d_in_off, const int64_t* d_out_off, const int32_t* d_toff,
                                const int32_t* d_tclip, int32_t ntiles, int16_t* d_out, hipStream_t stream, bool* staged);
+
+// The wide launch (tfp_resample_wide.hip): clip c is the frames [in_off[c], in_off[c + 1]) of d_in, C
+// interleaved int32 Q31 each, the outputs and tiles as launch_resample's. downmix: equal rates, out_off =
+// in_off, no table is read (P and d_taps are ignored). *form receives the form that ran. The caller has
+// checked resample_wide_in_range for the pair. One launch; ntiles = 0 launches nothing.
+enum ResampleWideForm : int32_t { kRsWideNone = 0, kRsWideStagedMono, kRsWideStagedSums, kRsWideGlobal, kRsWideDownmix };
+hipError_t launch_resample_wide(const ResamplePlan& P, const int16_t* d_taps, bool downmix, int32_t C, const int32_t* d_in,
+                                const int64_t* d_in_off, const int64_t* d_out_off, const int32_t* d_toff,
+                                const int32_t* d_tclip, int32_t ntiles, int16_t* d_out, hipStream_t stream,
+                                ResampleWideForm* form);
 #endif
 
 }  // namespace tfp

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "tfp_g711.hpp"
+#include "tfp_resample.hpp"
 #include "tiresias_fp.h"
 
 namespace {
@@ -189,6 +190,60 @@ extern "C" int tfp_wav_read_interleaved(const char* path, int16_t* pcm, int64_t 
   const int rc = read_file(path, buf);
   if (rc) return rc;
   return tfp_wav_decode_interleaved(buf.data(), (int64_t)buf.size(), pcm, cap, nframes, channels, sample_rate);
+}
+
+// Q31 form: integer PCM of 8, 16, 24 or 32 bits and float data of 32 or 64 bits, 1 to 32 channels, each
+// sample as int32 Q31 (frame i, channel c at q31[i * channels + c]) for the wide rate forms
+// (tfp_resample_wide_pcm, tfp_fingerprint_wide_rate_batch). Integer samples are shifted to the top of the
+// word, float samples go through q31_from_f32 / q31_from_f64. No downmix happens here.
+extern "C" int tfp_wav_decode_interleaved_q31(const void* bytes, int64_t nbytes, int32_t* q31, int64_t cap, int64_t* nframes,
+                                              int32_t* channels, int32_t* sample_rate) {
+  if (!bytes || nbytes < 0 || !nframes || cap < 0 || (cap > 0 && !q31)) return fail(TFP_E_ARG, "bad argument");
+  WavData w;
+  if (const int rc = find_data(static_cast<const uint8_t*>(bytes), (uint64_t)nbytes, &w)) return rc;
+  const WavFormat& f = w.f;
+  const bool pcm = f.tag == kFormatPcm && (f.bits == 8 || f.bits == 16 || f.bits == 24 || f.bits == 32);
+  const bool flt = f.tag == kFormatFloat && (f.bits == 32 || f.bits == 64);
+  if (!pcm && !flt)
+    return fail(TFP_E_FORMAT, "format tag " + std::to_string(f.tag) + " with " + std::to_string(f.bits) +
+                                  "-bit samples is neither 8/16/24/32-bit PCM nor 32/64-bit float (G.711 is not taken)");
+  if (f.channels < 1 || f.channels > TFP_MIX_CHANNELS_MAX)
+    return fail(TFP_E_FORMAT, std::to_string(f.channels) + " channels: 1 to " + std::to_string(TFP_MIX_CHANNELS_MAX) + " are taken");
+  if (f.rate == 0 || f.rate > (uint32_t)INT32_MAX) return fail(TFP_E_FORMAT, "bad sample rate");
+  const uint32_t width = f.bits / 8;
+  if (f.block_align != width * f.channels) return fail(TFP_E_FORMAT, "block align does not match the format");
+  const int64_t nf = (int64_t)(w.size / f.block_align), ns = nf * f.channels;  // a trailing partial frame is dropped
+  *nframes = nf;
+  if (channels) *channels = (int32_t)f.channels;
+  if (sample_rate) *sample_rate = (int32_t)f.rate;
+  if (!q31) return TFP_OK;  // size query
+  if (cap < ns) return fail(TFP_E_CAPACITY, "sample buffer holds " + std::to_string(cap) + " of " + std::to_string(ns) + " samples");
+  const uint8_t* d = w.data;
+  for (int64_t i = 0; i < ns; ++i) {
+    const uint8_t* p = d + (uint64_t)i * width;
+    if (flt && width == 4) {
+      q31[i] = tfp::q31_from_f32(__builtin_bit_cast(float, le32(p)));
+    } else if (flt) {
+      q31[i] = tfp::q31_from_f64(__builtin_bit_cast(double, (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32)));
+    } else if (width == 1) {
+      q31[i] = (int32_t)((uint32_t)((int)p[0] - 128) << 24);
+    } else if (width == 2) {
+      q31[i] = (int32_t)((uint32_t)le16(p) << 16);
+    } else if (width == 3) {
+      q31[i] = (int32_t)(((uint32_t)p[0] << 8) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 24));
+    } else {
+      q31[i] = (int32_t)le32(p);
+    }
+  }
+  return TFP_OK;
+}
+
+extern "C" int tfp_wav_read_interleaved_q31(const char* path, int32_t* q31, int64_t cap, int64_t* nframes, int32_t* channels,
+                                            int32_t* sample_rate) {
+  std::vector<uint8_t> buf;
+  const int rc = read_file(path, buf);
+  if (rc) return rc;
+  return tfp_wav_decode_interleaved_q31(buf.data(), (int64_t)buf.size(), q31, cap, nframes, channels, sample_rate);
 }
 
 // fp32 form: every PCM width and float data, any channel count, as aubio 0.4.5's sndfile and

@@ -7,4 +7,5 @@ from ._lib import LIB_PATH, NULL_MICRO, TfpError, header_symbols, lib  # noqa: F
 from .engine import (ALAW, FRAME_DTYPE, MIX_CHANNELS_MAX, ULAW, Engine, Group, GroupLive, GroupStream, Live, Plan, Stream, census_at_least,  # noqa: F401
                      decode_g711, decode_wav_g711, decode_wav_interleaved, device_count, frame_count, params, read_wav_g711, read_wav_interleaved, resample_count, resample_mix_pcm, resample_pcm,
                      resample_taps, sliding_windows, synth_pcm)
+from .engine import decode_wav_interleaved_q31, q31_from_float, read_wav_interleaved_q31, resample_wide_pcm  # noqa: F401
 from .fp_handler import FpHandler  # noqa: F401

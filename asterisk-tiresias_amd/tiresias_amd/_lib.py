@@ -141,6 +141,25 @@ _SIGS = {
                                                   C.POINTER(SearchParams), P]),
     "tfp_group_search_scoped_mix_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                          C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_wav_decode_interleaved_q31": (C.c_int, [P, C.c_int64, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int32)]),
+    "tfp_wav_read_interleaved_q31": (C.c_int, [C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32)]),
+    "tfp_q31_from_f32": (C.c_int, [P, C.c_int64, P]),
+    "tfp_q31_from_f64": (C.c_int, [P, C.c_int64, P]),
+    "tfp_resample_wide_pcm": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_fingerprint_wide_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                  C.POINTER(C.c_int64)]),
+    "tfp_search_wide_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_search_scoped_wide_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                    C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_resample_wide_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 4),
+    "tfp_group_fingerprint_wide_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                        C.POINTER(C.c_int64)]),
+    "tfp_group_search_wide_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.POINTER(SearchParams), P]),
+    "tfp_group_search_scoped_wide_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                          C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
     "tfp_fingerprint_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
     "tfp_search_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_fingerprint_pcm": (C.c_int, [P, P, C.c_int64, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),

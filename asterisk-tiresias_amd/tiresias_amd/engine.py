@@ -117,10 +117,10 @@ def resample_mix_pcm(pcm, channels: int, rate_in: int, rate_out: int) -> np.ndar
     return out
 
 
-def _wav_interleaved(call) -> tuple[np.ndarray, int]:
+def _wav_interleaved(call, dtype=np.int16) -> tuple[np.ndarray, int]:
     n, ch, sr = C.c_int64(), C.c_int32(), C.c_int32()
     check(call(None, 0, C.byref(n), C.byref(ch), C.byref(sr)))
-    pcm = np.empty(n.value * ch.value, np.int16)
+    pcm = np.empty(n.value * ch.value, dtype)
     check(call(pcm.ctypes.data, len(pcm), C.byref(n), C.byref(ch), C.byref(sr)))
     return pcm.reshape(n.value, ch.value), sr.value
 
@@ -136,6 +136,45 @@ def read_wav_interleaved(path: str) -> tuple[np.ndarray, int]:
     """tfp_wav_read_interleaved: decode_wav_interleaved of a file."""
     p = path.encode()
     return _wav_interleaved(lambda x, cap, n, ch, sr: lib().tfp_wav_read_interleaved(p, x, cap, n, ch, sr))
+
+
+def resample_wide_pcm(q31, channels: int, rate_in: int, rate_out: int) -> np.ndarray:
+    """tfp_resample_wide_pcm: one clip of interleaved int32 Q31 frames ([nframes, channels], or flat) downmixed and
+    brought to rate_out as int16, the map the GPU wide forms compute (exact)."""
+    q31 = np.ascontiguousarray(q31, np.int32).reshape(-1)
+    channels = int(channels)
+    nfr = len(q31) // channels if channels > 0 else 0
+    n = C.c_int64()
+    check(lib().tfp_resample_wide_pcm(q31.ctypes.data, nfr, channels, int(rate_in), int(rate_out), None, 0, C.byref(n)))
+    out = np.empty(n.value, np.int16)
+    check(lib().tfp_resample_wide_pcm(q31.ctypes.data, nfr, channels, int(rate_in), int(rate_out), out.ctypes.data, len(out),
+                                      C.byref(n)))
+    return out
+
+
+def q31_from_float(x) -> np.ndarray:
+    """tfp_q31_from_f32 / tfp_q31_from_f64: float samples (float64 stays double, everything else goes through float32)
+    to int32 Q31, rounded to nearest even and clamped; NaN becomes 0."""
+    x = np.asarray(x)
+    f64 = x.dtype == np.float64
+    x = np.ascontiguousarray(x, np.float64 if f64 else np.float32)
+    out = np.empty(x.shape, np.int32)
+    check((lib().tfp_q31_from_f64 if f64 else lib().tfp_q31_from_f32)(x.ctypes.data, x.size, out.ctypes.data))
+    return out
+
+
+def decode_wav_interleaved_q31(data: bytes) -> tuple[np.ndarray, int]:
+    """tfp_wav_decode_interleaved_q31: RIFF/WAVE bytes of 8/16/24/32-bit integer PCM or 32/64-bit float with 1 to 32
+    channels -> (int32 Q31 [nframes, channels], native rate). TfpError(TFP_E_FORMAT) for every other file."""
+    buf = C.create_string_buffer(bytes(data), len(data))
+    return _wav_interleaved(lambda x, cap, n, ch, sr: lib().tfp_wav_decode_interleaved_q31(buf, len(data), x, cap, n, ch, sr),
+                            np.int32)
+
+
+def read_wav_interleaved_q31(path: str) -> tuple[np.ndarray, int]:
+    """tfp_wav_read_interleaved_q31: decode_wav_interleaved_q31 of a file."""
+    p = path.encode()
+    return _wav_interleaved(lambda x, cap, n, ch, sr: lib().tfp_wav_read_interleaved_q31(p, x, cap, n, ch, sr), np.int32)
 
 
 def _wav_g711(call) -> tuple[np.ndarray, int, int]:
@@ -401,30 +440,41 @@ class _MixCalls:
 
     def fingerprint_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int) -> np.ndarray:
         """The frames of fingerprint_batch(resample_mix_pcm(clip), rate_out) per clip, bit for bit."""
-        pcm = np.ascontiguousarray(pcm, np.int16)
+        return self._frames_fingerprint("mix", np.int16, pcm, offsets, channels, rate_in, rate_out)
+
+    def search_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams):
+        """search_pcm_batch at rate_out on the downmixed, resampled queries."""
+        return self._frames_search("mix", np.int16, pcm, offsets, channels, rate_in, rate_out, p)
+
+    def search_scoped_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams, scopes,
+                                     k: int):
+        """search_scoped_pcm_batch at rate_out on the downmixed, resampled queries: (rows per query, frame counts)."""
+        return self._frames_search_scoped("mix", np.int16, pcm, offsets, channels, rate_in, rate_out, p, scopes, k)
+
+    # the bodies, shared with the wide forms (_WideCalls): kind names the entry point, dtype the samples
+    def _frames_fingerprint(self, kind: str, dtype, pcm, offsets, channels: int, rate_in: int, rate_out: int) -> np.ndarray:
+        pcm = np.ascontiguousarray(pcm, dtype)
         offsets = np.ascontiguousarray(offsets, np.int64)
         nclips = len(offsets) - 1
         n = sum(frame_count(self._mix_count(int(offsets[i + 1] - offsets[i]), rate_in, rate_out)) for i in range(nclips))
         out = np.zeros(max(n, 1), FRAME_DTYPE)
         got = C.c_int64()
-        self._chk(self._fn("_fingerprint_mix_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nclips, int(channels),
+        self._chk(self._fn("_fingerprint_%s_rate_batch" % kind)(self._h, pcm.ctypes.data, offsets.ctypes.data, nclips, int(channels),
                                                           int(rate_in), int(rate_out), out.ctypes.data, n, C.byref(got)))
         return out[:got.value]
 
-    def search_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams):
-        """search_pcm_batch at rate_out on the downmixed, resampled queries."""
-        pcm = np.ascontiguousarray(pcm, np.int16)
+    def _frames_search(self, kind: str, dtype, pcm, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams):
+        pcm = np.ascontiguousarray(pcm, dtype)
         offsets = np.ascontiguousarray(offsets, np.int64)
         nq = len(offsets) - 1
         res = (Result * max(1, nq))()
-        self._chk(self._fn("_search_mix_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(channels),
+        self._chk(self._fn("_search_%s_rate_batch" % kind)(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(channels),
                                                      int(rate_in), int(rate_out), C.byref(p), res))
         return Engine._results(res, nq)
 
-    def search_scoped_mix_rate_batch(self, pcm, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams, scopes,
-                                     k: int):
-        """search_scoped_pcm_batch at rate_out on the downmixed, resampled queries: (rows per query, frame counts)."""
-        pcm = np.ascontiguousarray(pcm, np.int16)
+    def _frames_search_scoped(self, kind: str, dtype, pcm, offsets, channels: int, rate_in: int, rate_out: int,
+                              p: SearchParams, scopes, k: int):
+        pcm = np.ascontiguousarray(pcm, dtype)
         offsets = np.ascontiguousarray(offsets, np.int64)
         nq, k = len(offsets) - 1, int(k)
         scopes = np.ascontiguousarray(scopes, np.int32)
@@ -432,10 +482,30 @@ class _MixCalls:
             raise ValueError("one scope per query")
         out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
         fc = (C.c_int32 * max(1, nq))()
-        self._chk(self._fn("_search_scoped_mix_rate_batch")(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(channels),
+        self._chk(self._fn("_search_scoped_%s_rate_batch" % kind)(self._h, pcm.ctypes.data, offsets.ctypes.data, nq, int(channels),
                                                             int(rate_in), int(rate_out), C.byref(p), scopes.ctypes.data, k, out,
                                                             counts, fc))
         return Engine._candidates(out, counts, nq, k), list(fc[:nq])
+
+
+class _WideCalls:
+    """Rate-normalised ingest of 24/32-bit and float audio, the same calls on an Engine and on a Group: q31 holds
+    interleaved frames of `channels` int32 Q31 each and offsets count frames (the bodies are _MixCalls')."""
+
+    resample_wide_pcm = staticmethod(resample_wide_pcm)
+
+    def fingerprint_wide_rate_batch(self, q31, offsets, channels: int, rate_in: int, rate_out: int) -> np.ndarray:
+        """The frames of fingerprint_batch(resample_wide_pcm(clip), rate_out) per clip, bit for bit."""
+        return self._frames_fingerprint("wide", np.int32, q31, offsets, channels, rate_in, rate_out)
+
+    def search_wide_rate_batch(self, q31, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams):
+        """search_pcm_batch at rate_out on the converted queries."""
+        return self._frames_search("wide", np.int32, q31, offsets, channels, rate_in, rate_out, p)
+
+    def search_scoped_wide_rate_batch(self, q31, offsets, channels: int, rate_in: int, rate_out: int, p: SearchParams, scopes,
+                                      k: int):
+        """search_scoped_pcm_batch at rate_out on the converted queries: (rows per query, frame counts)."""
+        return self._frames_search_scoped("wide", np.int32, q31, offsets, channels, rate_in, rate_out, p, scopes, k)
 
 
 class _CensusCalls:
@@ -472,7 +542,7 @@ class _CensusCalls:
                             (int(sample_rate),), p, scopes, nbins)
 
 
-class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls):
+class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _WideCalls):
     """One engine per GPU (tfp_engine)."""
     _PFX = "tfp"
 
@@ -577,6 +647,13 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls):
         wrote, and how many of the launches staged their channel sums in LDS."""
         v = [C.c_int64() for _ in range(4)]
         self._chk(lib().tfp_resample_mix_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("launches", "frames_in", "samples_out", "staged_launches"), (x.value for x in v)))
+
+    def resample_wide_stats(self) -> dict:
+        """tfp_resample_wide_stats: the wide kernel's launches, the frames they read, the samples they wrote, and
+        how many of the launches staged in LDS."""
+        v = [C.c_int64() for _ in range(4)]
+        self._chk(lib().tfp_resample_wide_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("launches", "frames_in", "samples_out", "staged_launches"), (x.value for x in v)))
 
     def fingerprint_stats(self) -> dict:
@@ -1253,7 +1330,7 @@ class Plan:
             self._h = C.c_void_p()
 
 
-class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls):
+class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _WideCalls):
     """tfp_group: one engine per listed device (a device may repeat), the enrolled clips sharded
     over them, searches combined on the host (tiresias_fp.h, device groups)."""
     _PFX = "tfp_group"
@@ -1342,6 +1419,15 @@ class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls):
         for sh in range(self.size()):
             v = [C.c_int64() for _ in range(4)]
             check(lib().tfp_resample_mix_stats(lib().tfp_group_engine(self._h, sh), *[C.byref(x) for x in v]))
+            out.append(dict(zip(keys, (x.value for x in v))))
+        return out
+
+    def resample_wide_stats(self) -> list:
+        """tfp_resample_wide_stats of every shard's engine, in shard order."""
+        keys, out = ("launches", "frames_in", "samples_out", "staged_launches"), []
+        for sh in range(self.size()):
+            v = [C.c_int64() for _ in range(4)]
+            check(lib().tfp_resample_wide_stats(lib().tfp_group_engine(self._h, sh), *[C.byref(x) for x in v]))
             out.append(dict(zip(keys, (x.value for x in v))))
         return out
 

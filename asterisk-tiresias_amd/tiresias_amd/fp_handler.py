@@ -28,7 +28,8 @@ import numpy as np
 from . import dbio
 from ._lib import TFP_RANK_MAX, TfpError
 from .engine import (ALAW, ULAW, Engine, decode_g711, frame_count as frame_count_of, params, read_wav, read_wav_f32,
-                     read_wav_g711, read_wav_interleaved, resample_count, resample_mix_pcm, resample_pcm)
+                     read_wav_g711, read_wav_interleaved, read_wav_interleaved_q31, resample_count, resample_mix_pcm, resample_pcm,
+                     resample_wide_pcm)
 
 TFP_E_FORMAT = -8
 
@@ -93,7 +94,8 @@ def write_wav_mono16(filename: str, pcm: np.ndarray, sample_rate: int = 8000):
 class FpHandler:
     """One loaded module instance (g_db_ctx + the GPU engine)."""
 
-    def __init__(self, device: int = 0, backup_path: str | None = None, index_rate: int = 0, mix_channels: bool = False):
+    def __init__(self, device: int = 0, backup_path: str | None = None, index_rate: int = 0, mix_channels: bool = False,
+                 wide_samples: bool = False):
         """backup_path: the snapshot file (the reference hard-codes dbio.DEF_BACKUP_DATABASE);
         None keeps the state in memory only. index_rate: 0 takes every file at its native rate, as the
         reference does (DEF_AUBIO_SAMPLERATE 0); a rate > 0 is the index's rate (new behaviour): int16 and
@@ -104,11 +106,16 @@ class FpHandler:
         too instead of refused (tfp_resample_mix_pcm's map: the integer downmix, defined for the rate change;
         at the index's own rate such a file keeps the fp32 path, the reference's value). It is off by
         default, so that a handler behaves as it did before the option existed; 24/32-bit and float files
-        of another rate are refused either way."""
+        of another rate are refused either way, unless wide_samples is set. wide_samples (with an index rate;
+        off by default for the same reason): a 24/32-bit integer or 32/64-bit float file of another rate is read
+        as int32 Q31 frames (tfp_wav_read_interleaved_q31) and normalised by tfp_resample_wide_pcm's map, on
+        the GPU in the directory enrolment and on the host for a single file and the searches; several
+        channels still need mix_channels."""
         self.device = device
         self.backup_path = backup_path
         self.index_rate = int(index_rate)
         self.mix_channels = bool(mix_channels)
+        self.wide_samples = bool(wide_samples)
         self.last_error = ""  # why the last file was refused for its rate
         self.db = None
         self.engine = None
@@ -294,6 +301,12 @@ class FpHandler:
         return self.index_rate > 0 and sr != self.index_rate
 
     def _refuse_f32(self, filename: str, sr: int) -> str:
+        if self.wide_samples:  # what is still missing: the channel option, or a format no reader takes
+            why = ("integer PCM of 8 to 32 bits and 32/64-bit float of 1 to 32 channels are taken" if self.mix_channels else
+                   "several channels need mix_channels")
+            self.last_error = ("%s: fp32 audio at %d Hz cannot be normalised to the index rate %d Hz (%s)"
+                               % (filename, sr, self.index_rate, why))
+            return self.last_error
         self.last_error = ("%s: fp32 audio at %d Hz cannot be normalised to the index rate %d Hz "
                            "(rate conversion takes 8/16-bit integer PCM and G.711 only%s)"
                            % (filename, sr, self.index_rate, "" if self.mix_channels else ", of several channels with mix_channels"))
@@ -302,20 +315,31 @@ class FpHandler:
     def _read_interleaved(self, filename: str):
         """With mix_channels, an fp32 file of another rate as int16[nframes, channels], if it is 8/16-bit
         integer PCM of 1 to 32 channels (tfp_wav_read_interleaved); None for the files that stay refused
-        (24/32-bit, float; every fp32 file without mix_channels)."""
-        if not self.mix_channels:
-            return None
-        try:
-            return read_wav_interleaved(filename)[0]
-        except TfpError as e:
-            if e.code != TFP_E_FORMAT:
-                raise
+        (24/32-bit, float; every fp32 file without mix_channels). With wide_samples, a file the int16 reader
+        does not take as int32 Q31 [nframes, channels] (tfp_wav_read_interleaved_q31), several channels only
+        with mix_channels; the callers tell the two by the dtype."""
+        if self.mix_channels:
+            try:
+                return read_wav_interleaved(filename)[0]
+            except TfpError as e:
+                if e.code != TFP_E_FORMAT:
+                    raise
+        if self.wide_samples:
+            try:
+                q31 = read_wav_interleaved_q31(filename)[0]
+            except TfpError as e:
+                if e.code != TFP_E_FORMAT:
+                    raise
+                return None
+            if q31.shape[1] == 1 or self.mix_channels:
+                return q31
         return None
 
     def _read_query(self, filename: str):
         """read_audio for a search: with an index rate set, a file of another rate is normalised on the host
-        (G.711 expanded first; an 8/16-bit integer file of several channels by tfp_resample_mix_pcm); a
-        24/32-bit or float file of another rate raises TfpError(TFP_E_FORMAT)."""
+        (G.711 expanded first; an 8/16-bit integer file of several channels by tfp_resample_mix_pcm; with
+        wide_samples a 24/32-bit or float file by tfp_resample_wide_pcm); a file none of them takes raises
+        TfpError(TFP_E_FORMAT)."""
         pcm, sr = read_audio(filename)
         if not self._other_rate(sr):
             return pcm, sr
@@ -323,11 +347,14 @@ class FpHandler:
             frames = self._read_interleaved(filename)
             if frames is None:
                 raise TfpError(TFP_E_FORMAT, self._refuse_f32(filename, sr))
-            return resample_mix_pcm(frames, frames.shape[1], sr, self.index_rate), self.index_rate
+            convert = resample_wide_pcm if frames.dtype == np.int32 else resample_mix_pcm
+            return convert(frames, frames.shape[1], sr, self.index_rate), self.index_rate
         return resample_pcm(pcm, sr, self.index_rate), self.index_rate
 
     def _fingerprint(self, samples: np.ndarray, offsets, sr: int, law=None, channels: int = 1):
         if self._other_rate(sr):  # (int16: the enrolment expanded G.711 and refused fp32)
+            if samples.dtype == np.int32:  # interleaved Q31 frames (wide_samples), offsets in frames
+                return self.engine.fingerprint_wide_rate_batch(samples, offsets, channels, sr, self.index_rate)
             if channels > 1:  # interleaved frames, offsets in frames
                 return self.engine.fingerprint_mix_rate_batch(samples, offsets, channels, sr, self.index_rate)
             return self.engine.fingerprint_rate_batch(samples, offsets, sr, self.index_rate)
@@ -345,7 +372,7 @@ class FpHandler:
         are written in the same order and with the same per-context MD5 dedup (also among the
         files of this scan). The fingerprints of all new files are computed by one fingerprint
         call per sample rate and kind (int16, fp32, G.711 codes of one law, which go to the GPU
-        as codes, or with an index rate set interleaved int16 of one channel count) and enrolled by one
+        as codes, or with an index rate set interleaved int16 or int32 Q31 of one channel count) and enrolled by one
         tfp_index_add_batch."""
         ctx = self.fp_get_context_list_info(context) if context is not None else None
         if ctx is None or ctx["directory"] is None:

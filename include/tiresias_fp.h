@@ -1285,7 +1285,8 @@ int tfp_group_stream_push_g711(tfp_group_stream* st, const uint8_t* codes, int32
  * "unsupported rate ratio". rate_in == rate_out runs no filter: the rate forms are then the plain forms.
  * Not covered: tfp_stream_push (the ring), fp32 input. A live object takes its ticks at another rate
  * through tfp_live_create_rate (the last section of this header). Interleaved multichannel int16 has
- * forms of its own (tfp_fingerprint_mix_rate_batch, the section after tfp_synchronize). No claim of
+ * forms of its own (tfp_fingerprint_mix_rate_batch), and so have 24/32-bit and float files, as int32
+ * Q31 frames (tfp_fingerprint_wide_rate_batch): the two sections after tfp_synchronize. No claim of
  * equality with any other resampler is made. */
 /* n_out for nsamples at rate_in; 0 for nsamples <= 0, -1 for a bad or unsupported pair. Host-only. */
 int64_t tfp_resample_count(int64_t nsamples, int32_t rate_in, int32_t rate_out);
@@ -1347,6 +1348,87 @@ int tfp_synth_pcm_device(tfp_engine* eng, const tfp_synth_spec* specs, int32_t n
 /* ---- misc --------------------------------------------------------------------------- */
 int tfp_synchronize(tfp_engine* eng, void* stream);
 
+/* ---- rate-normalised ingest of 24/32-bit and float audio: Q31 forms on the GPU (new) ------------ */
+/* A prompt master out of a DAW or a studio is a 24-bit, 32-bit or float WAV at 44.1 or 48 kHz, usually
+ * stereo. These forms take such audio without an outside requantisation to int16, which would be a
+ * second definition. Wide samples are int32 Q31: value v in [-1, 1) is stored as v 2^31. Frames are
+ * interleaved, q[i * C + c] with 1 <= C <= TFP_MIX_CHANNELS_MAX; clip lengths and offsets[] count FRAMES.
+ * L, M, k_lo, ntaps, h[p][k] and n_out are exactly those of the pair's table (tfp_resample_taps,
+ * tfp_resample_count of the frame count); no new table is built. The converter is linear, so widening
+ * the samples changes only the accumulator's range and the final rounding:
+ *   S[i] = sum_c q[i][c]                        (exact, |S| <= 2^36; 0 outside the clip's own frames)
+ *   acc  = sum_k h[p][k] S[i0 + k]              (exact, 64-bit; i0 = n M div L, p = n M mod L)
+ *   y[n] = clamp(floor((acc + 2^30 C) / (2^31 C)), -32768, 32767)
+ * The division is a floor, not a truncation: q = (acc + 2^30 C) >> 31, then a 32-bit floor division by C.
+ * rate_in == rate_out runs no filter: y[i] = clamp(floor((S[i] + 2^15 C) / (2^16 C))); the clamp is
+ * needed there, since Q31 full scale rounds to 32768.
+ * Consistency: for int16 frames x, the wide form on x << 16 is tfp_resample_mix_pcm of x bit for bit
+ * (acc_wide = 2^16 acc), and for C = 1 it is tfp_resample_pcm. Host and GPU agree bit for bit.
+ * Range: with A = max_p sum_k |h[p][k]| of the pair's table, |acc| <= 2^31 C A. A wide call with
+ * A C >= 2^30 is TFP_E_ARG with "unsupported rate ratio"; below that acc stays under 2^61 and q fits
+ * int32. The largest A over the pairs tests/test_resample_wide_host.py lists is 70,210 (7999 -> 8001,
+ * about 2.14 * 32768), so A C stays below 2^22 at C = 32 and no supported pair met so far is refused.
+ * Sample to Q31 happens on the host only (tfp_wav_decode_interleaved_q31, tfp_q31_from_f32 / _f64):
+ * unsigned 8-bit (u - 128) << 24, signed 16-bit << 16, signed 24-bit << 8, signed 32-bit as stored,
+ * float32 clamp(nearbyintf(x * 2^31f)) and float64 the same in double, ties to even (the product is exact:
+ * a power-of-two scale), clamped to [-2^31, 2^31 - 1] so that +1.0 becomes 2^31 - 1, NaN 0, +-inf clamped.
+ * It is not done on the GPU: denormal handling there would be a second definition.
+ * Like the int16 mix form this is a new definition and NOT aubio's fp32 value (fp_handler.c:604, :633):
+ * a file at the index's own rate should keep using tfp_wav_decode_f32 and the f32 forms.
+ * Refusals and messages are those of the mix forms ("unsupported channel count", "bad sample rate",
+ * "unsupported rate ratio"), plus the range refusal above. An argument error writes nothing to the outputs.
+ * Not covered: live pushes and tfp_stream_push of wide samples, the compiled shim, per-clip channel
+ * counts inside one call, packed 24-bit samples on the device, float-to-Q31 on the device. */
+/* RIFF/WAVE -> interleaved int32 Q31: integer PCM of 8, 16, 24 or 32 bits (format 1) and float of 32 or
+ * 64 bits (format 3), or EXTENSIBLE with either subformat, 1 to TFP_MIX_CHANNELS_MAX channels. G.711 and
+ * more channels are TFP_E_FORMAT with a reason. *nframes receives the whole frames present (a trailing
+ * partial frame is dropped); cap counts samples, nframes * channels of them are written. Chunk skipping,
+ * unpatched and truncated data sizes, the size query (q31 == NULL, cap 0) and TFP_E_CAPACITY (with
+ * *nframes / *channels set) as tfp_wav_decode_interleaved. Host-only. */
+int tfp_wav_decode_interleaved_q31(const void* bytes, int64_t nbytes, int32_t* q31, int64_t cap, int64_t* nframes,
+                                   int32_t* channels, int32_t* sample_rate);
+int tfp_wav_read_interleaved_q31(const char* path, int32_t* q31, int64_t cap, int64_t* nframes, int32_t* channels,
+                                 int32_t* sample_rate);
+/* The float maps above, n samples from src to dst (which may not overlap). Host-only. */
+int tfp_q31_from_f32(const float* src, int64_t n, int32_t* dst);
+int tfp_q31_from_f64(const double* src, int64_t n, int32_t* dst);
+/* One clip on the host: the map the GPU forms compute, sample for sample. The size query and
+ * TFP_E_CAPACITY as tfp_resample_mix_pcm (*nout = tfp_resample_count(nframes), or nframes at equal rates). */
+int tfp_resample_wide_pcm(const int32_t* q31, int64_t nframes, int32_t channels, int32_t rate_in, int32_t rate_out,
+                          int16_t* out, int64_t cap, int64_t* nout);
+/* The twins of the mix forms over Q31 frames: the frames / results / rows equal the pcm forms at rate_out
+ * over each clip's tfp_resample_wide_pcm, bit for bit. The int32 frames are copied to the GPU as they are
+ * and converted there by one launch (each clip on its own); the fingerprint launch is the one an int16
+ * batch of the output lengths takes. channels == 1 and equal rates are forms of this launch too (the
+ * samples are not the rate forms' int16): equal rates round and clamp only. Not coalesced. */
+int tfp_fingerprint_wide_rate_batch(tfp_engine* eng, const int32_t* q31, const int64_t* offsets, int32_t nclips,
+                                    int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                    int64_t* nframes);
+int tfp_search_wide_rate_batch(tfp_engine* eng, const int32_t* q31, const int64_t* offsets, int32_t nqueries,
+                               int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                               tfp_result* out);
+int tfp_search_scoped_wide_rate_batch(tfp_engine* eng, const int32_t* q31, const int64_t* offsets, int32_t nqueries,
+                                      int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                                      const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                      int32_t* frame_counts);
+/* The wide kernel's launches so far, the frames they read, the samples they wrote, and how many of the
+ * launches staged in LDS (one channel: up to 15,360 int32 samples per tile; several: up to 7,680 int64
+ * sums; equal rates always) rather than reading global memory per tap. Counted where the kernel is
+ * issued; tfp_resample_stats and tfp_resample_mix_stats do not count these. Any pointer may be NULL. */
+int tfp_resample_wide_stats(tfp_engine* eng, int64_t* launches, int64_t* frames_in, int64_t* samples_out,
+                            int64_t* staged_launches);
+/* The same on a group, split and combined exactly as the mix twins. */
+int tfp_group_fingerprint_wide_rate_batch(tfp_group* g, const int32_t* q31, const int64_t* offsets, int32_t nclips,
+                                          int32_t channels, int32_t rate_in, int32_t rate_out, tfp_frame* out, int64_t cap,
+                                          int64_t* nframes);
+int tfp_group_search_wide_rate_batch(tfp_group* g, const int32_t* q31, const int64_t* offsets, int32_t nqueries,
+                                     int32_t channels, int32_t rate_in, int32_t rate_out, const tfp_search_params* params,
+                                     tfp_result* out);
+int tfp_group_search_scoped_wide_rate_batch(tfp_group* g, const int32_t* q31, const int64_t* offsets, int32_t nqueries,
+                                            int32_t channels, int32_t rate_in, int32_t rate_out,
+                                            const tfp_search_params* params, const int32_t* scopes, int32_t k,
+                                            tfp_candidate* out, int32_t* counts, int32_t* frame_counts);
+
 /* ---- rate-normalised ingest of multichannel int16: downmix and convert on the GPU (new) -------- */
 /* The files the rate forms were built for are seldom mono: a prompt master is 44.1 or 48 kHz stereo, a
  * MixMonitor recording is two-channel. These forms take interleaved int16 frames of C channels
@@ -1369,8 +1451,9 @@ int tfp_synchronize(tfp_engine* eng, void* stream);
  * channels < 1 or > TFP_MIX_CHANNELS_MAX is TFP_E_ARG with "unsupported channel count"; a bad rate and
  * an unsupported pair are refused as the rate forms refuse them. An argument error writes nothing to
  * the outputs.
- * Not covered: 24/32-bit and float input, live pushes and tfp_stream_push with more than one channel,
- * the compiled shim, per-clip channel counts inside one call. */
+ * Not covered: live pushes and tfp_stream_push with more than one channel, the compiled shim,
+ * per-clip channel counts inside one call. 24/32-bit and float input is not taken by these int16 forms:
+ * it goes through the Q31 forms of the section before this one (tfp_fingerprint_wide_rate_batch). */
 #define TFP_MIX_CHANNELS_MAX 32
 /* RIFF/WAVE -> the interleaved int16 samples as stored: integer PCM (format 1, or EXTENSIBLE with the
  * PCM subformat), 8-bit ((u - 128) << 8) or 16-bit, 1 to TFP_MIX_CHANNELS_MAX channels. 24/32-bit,
