@@ -27,6 +27,7 @@
 #include "tfp_coalesce.hpp"
 #include "tfp_g711.hpp"
 #include "tfp_resample.hpp"
+#include "tfp_resample_any.hpp"
 #include "tfp_index.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
@@ -348,6 +349,12 @@ struct tfp_engine {
   int64_t n_rs_launch = 0, n_rs_in = 0, n_rs_out = 0;  // tfp_resample_stats
   int64_t n_mix_launch = 0, n_mix_in = 0, n_mix_out = 0, n_mix_staged = 0;  // tfp_resample_mix_stats
   int64_t n_wide_launch = 0, n_wide_in = 0, n_wide_out = 0, n_wide_staged = 0;  // tfp_resample_wide_stats
+  // mixed batches (tfp_resample_any.hpp): the last call's plans' tables laid end to end on the device, kept
+  // while the next call names the same plans in the same order (any_taps_key: their (M, L))
+  DevBuf any_taps;
+  std::vector<std::pair<int32_t, int32_t>> any_taps_key;
+  int64_t n_any_launch = 0, n_any_clips = 0, n_any_in = 0, n_any_out = 0;  // tfp_resample_any_stats
+  int64_t n_any_staged = 0, n_any_global = 0, n_any_plain = 0;             // ... its tiles by form
   // launch configuration and test/A-B knobs, read once at engine creation
   FpLaunchCfg fpcfg;
   FpLaunchStats fpstats;  // fingerprint launches so far per kernel (tfp_fingerprint_stats)
@@ -549,6 +556,15 @@ struct MixSrc {
   const int16_t* d_taps;
 };
 
+// A mixed batch (tfp_resample_any.hpp): the call's bytes as the caller gave them, the validated call and
+// its plans' tables on the device. The call's lens are the output lengths (B->out_off).
+struct AnySrc {
+  const void* data;
+  int64_t nbytes;
+  const AnyBatch* B;
+  const int16_t* d_taps;
+};
+
 // Fingerprint host samples (int16 PCM, or with f32 the fp32 values aubio_source produced):
 // clip c is the lens[c] samples at ptrs[c] (the clips may lie anywhere: a coalesced batch gathers
 // the queries of several callers); leaves micro/db on the device in e->micro / e->db.
@@ -562,14 +578,18 @@ struct MixSrc {
 // conversion into e->pcm; the layout, tile choice and launch are the int16 call's of lens.
 // mix: the same for interleaved multichannel int16 at mix->pcm, by resample_mix_kernel (offsets in frames),
 // or for interleaved int32 Q31 at mix->q31, by resample_wide_kernel.
+// any: a mixed batch: the call's bytes go to the device as they are and resample_any_kernel writes every
+// clip's conversion into e->pcm.
 int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens, bool f32, int32_t nclips, int32_t sr,
                      int64_t* nframes_out, std::vector<int64_t>* foff_out, bool exact_q = true,
-                     const G711Src* g711 = nullptr, const RateSrc* rate = nullptr, const MixSrc* mix = nullptr) {
+                     const G711Src* g711 = nullptr, const RateSrc* rate = nullptr, const MixSrc* mix = nullptr,
+                     const AnySrc* any = nullptr) {
   const size_t ss = f32 ? sizeof(float) : sizeof(int16_t);
   const bool wide = mix && mix->q31;
-  const size_t hs = g711 ? sizeof(uint8_t) : wide ? sizeof(int32_t) : ss;  // bytes per sample as the host hands them over
-  const bool flat = g711 || rate || mix;          // one flat source array in front of e->pcm
-  const std::vector<int64_t>* rs_in_off = rate ? &rate->in_off : mix ? &mix->in_off : nullptr;  // a converting launch's input offsets
+  const size_t hs = g711 || any ? sizeof(uint8_t) : wide ? sizeof(int32_t) : ss;  // bytes per sample as the host hands them over
+  const bool flat = g711 || rate || mix || any;   // one flat source array in front of e->pcm
+  const std::vector<int64_t>* rs_in_off =  // a converting launch's input offsets (a mixed batch: its running frames)
+      rate ? &rate->in_off : mix ? &mix->in_off : any ? &any->B->in_off : nullptr;
   const DspTables* T;
   bool fx = false;
   int rc = ensure_tables(e, sr, &T, &fx);
@@ -608,7 +628,10 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     ns += lens[c];
     if (!flat && c + 1 < nclips && static_cast<const char*>(ptrs[c]) + ss * lens[c] != ptrs[c + 1]) contiguous = false;
   }
-  const int64_t n_src = rate ? rate->in_off[nclips] : mix ? mix->in_off[nclips] * mix->channels : ns;  // samples the host hands over
+  const int64_t n_src = rate  ? rate->in_off[nclips]  // samples (a mixed batch: bytes) the host hands over
+                        : mix ? mix->in_off[nclips] * mix->channels
+                        : any ? any->nbytes
+                              : ns;
   std::vector<int64_t> sbeg(nclips + 1, 0), send(nclips + 1, 0);
   const char* base_dev = nullptr;
   bool in_place = !flat && ns > 0 && (small || !contiguous);
@@ -643,7 +666,11 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
                b_tc = al(sizeof(int32_t) * tclip.size());
   const size_t b_ro = rs_in_off ? al(sizeof(int64_t) * (nclips + 1)) : 0, b_rt = rs_in_off ? al(sizeof(int32_t) * rs_toff.size()) : 0,
                b_rc = rs_in_off ? al(sizeof(int32_t) * rs_tclip.size()) : 0;
-  const size_t lay_fp = 2 * b_sb + b_fo + b_to + b_tc, lay = lay_fp + 2 * b_ro + b_rt + b_rc, total = b_pcm + lay;
+  // a mixed batch's clip descriptors and plans, behind the resample layout (one plan slot at least)
+  const size_t b_ad = any ? al(sizeof(AnyClipDev) * std::max<size_t>(any->B->clips.size(), 1)) : 0,
+               b_ap = any ? al(sizeof(AnyPlanDev) * std::max<size_t>(any->B->plans.size(), 1)) : 0;
+  const size_t lay_fp = 2 * b_sb + b_fo + b_to + b_tc, lay_rs = lay_fp + 2 * b_ro + b_rt + b_rc, lay = lay_rs + b_ad + b_ap,
+               total = b_pcm + lay;
   auto pack_layout = [&](char* h) {
     memcpy(h, sbeg.data(), sizeof(int64_t) * nclips);
     memcpy(h + b_sb, send.data(), sizeof(int64_t) * nclips);
@@ -655,6 +682,10 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     memcpy(h + lay_fp + b_ro, sbeg.data(), sizeof(int64_t) * (nclips + 1));
     memcpy(h + lay_fp + 2 * b_ro, rs_toff.data(), sizeof(int32_t) * rs_toff.size());
     if (!rs_tclip.empty()) memcpy(h + lay_fp + 2 * b_ro + b_rt, rs_tclip.data(), sizeof(int32_t) * rs_tclip.size());
+    if (!any) return;
+    memset(h + lay_rs, 0, b_ad + b_ap);
+    if (!any->B->clips.empty()) memcpy(h + lay_rs, any->B->clips.data(), sizeof(AnyClipDev) * any->B->clips.size());
+    if (!any->B->plans.empty()) memcpy(h + lay_rs + b_ad, any->B->plans.data(), sizeof(AnyPlanDev) * any->B->plans.size());
   };
   auto pack_samples = [&](char* h) {
     if (contiguous) {
@@ -662,6 +693,7 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
                         : rate ? static_cast<const void*>(rate->pcm)
                         : wide ? static_cast<const void*>(mix->q31)
                         : mix  ? static_cast<const void*>(mix->pcm)
+                        : any  ? any->data
                                : ptrs[0];
       if (n_src) memcpy(h, src, hs * n_src);
       return;
@@ -721,7 +753,11 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
       if ((rc = upload(e, e->g711_codes, g711->codes, hs * ns))) return rc;
       d_pcm = e->g711_codes.p;
     } else if (rs_in_off) {
-      if ((rc = upload(e, e->rs_in, rate ? static_cast<const void*>(rate->pcm) : wide ? static_cast<const void*>(mix->q31) : mix->pcm,
+      if ((rc = upload(e, e->rs_in,
+                       rate   ? static_cast<const void*>(rate->pcm)
+                       : wide ? static_cast<const void*>(mix->q31)
+                       : mix  ? static_cast<const void*>(mix->pcm)
+                              : any->data,
                        hs * n_src))) return rc;
       d_pcm = e->rs_in.p;
     } else {
@@ -775,6 +811,25 @@ int fingerprint_host(tfp_engine* e, const void* const* ptrs, const int64_t* lens
     e->n_wide_in += mix->in_off[nclips];
     e->n_wide_out += ns;
     e->n_wide_staged += form != kRsWideGlobal ? 1 : 0;
+    d_pcm = e->pcm.p;
+  }
+  if (any && ns) {
+    // d_pcm holds the call's bytes so far (staging, or rs_in: 256-byte aligned, as the Q31 and word reads
+    // need): every clip's conversion into the device PCM buffer, one launch
+    HIPCHK(e, e->pcm.reserve(ss * ns));
+    const char* r = lay_d + lay_fp;
+    HIPCHK(e, launch_resample_any(static_cast<const uint8_t*>(d_pcm), reinterpret_cast<const AnyClipDev*>(lay_d + lay_rs),
+                                  reinterpret_cast<const AnyPlanDev*>(lay_d + lay_rs + b_ad), any->d_taps,
+                                  reinterpret_cast<const int32_t*>(r + 2 * b_ro),
+                                  reinterpret_cast<const int32_t*>(r + 2 * b_ro + b_rt), rs_toff[nclips], any->B->lds_bytes,
+                                  e->pcm.as<int16_t>(), e->stream));
+    e->n_any_launch++;
+    e->n_any_clips += nclips;
+    e->n_any_in += any->B->in_off[nclips];
+    e->n_any_out += ns;
+    e->n_any_staged += any->B->tiles_staged;
+    e->n_any_global += any->B->tiles_global;
+    e->n_any_plain += any->B->tiles_plain;
     d_pcm = e->pcm.p;
   }
   if (mix && !wide && ns) {
@@ -3347,6 +3402,8 @@ struct QuerySrc {
   const RateSrc* rate = nullptr;
   // interleaved multichannel samples (mix_source): off are the offsets at sr and data is mix->pcm
   const MixSrc* mix = nullptr;
+  // a mixed batch (any_source): off are the offsets at sr and data is the call's bytes
+  const AnySrc* any = nullptr;
 
   int check_offsets(tfp_engine* e, int32_t n) const { return check_monotone(e, off, n, samples); }
   int check_data(tfp_engine* e, int64_t nframes) const {  // frames to search need their data
@@ -3367,8 +3424,8 @@ struct QuerySrc {
       std::vector<int64_t> lens;
       split_offsets(data, sizeof(int16_t), off, n, &ptrs, &lens);
       int64_t nf;
-      rc = fingerprint_host(e, rate || mix ? nullptr : ptrs.data(), lens.data(), false, n, sr, &nf, nullptr, P->coefs == 2,
-                            nullptr, rate, mix);
+      rc = fingerprint_host(e, rate || mix || any ? nullptr : ptrs.data(), lens.data(), false, n, sr, &nf, nullptr,
+                            P->coefs == 2, nullptr, rate, mix, any);
       fingerprinted = rc == TFP_OK;
     }
     *d_q = samples ? e->db.as<double>() : e->q.as<double>();
@@ -4184,7 +4241,7 @@ namespace {
 // One search over host samples, the queries given as (pointer, samples); no coalescing.
 int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* lens, int32_t nq, bool f32, int32_t sr,
                        const tfp_search_params* P, tfp_result* out, const G711Src* g711 = nullptr,
-                       const RateSrc* rate = nullptr, const MixSrc* mix = nullptr) {
+                       const RateSrc* rate = nullptr, const MixSrc* mix = nullptr, const AnySrc* any = nullptr) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   std::vector<int64_t> foff(nq + 1, 0);
@@ -4196,7 +4253,7 @@ int search_gather_impl(tfp_engine* e, const void* const* ptrs, const int64_t* le
   std::vector<unsigned long long> keys(nq, 0ull);
   if (valid_params(P) && nq && foff[nq] > 0) {
     int64_t nf;
-    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2, g711, rate, mix);
+    int rc = fingerprint_host(e, ptrs, lens, f32, nq, sr, &nf, nullptr, P->coefs == 2, g711, rate, mix, any);
     if (rc) return rc;
     if ((rc = search_core(e, foff.data(), nq, e->db.as<double>(), P, keys, nullptr, e->stream))) return rc;
     e->stage_pending = false;  // search_core waited for e->stream (keys on the host)
@@ -4577,6 +4634,104 @@ int tfp_resample_wide_stats(tfp_engine* e, int64_t* launches, int64_t* frames_in
   if (frames_in) *frames_in = e->n_wide_in;
   if (samples_out) *samples_out = e->n_wide_out;
   if (staged_launches) *staged_launches = e->n_wide_staged;
+  return TFP_OK;
+}
+
+// ---- mixed batches: clips of any rate, channel count and sample kind (tfp_resample_any.hpp) ----
+namespace {
+// The source of a mixed batch: any_prepare's rules (nothing touches the device before they pass), then the
+// call's plans' tables laid end to end on the device, kept from the last call while the plans are the same.
+int any_source(tfp_engine* e, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t n, int32_t rate_out,
+               AnyBatch* B, AnySrc* as) {
+  std::string err;
+  if (!any_prepare(clips, n, nbytes, rate_out, resample_table, B, &err)) return fail(e, TFP_E_ARG, "%s", err.c_str());
+  if (!data && B->in_off[(size_t)n] > 0) return fail(e, TFP_E_ARG, "samples are NULL");
+  HIPCHK(e, hipSetDevice(e->device));
+  std::vector<std::pair<int32_t, int32_t>> key;
+  for (const AnyPlanDev& p : B->plans) key.emplace_back(p.P.M, p.P.L);
+  if (!key.empty() && key != e->any_taps_key) {
+    std::vector<int16_t> all((size_t)B->taps_total);
+    for (size_t i = 0; i < B->plans.size(); i++)
+      std::copy(B->tables[i]->taps.begin(), B->tables[i]->taps.end(), all.begin() + B->plans[i].taps_off);
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (no launch of an earlier call reads the old tables any more)
+    e->any_taps_key.clear();
+    if (int rc = upload(e, e->any_taps, all.data(), sizeof(int16_t) * all.size())) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (all is released on return)
+    e->any_taps_key = key;
+  }
+  as->data = data;
+  as->nbytes = nbytes;
+  as->B = B;
+  as->d_taps = key.empty() ? nullptr : e->any_taps.as<int16_t>();
+  return TFP_OK;
+}
+}  // namespace
+
+int tfp_fingerprint_any_batch(tfp_engine* e, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nclips,
+                              int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!nframes) return fail(e, TFP_E_ARG, "bad arguments");
+  AnyBatch B;
+  AnySrc as;
+  if (int rc = any_source(e, data, nbytes, clips, nclips, rate_out, &B, &as)) return rc;
+  const int64_t need = sample_frame_offsets(B.out_off.data(), nclips)[nclips];
+  *nframes = need;
+  if (need > 0 && (!out || cap < need)) return fail(e, TFP_E_CAPACITY, "need %lld frames", (long long)need);
+  if (need == 0) return TFP_OK;
+  std::vector<int64_t> lens(nclips), foff;
+  for (int32_t c = 0; c < nclips; c++) lens[c] = B.clips[c].n_out;
+  int64_t nf;
+  if (int rc = fingerprint_host(e, nullptr, lens.data(), false, nclips, rate_out, &nf, &foff, true, nullptr, nullptr, nullptr, &as))
+    return rc;
+  return copy_frames_out(e, nf, foff, out);
+}
+
+int tfp_search_any_batch(tfp_engine* e, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nq,
+                         int32_t rate_out, const tfp_search_params* P, tfp_result* out) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!out) return fail(e, TFP_E_ARG, "bad arguments");
+  AnyBatch B;
+  AnySrc as;
+  if (int rc = any_source(e, data, nbytes, clips, nq, rate_out, &B, &as)) return rc;
+  std::vector<int64_t> lens(nq);
+  for (int32_t i = 0; i < nq; i++) lens[i] = B.clips[i].n_out;
+  return search_gather_impl(e, nullptr, lens.data(), nq, false, rate_out, P, out, nullptr, nullptr, nullptr, &as);
+}
+
+int tfp_search_scoped_any_batch(tfp_engine* e, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nq,
+                                int32_t rate_out, const tfp_search_params* P, const int32_t* scopes, int32_t k,
+                                tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  // the cheap arguments first, in search_ranked's order: an argument error does no device work
+  if (nq < 0 || !out || !counts) return fail(e, TFP_E_ARG, "ranked search: bad query count or NULL output");
+  if (int rc0 = check_k(e, "ranked search", k)) return rc0;
+  if (int rc0 = check_params(e, "ranked search", P)) return rc0;
+  if (nq && !scopes) return fail(e, TFP_E_ARG, "scoped search: scopes is NULL");
+  if (int rc0 = check_scopes(e, "scoped search", scopes, nq, "query")) return rc0;
+  AnyBatch B;
+  AnySrc as;
+  if (int rc = any_source(e, data, nbytes, clips, nq, rate_out, &B, &as)) return rc;
+  QuerySrc src{data, B.out_off.data(), rate_out, true};
+  src.any = &as;
+  if (int rc = search_ranked(e, src, nq, P, k, out, counts, nullptr, true, scopes)) return rc;
+  for (int32_t i = 0; frame_counts && i < nq; i++) frame_counts[i] = (int32_t)tfp_frame_count(B.clips[i].n_out);
+  return TFP_OK;
+}
+
+int tfp_resample_any_stats(tfp_engine* e, int64_t* launches, int64_t* clips, int64_t* frames_in, int64_t* samples_out,
+                           int64_t* tiles_staged, int64_t* tiles_global, int64_t* tiles_plain) {
+  if (!e) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (launches) *launches = e->n_any_launch;
+  if (clips) *clips = e->n_any_clips;
+  if (frames_in) *frames_in = e->n_any_in;
+  if (samples_out) *samples_out = e->n_any_out;
+  if (tiles_staged) *tiles_staged = e->n_any_staged;
+  if (tiles_global) *tiles_global = e->n_any_global;
+  if (tiles_plain) *tiles_plain = e->n_any_plain;
   return TFP_OK;
 }
 

@@ -40,6 +40,7 @@
 #include "tfp_coalesce.hpp"
 #include "tfp_g711.hpp"
 #include "tfp_resample.hpp"
+#include "tfp_resample_any.hpp"
 #include "tfp_internal.hpp"
 #include "tfp_kernels.hpp"
 #include "tfp_live_occur.hpp"
@@ -664,6 +665,57 @@ int tfp_group_fingerprint_wide_rate_batch(tfp_group* g, const int32_t* q31, cons
                                   });
 }
 
+namespace {
+// A mixed batch's rules on a group: any_prepare's, with the engine forms' messages.
+int group_any_batch(tfp_group* g, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t n, int32_t rate_out,
+                    tfp::AnyBatch* B) {
+  std::string err;
+  if (!tfp::any_prepare(clips, n, nbytes, rate_out, tfp::resample_table, B, &err)) return gfail(g, TFP_E_ARG, "%s", err.c_str());
+  if (!data && B->in_off[(size_t)n] > 0) return gfail(g, TFP_E_ARG, "samples are NULL");
+  return TFP_OK;
+}
+}  // namespace
+
+// A mixed batch on a group (tfp_resample_any.hpp): the clips are cut by their frames at rate_out as
+// tfp_group_fingerprint_rate_batch cuts its own, and each shard converts the clips it fingerprints in one
+// launch of its own. A shard is handed the byte range its clips span (from a 4-byte aligned start, so every
+// offset keeps its alignment), not the whole call's bytes.
+int tfp_group_fingerprint_any_batch(tfp_group* g, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nclips,
+                                    int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes) {
+  if (!g) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);  // (before the first message is written)
+  if (!nframes) return gfail(g, TFP_E_ARG, "bad arguments");
+  tfp::AnyBatch B;
+  if (int rc = group_any_batch(g, data, nbytes, clips, nclips, rate_out, &B)) return rc;
+  const int n = (int)g->eng.size();
+  std::vector<int64_t> foff(nclips + 1, 0);
+  for (int32_t c = 0; c < nclips; c++) foff[c + 1] = foff[c] + tfp_frame_count(B.clips[c].n_out);
+  *nframes = foff[nclips];
+  if (foff[nclips] > 0 && (!out || cap < foff[nclips])) return gfail(g, TFP_E_CAPACITY, "need %lld frames", (long long)foff[nclips]);
+  if (!foff[nclips]) return TFP_OK;
+  std::vector<int32_t> cut(n + 1, nclips);
+  cut[0] = 0;
+  for (int s = 1; s < n; s++)
+    cut[s] = (int32_t)(std::lower_bound(foff.begin(), foff.end(), foff[nclips] * s / n) - foff.begin());
+  for (int s = 1; s <= n; s++) cut[s] = std::max(cut[s], cut[s - 1]);
+  return run_all(g, [&](int s) -> int {
+    const int32_t a = cut[s], b = cut[s + 1];
+    if (a >= b) return TFP_OK;
+    int64_t lo = INT64_MAX, hi = 0;
+    for (int32_t c = a; c < b; c++) {
+      const int64_t len = clips[c].nframes * clips[c].channels * tfp::any_sample_size(clips[c].kind);
+      lo = std::min(lo, clips[c].offset);
+      hi = std::max(hi, clips[c].offset + len);
+    }
+    lo &= ~(int64_t)3;
+    std::vector<tfp_audio_clip> mine(clips + a, clips + b);
+    for (tfp_audio_clip& k : mine) k.offset -= lo;
+    int64_t got = 0;
+    return tfp_fingerprint_any_batch(g->eng[s], data ? static_cast<const char*>(data) + lo : nullptr, hi - lo, mine.data(), b - a,
+                                     rate_out, out + foff[a], foff[b] - foff[a], &got);
+  });
+}
+
 int tfp_group_index_add(tfp_group* g, const char* uuid, const int32_t* m1, const int32_t* m2, int32_t nframes) {
   if (!g) return TFP_E_ARG;
   std::lock_guard<std::recursive_mutex> lk(g->mu);
@@ -1031,6 +1083,23 @@ int tfp_group_search_scoped_wide_rate_batch(tfp_group* g, const int32_t* q31, co
     const int64_t len = offsets[i + 1] - offsets[i];
     frame_counts[i] = (int32_t)tfp_frame_count(rate_in == rate_out ? len : tfp::resample_count(rp, len));
   }
+  return TFP_OK;
+}
+
+// The mixed twin: every shard converts (one launch) and fingerprints the batch.
+int tfp_group_search_scoped_any_batch(tfp_group* g, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nq,
+                                      int32_t rate_out, const tfp_search_params* P, const int32_t* scopes, int32_t k,
+                                      tfp_candidate* out, int32_t* counts, int32_t* frame_counts) {
+  if (!g) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);  // (before the first message is written)
+  tfp::AnyBatch B;
+  if (int rc = group_any_batch(g, data, nbytes, clips, nq, rate_out, &B)) return rc;
+  if (int rc = group_scope_args(g, scopes, nq)) return rc;
+  const int rc = group_rank(g, nq, P, k, out, counts, [&](int s, tfp_candidate* o, int32_t* c) {
+    return tfp_search_scoped_any_batch(g->eng[s], data, nbytes, clips, nq, rate_out, P, scopes, k, o, c, nullptr);
+  });
+  if (rc) return rc;
+  for (int32_t i = 0; frame_counts && i < nq; i++) frame_counts[i] = (int32_t)tfp_frame_count(B.clips[i].n_out);
   return TFP_OK;
 }
 
@@ -1556,6 +1625,24 @@ int tfp_group_search_wide_rate_batch(tfp_group* g, const int32_t* q31, const int
   rc = run_all(g, [&](int s) {
     return tfp_search_wide_rate_batch(g->eng[s], q31, offsets, nq, channels, rate_in, rate_out, P, res[s].data());
   });
+  if (rc) return rc;
+  combine(g, res, nq, out);
+  return TFP_OK;
+}
+
+// The mixed twin: every shard converts (one launch) and fingerprints the batch. Not coalesced.
+int tfp_group_search_any_batch(tfp_group* g, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nq,
+                               int32_t rate_out, const tfp_search_params* P, tfp_result* out) {
+  if (!g) return TFP_E_ARG;
+  std::lock_guard<std::recursive_mutex> lk(g->mu);  // (before the first message is written)
+  if (!out) return gfail(g, TFP_E_ARG, "bad arguments");
+  tfp::AnyBatch B;
+  if (int rc = group_any_batch(g, data, nbytes, clips, nq, rate_out, &B)) return rc;
+  int rc = refresh_ranks(g);
+  if (rc) return rc;
+  const int n = (int)g->eng.size();
+  std::vector<std::vector<tfp_result>> res(n, std::vector<tfp_result>(std::max(nq, 1)));
+  rc = run_all(g, [&](int s) { return tfp_search_any_batch(g->eng[s], data, nbytes, clips, nq, rate_out, P, res[s].data()); });
   if (rc) return rc;
   combine(g, res, nq, out);
   return TFP_OK;

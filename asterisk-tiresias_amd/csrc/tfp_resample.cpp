@@ -1,5 +1,6 @@
 // tfp_resample.cpp — the host side of rate conversion (tfp_resample.hpp): the process's tables and the
-// host-only entry points tfp_resample_count / _taps / _pcm / _mix_pcm / _wide_pcm and tfp_q31_from_*.
+// host-only entry points tfp_resample_count / _taps / _pcm / _mix_pcm / _wide_pcm / _any_pcm, tfp_q31_from_*
+// and tfp_audio_clips_check.
 // tfp_resample_pcm is the map the kernel of
 // tfp_resample.hip computes (one routine, resample_sample), for the search forms without a rate twin.
 #include <cstring>
@@ -7,7 +8,7 @@
 #include <mutex>
 #include <string>
 
-#include "tfp_resample.hpp"
+#include "tfp_resample_any.hpp"
 #include "tiresias_fp.h"
 
 // engine-less calls report through tfp_engine_last_error(NULL) (tfp_wav.cpp)
@@ -166,5 +167,42 @@ extern "C" int tfp_q31_from_f32(const float* src, int64_t n, int32_t* dst) {
 extern "C" int tfp_q31_from_f64(const double* src, int64_t n, int32_t* dst) {
   if (n < 0 || (n > 0 && (!src || !dst))) return fail(TFP_E_ARG, "bad argument");
   for (int64_t i = 0; i < n; i++) dst[i] = tfp::q31_from_f64(src[i]);
+  return TFP_OK;
+}
+
+// ---- mixed batches (tfp_resample_any.hpp): the dispatch to the four host maps above ----------------
+// One clip on the host. The clip's own rules are any_prepare's (a batch of one clip that reaches exactly
+// its own end), so the messages are the engine forms'; the arithmetic is the class's existing entry point.
+extern "C" int tfp_resample_any_pcm(const void* data, const tfp_audio_clip* clip, int32_t rate_out, int16_t* out, int64_t cap,
+                                    int64_t* nout) {
+  if (!clip || !nout) return fail(TFP_E_ARG, "bad argument");
+  tfp::AnyBatch B;
+  std::string err;
+  tfp_audio_clip k = *clip;
+  k.offset = clip->offset < 0 ? clip->offset : clip->offset % tfp::any_sample_size(clip->kind);  // (alignment alone)
+  if (!tfp::any_prepare(&k, 1, INT64_MAX, rate_out, tfp::resample_table, &B, &err)) return fail(TFP_E_ARG, err);
+  if (clip->nframes > 0 && !data) return fail(TFP_E_ARG, "clip 0: samples are NULL");
+  const uint8_t* src = static_cast<const uint8_t*>(data) + (data ? clip->offset : 0);
+  switch (clip->kind) {
+    case TFP_AUDIO_S16:
+      return tfp_resample_mix_pcm(reinterpret_cast<const int16_t*>(src), clip->nframes, clip->channels, clip->rate_in, rate_out,
+                                  out, cap, nout);
+    case TFP_AUDIO_Q31:
+      return tfp_resample_wide_pcm(reinterpret_cast<const int32_t*>(src), clip->nframes, clip->channels, clip->rate_in,
+                                   rate_out, out, cap, nout);
+    default: {
+      std::vector<int16_t> pcm((size_t)clip->nframes);
+      if (int rc = tfp_g711_decode(src, clip->nframes, clip->kind - TFP_AUDIO_ULAW, pcm.data())) return rc;
+      return tfp_resample_pcm(pcm.data(), clip->nframes, clip->rate_in, rate_out, out, cap, nout);
+    }
+  }
+}
+
+extern "C" int tfp_audio_clips_check(const tfp_audio_clip* clips, int32_t nclips, int64_t nbytes, int32_t rate_out,
+                                     int64_t* nout) {
+  tfp::AnyBatch B;
+  std::string err;
+  if (!tfp::any_prepare(clips, nclips, nbytes, rate_out, tfp::resample_table, &B, &err)) return fail(TFP_E_ARG, err);
+  for (int32_t c = 0; nout && c < nclips; c++) nout[c] = B.clips[(size_t)c].n_out;
   return TFP_OK;
 }

@@ -26,7 +26,7 @@ namespace tfp {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int64_t kSpanMax = 30720;  // staged samples per tile (60 KiB of LDS)
+constexpr int64_t kSpanMax = kRsSpanMax;  // staged samples per tile (60 KiB of LDS)
 
 // The staged span of a tile of a plan is at most this many samples.
 inline int64_t span_max(const ResamplePlan& P) { return ((int64_t)(kRsTile - 1) * P.M) / P.L + 1 + P.ntaps; }

@@ -38,6 +38,7 @@ constexpr double kRsBeta = 8.0;         // Kaiser window
 constexpr double kRsRho = 0.90;         // cutoff, as a fraction of the lower rate's Nyquist
 constexpr int64_t kRsMaxEntries = (int64_t)1 << 20;  // L * ntaps
 constexpr int32_t kRsTile = 1024;       // outputs per workgroup (tests/resample_util.py reads it here)
+constexpr int32_t kRsSpanMax = 30720;   // int16 samples a workgroup of tfp_resample.hip stages per tile (60 KiB of LDS)
 
 struct ResamplePlan {
   int32_t L, M, k_lo, ntaps;  // k_hi = k_lo + ntaps - 1

@@ -160,6 +160,18 @@ _SIGS = {
                                                    C.POINTER(SearchParams), P]),
     "tfp_group_search_scoped_wide_rate_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                           C.POINTER(SearchParams), P, C.c_int32, P, P, P]),
+    "tfp_resample_any_pcm": (C.c_int, [P, P, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_audio_clips_check": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P]),
+    "tfp_fingerprint_any_batch": (C.c_int, [P, P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
+    "tfp_search_any_batch": (C.c_int, [P, P, C.c_int64, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_search_scoped_any_batch": (C.c_int, [P, P, C.c_int64, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P, C.c_int32,
+                                              P, P, P]),
+    "tfp_resample_any_stats": (C.c_int, [P] + [C.POINTER(C.c_int64)] * 7),
+    "tfp_group_fingerprint_any_batch": (C.c_int, [P, P, C.c_int64, P, C.c_int32, C.c_int32, P, C.c_int64,
+                                                  C.POINTER(C.c_int64)]),
+    "tfp_group_search_any_batch": (C.c_int, [P, P, C.c_int64, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
+    "tfp_group_search_scoped_any_batch": (C.c_int, [P, P, C.c_int64, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P,
+                                                    C.c_int32, P, P, P]),
     "tfp_fingerprint_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),
     "tfp_search_f32_batch": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.POINTER(SearchParams), P]),
     "tfp_fingerprint_pcm": (C.c_int, [P, P, C.c_int64, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]),

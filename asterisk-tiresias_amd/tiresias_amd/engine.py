@@ -152,6 +152,67 @@ def resample_wide_pcm(q31, channels: int, rate_in: int, rate_out: int) -> np.nda
     return out
 
 
+AUDIO_S16, AUDIO_Q31, AUDIO_ULAW, AUDIO_ALAW = 0, 1, 2, 3  # TFP_AUDIO_*
+ANY_RATES_MAX = 64  # TFP_ANY_RATES_MAX
+# tfp_audio_clip: a clip of a mixed batch, offset in BYTES into the call's data
+CLIP_DTYPE = np.dtype([("offset", "<i8"), ("nframes", "<i8"), ("rate_in", "<i4"), ("channels", "<i4"), ("kind", "<i4"),
+                       ("reserved", "<i4")])
+_KIND_DTYPE = {AUDIO_S16: np.int16, AUDIO_Q31: np.int32, AUDIO_ULAW: np.uint8, AUDIO_ALAW: np.uint8}
+
+
+def _any_args(data, clips):
+    """(data as contiguous bytes, its size, clips as CLIP_DTYPE records) of a mixed call."""
+    data = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    clips = np.ascontiguousarray(clips, CLIP_DTYPE).reshape(-1)
+    return data, len(data), clips
+
+
+def pack_audio_clips(items) -> tuple[np.ndarray, np.ndarray]:
+    """The (data, clips) of a mixed batch from (samples, rate_in) or (samples, rate_in, kind) items. samples is
+    [nframes, channels] or flat mono; without a kind, int16 samples are AUDIO_S16, int32 AUDIO_Q31 and uint8
+    AUDIO_ULAW. Every clip starts at a 4-byte aligned offset."""
+    parts, clips, pos = [], np.zeros(len(items), CLIP_DTYPE), 0
+    for i, it in enumerate(items):
+        x = np.asarray(it[0])
+        kind = it[2] if len(it) > 2 else {np.dtype(np.int16): AUDIO_S16, np.dtype(np.int32): AUDIO_Q31,
+                                          np.dtype(np.uint8): AUDIO_ULAW}[x.dtype]
+        x = np.ascontiguousarray(x, _KIND_DTYPE[kind])
+        ch = x.shape[1] if x.ndim == 2 else 1
+        raw = x.reshape(-1).view(np.uint8)
+        clips[i] = (pos, len(x) if x.ndim == 2 else x.size, int(it[1]), ch, kind, 0)
+        pad = -len(raw) % 4
+        parts += [raw, np.zeros(pad, np.uint8)]
+        pos += len(raw) + pad
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), clips
+
+
+def audio_clips_check(clips, nbytes: int, rate_out: int) -> np.ndarray:
+    """tfp_audio_clips_check: a mixed call's argument rules without an engine; the clips' output lengths at
+    rate_out, or TfpError(TFP_E_ARG) naming the first offending clip."""
+    clips = np.ascontiguousarray(clips, CLIP_DTYPE).reshape(-1)
+    nout = np.zeros(max(len(clips), 1), np.int64)
+    check(lib().tfp_audio_clips_check(clips.ctypes.data, len(clips), int(nbytes), int(rate_out), nout.ctypes.data))
+    return nout[:len(clips)]
+
+
+def resample_any_pcm(data, clip, rate_out: int) -> np.ndarray:
+    """tfp_resample_any_pcm: one clip of a mixed batch (a CLIP_DTYPE record or its tuple, offset in bytes into
+    data) as int16 at rate_out: the existing host map of the clip's class, which the GPU forms compute (exact)."""
+    data, nbytes, clip = _any_args(data, clip)
+    if len(clip) != 1:
+        raise ValueError("one clip")
+    # the clip's extent is the caller's to guarantee in the C call: check it here
+    need = int(clip["offset"][0]) + int(clip["nframes"][0]) * int(clip["channels"][0]) * \
+        np.dtype(_KIND_DTYPE.get(int(clip["kind"][0]), np.uint8)).itemsize
+    if int(clip["nframes"][0]) > 0 and int(clip["channels"][0]) > 0 and need > nbytes:
+        raise ValueError("the clip reaches past data")
+    n = C.c_int64()
+    check(lib().tfp_resample_any_pcm(data.ctypes.data, clip.ctypes.data, int(rate_out), None, 0, C.byref(n)))
+    out = np.empty(n.value, np.int16)
+    check(lib().tfp_resample_any_pcm(data.ctypes.data, clip.ctypes.data, int(rate_out), out.ctypes.data, len(out), C.byref(n)))
+    return out
+
+
 def q31_from_float(x) -> np.ndarray:
     """tfp_q31_from_f32 / tfp_q31_from_f64: float samples (float64 stays double, everything else goes through float32)
     to int32 Q31, rounded to nearest even and clamped; NaN becomes 0."""
@@ -508,6 +569,48 @@ class _WideCalls:
         return self._frames_search_scoped("wide", np.int32, q31, offsets, channels, rate_in, rate_out, p, scopes, k)
 
 
+class _AnyCalls:
+    """Mixed batches, the same calls on an Engine and on a Group: data holds the call's bytes and clips its
+    tfp_audio_clip records (CLIP_DTYPE, or tuples in its order; pack_audio_clips builds both)."""
+
+    resample_any_pcm = staticmethod(resample_any_pcm)
+
+    def fingerprint_any_batch(self, data, clips, rate_out: int) -> np.ndarray:
+        """The frames of fingerprint_batch(resample_any_pcm(clip), rate_out) per clip, bit for bit; one conversion launch."""
+        data, nbytes, clips = _any_args(data, clips)
+        nout = np.zeros(max(len(clips), 1), np.int64)
+        # the host check sizes the output; a call it refuses goes on to the engine, whose refusal is the one raised
+        ok = lib().tfp_audio_clips_check(clips.ctypes.data, len(clips), nbytes, int(rate_out), nout.ctypes.data) == 0
+        n = sum(frame_count(int(x)) for x in nout[:len(clips)]) if ok else 0
+        out = np.zeros(max(n, 1), FRAME_DTYPE)
+        got = C.c_int64()
+        self._chk(self._fn("_fingerprint_any_batch")(self._h, data.ctypes.data, nbytes, clips.ctypes.data, len(clips),
+                                                     int(rate_out), out.ctypes.data, n, C.byref(got)))
+        return out[:got.value]
+
+    def search_any_batch(self, data, clips, rate_out: int, p: SearchParams):
+        """search_pcm_batch at rate_out on the converted queries."""
+        data, nbytes, clips = _any_args(data, clips)
+        nq = len(clips)
+        res = (Result * max(1, nq))()
+        self._chk(self._fn("_search_any_batch")(self._h, data.ctypes.data, nbytes, clips.ctypes.data, nq, int(rate_out),
+                                                C.byref(p), res))
+        return Engine._results(res, nq)
+
+    def search_scoped_any_batch(self, data, clips, rate_out: int, p: SearchParams, scopes, k: int):
+        """search_scoped_pcm_batch at rate_out on the converted queries: (rows per query, frame counts)."""
+        data, nbytes, clips = _any_args(data, clips)
+        nq, k = len(clips), int(k)
+        scopes = np.ascontiguousarray(scopes, np.int32)
+        if len(scopes) != nq:
+            raise ValueError("one scope per query")
+        out, counts = (Candidate * max(1, nq * max(k, 1)))(), (C.c_int32 * max(1, nq))()
+        fc = (C.c_int32 * max(1, nq))()
+        self._chk(self._fn("_search_scoped_any_batch")(self._h, data.ctypes.data, nbytes, clips.ctypes.data, nq, int(rate_out),
+                                                       C.byref(p), scopes.ctypes.data, k, out, counts, fc))
+        return Engine._candidates(out, counts, nq, k), list(fc[:nq])
+
+
 class _CensusCalls:
     """The match census, the same calls on an Engine (tfp_*) and on a Group (tfp_group_*), as _ScopedCalls."""
 
@@ -542,7 +645,7 @@ class _CensusCalls:
                             (int(sample_rate),), p, scopes, nbins)
 
 
-class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _WideCalls):
+class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _WideCalls, _AnyCalls):
     """One engine per GPU (tfp_engine)."""
     _PFX = "tfp"
 
@@ -655,6 +758,15 @@ class Engine(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _
         v = [C.c_int64() for _ in range(4)]
         self._chk(lib().tfp_resample_wide_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("launches", "frames_in", "samples_out", "staged_launches"), (x.value for x in v)))
+
+    _ANY_STATS = ("launches", "clips", "frames_in", "samples_out", "tiles_staged", "tiles_global", "tiles_plain")
+
+    def resample_any_stats(self) -> dict:
+        """tfp_resample_any_stats: the mixed kernel's launches, the clips and frames they read, the samples they
+        wrote, and their tiles by form (staged in LDS, per-tap in global memory, plain at equal rates)."""
+        v = [C.c_int64() for _ in range(7)]
+        self._chk(lib().tfp_resample_any_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(Engine._ANY_STATS, (x.value for x in v)))
 
     def fingerprint_stats(self) -> dict:
         """tfp_fingerprint_stats: fingerprint kernel launches so far, by kernel."""
@@ -1330,7 +1442,7 @@ class Plan:
             self._h = C.c_void_p()
 
 
-class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _WideCalls):
+class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _WideCalls, _AnyCalls):
     """tfp_group: one engine per listed device (a device may repeat), the enrolled clips sharded
     over them, searches combined on the host (tiresias_fp.h, device groups)."""
     _PFX = "tfp_group"
@@ -1429,6 +1541,15 @@ class Group(_ScopedCalls, _SlidingCalls, _CensusCalls, _RateCalls, _MixCalls, _W
             v = [C.c_int64() for _ in range(4)]
             check(lib().tfp_resample_wide_stats(lib().tfp_group_engine(self._h, sh), *[C.byref(x) for x in v]))
             out.append(dict(zip(keys, (x.value for x in v))))
+        return out
+
+    def resample_any_stats(self) -> list:
+        """tfp_resample_any_stats of every shard's engine, in shard order."""
+        out = []
+        for sh in range(self.size()):
+            v = [C.c_int64() for _ in range(7)]
+            check(lib().tfp_resample_any_stats(lib().tfp_group_engine(self._h, sh), *[C.byref(x) for x in v]))
+            out.append(dict(zip(Engine._ANY_STATS, (x.value for x in v))))
         return out
 
     def fingerprint_g711_batch(self, codes, offsets, law: int, sample_rate: int = 8000) -> np.ndarray:

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import dbio
 from ._lib import TFP_RANK_MAX, TfpError
-from .engine import (ALAW, ULAW, Engine, decode_g711, frame_count as frame_count_of, params, read_wav, read_wav_f32,
+from .engine import (ALAW, AUDIO_Q31, AUDIO_S16, AUDIO_ULAW, ULAW, Engine, audio_clips_check, pack_audio_clips, decode_g711, frame_count as frame_count_of, params, read_wav, read_wav_f32,
                      read_wav_g711, read_wav_interleaved, read_wav_interleaved_q31, resample_count, resample_mix_pcm, resample_pcm,
                      resample_wide_pcm)
 
@@ -95,7 +95,7 @@ class FpHandler:
     """One loaded module instance (g_db_ctx + the GPU engine)."""
 
     def __init__(self, device: int = 0, backup_path: str | None = None, index_rate: int = 0, mix_channels: bool = False,
-                 wide_samples: bool = False):
+                 wide_samples: bool = False, mixed_batch: bool = False):
         """backup_path: the snapshot file (the reference hard-codes dbio.DEF_BACKUP_DATABASE);
         None keeps the state in memory only. index_rate: 0 takes every file at its native rate, as the
         reference does (DEF_AUBIO_SAMPLERATE 0); a rate > 0 is the index's rate (new behaviour): int16 and
@@ -110,12 +110,17 @@ class FpHandler:
         off by default for the same reason): a 24/32-bit integer or 32/64-bit float file of another rate is read
         as int32 Q31 frames (tfp_wav_read_interleaved_q31) and normalised by tfp_resample_wide_pcm's map, on
         the GPU in the directory enrolment and on the host for a single file and the searches; several
-        channels still need mix_channels."""
+        channels still need mix_channels. mixed_batch (with an index rate; off by default, so that the
+        per-group calls and their counters stay as they were): the directory enrolment hands every file of
+        another rate that the options above admit to ONE fingerprint_any_batch (one conversion launch for
+        all rates, channel counts and sample kinds; G.711 files go as codes) instead of one call per
+        (rate, kind, channels) group. The rows and fingerprints are the same either way."""
         self.device = device
         self.backup_path = backup_path
         self.index_rate = int(index_rate)
         self.mix_channels = bool(mix_channels)
         self.wide_samples = bool(wide_samples)
+        self.mixed_batch = bool(mixed_batch)
         self.last_error = ""  # why the last file was refused for its rate
         self.db = None
         self.engine = None
@@ -399,7 +404,8 @@ class FpHandler:
             channels = 1
             if self._other_rate(sr):
                 if law is not None:
-                    pcm, law = decode_g711(pcm, law), None  # (the converter takes int16)
+                    if not self.mixed_batch:
+                        pcm, law = decode_g711(pcm, law), None  # (the converter takes int16)
                 elif pcm.dtype == np.float32:
                     try:
                         pcm = self._read_interleaved(path)
@@ -412,11 +418,29 @@ class FpHandler:
                 if resample_count(len(pcm), sr, self.index_rate) < 0:  # before any catalog row is written
                     self.last_error = "%s: unsupported rate ratio %d -> %d" % (path, sr, self.index_rate)
                     continue
+                if self.mixed_batch:  # every rule of the mixed call on this clip alone, before any catalog row is written
+                    kind = {np.dtype(np.int16): AUDIO_S16, np.dtype(np.int32): AUDIO_Q31}.get(pcm.dtype, AUDIO_ULAW + (law or 0))
+                    try:
+                        audio_clips_check([(0, len(pcm), sr, channels, kind, 0)], pcm.nbytes, self.index_rate)
+                    except TfpError as e:
+                        self.last_error = "%s: %s" % (path, e)
+                        continue
             uuid = self.fp_generate_uuid()
             self.db.execute("insert into audio_list(uuid, name, context, hash) values (?, ?, ?, ?);",
                             (uuid, os.path.basename(path), context, h))
             seen.add(h)
             new.append((uuid, pcm, sr, law, channels))
+        if self.mixed_batch and self.index_rate > 0:
+            # every file of another rate in one call, each clip with its own rate, channel count and kind
+            mixed = [n for n in new if self._other_rate(n[2])]
+            new = [n for n in new if not self._other_rate(n[2])]
+            if mixed:
+                data, clips = pack_audio_clips([(n[1], n[2]) if n[3] is None else (n[1], n[2], AUDIO_ULAW + n[3]) for n in mixed])
+                fr = self.engine.fingerprint_any_batch(data, clips, self.index_rate)
+                lens = audio_clips_check(clips, len(data), self.index_rate)
+                foff = np.concatenate([[0], np.cumsum([(int(n) + 255) // 256 for n in lens])]).astype(np.int64)
+                self.engine.index_add_batch([n[0] for n in mixed], foff, fr["m1"], fr["m2"])
+                self.engine.index_set_scope([n[0] for n in mixed], [self._scope_of(context, True)] * len(mixed))
         for sr, dt, law, channels in sorted({(n[2], n[1].dtype.str, -1 if n[3] is None else n[3], n[4]) for n in new}):
             law = None if law < 0 else law
             group = [n for n in new if n[2] == sr and n[1].dtype.str == dt and n[3] == law and n[4] == channels]

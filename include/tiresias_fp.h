@@ -1348,6 +1348,78 @@ int tfp_synth_pcm_device(tfp_engine* eng, const tfp_synth_spec* specs, int32_t n
 /* ---- misc --------------------------------------------------------------------------- */
 int tfp_synchronize(tfp_engine* eng, void* stream);
 
+/* ---- mixed batches: clips of any rate, channel count and sample kind in one call (new) ------------ */
+/* The three rate-normalised families below take ONE (rate_in, channels, sample kind) for a whole batch. A
+ * prompt directory is mixed: 8 kHz .ulaw files, 16-bit mono WAVs at 8 and 16 kHz, 44.1/48 kHz stereo
+ * masters of 16 and 24 bits. These forms take such a batch as it is: every clip carries its own rate,
+ * channel count and kind, the whole call is converted to rate_out by ONE launch, and the unchanged
+ * fingerprint kernels run behind it.
+ * Nothing new is defined. A clip's int16 output is, by decree, the existing host map of its own class:
+ *   TFP_AUDIO_S16, 1 channel     tfp_resample_pcm
+ *   TFP_AUDIO_S16, C >= 2        tfp_resample_mix_pcm
+ *   TFP_AUDIO_Q31                tfp_resample_wide_pcm        (int32 Q31, any C)
+ *   TFP_AUDIO_ULAW / _ALAW       tfp_g711_decode, then tfp_resample_pcm
+ * bit for bit, equal rates included (a copy, the integer mean, the Q31 mean, the expansion), and
+ * tfp_resample_any_pcm is that dispatch on the host. The frames / results / rows of the engine forms equal
+ * the pcm forms at rate_out over each clip's tfp_resample_any_pcm.
+ * data is read-only and clips may overlap in it or name the same bytes. offset counts BYTES.
+ * Argument rules, all TFP_E_ARG and all-or-nothing (nothing is launched or written; the message names the
+ * first offending clip as "clip i: ..."): a rate <= 0 ("bad sample rate"); a pair the table builder refuses,
+ * a Q31 clip with A C >= 2^30, or G.711 codes at a reduction past the int16 staging limit, about 29 to 1
+ * ("unsupported rate ratio"); channels outside 1 .. TFP_MIX_CHANNELS_MAX; a G.711 kind with channels != 1;
+ * an unknown kind; reserved != 0; an offset that is negative or no multiple of the sample size; nframes <
+ * 0; a clip reaching past nbytes; more than TFP_ANY_RATES_MAX distinct rate_in values.
+ * Out of scope: float-to-Q31 and packed 24-bit samples on the device (tfp_wav_decode_interleaved_q31 does
+ * both on the host), taps in LDS, live pushes and tfp_stream_push of anything but mono int16 and G.711, a
+ * query-sharded group search (every shard converts a search batch), coalescing. */
+enum { TFP_AUDIO_S16 = 0, TFP_AUDIO_Q31 = 1, TFP_AUDIO_ULAW = 2, TFP_AUDIO_ALAW = 3 };
+#define TFP_ANY_RATES_MAX 64       /* distinct rate_in values in one call */
+typedef struct tfp_audio_clip {
+  int64_t offset;    /* BYTES into `data`; a multiple of the sample size (2, 4, 1, 1) */
+  int64_t nframes;   /* frames of `channels` interleaved samples; 0 is a clip without frames */
+  int32_t rate_in;
+  int32_t channels;  /* 1 .. TFP_MIX_CHANNELS_MAX; G.711 kinds: 1 only */
+  int32_t kind;
+  int32_t reserved;  /* 0 */
+} tfp_audio_clip;
+/* One clip on the host: the dispatch to the four host maps above, sample for sample what the GPU forms
+ * compute. clip->offset is applied to data; the clip's extent is the caller's to guarantee here (there is
+ * no nbytes). The size query (out == NULL, cap 0) and TFP_E_CAPACITY as tfp_resample_pcm. Host-only. */
+int tfp_resample_any_pcm(const void* data, const tfp_audio_clip* clip, int32_t rate_out, int16_t* out, int64_t cap,
+                         int64_t* nout);
+/* The argument rules above on their own, without an engine: TFP_OK, or TFP_E_ARG with the message the
+ * engine forms give (tfp_engine_last_error(NULL)). nout, if not NULL, receives nclips output lengths at
+ * rate_out. Host-only; builds the pairs' tables (cached per process). */
+int tfp_audio_clips_check(const tfp_audio_clip* clips, int32_t nclips, int64_t nbytes, int32_t rate_out, int64_t* nout);
+/* The twins of the *_rate_batch forms, (data, nbytes, clips, nclips) in place of (pcm, offsets, nclips,
+ * rate_in): output conventions are theirs (frame_counts[i] = frames of query i at rate_out). The bytes are
+ * copied to the GPU as they are, in one copy, and converted there by one launch whatever the number of
+ * classes; no launch when no clip has output. Not coalesced. */
+int tfp_fingerprint_any_batch(tfp_engine* eng, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nclips,
+                              int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes);
+int tfp_search_any_batch(tfp_engine* eng, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nqueries,
+                         int32_t rate_out, const tfp_search_params* params, tfp_result* out);
+int tfp_search_scoped_any_batch(tfp_engine* eng, const void* data, int64_t nbytes, const tfp_audio_clip* clips,
+                                int32_t nqueries, int32_t rate_out, const tfp_search_params* params, const int32_t* scopes,
+                                int32_t k, tfp_candidate* out, int32_t* counts, int32_t* frame_counts);
+/* The mixed kernel's launches so far, the clips and frames they read, the samples they wrote, and their
+ * tiles of 1,024 outputs by form: staged in LDS under the clip's class's own limit, read per tap in global
+ * memory past it, or plain (equal rates: no filter). Counted where the kernel is issued. A mixed call
+ * moves none of tfp_resample_stats, tfp_resample_mix_stats, tfp_resample_wide_stats or tfp_g711_stats.
+ * Any pointer may be NULL. */
+int tfp_resample_any_stats(tfp_engine* eng, int64_t* launches, int64_t* clips, int64_t* frames_in, int64_t* samples_out,
+                           int64_t* tiles_staged, int64_t* tiles_global, int64_t* tiles_plain);
+/* The same on a group. A fingerprint batch is cut by its frames at rate_out as the rate twins cut theirs,
+ * and each shard is handed only the byte range its clips span; every shard converts a search batch. */
+int tfp_group_fingerprint_any_batch(tfp_group* g, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nclips,
+                                    int32_t rate_out, tfp_frame* out, int64_t cap, int64_t* nframes);
+int tfp_group_search_any_batch(tfp_group* g, const void* data, int64_t nbytes, const tfp_audio_clip* clips, int32_t nqueries,
+                               int32_t rate_out, const tfp_search_params* params, tfp_result* out);
+int tfp_group_search_scoped_any_batch(tfp_group* g, const void* data, int64_t nbytes, const tfp_audio_clip* clips,
+                                      int32_t nqueries, int32_t rate_out, const tfp_search_params* params,
+                                      const int32_t* scopes, int32_t k, tfp_candidate* out, int32_t* counts,
+                                      int32_t* frame_counts);
+
 /* ---- rate-normalised ingest of 24/32-bit and float audio: Q31 forms on the GPU (new) ------------ */
 /* A prompt master out of a DAW or a studio is a 24-bit, 32-bit or float WAV at 44.1 or 48 kHz, usually
  * stereo. These forms take such audio without an outside requantisation to int16, which would be a
@@ -1378,7 +1450,8 @@ int tfp_synchronize(tfp_engine* eng, void* stream);
  * Refusals and messages are those of the mix forms ("unsupported channel count", "bad sample rate",
  * "unsupported rate ratio"), plus the range refusal above. An argument error writes nothing to the outputs.
  * Not covered: live pushes and tfp_stream_push of wide samples, the compiled shim, per-clip channel
- * counts inside one call, packed 24-bit samples on the device, float-to-Q31 on the device. */
+ * counts inside one call (tfp_fingerprint_any_batch, "mixed batches" above, takes those), packed 24-bit samples
+ * on the device, float-to-Q31 on the device. */
 /* RIFF/WAVE -> interleaved int32 Q31: integer PCM of 8, 16, 24 or 32 bits (format 1) and float of 32 or
  * 64 bits (format 3), or EXTENSIBLE with either subformat, 1 to TFP_MIX_CHANNELS_MAX channels. G.711 and
  * more channels are TFP_E_FORMAT with a reason. *nframes receives the whole frames present (a trailing
@@ -1452,7 +1525,8 @@ int tfp_group_search_scoped_wide_rate_batch(tfp_group* g, const int32_t* q31, co
  * an unsupported pair are refused as the rate forms refuse them. An argument error writes nothing to
  * the outputs.
  * Not covered: live pushes and tfp_stream_push with more than one channel, the compiled shim,
- * per-clip channel counts inside one call. 24/32-bit and float input is not taken by these int16 forms:
+ * per-clip channel counts inside one call (tfp_fingerprint_any_batch takes those).
+ * 24/32-bit and float input is not taken by these int16 forms:
  * it goes through the Q31 forms of the section before this one (tfp_fingerprint_wide_rate_batch). */
 #define TFP_MIX_CHANNELS_MAX 32
 /* RIFF/WAVE -> the interleaved int16 samples as stored: integer PCM (format 1, or EXTENSIBLE with the

@@ -41,6 +41,15 @@ void fp_set_gpu_devices(const char* list)
 	snprintf(g_devices, sizeof(g_devices), "%s", list ? list : "");
 }
 
+/* fp_set_index_rate: the rate every enrolled and searched file is brought to (before fp_init, e.g. from
+ * an "index_rate" option of tiresias.conf). 0, the default: every file at its native rate, as the
+ * reference (DEF_AUBIO_SAMPLERATE 0); then nothing below differs from a shim without the setting. */
+static int32_t g_index_rate = 0;
+void fp_set_index_rate(int rate)
+{
+	g_index_rate = rate > 0 ? rate : 0;
+}
+
 static bool create_group(void)
 {
 	int32_t dev[64], n = 0, count = 0, a, b;
@@ -389,21 +398,120 @@ static int read_g711(const char* filename, uint8_t* codes, int64_t cap, int64_t*
 	return got == (size_t)size ? TFP_OK : TFP_E_NOENT;
 }
 
+/* With an index rate: a file as a clip of a mixed batch (include/tiresias_fp.h, "mixed batches"), by the
+ * reader of its kind, in read_audio's order: 8/16-bit integer PCM of 1 to 32 channels as interleaved int16
+ * (tfp_wav_read_interleaved), G.711 codes as they are (read_g711), 24/32-bit integer and float as
+ * interleaved int32 Q31 (tfp_wav_read_interleaved_q31). dst == NULL: the size query, which fills *clip
+ * (offset 0) and *nbytes; else the samples into dst[*nbytes]. A file no reader takes is the last reader's
+ * error, its reason in tfp_engine_last_error(NULL). */
+static int read_any(const char* filename, void* dst, tfp_audio_clip* clip, int64_t* nbytes)
+{
+	const bool raw = raw_g711_law(filename) >= 0;
+	int64_t ns = 0;
+	int32_t sr = 0, law = -1, ch = 1;
+	int rc;
+
+	if(dst != NULL) {
+		const int64_t cap = clip->nframes * clip->channels;
+		if(clip->kind == TFP_AUDIO_S16) {
+			rc = tfp_wav_read_interleaved(filename, dst, cap, &ns, &ch, &sr);
+		}
+		else if(clip->kind == TFP_AUDIO_Q31) {
+			rc = tfp_wav_read_interleaved_q31(filename, dst, cap, &ns, &ch, &sr);
+		}
+		else {
+			rc = read_g711(filename, dst, cap, &ns, &sr, &law);
+		}
+		return (rc == TFP_OK && (ns != clip->nframes || sr != clip->rate_in || ch != clip->channels)) ? TFP_E_FORMAT : rc;
+	}
+	memset(clip, 0, sizeof(*clip));
+	if(!raw && (rc = tfp_wav_read_interleaved(filename, NULL, 0, &ns, &ch, &sr)) == TFP_OK) {
+		clip->kind = TFP_AUDIO_S16;
+		*nbytes = ns * ch * 2;
+	}
+	else if((rc = read_g711(filename, NULL, 0, &ns, &sr, &law)) == TFP_OK) {
+		clip->kind = law == TFP_G711_ALAW ? TFP_AUDIO_ALAW : TFP_AUDIO_ULAW;
+		ch = 1;
+		*nbytes = ns;
+	}
+	else if(!raw && (rc = tfp_wav_read_interleaved_q31(filename, NULL, 0, &ns, &ch, &sr)) == TFP_OK) {
+		clip->kind = TFP_AUDIO_Q31;
+		*nbytes = ns * ch * 4;
+	}
+	else {
+		return rc;
+	}
+	clip->nframes = ns;
+	clip->rate_in = sr;
+	clip->channels = ch;
+	return TFP_OK;
+}
+
+/* With an index rate: whether a file is of another rate (*other) and, if so, whether the mixed call takes
+ * it: the engine's own argument rules on its clip (tfp_audio_clips_check: an unsupported ratio, a Q31 pair
+ * out of range), with *nout its length at the index rate. Run before a catalog row is written, so a file
+ * that is refused leaves none. false: unreadable or refused, logged with the engine's message. */
+static bool probe_any(const char* filename, bool* other, tfp_audio_clip* clip, int64_t* nbytes, int64_t* nout)
+{
+	*other = false;
+	if(g_index_rate <= 0) {
+		return true;
+	}
+	if(read_any(filename, NULL, clip, nbytes) != TFP_OK) {
+		return true; /* (no mixed reader takes it: the native-rate readers decide, as without the setting) */
+	}
+	if(clip->rate_in == g_index_rate) {
+		return true;
+	}
+	*other = true;
+	if(tfp_audio_clips_check(clip, 1, *nbytes, g_index_rate, nout) != TFP_OK) {
+		ast_log(LOG_WARNING, "Could not take %s at the index rate %d: %s\n", filename, (int)g_index_rate, tfp_engine_last_error(NULL));
+		return false;
+	}
+	return true;
+}
+
 /* aubio_source (fp_handler.c:37,604,633): a file's mono hop values at its own rate — int16 PCM for
  * 8/16-bit mono (every Asterisk recording; in a pooled pcm_get buffer of *cap samples), then the
  * int16 expansion of G.711 codes (a mu-law / A-law WAV, or a headerless file; tfp_g711_decode on
  * the host: file searches are not hot), else (TFP_E_FORMAT) the fp32 values (multichannel mean,
  * 24/32-bit, float). Exactly one of *pcm / *x is set; release with pcm_put(*pcm, *cap) and
- * ast_free(*x). */
+ * ast_free(*x). With an index rate (fp_set_index_rate) a file of another rate comes back as the int16 PCM
+ * of the mixed call's host map (tfp_resample_any_pcm: what the enrolment's GPU launch computes, bit for
+ * bit) with *sr the index rate; the conversion runs on the host, since file searches and single-file
+ * enrolments are not hot. */
 static int read_audio(const char* filename, int16_t** pcm, int64_t* cap, float** x, int64_t* ns, int32_t* sr)
 {
 	const bool raw = raw_g711_law(filename) >= 0;
 	int32_t law = -1;
 	int rc;
+	bool other = false;
+	tfp_audio_clip clip;
+	int64_t nbytes = 0, nout = 0;
 
 	*pcm = NULL;
 	*cap = 0;
 	*x = NULL;
+	if(probe_any(filename, &other, &clip, &nbytes, &nout) == false) {
+		return -1;
+	}
+	if(other) {
+		void* bytes = ast_malloc(nbytes ? (size_t)nbytes : 1);
+		*pcm = pcm_get(nout ? nout : 1, cap);
+		rc = (bytes && *pcm) ? read_any(filename, bytes, &clip, &nbytes) : TFP_E_NOMEM;
+		if(rc == TFP_OK) {
+			rc = tfp_resample_any_pcm(bytes, &clip, g_index_rate, *pcm, *cap, ns);
+		}
+		ast_free(bytes);
+		if(rc != TFP_OK) {
+			ast_log(LOG_WARNING, "Could not read %s: %s\n", filename, tfp_engine_last_error(NULL));
+			pcm_put(*pcm, *cap);
+			*pcm = NULL;
+			return -1;
+		}
+		*sr = g_index_rate;
+		return 0;
+	}
 	rc = raw ? TFP_E_FORMAT : tfp_wav_read(filename, NULL, 0, ns, sr);
 	if(rc == TFP_OK) {
 		*pcm = pcm_get(*ns ? *ns : 1, cap);
@@ -510,6 +618,14 @@ bool fp_craete_audio_list_info(const char* context, const char* filename)
 		ast_log(LOG_WARNING, "Wrong input parameter.\n");
 		return false;
 	}
+	if(g_index_rate > 0) { /* a file the index rate refuses leaves no catalog row */
+		bool other;
+		tfp_audio_clip clip;
+		int64_t nbytes = 0, nout = 0;
+		if(probe_any(filename, &other, &clip, &nbytes, &nout) == false) {
+			return false;
+		}
+	}
 	uuid = fp_generate_uuid();
 	if(uuid == NULL) {
 		return false;
@@ -547,7 +663,12 @@ bool fp_craete_audio_list_info(const char* context, const char* filename)
  * tfp_group_index_add_batch, instead of a GPU round trip per file. The kinds: int16 PCM, fp32 hop
  * values, and G.711 codes of one law (a directory of .ulaw prompts is one
  * tfp_group_fingerprint_g711_batch per flush: the codes go to the GPU as they are). */
-enum { ENROL_I16 = 0, ENROL_F32 = 1, ENROL_G711 = 2 };
+/* With an index rate (fp_set_index_rate) every file of another rate goes into one more bucket, ENROL_ANY,
+ * whatever its rate, channel count and kind: its samples as read_any hands them out, a tfp_audio_clip per
+ * file, and off[] the clips' running lengths at the index rate, so the batch bound and the frame counts
+ * below are in output samples. It is flushed by one tfp_group_fingerprint_any_batch (one conversion launch
+ * per shard). Files at the index rate keep the buckets above, fp32 for multichannel included. */
+enum { ENROL_I16 = 0, ENROL_F32 = 1, ENROL_G711 = 2, ENROL_ANY = 3 };
 #define ENROL_GROUPS 6
 #define ENROL_BATCH_SAMPLES ((int64_t)1 << 27) /* 256 MB of int16 per batch */
 
@@ -560,7 +681,9 @@ typedef struct {
 	char** uuid;
 	int64_t* off;      /* [n + 1] sample offsets */
 	int64_t scap;      /* samples allocated */
-	void* x;           /* int16 PCM, fp32 hop values or uint8 G.711 codes */
+	void* x;           /* int16 PCM, fp32 hop values or uint8 G.711 codes; ENROL_ANY: the mixed call's bytes */
+	tfp_audio_clip* clips; /* ENROL_ANY: [n], offsets into x */
+	int64_t nbytes;        /* ENROL_ANY: bytes of x in use (scap counts bytes) */
 } enrol_group;
 
 static void group_reset(enrol_group* g)
@@ -570,6 +693,7 @@ static void group_reset(enrol_group* g)
 		ast_free(g->uuid[i]);
 	}
 	g->n = 0;
+	g->nbytes = 0;
 	if(g->off) {
 		g->off[0] = 0;
 	}
@@ -582,6 +706,7 @@ static void group_free(enrol_group* g)
 	ast_free(g->uuid);
 	ast_free(g->off);
 	ast_free(g->x);
+	ast_free(g->clips);
 	memset(g, 0, sizeof(*g));
 }
 
@@ -611,6 +736,7 @@ static int group_flush(const char* context, enrol_group* g, bool* ok)
 	if(rows && m1 && m2 && foff && uu) {
 		rc = g->kind == ENROL_F32 ? tfp_group_fingerprint_f32_batch(g_tfp, (const float*)g->x, g->off, g->n, g->sr, rows, nf, &got)
 		   : g->kind == ENROL_G711 ? tfp_group_fingerprint_g711_batch(g_tfp, (const uint8_t*)g->x, g->off, g->n, g->law, g->sr, rows, nf, &got)
+		   : g->kind == ENROL_ANY ? tfp_group_fingerprint_any_batch(g_tfp, g->x, g->nbytes, g->clips, g->n, g->sr, rows, nf, &got)
 		   : tfp_group_fingerprint_batch(g_tfp, (const int16_t*)g->x, g->off, g->n, g->sr, rows, nf, &got);
 	}
 	if(rc != TFP_OK) {
@@ -721,6 +847,52 @@ static bool group_add(enrol_group* g, int f, const char* filename, char* uuid, i
 	return true;
 }
 
+/* appends file f (clip, of nbytes bytes and nout samples at the index rate) to the mixed bucket g */
+static bool group_add_any(enrol_group* g, int f, const char* filename, char* uuid, tfp_audio_clip clip, int64_t nbytes, int64_t nout)
+{
+	const int64_t at = (g->nbytes + 3) & ~(int64_t)3; /* every clip 4-byte aligned: a multiple of each sample size */
+	if(g->n + 1 >= g->cap) {
+		int nc = g->cap ? 2 * g->cap : 64;
+		int* nf = ast_realloc(g->file, sizeof(int) * (size_t)nc);
+		char** nu = nf ? ast_realloc(g->uuid, sizeof(char*) * (size_t)nc) : NULL;
+		int64_t* no = nu ? ast_realloc(g->off, sizeof(int64_t) * ((size_t)nc + 1)) : NULL;
+		tfp_audio_clip* ncl = no ? ast_realloc(g->clips, sizeof(tfp_audio_clip) * (size_t)nc) : NULL;
+		if(nf) g->file = nf;
+		if(nu) g->uuid = nu;
+		if(no) g->off = no;
+		if(ncl) g->clips = ncl;
+		if(ncl == NULL) {
+			return false;
+		}
+		g->cap = nc;
+	}
+	if(at + nbytes + 1 > g->scap) {
+		int64_t nc = g->scap ? g->scap : (int64_t)1 << 20;
+		void* nx;
+		while(nc < at + nbytes + 1) {
+			nc *= 2;
+		}
+		nx = ast_realloc(g->x, (size_t)nc);
+		if(nx == NULL) {
+			return false;
+		}
+		g->x = nx;
+		g->scap = nc;
+	}
+	memset((char*)g->x + g->nbytes, 0, (size_t)(at - g->nbytes));
+	if(read_any(filename, (char*)g->x + at, &clip, &nbytes) != TFP_OK) {
+		return false;
+	}
+	clip.offset = at;
+	g->clips[g->n] = clip;
+	g->file[g->n] = f;
+	g->uuid[g->n] = uuid;
+	g->off[g->n + 1] = g->off[g->n] + nout;
+	g->nbytes = at + nbytes;
+	g->n++;
+	return true;
+}
+
 int fp_create_audio_list_infos(const char* context, const char* const* filenames, int count, bool* ok)
 {
 	enrol_group groups[ENROL_GROUPS];
@@ -758,9 +930,15 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
 		enrol_group* g = NULL;
 
 		char existing[64] = "";
+		bool other = false;
+		tfp_audio_clip clip;
+		int64_t nbytes = 0, nout = 0;
 
 		if(f == NULL) {
 			continue;
+		}
+		if(probe_any(f, &other, &clip, &nbytes, &nout) == false) {
+			continue; /* refused at the index rate, before any catalog row */
 		}
 		uuid = fp_generate_uuid();
 		if(uuid == NULL) {
@@ -789,9 +967,14 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
 		if(made[i] != NULL) {
 			memcpy(made[i], uuid, strlen(uuid) + 1);
 		}
+		if(other) { /* of another rate than the index's: the one mixed bucket */
+			kind = ENROL_ANY;
+			sr = g_index_rate;
+			ns = nout;
+		}
 		/* aubio_source at the native rate: int16 PCM, then G.711 codes, else the fp32 hop values
 		 * (read_audio's order; a headerless G.711 file is nothing else) */
-		if(raw_g711_law(f) >= 0 || tfp_wav_read(f, NULL, 0, &ns, &sr) != TFP_OK) {
+		else if(raw_g711_law(f) >= 0 || tfp_wav_read(f, NULL, 0, &ns, &sr) != TFP_OK) {
 			if(read_g711(f, NULL, 0, &ns, &sr, &law) == TFP_OK) {
 				kind = ENROL_G711;
 			}
@@ -837,7 +1020,7 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
 		if(g->n > 0 && g->off[g->n] + ns > ENROL_BATCH_SAMPLES) {
 			enrolled += group_flush(context, g, res);
 		}
-		if(group_add(g, i, f, uuid, ns) == false) {
+		if((other ? group_add_any(g, i, f, uuid, clip, nbytes, nout) : group_add(g, i, f, uuid, ns)) == false) {
 			ast_log(LOG_WARNING, "Could not read %s: %s\n", f, tfp_engine_last_error(NULL));
 			fpc_delete_audio_list_info(uuid);
 			ast_free(uuid);

@@ -36,6 +36,21 @@ int fp_create_audio_list_infos(const char* context, const char* const* filenames
  * "0-7", "0,2,5", or "" / NULL for every visible GPU (the default). */
 void fp_set_gpu_devices(const char* list);
 
+/* New: the index rate, before fp_init like fp_set_gpu_devices, e.g. from an "index_rate" option of
+ * tiresias.conf. 0, the default, keeps every file at its native rate, as the reference does, and then
+ * nothing changes. With a rate set (8000 for a telephony deployment), a file of another rate, of any
+ * channel count (1 to 32) and kind (8/16/24/32-bit integer, float, G.711), is brought to it, so a prompt
+ * enrolled from a 44.1 kHz stereo master matches the same prompt heard on an 8 kHz call:
+ *  - fp_create_audio_list_infos collects such files into one mixed bucket, flushed by one
+ *    tfp_group_fingerprint_any_batch (converted on the GPU, one launch per shard);
+ *  - fp_craete_audio_list_info and every file search read such a file as the same map computed on the
+ *    host (tfp_resample_any_pcm; bit-equal to the GPU's), at the index rate;
+ *  - a file no reader takes, or at an unsupported rate ratio, is refused with the engine's message in the
+ *    log, before any catalog row is written;
+ *  - files at the index rate keep their paths (fp32 for multichannel included), and fp_live_open and
+ *    fp_channel_* are unchanged: a call is opened at its own rate. */
+void fp_set_index_rate(int rate);
+
 /* New: how the channel threads' fp_search_fingerprint_info calls ran. Concurrent calls are
  * coalesced into shared GPU batches (tfp_group_search_pcm_batch, include/tiresias_fp.h): *calls
  * searches went through the coalescer as *batches batches. false before fp_init. */
